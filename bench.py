@@ -17,9 +17,18 @@ pose-gradient rows), overlapped with the next step; `--scaling weak` (default): 
 keyframes of the same (replicated) map; `--scaling strong`: ONE window of `--views` keyframes dealt over the ranks (BASELINE
 config 4: "8 keyframes sharded across 8 MI355X").
 An interaction = one (pixel, Gaussian) pair the compositor visits: I = sum over views and pixels of n_contrib.
-Beside it: the same workload one frame at a time through the single-view entry points (`single_stream`, the latency a
-sequential tracking loop sees; the per-kernel roofline numbers of the single-view kernels come from that pass).
 Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the --steps steps and prints the headline (value, ms_per_step).  `--full` adds
+everything else, each in passes of its own after the timed steps: the per-stage HIP-event profile and the roofline figures
+built on it, the gradient exchange on its own (N > 1), the same workload one frame at a time through the single-view entry
+points (`single_stream`, the latency a sequential tracking loop sees) with the batched-vs-single `selfcheck`, and the CPU
+oracle baseline (`cpu_baseline`, N = 1).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step handed its caller (rank 0): the K images
+(color, depth, alpha), radii, dL/dmean2D per view, the per-Gaussian gradients summed over the window and dL/dtau per
+keyframe, as DIR/<name>.npy in float32.  An array of more than DUMP_CAP elements is written as the values at a fixed, seeded
+sample of DUMP_CAP flat indices (sorted), the same for every run of the same arguments, so two builds compare value for value.
 """
 import argparse
 import hashlib
@@ -43,6 +52,8 @@ PRIMING_STEPS = 24  # untimed windows before the warm-up the command line asks f
                     # load every code object, and the GPU needs ~15 ms of work to reach its steady clocks (20 timed windows after
                     # 8 untimed ones ran 6 % slower than after 30); reported as priming_steps, never counted as warm-up
 PMC_FILE = "profiles/r03_pmc_summary.json"
+DUMP_CAP = 1 << 20  # elements per --dump-outputs file (4 MiB of float32; 11 files): larger arrays are written as a seeded sample
+DUMP_SEED = 20240601
 
 
 def parse(argv=None):
@@ -58,10 +69,16 @@ def parse(argv=None):
     ap.add_argument("--streams", type=int, default=1, choices=[1, 2],
                     help="HIP streams the window's views are spread over (2: two view groups, the accumulating per-Gaussian chains stay "
                          "ordered; measured SLOWER than 1 at cfg2, K = 8: 1.10 vs 1.03 ms -- the batched grids already fill the chip)")
-    ap.add_argument("--skip-single", action="store_true", help="profiling runs: only the batched window, no single-view pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-stage profile / roofline, the gradient exchange (N > 1), the "
+                         "single-view pass with its selfcheck and the CPU baseline (a plain run reports the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32, at most %d elements per "
+                         "array (a fixed, seeded sample of larger ones)" % DUMP_CAP)
+    ap.add_argument("--skip-single", action="store_true", help="with --full, profiling runs: only the batched window, no single-view pass")
     ap.add_argument("--sh-degree", type=int, default=3)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (--full, rank 0, N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline leg")
     ap.add_argument("--records", default="fp32", choices=["fp32", "fp16"],
                     help="storage of the per-Gaussian splat rows the compositors gather (fp16: conic / opacity / colour as halves, config 5)")
     a = ap.parse_args(argv)
@@ -196,66 +213,70 @@ def run(a):
     assert not any(ab for _, _, ab in st), "a view was aborted on the device (arena too small): %r" % (st,)
     inter = ctx.interactions()
     R = sum(r for r, _, _ in st)
-    tau_batched = ctx.slots[(counter[0] - 1) & 1 if world > 1 else 0]["tau_all"].clone()  # [K, 6] of the last step (before any all-reduce of ANOTHER step lands: slots alternate)
+    last = (counter[0] - 1) & 1 if world > 1 else 0  # the last step's gradient slot (slots alternate)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, ctx, last)
 
-    # the same steps again with every kernel bracketed by HIP events on its launch stream (outside the timed region)
-    fence()
-    with profile_stages(max_records=a.steps * 24) as prof:
-        for _ in range(a.steps):
-            step()
+    comm = selfcheck = None
+    if a.full:  # everything below the headline: passes of their own, after the timed steps and the dump
+        tau_batched = ctx.slots[last]["tau_all"].clone()  # [K, 6] of the last step (before any all-reduce of ANOTHER step lands: slots alternate)
+
+        # the same steps again with every kernel bracketed by HIP events on its launch stream (outside the timed region)
         fence()
+        with profile_stages(max_records=a.steps * 24) as prof:
+            for _ in range(a.steps):
+                step()
+            fence()
 
-    # the gradient exchange on its own (N > 1): blocking collectives of the bucket, outside the timed region
-    comm = None
-    if world > 1:
-        comm = {"bucket_bytes": int(ctx.buckets[0].numel() * 4), "backend": backend}
-        for form in ("all_reduce", "reduce_scatter+all_gather"):
-            try:
-                ks.exchange_gaussian_grads(ctx.buckets[0], form=form)  # (warm)
-                fence()
-                t1 = time.perf_counter()
-                for _ in range(10):
-                    ks.exchange_gaussian_grads(ctx.buckets[0], form=form)
-                torch.cuda.synchronize(dev)
-                comm[form + "_ms"] = 1e2 * (time.perf_counter() - t1)
-            except Exception as e:  # (gloo has no reduce-scatter; informational leg, outside the timed region: never fatal)
-                comm[form + "_ms"] = None
-                comm[form + "_error"] = str(e).splitlines()[0][:120]
-        fence()
+        # the gradient exchange on its own (N > 1): blocking collectives of the bucket, outside the timed region
+        if world > 1:
+            comm = {"bucket_bytes": int(ctx.buckets[0].numel() * 4), "backend": backend}
+            for form in ("all_reduce", "reduce_scatter+all_gather"):
+                try:
+                    ks.exchange_gaussian_grads(ctx.buckets[0], form=form)  # (warm)
+                    fence()
+                    t1 = time.perf_counter()
+                    for _ in range(10):
+                        ks.exchange_gaussian_grads(ctx.buckets[0], form=form)
+                    torch.cuda.synchronize(dev)
+                    comm[form + "_ms"] = 1e2 * (time.perf_counter() - t1)
+                except Exception as e:  # (gloo has no reduce-scatter; informational leg, outside the timed region: never fatal)
+                    comm[form + "_ms"] = None
+                    comm[form + "_error"] = str(e).splitlines()[0][:120]
+            fence()
 
-    # one frame at a time through the single-view entry points: the latency of a sequential tracking loop
-    fc = FrameContext(P, W, H, M, dev, record_bits=bits)
-    n_single = 0 if a.skip_single else max(a.steps, 20)
-    tau_single = []
+        # one frame at a time through the single-view entry points: the latency of a sequential tracking loop
+        fc = FrameContext(P, W, H, M, dev, record_bits=bits)
+        n_single = 0 if a.skip_single else max(a.steps, 20)
+        tau_single = []
 
-    def single(n):
-        k = n % K
-        fc.forward(bg, means, opac, views[k], projs[k], campos[k], tx, ty, sync=(n < K), **geo)
-        return fc.backward(bg, means, views[k], projs[k], proj_raw, campos[k], tx, ty, dLc[k], dLd[k], **geo)
+        def single(n):
+            k = n % K
+            fc.forward(bg, means, opac, views[k], projs[k], campos[k], tx, ty, sync=(n < K), **geo)
+            return fc.backward(bg, means, views[k], projs[k], proj_raw, campos[k], tx, ty, dLc[k], dLd[k], **geo)
 
-    for n in range(K if n_single else 0):  # every camera once, synchronously: sizes the arena for the largest view
-        tau_single.append(single(n)["tau_sum"].clone())
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for n in range(K, K + n_single):
-        single(n)
-    torch.cuda.synchronize(dev)
-    elapsed_single = max(time.perf_counter() - t0, 1e-9)
-    if n_single:
-        fc.status()
-    with profile_stages(max_records=max(16, n_single * 16)) as prof1:
+        for n in range(K if n_single else 0):  # every camera once, synchronously: sizes the arena for the largest view
+            tau_single.append(single(n)["tau_sum"].clone())
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
         for n in range(K, K + n_single):
             single(n)
         torch.cuda.synchronize(dev)
-    inter_1 = inter / K  # mean interactions per frame of the window
-    # self-check of the timed path: the batched window's K rows of dL/dtau against the single-view kernels' (different kernels
-    # for the per-Gaussian chain and its sums; the parity tests hold both to the oracle)
-    selfcheck = None
-    if tau_single:
-        ts = torch.stack(tau_single)
-        tb = tau_batched if world == 1 else tau_batched  # (rows of this rank's keyframes; other ranks' rows are theirs)
-        selfcheck = {"tau_max_rel": float((tb - ts).abs().max() / ts.abs().max()), "what": "max |dL/dtau batched - single view| / max |dL/dtau| "
-                     "over the window's %d keyframes (rank 0)" % K}
+        elapsed_single = max(time.perf_counter() - t0, 1e-9)
+        if n_single:
+            fc.status()
+        with profile_stages(max_records=max(16, n_single * 16)) as prof1:
+            for n in range(K, K + n_single):
+                single(n)
+            torch.cuda.synchronize(dev)
+        inter_1 = inter / K  # mean interactions per frame of the window
+        # self-check of the timed path: the batched window's K rows of dL/dtau against the single-view kernels' (different kernels
+        # for the per-Gaussian chain and its sums; the parity tests hold both to the oracle)
+        if tau_single:
+            ts = torch.stack(tau_single)
+            tb = tau_batched  # (rows of this rank's keyframes; other ranks' rows are theirs)
+            selfcheck = {"tau_max_rel": float((tb - ts).abs().max() / ts.abs().max()), "what": "max |dL/dtau batched - single view| / max |dL/dtau| "
+                         "over the window's %d keyframes (rank 0)" % K}
 
     stats = torch.tensor([elapsed, float(inter), float(R)], dtype=torch.float64, device=dev)
     if world > 1:
@@ -271,29 +292,6 @@ def run(a):
         ms_step = 1e3 * elapsed / a.steps
         value = inter_total * a.steps / elapsed
 
-        def per_launch(p, k):
-            return p.ms[k] / max(p.launches[k], 1) * 1e-3
-
-        shf = 3 * M * 4
-        # algorithmic bytes per launch of the batched kernels (K views), SURVEY 8(d) regime 1
-        pre_bytes = K * P * ((12 + 12 + 16 + 4 + shf) + (4 + 4 + 4 + 3 + 4 + 4 + 52 + 8)) + P * 24
-        gather_bytes = R * (48 + 1) + K * P * (4 + 4 + 48)   # instance rows + flags in; tiles_touched, offsets in; 48-B sums out
-        chain_bytes = K * P * (48 + 4 + 3 + 12 + 24 + shf + 64 + 4 * M + 12) + P * (K * (64 + 4 * M) + 28 + (12 + 4 + 24 + shf + 12 + 16))
-        scat_bytes = K * P * 8 * 8 + R * 4                   # the 8-byte rectangles, read by the 8 tile-row classes; one id per instance out
-        sort_bytes = R * (4 + 4 + 4 + 1)                     # ids in, gathered depths, sorted ids out, cleared flags
-        t_bwd, t_fwd = per_launch(prof, "render_bwd"), per_launch(prof, "render_fwd")
-        ach = FLOP_BWD * inter / t_bwd / 1e12 if t_bwd > 0 else 0.0
-        pmc = pmc_summary()
-        bwd_pmc = (pmc or {}).get("k_render_bwd", {})
-        pmc_ok = bool(bwd_pmc) and bwd_pmc.get("csrc_sha1") == csrc_hash()
-
-        def hbm(name, stage, nbytes, p=prof, launches=1):
-            tl = per_launch(p, stage) * launches
-            return {"bound": "hbm", "achieved": nbytes / tl / 1e9 if tl > 0 else 0.0, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": nbytes / tl / 1e9 / PEAK_HBM_GBS if tl > 0 else 0.0, "avg_launch_ms": tl * 1e3, "algorithmic_bytes": nbytes,
-                    "traffic": traffic_of((pmc or {}).get(name))}
-
-        t1_bwd, t1_fwd = per_launch(prof1, "render_bwd"), per_launch(prof1, "render_fwd")
         out = {
             "metric": "Gaussian-pixel interactions/sec (fwd+Jacobian), 640x480",
             "value": value, "unit": "interactions/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -310,49 +308,97 @@ def run(a):
                                        "+ pose-gradient rows), overlapped with the next step"
                                        % (a.scaling, K, "one window dealt over the ranks" if strong else "one window per rank", ctx.buckets[0].numel())) if world > 1
                        else "single GPU, batched launches (grids x views), the window's %d views in %d group(s) on %d HIP stream(s)" % (K, a.streams, a.streams)},
-            "roofline": {"bound": "valu", "kernel": "k_render_bwd", "achieved": ach, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                         "frac": ach / PEAK_FP32_TFLOPS, "traffic": traffic_of(bwd_pmc),
-                         "traffic_unit": "bytes/launch (2 x FETCH_SIZE + WRITE_SIZE, separate rocprofv3 --pmc passes; algorithmic: %d)" % (R * (4 + 48 + 48 + 1) + K * W * H * 32),
-                         "traffic_source": {"file": PMC_FILE, "csrc_sha1_of_file": bwd_pmc.get("csrc_sha1"), "csrc_sha1_running": csrc_hash(),
-                                            "quoted": pmc_ok, "note": "PMC counters cannot be read inside the timed process: they come from the committed "
-                                            "summary and are quoted only when its fingerprint equals the kernel sources being run"},
-                         "executed_valu_util": valu_util(bwd_pmc, t_bwd),
-                         "inst_mix": inst_mix(bwd_pmc),
-                         "note": "fp32 VALU / transcendental-bound reverse compositor (not MFMA, not HBM): NOTIONAL fraction = 87 fp32 flop x "
-                                 "interactions per launch / HIP-event launch time / fp32 vector peak; culling skips most lane-operations, so "
-                                 "executed_valu_util is the pipe utilisation as a RANGE: SQ_INSTS_VALU (PMC, same kernel sources) x [2.8, 4] cycles per "
-                                 "wave-instruction (2.8: plain fma / mul / add measured by tools/op_cost.hip, 4: every other VALU form and the "
-                                 "guide's single-wave issue cost) / (launch time x 2.4 GHz x 1024 SIMDs)",
-                         "avg_launch_ms": t_bwd * 1e3, "launch_covers_views": K},
-            "roofline_other": {
-                "k_render_fwd": {"bound": "valu", "achieved": FLOP_FWD * inter / t_fwd / 1e12 if t_fwd > 0 else 0.0, "peak": PEAK_FP32_TFLOPS,
-                                 "unit": "TFLOP/s", "frac": FLOP_FWD * inter / t_fwd / 1e12 / PEAK_FP32_TFLOPS if t_fwd > 0 else 0.0,
-                                 "avg_launch_ms": t_fwd * 1e3, "executed_valu_util": valu_util((pmc or {}).get("k_render_fwd"), t_fwd)},
-                "k_preprocess+k_frame_scan": hbm("k_preprocess", "preprocess", pre_bytes),
-                "k_scatter_instances": hbm("k_scatter_instances", "scatter_instances", scat_bytes),
-                "k_tile_sort": hbm("k_tile_sort", "tile_sort_records", sort_bytes),
-                "k_gather_sums": hbm("k_gather_sums", "gather_sums", gather_bytes),
-                "k_chain_window+k_tau_sum": dict(hbm("k_chain_window", "gaussian_bwd", chain_bytes),
-                                                 note="timed as one stage: the per-(view, Gaussian) chain with the sum over views (one launch per 8 views) and the fp64 dL/dtau tree")},
-            "stage_ms_per_step": {k: v / a.steps for k, v in prof.ms.items() if prof.launches[k]},
-            "non_compositor_ms_per_step": sum(v for k, v in prof.ms.items() if prof.launches[k] and k not in ("render_fwd", "render_bwd")) / a.steps,
-            "single_stream": None if not n_single else {"ms_per_frame": 1e3 * elapsed_single / n_single, "value_rank0": inter_1 * n_single / elapsed_single,
-                              "stage_ms_per_frame": {k: v / n_single for k, v in prof1.ms.items() if prof1.launches[k]},
-                              "k_render_bwd_frac": FLOP_BWD * inter_1 / t1_bwd / 1e12 / PEAK_FP32_TFLOPS if t1_bwd > 0 else 0.0,
-                              "k_render_fwd_frac": FLOP_FWD * inter_1 / t1_fwd / 1e12 / PEAK_FP32_TFLOPS if t1_fwd > 0 else 0.0,
-                              "note": "the window's keyframes one at a time through the single-view entry points on one HIP stream (sequential "
-                                      "tracking iterations), no host sync per frame"},
-            "selfcheck": selfcheck,
-            "gradient_exchange": comm,
+            "full": a.full,
             "host_enqueue_ms_per_step": 1e3 * t_enqueued / a.steps,
             "csrc_sha1": csrc_hash(),
         }
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cams[0], sc, deg, a.cpu_seconds)
+        if a.full:
+            def per_launch(p, k):
+                return p.ms[k] / max(p.launches[k], 1) * 1e-3
+
+            shf = 3 * M * 4
+            # algorithmic bytes per launch of the batched kernels (K views), SURVEY 8(d) regime 1
+            pre_bytes = K * P * ((12 + 12 + 16 + 4 + shf) + (4 + 4 + 4 + 3 + 4 + 4 + 52 + 8)) + P * 24
+            gather_bytes = R * (48 + 1) + K * P * (4 + 4 + 48)   # instance rows + flags in; tiles_touched, offsets in; 48-B sums out
+            chain_bytes = K * P * (48 + 4 + 3 + 12 + 24 + shf + 64 + 4 * M + 12) + P * (K * (64 + 4 * M) + 28 + (12 + 4 + 24 + shf + 12 + 16))
+            scat_bytes = K * P * 8 * 8 + R * 4                   # the 8-byte rectangles, read by the 8 tile-row classes; one id per instance out
+            sort_bytes = R * (4 + 4 + 4 + 1)                     # ids in, gathered depths, sorted ids out, cleared flags
+            t_bwd, t_fwd = per_launch(prof, "render_bwd"), per_launch(prof, "render_fwd")
+            ach = FLOP_BWD * inter / t_bwd / 1e12 if t_bwd > 0 else 0.0
+            pmc = pmc_summary()
+            bwd_pmc = (pmc or {}).get("k_render_bwd", {})
+            pmc_ok = bool(bwd_pmc) and bwd_pmc.get("csrc_sha1") == csrc_hash()
+
+            def hbm(name, stage, nbytes, p=prof, launches=1):
+                tl = per_launch(p, stage) * launches
+                return {"bound": "hbm", "achieved": nbytes / tl / 1e9 if tl > 0 else 0.0, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                        "frac": nbytes / tl / 1e9 / PEAK_HBM_GBS if tl > 0 else 0.0, "avg_launch_ms": tl * 1e3, "algorithmic_bytes": nbytes,
+                        "traffic": traffic_of((pmc or {}).get(name))}
+
+            t1_bwd, t1_fwd = per_launch(prof1, "render_bwd"), per_launch(prof1, "render_fwd")
+            out.update({
+                "roofline": {"bound": "valu", "kernel": "k_render_bwd", "achieved": ach, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                             "frac": ach / PEAK_FP32_TFLOPS, "traffic": traffic_of(bwd_pmc),
+                             "traffic_unit": "bytes/launch (2 x FETCH_SIZE + WRITE_SIZE, separate rocprofv3 --pmc passes; algorithmic: %d)" % (R * (4 + 48 + 48 + 1) + K * W * H * 32),
+                             "traffic_source": {"file": PMC_FILE, "csrc_sha1_of_file": bwd_pmc.get("csrc_sha1"), "csrc_sha1_running": csrc_hash(),
+                                                "quoted": pmc_ok, "note": "PMC counters cannot be read inside the timed process: they come from the committed "
+                                                "summary and are quoted only when its fingerprint equals the kernel sources being run"},
+                             "executed_valu_util": valu_util(bwd_pmc, t_bwd),
+                             "inst_mix": inst_mix(bwd_pmc),
+                             "note": "fp32 VALU / transcendental-bound reverse compositor (not MFMA, not HBM): NOTIONAL fraction = 87 fp32 flop x "
+                                     "interactions per launch / HIP-event launch time / fp32 vector peak; culling skips most lane-operations, so "
+                                     "executed_valu_util is the pipe utilisation as a RANGE: SQ_INSTS_VALU (PMC, same kernel sources) x [2.8, 4] cycles per "
+                                     "wave-instruction (2.8: plain fma / mul / add measured by tools/op_cost.hip, 4: every other VALU form and the "
+                                     "guide's single-wave issue cost) / (launch time x 2.4 GHz x 1024 SIMDs)",
+                             "avg_launch_ms": t_bwd * 1e3, "launch_covers_views": K},
+                "roofline_other": {
+                    "k_render_fwd": {"bound": "valu", "achieved": FLOP_FWD * inter / t_fwd / 1e12 if t_fwd > 0 else 0.0, "peak": PEAK_FP32_TFLOPS,
+                                     "unit": "TFLOP/s", "frac": FLOP_FWD * inter / t_fwd / 1e12 / PEAK_FP32_TFLOPS if t_fwd > 0 else 0.0,
+                                     "avg_launch_ms": t_fwd * 1e3, "executed_valu_util": valu_util((pmc or {}).get("k_render_fwd"), t_fwd)},
+                    "k_preprocess+k_frame_scan": hbm("k_preprocess", "preprocess", pre_bytes),
+                    "k_scatter_instances": hbm("k_scatter_instances", "scatter_instances", scat_bytes),
+                    "k_tile_sort": hbm("k_tile_sort", "tile_sort_records", sort_bytes),
+                    "k_gather_sums": hbm("k_gather_sums", "gather_sums", gather_bytes),
+                    "k_chain_window+k_tau_sum": dict(hbm("k_chain_window", "gaussian_bwd", chain_bytes),
+                                                     note="timed as one stage: the per-(view, Gaussian) chain with the sum over views (one launch per 8 views) and the fp64 dL/dtau tree")},
+                "stage_ms_per_step": {k: v / a.steps for k, v in prof.ms.items() if prof.launches[k]},
+                "non_compositor_ms_per_step": sum(v for k, v in prof.ms.items() if prof.launches[k] and k not in ("render_fwd", "render_bwd")) / a.steps,
+                "single_stream": None if not n_single else {"ms_per_frame": 1e3 * elapsed_single / n_single, "value_rank0": inter_1 * n_single / elapsed_single,
+                                  "stage_ms_per_frame": {k: v / n_single for k, v in prof1.ms.items() if prof1.launches[k]},
+                                  "k_render_bwd_frac": FLOP_BWD * inter_1 / t1_bwd / 1e12 / PEAK_FP32_TFLOPS if t1_bwd > 0 else 0.0,
+                                  "k_render_fwd_frac": FLOP_FWD * inter_1 / t1_fwd / 1e12 / PEAK_FP32_TFLOPS if t1_fwd > 0 else 0.0,
+                                  "note": "the window's keyframes one at a time through the single-view entry points on one HIP stream (sequential "
+                                          "tracking iterations), no host sync per frame"},
+                "selfcheck": selfcheck,
+                "gradient_exchange": comm,
+            })
+            if world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cams[0], sc, deg, a.cpu_seconds)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(d, ctx, slot):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy in float32 (radii: small integers, exact).
+    Arrays of more than DUMP_CAP elements: the values at DUMP_CAP flat indices drawn (sorted) from a generator seeded with
+    DUMP_SEED -- the same indices for the same shape, so two builds compare element for element."""
+    import torch
+
+    g = ctx.slots[slot]
+    arrays = {"color": ctx.color, "depth": ctx.depth, "alpha": ctx.opacity, "radii": ctx.radii, "dL_dmean2D": g["mean2D"],
+              "dL_dmeans3D": g["mean3D"], "dL_dopacity": g["opacity"], "dL_dshs": g["sh"], "dL_dscales": g["scale"],
+              "dL_drotations": g["rot"],
+              "dL_dtau": g["tau_all"] if g["tau_every_window"] is None else g["tau_every_window"]}  # N > 1: every rank's rows
+    os.makedirs(d, exist_ok=True)
+    for name, x in arrays.items():
+        if x is None:
+            continue
+        if x.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.numel(), DUMP_CAP, replace=False))
+            x = x.reshape(-1)[torch.as_tensor(idx, device=x.device)]
+        np.save(os.path.join(d, name + ".npy"), x.to(torch.float32).cpu().numpy())
 
 
 def pmc_summary():

@@ -1,4 +1,4 @@
-"""Print the few numbers of a bench.py JSON line that an A/B comparison looks at.  usage: python tools/ab_show.py FILE..."""
+"""Print the few numbers of a `bench.py --full` JSON line that an A/B comparison looks at.  usage: python tools/ab_show.py FILE..."""
 import json
 import sys
 

@@ -7,11 +7,11 @@ tag=${1:-r03}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 300 python bench.py > $out/bench.json 2> $out/bench.err
-for w in cfg3 cfg4 cfg5; do timeout -k 10 300 python bench.py --workload $w --steps 20 --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err; done
-timeout -k 10 300 python bench.py --workload cfg5 --records fp16 --steps 20 --no-cpu-baseline > $out/bench_cfg5_fp16.json 2> $out/bench_cfg5_fp16.err
-GSAJ_SHARE_DEVICE=1 timeout -k 10 300 python bench.py --gpus 2 --steps 5 --warmup 1 --no-cpu-baseline --skip-single > $out/bench_2rank_gloo_shared_gpu_weak.txt 2>&1 || true
-GSAJ_SHARE_DEVICE=1 timeout -k 10 300 python bench.py --gpus 2 --scaling strong --steps 5 --warmup 1 --no-cpu-baseline --skip-single > $out/bench_2rank_gloo_shared_gpu_strong.txt 2>&1 || true
+timeout -k 10 300 python bench.py --full > $out/bench.json 2> $out/bench.err
+for w in cfg3 cfg4 cfg5; do timeout -k 10 300 python bench.py --full --workload $w --steps 20 --no-cpu-baseline > $out/bench_$w.json 2> $out/bench_$w.err; done
+timeout -k 10 300 python bench.py --full --workload cfg5 --records fp16 --steps 20 --no-cpu-baseline > $out/bench_cfg5_fp16.json 2> $out/bench_cfg5_fp16.err
+GSAJ_SHARE_DEVICE=1 timeout -k 10 300 python bench.py --full --gpus 2 --steps 5 --warmup 1 --no-cpu-baseline --skip-single > $out/bench_2rank_gloo_shared_gpu_weak.txt 2>&1 || true
+GSAJ_SHARE_DEVICE=1 timeout -k 10 300 python bench.py --full --gpus 2 --scaling strong --steps 5 --warmup 1 --no-cpu-baseline --skip-single > $out/bench_2rank_gloo_shared_gpu_strong.txt 2>&1 || true
 bash tools/pmc_collect.sh $out/pmc > $out/pmc.log 2>&1
 timeout -k 10 200 python tools/device_tracker_bench.py > $out/device_tracker.json 2> $out/device_tracker.err
 timeout -k 10 200 python tools/mapping_iter_bench.py > $out/mapping_iter.json 2> $out/mapping_iter.err || true
