@@ -73,6 +73,11 @@ SIGNATURES = {
     "gsaj_isotropic_loss": (c_int, [c_int, c_int, c_float, P, P, c_int, P, P, P]),
     "gsaj_loss_seeds": (c_int, [c_int, c_int, c_int, c_float, c_float] + [P] * 8 + [P] * 4 + [P, P]),
     "gsaj_loss_seeds_batch": (c_int, [c_int] + [c_int, c_int, c_int, c_float, c_float] + [P] * 8 + [P] * 4 + [P, P]),
+    "gsaj_ssim_workspace_bytes": (c_size_t, [c_int] * 4),
+    "gsaj_ssim_forward": (c_int, [c_int] * 4 + [P] * 6),
+    "gsaj_ssim_backward": (c_int, [c_int] * 4 + [P] * 6),
+    "gsaj_refine_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsaj_refine_loss_seeds": (c_int, [c_int, c_int, c_float] + [P] * 6),
 }
 
 _lib = None

@@ -156,3 +156,28 @@ class IsotropicLoss:
                                                 1 if accumulate else 0, self.loss.data_ptr(), self.ws.data_ptr(),
                                                 torch.cuda.current_stream(self.dev).cuda_stream), "gsaj_isotropic_loss")
         return self.loss[0], g
+
+
+class RefinementLoss:
+    """The loss of colour refinement (reference utils/slam_backend.py:320-352) and its pixel-gradient seeds, two launches with no
+    host synchronisation (C ABI gsaj_refine_loss_seeds): loss = (1 - lambda_dssim) * l1_loss(image, gt) +
+    lambda_dssim * (1 - ssim(image, gt)) over [3,H,W] images.  Pre-allocated for one image size, like LossSeeds; calling it
+    returns {"loss", "l1", "ssim"} (device scalars) and "dL_dcolor" [3,H,W], what FrameContext.backward(dL_dcolor=...) takes."""
+
+    def __init__(self, W, H, device, lambda_dssim=0.2):
+        self.lib = _lib.load()
+        self.W, self.H, self.dev, self.lambda_dssim = int(W), int(H), torch.device(device), float(lambda_dssim)
+        if self.dev.type != "cuda":
+            raise _lib.GsajError("RefinementLoss needs a HIP device (there is no CPU path)")
+        self.ws = torch.zeros(self.lib.gsaj_refine_loss_workspace_bytes(self.W, self.H), dtype=torch.uint8, device=self.dev)
+        self.dL_dcolor = torch.empty((3, self.H, self.W), dtype=torch.float32, device=self.dev)
+        self.scalars = torch.zeros(3, dtype=torch.float32, device=self.dev)  # loss, L1, SSIM
+
+    def __call__(self, image, gt):
+        for name, t in (("image", image), ("gt", gt)):
+            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (3, self.H, self.W):
+                raise _lib.GsajError("%s must be a contiguous float32 device tensor of shape (3, %d, %d)" % (name, self.H, self.W))
+        _lib.check(self.lib.gsaj_refine_loss_seeds(self.W, self.H, self.lambda_dssim, image.data_ptr(), gt.data_ptr(),
+                                                   self.dL_dcolor.data_ptr(), self.scalars.data_ptr(), self.ws.data_ptr(),
+                                                   torch.cuda.current_stream(self.dev).cuda_stream), "gsaj_refine_loss_seeds")
+        return {"loss": self.scalars[0], "l1": self.scalars[1], "ssim": self.scalars[2], "dL_dcolor": self.dL_dcolor}

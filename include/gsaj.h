@@ -334,6 +334,27 @@ size_t gsaj_isotropic_workspace_bytes(int P);
 int gsaj_isotropic_loss(int P, int C, float weight, const float *scales, float *dL_dscales, int accumulate, float *out_loss,
                         void *iso_ws, void *stream);
 
+/* ---- SSIM and the L1 + D-SSIM loss of colour refinement -------------------------------------------------------------
+ * ssim (gaussian_splatting/utils/loss_utils.py:42-101): 11x11 Gaussian window (sigma 1.5), zero padding 5, C1 = 0.01^2,
+ * C2 = 0.03^2, over img / gt [N,C,H,W] fp32 (contiguous, planes independent; any N, C, W, H >= 1).  Deterministic: workgroup
+ * partials are summed in a fixed order by the last workgroup.  ssim_ws: gsaj_ssim_workspace_bytes(N, C, W, H) bytes, ZEROED
+ * ONCE by the caller when allocated (it holds the ticket, reset by the last workgroup). */
+size_t gsaj_ssim_workspace_bytes(int N, int C, int W, int H);
+/* ssim_out [N+1] (dev): per-image mean of the SSIM map (size_average=False), then the mean over all N*C*H*W (size_average=True).
+ * ssim_map [N,C,H,W] (dev) may be NULL.  Leaves the partial maps the backward needs in ssim_ws. */
+int gsaj_ssim_forward(int N, int C, int W, int H, const float *img, const float *gt, float *ssim_out, float *ssim_map,
+                      void *ssim_ws, void *stream);
+/* dL_dssim [N+1] (dev): upstream gradient of each entry of ssim_out -> dL_dimg [N,C,H,W] (dev), the gradient w.r.t. img only.
+ * Uses the partial maps the last gsaj_ssim_forward on the same inputs left in ssim_ws. */
+int gsaj_ssim_backward(int N, int C, int W, int H, const float *img, const float *gt, const float *dL_dssim, float *dL_dimg,
+                       void *ssim_ws, void *stream);
+/* Colour refinement, one view (utils/slam_backend.py:320-352): image, gt [3,H,W] -> dL_dcolor [3,H,W] (the input of
+ * gsaj_rasterize_backward) and out_scalars [3] (dev) = {loss, L1, SSIM}, loss = (1 - lambda) L1 + lambda (1 - SSIM).
+ * Two launches, no host synchronisation.  ws: gsaj_refine_loss_workspace_bytes(W, H) bytes, zeroed once. */
+size_t gsaj_refine_loss_workspace_bytes(int W, int H);
+int gsaj_refine_loss_seeds(int W, int H, float lambda_dssim, const float *image, const float *gt, float *dL_dcolor,
+                           float *out_scalars, void *ws, void *stream);
+
 /* ---- densification / pruning bookkeeping ----------------------------------------------------------
  * What the reference's mapping loop does per rendered view after the backward (utils/slam_backend.py:113-121, 276-285):
  *   vis = radii > 0;  max_radii2D[vis] = max(max_radii2D[vis], radii[vis]);
