@@ -285,14 +285,24 @@ int gsaj_oracle_bin(int P, int W, int H, int R, const int *radii, const float *m
   return 0;
 }
 
+/* Deliberately wrong variants of the compositor walks (TEST ANALYSIS, not part of the restated algorithm): what a kernel with
+ * that bug would return, for the comparator canaries of tests/test_cpu_comparator_canaries.py.  0 = the restated algorithm. */
+enum {
+  MUTANT_NONE = 0,
+  MUTANT_LATE_STOP = 1,        /* forward: the entry that takes T below 1e-4 is composited before the walk ends */
+  MUTANT_NO_ALPHA_CLAMP = 2,   /* forward and backward: alpha = o G, without min(0.99, .) */
+  MUTANT_TOUCHED_NO_CUTOFF = 3, /* forward: n_touched counts entries with alpha < 1/255 (T (1 - alpha) > 0.5) too */
+  MUTANT_DG_ZERO_CLAMPED = 4   /* backward: dL/dG = 0 where the clamp is active (the reference keeps o dL/dalpha) */
+};
+
 /* Stage 3: per-pixel front-to-back compositing (forward.cu:406-535).
  * out_color [3,H,W], out_depth [H,W], out_opacity [H,W], final_T [H,W], n_contrib [H,W],
  * n_touched [P] (must be zeroed by caller). Returns sum over pixels of n_contrib
  * (= the interaction count I of SURVEY 8d).  Tiles are independent (one thread per tile at a time). */
-long gsaj_oracle_render(int W, int H, const int *ranges, const uint32_t *point_list, const float *means2D,
+static long render_walk(int W, int H, const int *ranges, const uint32_t *point_list, const float *means2D,
                         const float *features, const float *conic_opacity, const float *depths, const float *bg,
                         float *out_color, float *out_depth, float *out_opacity, float *final_T,
-                        uint32_t *n_contrib, int *n_touched) {
+                        uint32_t *n_contrib, int *n_touched, int mutant) {
   const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
   long interactions = 0;
 #pragma omp parallel for num_threads(g_threads) schedule(dynamic, 4) reduction(+ : interactions)
@@ -311,10 +321,16 @@ long gsaj_oracle_render(int W, int H, const int *ranges, const uint32_t *point_l
           const float *co = conic_opacity + 4 * g;
           float power = -0.5f * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
           if (power > 0.0f) continue;
-          float alpha = fminf(0.99f, co[3] * expf(power));
-          if (alpha < 1.0f / 255.0f) continue;
+          float alpha = mutant == MUTANT_NO_ALPHA_CLAMP ? co[3] * expf(power) : fminf(0.99f, co[3] * expf(power));
+          if (alpha < 1.0f / 255.0f) {
+            if (mutant == MUTANT_TOUCHED_NO_CUTOFF && T * (1 - alpha) > 0.5f) {
+#pragma omp atomic
+              n_touched[g]++;
+            }
+            continue;
+          }
           float test_T = T * (1 - alpha);
-          if (test_T < 0.0001f) break;
+          if (test_T < 0.0001f && mutant != MUTANT_LATE_STOP) break;
           for (int ch = 0; ch < 3; ch++) C[ch] += features[3 * g + ch] * alpha * T;
           Dp += depths[g] * alpha * T;
           if (test_T > 0.5f) {
@@ -323,6 +339,7 @@ long gsaj_oracle_render(int W, int H, const int *ranges, const uint32_t *point_l
           }
           T = test_T;
           last = contributor;
+          if (test_T < 0.0001f) break; /* (MUTANT_LATE_STOP only: the restated walk has ended above) */
         }
         size_t pid = (size_t)py * W + px;
         final_T[pid] = T; n_contrib[pid] = last;
@@ -334,17 +351,33 @@ long gsaj_oracle_render(int W, int H, const int *ranges, const uint32_t *point_l
   return interactions;
 }
 
+long gsaj_oracle_render(int W, int H, const int *ranges, const uint32_t *point_list, const float *means2D,
+                        const float *features, const float *conic_opacity, const float *depths, const float *bg,
+                        float *out_color, float *out_depth, float *out_opacity, float *final_T,
+                        uint32_t *n_contrib, int *n_touched) {
+  return render_walk(W, H, ranges, point_list, means2D, features, conic_opacity, depths, bg, out_color, out_depth, out_opacity,
+                     final_T, n_contrib, n_touched, MUTANT_NONE);
+}
+
+long gsaj_oracle_render_mutant(int W, int H, const int *ranges, const uint32_t *point_list, const float *means2D,
+                               const float *features, const float *conic_opacity, const float *depths, const float *bg,
+                               float *out_color, float *out_depth, float *out_opacity, float *final_T,
+                               uint32_t *n_contrib, int *n_touched, int mutant) {
+  return render_walk(W, H, ranges, point_list, means2D, features, conic_opacity, depths, bg, out_color, out_depth, out_opacity,
+                     final_T, n_contrib, n_touched, mutant);
+}
+
 /* Stage 4: reverse compositor (backward.cu:648-872).  The reference adds every pixel's 10 partials to the Gaussian's
  * row with float atomics (no defined order).  Here every (tile, Gaussian) instance first gets its own double-precision
  * partial sums (pixels of the tile in row-major order), then a Gaussian's instances are added in sorted-instance order
  * and rounded once.
  * dL_dmean2D [P,3] (z unused), dL_dconic [P,4] (slots 0,1,3), dL_dopacity [P], dL_dcolor [P,3], dL_ddepth [P]. */
-void gsaj_oracle_render_backward(int P, int W, int H, const int *ranges, const uint32_t *point_list,
+static void render_backward_walk(int P, int W, int H, const int *ranges, const uint32_t *point_list,
                                  const float *means2D, const float *conic_opacity, const float *colors,
                                  const float *depths, const float *bg, const float *final_T,
                                  const uint32_t *n_contrib, const float *dL_dpix, const float *dL_dpix_depth,
                                  float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor,
-                                 float *dL_ddepth) {
+                                 float *dL_ddepth, int mutant) {
   const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
   int R = 0;
   for (int t = 0; t < gx * gy; t++) R = imax(R, ranges[2 * t + 1]);
@@ -377,7 +410,7 @@ void gsaj_oracle_render_backward(int P, int W, int H, const int *ranges, const u
           float power = -0.5f * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
           if (power > 0.0f) continue;
           float G = expf(power);
-          float alpha = fminf(0.99f, co[3] * G);
+          float alpha = mutant == MUTANT_NO_ALPHA_CLAMP ? co[3] * G : fminf(0.99f, co[3] * G);
           if (alpha < 1.0f / 255.0f) continue;
           T = T / (1.f - alpha);
           float dchannel_dcolor = alpha * T;
@@ -399,6 +432,7 @@ void gsaj_oracle_render_backward(int P, int W, int H, const int *ranges, const u
           last_alpha = alpha;
           dL_dalpha += (-T_final / (1.f - alpha)) * bg_dot;
           float dL_dG = co[3] * dL_dalpha;
+          if (mutant == MUTANT_DG_ZERO_CLAMPED && co[3] * G > 0.99f) dL_dG = 0.0f;
           float gdx = G * dx, gdy = G * dy;
           float dG_ddelx = -gdx * co[0] - gdy * co[1];
           float dG_ddely = -gdy * co[2] - gdx * co[1];
@@ -426,6 +460,26 @@ void gsaj_oracle_render_backward(int P, int W, int H, const int *ranges, const u
   }
   free(acc);
   free(inst);
+}
+
+void gsaj_oracle_render_backward(int P, int W, int H, const int *ranges, const uint32_t *point_list,
+                                 const float *means2D, const float *conic_opacity, const float *colors,
+                                 const float *depths, const float *bg, const float *final_T,
+                                 const uint32_t *n_contrib, const float *dL_dpix, const float *dL_dpix_depth,
+                                 float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor,
+                                 float *dL_ddepth) {
+  render_backward_walk(P, W, H, ranges, point_list, means2D, conic_opacity, colors, depths, bg, final_T, n_contrib, dL_dpix,
+                       dL_dpix_depth, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, MUTANT_NONE);
+}
+
+void gsaj_oracle_render_backward_mutant(int P, int W, int H, const int *ranges, const uint32_t *point_list,
+                                        const float *means2D, const float *conic_opacity, const float *colors,
+                                        const float *depths, const float *bg, const float *final_T,
+                                        const uint32_t *n_contrib, const float *dL_dpix, const float *dL_dpix_depth,
+                                        float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor,
+                                        float *dL_ddepth, int mutant) {
+  render_backward_walk(P, W, H, ranges, point_list, means2D, conic_opacity, colors, depths, bg, final_T, n_contrib, dL_dpix,
+                       dL_dpix_depth, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, mutant);
 }
 
 /* ------------------------------------------------------------------------------------------------------------

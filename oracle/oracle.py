@@ -37,6 +37,8 @@ def _load():
         _lib.gsaj_oracle_bin.restype = ctypes.c_int
         _lib.gsaj_oracle_render.restype = ctypes.c_long
         _lib.gsaj_oracle_render_backward.restype = None
+        _lib.gsaj_oracle_render_mutant.restype = ctypes.c_long
+        _lib.gsaj_oracle_render_backward_mutant.restype = None
         _lib.gsaj_oracle_preprocess_backward.restype = None
         _lib.gsaj_oracle_preprocess_backward_f64.restype = None
         _lib.gsaj_oracle_mark_visible.restype = None
@@ -145,12 +147,6 @@ def forward(means3D, opacities, viewmatrix, projmatrix, campos, tanfovx, tanfovy
         raise RuntimeError("oracle binning failed: %d" % rc)
     st["point_list"] = st["point_list"][:R]
     st["keys"] = st["keys"][:R]
-    color = np.zeros((3, H, W), _f)
-    depth = np.zeros((1, H, W), _f)
-    opacity = np.zeros((1, H, W), _f)
-    st["final_T"] = np.zeros((H, W), _f)
-    st["n_contrib"] = np.zeros((H, W), np.uint32)
-    n_touched = np.zeros(P, np.int32)
     feats = cols if cols is not None else st["rgb"]
     st["record_bits"] = record_bits
     if record_bits == 16:
@@ -158,22 +154,45 @@ def forward(means3D, opacities, viewmatrix, projmatrix, campos, tanfovx, tanfovy
         st["conic_opacity"] = round_to_half(st["conic_opacity"])
         feats = round_to_half(feats)
     st["features"] = feats
-    pl = st["point_list"] if R > 0 else np.zeros(1, np.uint32)
-    st["interactions"] = int(lib.gsaj_oracle_render(
-        ctypes.c_int(W), ctypes.c_int(H), _p(st["ranges"]), _p(pl), _p(st["means2D"]), _p(feats),
-        _p(st["conic_opacity"]), _p(st["depths"]), _p(bg), _p(color), _p(depth), _p(opacity), _p(st["final_T"]),
-        _p(st["n_contrib"]), _p(n_touched)))
+    img = render(st, bg)
+    st["final_T"], st["n_contrib"], st["interactions"] = img.pop("final_T"), img.pop("n_contrib"), img.pop("interactions")
     st["inputs"] = dict(means3D=means3D, shs=shs, colors_precomp=cols, scales=scales, rotations=rots,
                         cov3D_precomp=covp, viewmatrix=vm, projmatrix=pm, campos=cp, bg=bg,
                         tanfovx=tanfovx, tanfovy=tanfovy, scale_modifier=scale_modifier)
-    out = dict(color=color, depth=depth, opacity=opacity, radii=st["radii"].copy(), n_touched=n_touched,
-               num_rendered=R)
+    out = dict(img, radii=st["radii"].copy(), num_rendered=R)
     return out, st
 
 
-def backward(st, dL_dcolor_img, dL_ddepth_img, projmatrix_raw):
+def render(st, bg, mutant=0):
+    """The compositor (gsaj_oracle_render) on the binned state of `forward`: -> dict(color [3,H,W], depth [1,H,W],
+    opacity [1,H,W], n_touched [P], final_T [H,W], n_contrib [H,W], interactions).  Reads means2D, depths, conic_opacity,
+    features, ranges and point_list from `st` (a changed copy of the state renders what that change does).  mutant != 0: a
+    deliberately wrong walk (gsaj_oracle.c, MUTANT_*), for the comparator canaries only."""
+    lib = _load()
+    W, H, P = st["W"], st["H"], st["P"]
+    bg = _cf(bg).reshape(3)
+    color = np.zeros((3, H, W), _f)
+    depth = np.zeros((1, H, W), _f)
+    opacity = np.zeros((1, H, W), _f)
+    final_T = np.zeros((H, W), _f)
+    n_contrib = np.zeros((H, W), np.uint32)
+    n_touched = np.zeros(P, np.int32)
+    pl = st["point_list"] if st["num_rendered"] > 0 else np.zeros(1, np.uint32)
+    args = (ctypes.c_int(W), ctypes.c_int(H), _p(st["ranges"]), _p(pl), _p(st["means2D"]), _p(st["features"]),
+            _p(st["conic_opacity"]), _p(st["depths"]), _p(bg), _p(color), _p(depth), _p(opacity), _p(final_T), _p(n_contrib),
+            _p(n_touched))
+    if mutant:
+        interactions = lib.gsaj_oracle_render_mutant(*args, ctypes.c_int(int(mutant)))
+    else:
+        interactions = lib.gsaj_oracle_render(*args)
+    return dict(color=color, depth=depth, opacity=opacity, n_touched=n_touched, final_T=final_T, n_contrib=n_contrib,
+                interactions=int(interactions))
+
+
+def backward(st, dL_dcolor_img, dL_ddepth_img, projmatrix_raw, mutant=0):
     """Tiled backward from per-pixel seeds dL/dC [3,H,W] and dL/dD [1,H,W].
-    projmatrix_raw is P^T (gaussian_renderer/__init__.py:67)."""
+    projmatrix_raw is P^T (gaussian_renderer/__init__.py:67).  mutant != 0: a deliberately wrong reverse walk
+    (gsaj_oracle.c, MUTANT_*), for the comparator canaries only."""
     lib = _load()
     P, D, M, W, H = st["P"], st["D"], st["M"], st["W"], st["H"]
     inp = st["inputs"]
@@ -185,11 +204,14 @@ def backward(st, dL_dcolor_img, dL_ddepth_img, projmatrix_raw):
         dL_dcolor=np.zeros((P, 3), _f), dL_ddepth=np.zeros((P, 1), _f))
     feats = st["features"]
     pl = st["point_list"] if st["num_rendered"] > 0 else np.zeros(1, np.uint32)
-    lib.gsaj_oracle_render_backward(
-        ctypes.c_int(P), ctypes.c_int(W), ctypes.c_int(H), _p(st["ranges"]), _p(pl), _p(st["means2D"]),
-        _p(st["conic_opacity"]), _p(feats), _p(st["depths"]), _p(inp["bg"]), _p(st["final_T"]), _p(st["n_contrib"]),
-        _p(dLc), _p(dLd), _p(g["dL_dmean2D"]), _p(g["dL_dconic"]), _p(g["dL_dopacity"]), _p(g["dL_dcolor"]),
-        _p(g["dL_ddepth"]))
+    args = (ctypes.c_int(P), ctypes.c_int(W), ctypes.c_int(H), _p(st["ranges"]), _p(pl), _p(st["means2D"]),
+            _p(st["conic_opacity"]), _p(feats), _p(st["depths"]), _p(inp["bg"]), _p(st["final_T"]), _p(st["n_contrib"]),
+            _p(dLc), _p(dLd), _p(g["dL_dmean2D"]), _p(g["dL_dconic"]), _p(g["dL_dopacity"]), _p(g["dL_dcolor"]),
+            _p(g["dL_ddepth"]))
+    if mutant:
+        lib.gsaj_oracle_render_backward_mutant(*args, ctypes.c_int(int(mutant)))
+    else:
+        lib.gsaj_oracle_render_backward(*args)
     g.update(chain(st, g["dL_dmean2D"], g["dL_dconic"], g["dL_dcolor"], g["dL_ddepth"], projmatrix_raw))
     return g
 

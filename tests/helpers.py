@@ -25,7 +25,14 @@ SCENES = {
                               scene=dict(z_range=(1.0, 6.0), log_scale_range=(math.log(0.005), math.log(0.05)), sh_coeffs=4)),
     "p300_behind_64x48": dict(P=300, W=64, H=48, seed=5, deg=2, cam=lambda: small_camera(64, 48),
                               scene=dict(z_range=(-1.0, 2.0), log_scale_range=(math.log(0.02), math.log(0.2)), sh_coeffs=9, margin=0.6)),
+    # the comparator canaries' scene (tests/test_cpu_comparator_canaries.py): a ragged last tile column and row, opacities up to 1
+    # (o G > 0.99: the alpha clamp is active at the centres, and pixels saturate), SH degree 3 with wide coefficients (clamped
+    # colour channels) and a scale modifier other than 1
+    "canary_97x61": dict(P=400, W=97, H=61, seed=11, deg=3, mod=0.8, cam=lambda: small_camera(97, 61),
+                         scene=dict(z_range=(0.7, 3.0), log_scale_range=(math.log(0.02), math.log(0.25)), opacity_range=(0.3, 1.0),
+                                    sh_sigma=0.6, margin=0.1)),
 }
+PARITY_BG = (0.1, 0.2, 0.3)  # the background of the fixed parity scenes (test_gpu_tiled.test_forward_and_backward_parity)
 
 
 def make(name):
@@ -35,7 +42,11 @@ def make(name):
     return cam, sc, spec["deg"]
 
 
-def oracle_forward(cam, sc, deg, bg=(0.0, 0.0, 0.0), precomp=False, record_bits=32):
+def scale_modifier(name):
+    return SCENES[name].get("mod", 1.0)
+
+
+def oracle_forward(cam, sc, deg, bg=(0.0, 0.0, 0.0), precomp=False, record_bits=32, scale_modifier=1.0):
     kw = dict(sh_degree=deg)
     if precomp:
         rng = np.random.default_rng(99)
@@ -45,7 +56,7 @@ def oracle_forward(cam, sc, deg, bg=(0.0, 0.0, 0.0), precomp=False, record_bits=
         kw.update(shs=sc["shs"], scales=sc["scales"], rotations=sc["rotations"])
     return orc.forward(sc["means3D"], sc["opacities"], cam["viewmatrix"], cam["projmatrix"], cam["campos"],
                        cam["tanfovx"], cam["tanfovy"], cam["W"], cam["H"], np.asarray(bg, np.float32),
-                       record_bits=record_bits, **kw), kw
+                       record_bits=record_bits, scale_modifier=scale_modifier, **kw), kw
 
 
 def seeds(cam, seed=0):
@@ -55,8 +66,9 @@ def seeds(cam, seed=0):
             rng.normal(size=(1, H, W)).astype(np.float32) / (H * W))
 
 
-def gpu_forward(cam, sc, deg, bg=(0.0, 0.0, 0.0), kw=None, device="cuda:0", record_bits=32):
-    """Through the C ABI (gsaj.rasterizer = the `_C` module of the drop-in package)."""
+def gpu_forward(cam, sc, deg, bg=(0.0, 0.0, 0.0), kw=None, device="cuda:0", record_bits=32, scale_modifier=1.0):
+    """Through the C ABI (gsaj.rasterizer = the `_C` module of the drop-in package).  The returned args carry the scale
+    modifier, so gpu_backward uses the forward's."""
     import torch
     from gsaj import rasterizer as C
 
@@ -66,9 +78,9 @@ def gpu_forward(cam, sc, deg, bg=(0.0, 0.0, 0.0), kw=None, device="cuda:0", reco
     args = dict(bg=t(np.asarray(bg, np.float32)), means3D=t(sc["means3D"]), colors=g("colors_precomp"),
                 opacity=t(sc["opacities"]), scales=g("scales"), rotations=g("rotations"), cov3D=g("cov3D_precomp"),
                 view=t(cam["viewmatrix"]), proj=t(cam["projmatrix"]), proj_raw=t(cam["projmatrix_raw"]), sh=g("shs"),
-                campos=t(cam["campos"]))
+                campos=t(cam["campos"]), scale_modifier=float(scale_modifier))
     out = C.rasterize_gaussians(args["bg"], args["means3D"], args["colors"], args["opacity"], args["scales"],
-                                args["rotations"], 1.0, args["cov3D"], args["view"], args["proj"], args["proj_raw"],
+                                args["rotations"], args["scale_modifier"], args["cov3D"], args["view"], args["proj"], args["proj_raw"],
                                 cam["tanfovx"], cam["tanfovy"], cam["H"], cam["W"], args["sh"], deg, args["campos"],
                                 False, False, record_bits=record_bits)
     return out, args
@@ -81,7 +93,7 @@ def gpu_backward(cam, deg, fwd_out, args, dLc, dLd, device="cuda:0"):
     R, color, radii, geom, binning, img, depth, opacity, n_touched = fwd_out
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=device)  # noqa: E731
     return C.rasterize_gaussians_backward(args["bg"], args["means3D"], radii, args["colors"], args["scales"],
-                                          args["rotations"], 1.0, args["cov3D"], args["view"], args["proj"],
+                                          args["rotations"], args.get("scale_modifier", 1.0), args["cov3D"], args["view"], args["proj"],
                                           args["proj_raw"], cam["tanfovx"], cam["tanfovy"], t(dLc), t(dLd), args["sh"],
                                           deg, args["campos"], geom, R, binning, img, False)
 
@@ -91,6 +103,8 @@ def gpu_backward(cam, deg, fwd_out, args, dLc, dLd, device="cuda:0"):
 # v_exp_f32 / v_rcp_f32 where the oracle uses libm expf and a true division.  Measured worst cases over every test
 # scene are written to gpurun_out/parity_errors.jsonl (GSAJ_ERRLOG=1); the limits below are ~10-30x above them.
 IMG_TOL = 5e-5       # images, relative to the image's max, for pixels with no cut-off borderline contributor
+IMG_FLIP_FRACTION = 5e-5  # ... pixels beyond IMG_TOL: at most this fraction of the image (at least one), each borderline,
+IMG_FLIP_BOUND = 0.02     # ... and each within this (one contributor at the alpha threshold moves a pixel by < 1/255)
 GRAD_TOL = 5e-5      # every gradient tensor, max |err| relative to the tensor's max (Gaussians untouched by borderline pixels)
 GRAD_TOL_FLIPPED = 1e-2  # same, over all Gaussians incl. those where a cut-off decision may fall either way (sanity net: (A) bounds them exactly)
 # reverse-compositor sums, per Gaussian and component: |err| <= MASS_TOL * sum|term| + COND_K * cond_slack + FLIP_K * flip_budget
@@ -103,6 +117,15 @@ CHAIN_ROW_TOL = 1e-4  # per-Gaussian chain on the device's own sums, per row: re
 CHAIN_FLOOR = 1e-3
 CHAIN_COND_K = 16.0   # ... or within this many times what a +-1 ulp perturbation of the chain's fp32 inputs does to the fp64 chain (chain_sensitivity)
 CHAIN_K = 4.0
+# (C)'s clean check allows the Gaussians no borderline pixel touches what (A) allows their sums (MASS_TOL, COND_K) carried through
+# the chain, `cond`: the LARGEST such row bound over the clean Gaussians, relative to the tensor's max.  One ill-conditioned row sets
+# it for the whole tensor, so on ordinary scenes it is far above `tol`: the largest cond / tol over the GPU suite is 4.8e4
+# (test_random_scene_parity[P1000_200x150]: the check allows 2.4x the tensor's max), the fuzz seeds up to 8.4e3, the fixed parity
+# scenes 66 .. 2.1e3 (GSAJ_ERRLOG, key <tensor>/clean_cond_over_tol).  On those scenes the clean check is therefore no check: what
+# holds every Gaussian, clean or not, is the per-row check against its own propagated bound below it.  COND_CAP is set at twice the
+# measured maximum, 1e5 x GRAD_TOL = 5x the tensor's max: it only stops a scene beyond anything measured from passing unnoticed
+# (allow_cancellation=True lifts it; no caller needs that today -- a map painted in one colour reaches ~2e2).
+COND_CAP = 1e5
 ROW_FLOOR = 1e-2
 BORDER_REL = 1e-5    # a contributor is "borderline" if alpha is within this (relative) of 1/255 ...
 BORDER_REL_T = 1e-4  # ... or T(1-alpha) within this of 1e-4 (T carries the rounding of every nearer contributor)
@@ -201,7 +224,8 @@ def chain_sensitivity(st, sums, projmatrix_raw, trials=4, seed=0):
     return base, sens, noise32, o32
 
 
-def assert_grads_close(g, gref, tag, st=None, projmatrix_raw=None, tol=GRAD_TOL, skip=()):
+def assert_grads_close(g, gref, tag, st=None, projmatrix_raw=None, tol=GRAD_TOL, skip=(), layers=("A", "B", "C"),
+                       allow_cancellation=False):
     """Every output of rasterize_gaussians_backward (12-tuple, GRAD_NAMES order) against the oracle.  Three layers:
     (A) the reverse compositor's 10 per-Gaussian sums, element by element, against the oracle's fp64-accumulated sums, within
         what two correct fp32 evaluations may differ by (oracle.error_model, gref["error_model"]): MASS_TOL * sum|term| for the
@@ -220,11 +244,22 @@ def assert_grads_close(g, gref, tag, st=None, projmatrix_raw=None, tol=GRAD_TOL,
         borderline pixel touches; over ALL of them, row by row, within (A)'s bounds on the ten sums carried through the chain (it
         is linear in them: nine fp64 chain evaluations give |J| bound exactly) plus (B)'s allowance -- a flipped contributor
         moves a small Gaussian's gradient by one pixel's worth, and that is now priced per Gaussian instead of by a constant;
-        GRAD_TOL_FLIPPED stays as the net for callers without the oracle state and for dL/dtau summed over the Gaussians."""
+        GRAD_TOL_FLIPPED stays as the net for callers without the oracle state and for dL/dtau summed over the Gaussians.
+    `layers` selects the layers whose assertions run (every bound is computed as for all three); each failure message starts
+    with its layer, "(A)", "(B)" or "(C)".  The returned (and GSAJ_ERRLOG-logged) dict holds, among the per-tensor numbers,
+    every layer's worst err / allowed under "A", "B" and "C" (a value >= 1 is a rejection).  allow_cancellation: lift the
+    COND_CAP on the clean check's cond allowance, for scenes built to cancel."""
     from oracle import oracle as orc
 
     got = {nm: x for nm, x in zip(GRAD_NAMES, g) if x is not None and nm not in skip}
     worst = {}
+    margin = {"A": 0.0, "B": 0.0, "C": 0.0}  # per layer: worst err / allowed
+
+    def check(layer, ok, ratio, msg):
+        margin[layer] = max(margin[layer], float(ratio))
+        if layer in layers:
+            assert ok, ("(%s)" % layer,) + tuple(msg)
+
     chain_allow, chain_err32 = {}, {}  # per chain tensor, per row: what (B) allows / the oracle's own fp32 chain error
     chain_noise = {}  # per chain tensor: how far the oracle's own fp32 chain is from the fp64 chain (tensor-max relative)
     if st is not None and projmatrix_raw is not None and "dL_dmean2D" in got:  # (B)
@@ -246,13 +281,15 @@ def assert_grads_close(g, gref, tag, st=None, projmatrix_raw=None, tol=GRAD_TOL,
             worst[nm + "/chain_rows_needing_conditioning"] = int((err > CHAIN_ROW_TOL * scale).sum())
             chain_noise[nm] = rel_err(o32[nm], truth[nm])
             i = int(np.argmax(err / allowed))
-            assert err[i] <= allowed[i], (tag, nm, "per-Gaussian chain, row %d: error %.3e; allowed %.3e = max(%.0e x row scale %.3e, %g x "
-                                          "sensitivity to +-1 ulp inputs %.3e, %g x the fp32 oracle's worst error on this row over 5 samples %.3e)"
-                                          % (i, err[i], allowed[i], CHAIN_ROW_TOL, scale[i], CHAIN_COND_K, sens[nm][i], CHAIN_K, err32[i]))
+            check("B", err[i] <= allowed[i], err[i] / allowed[i],
+                  (tag, nm, "per-Gaussian chain, row %d: error %.3e; allowed %.3e = max(%.0e x row scale %.3e, %g x "
+                   "sensitivity to +-1 ulp inputs %.3e, %g x the fp32 oracle's worst error on this row over 5 samples %.3e)"
+                   % (i, err[i], allowed[i], CHAIN_ROW_TOL, scale[i], CHAIN_COND_K, sens[nm][i], CHAIN_K, err32[i])))
         if "dL_dtau_sum" in got and np.abs(truth["dL_dtau_sum"]).max() > 0:
             e_hip, e_o32 = rel_err(_np(got["dL_dtau_sum"]), truth["dL_dtau_sum"]), rel_err(o32["dL_dtau_sum"], truth["dL_dtau_sum"])
             worst["dL_dtau_sum/chain"], worst["dL_dtau_sum/chain_oracle32"] = e_hip, e_o32
-            assert e_hip < max(1e-5, CHAIN_K * e_o32), (tag, "dL_dtau_sum on the device's sums: device %.2e, fp32 oracle %.2e (vs fp64)" % (e_hip, e_o32))
+            check("B", e_hip < max(1e-5, CHAIN_K * e_o32), e_hip / max(1e-5, CHAIN_K * e_o32),
+                  (tag, "dL_dtau_sum on the device's sums: device %.2e, fp32 oracle %.2e (vs fp64)" % (e_hip, e_o32)))
     em = gref.get("error_model")
     # Gaussians no borderline pixel touches: their sums involve no cut-off decision that could fall either way
     clean = (em["flip_budget"].max(axis=1) == 0) if em is not None else None
@@ -286,30 +323,36 @@ def assert_grads_close(g, gref, tag, st=None, projmatrix_raw=None, tol=GRAD_TOL,
             continue
         x = _np(x).reshape(want.shape)
         if np.abs(want).max() == 0:
-            assert np.abs(x).max() == 0, (tag, nm)
+            check("C", np.abs(x).max() == 0, np.inf if np.abs(x).max() else 0.0, (tag, nm, "non-zero where the oracle's is zero"))
             continue
         worst[nm] = e = rel_err(x, want)
-        assert e < (tol if clean is None or nm == "dL_dtau_sum" and clean.all() else GRAD_TOL_FLIPPED), (tag, nm, e)
+        lim = tol if clean is None or nm == "dL_dtau_sum" and clean.all() else GRAD_TOL_FLIPPED
+        check("C", e < lim, e / lim, (tag, nm, e))
         if clean is not None and nm != "dL_dtau_sum" and clean.any():
             worst[nm + "/clean"] = e = float(np.abs(x[clean].astype(np.float64) - want[clean]).max() / (np.abs(want).max() + 1e-30))
             # (no flips, but the sums' conditioning still reaches these rows: what (A) allows them -- MASS_TOL, COND_K -- carried
             # through the chain; next to `tol` only where dL/dalpha cancels, e.g. a map painted in one colour, tools/fuzz_uniform.py)
             cond = float(np.max(derived[nm][clean]) / (np.abs(want).max() + 1e-30)) if derived is not None and nm in chain_allow else 0.0
-            assert e < max(tol, CHAIN_K * chain_noise.get(nm, 0.0)) + cond, (tag, nm, "Gaussians untouched by borderline pixels", e, chain_noise.get(nm), cond)
+            worst[nm + "/clean_cond_over_tol"] = cond / tol
+            if not allow_cancellation:
+                cond = min(cond, COND_CAP * tol)
+            lim = max(tol, CHAIN_K * chain_noise.get(nm, 0.0)) + cond
+            check("C", e < lim, e / lim, (tag, nm, "Gaussians untouched by borderline pixels", e, chain_noise.get(nm), cond))
         if derived is not None and nm in chain_allow:  # every Gaussian, flipped or not, against ITS propagated bound
             P = want.shape[0]
             err = np.abs(x.astype(np.float64) - want).reshape(P, -1).max(axis=1)
             allowed = derived[nm] + chain_allow[nm] + chain_err32[nm] + tol * np.abs(want).max()
             worst[nm + "/err_over_propagated_bound"] = float((err / allowed).max())
             i = int(np.argmax(err / allowed))
-            assert err[i] <= allowed[i], (tag, nm, "Gaussian %d: end-to-end error %.3e above the compositor bounds carried through the chain %.3e "
-                                          "+ chain allowance %.3e + oracle fp32 chain error %.3e" % (i, err[i], derived[nm][i], chain_allow[nm][i], chain_err32[nm][i]))
+            check("C", err[i] <= allowed[i], err[i] / allowed[i],
+                  (tag, nm, "Gaussian %d: end-to-end error %.3e above the compositor bounds carried through the chain %.3e "
+                   "+ chain allowance %.3e + oracle fp32 chain error %.3e" % (i, err[i], derived[nm][i], chain_allow[nm][i], chain_err32[nm][i])))
     if derived is not None and "dL_dtau_sum" in got and "dL_dtau" in chain_allow:
         want = np.asarray(gref["dL_dtau_sum"], np.float64)
         err = np.abs(_np(got["dL_dtau_sum"]).astype(np.float64).reshape(-1) - want.reshape(-1)).max()
         allowed = float((derived["dL_dtau"] + chain_allow["dL_dtau"] + chain_err32["dL_dtau"]).sum()) + tol * np.abs(want).max()
         worst["dL_dtau_sum/err_over_propagated_bound"] = float(err / allowed)
-        assert err <= allowed, (tag, "dL_dtau_sum", err, allowed)
+        check("C", err <= allowed, err / allowed, (tag, "dL_dtau_sum", err, allowed))
     em = gref.get("error_model")
     if em is not None and all(k in got for k in ("dL_dmean2D", "dL_dconic", "dL_dopacity", "dL_dcolor", "dL_ddepth")):  # (A)
         P = gref["dL_dopacity"].shape[0]
@@ -322,9 +365,11 @@ def assert_grads_close(g, gref, tag, st=None, projmatrix_raw=None, tol=GRAD_TOL,
         worst["compositor/err_over_mass_p999"] = float(np.quantile(err / (mass + 1e-30), 0.999))
         worst["compositor/needed_flip_budget"] = int((err > MASS_TOL * mass + COND_K * cond + 1e-9 * np.abs(want).max(axis=0, keepdims=True) + 1e-37).any(axis=1).sum())
         i, c = np.unravel_index(np.argmax(ratio), ratio.shape)
-        assert ratio.max() < 1.0, (tag, "compositor sum %d of Gaussian %d: got %.6e want %.6e; sum|terms| %.3e cond %.3e flip %.3e"
-                                   % (c, i, have[i, c], want[i, c], mass[i, c], cond[i, c], flip[i, c]))
-        assert np.abs(have[mass == 0]).max(initial=0.0) == 0.0, (tag, "non-zero sum where no pixel contributes")
+        check("A", ratio.max() < 1.0, ratio.max(), (tag, "compositor sum %d of Gaussian %d: got %.6e want %.6e; sum|terms| %.3e cond %.3e flip %.3e"
+                                                    % (c, i, have[i, c], want[i, c], mass[i, c], cond[i, c], flip[i, c])))
+        stray = np.abs(have[mass == 0]).max(initial=0.0)
+        check("A", stray == 0.0, np.inf if stray else 0.0, (tag, "non-zero sum where no pixel contributes"))
+    worst.update(margin)
     _errlog(tag, **worst)
     return worst
 
@@ -386,7 +431,7 @@ def borderline_pixel(st, px, py, rel=BORDER_REL, rel_T=BORDER_REL_T):
     return False
 
 
-def assert_image_close(got, want, tol, flip_fraction=5e-5, flip_bound=0.02, st=None, tag=None, border_mask=None):
+def assert_image_close(got, want, tol, flip_fraction=IMG_FLIP_FRACTION, flip_bound=IMG_FLIP_BOUND, st=None, tag=None, border_mask=None):
     """Images agree to `tol` (relative to the array's max).  Pixels beyond `tol` are tolerated only if (a) the oracle's own
     walk of that pixel meets a cut-off borderline contributor (`st` = oracle state: checked pixel by pixel), (b) there are at
     most `flip_fraction` of them, and (c) they stay within `flip_bound` (one contributor at the alpha threshold moves a pixel

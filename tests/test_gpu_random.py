@@ -46,15 +46,26 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", CASES, ids=[f"P{c[0]}_{c[1]}x{c[2]}" for c in CASES])
+CASE_IDS = [f"P{c[0]}_{c[1]}x{c[2]}" for c in CASES]
+RANDOM_BG = (0.3, 0.1, 0.7)
+
+
+def random_case_scene(case):
+    """-> cam, scene, SH degree of one CASES entry (also tests/test_cpu_comparator_canaries.py's map onto this test)."""
+    P, W, H, seed, deg, coeffs, zr, ls, orng, ortho = case
+    cam = hp.small_camera(W, H, f=0.8 * W, orthonormal=ortho)
+    sc = syn.make_scene(P, seed, cam, z_range=zr, log_scale_range=ls, opacity_range=orng, sh_coeffs=coeffs, margin=0.2)
+    return cam, sc, deg
+
+
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
 def test_random_scene_parity(case):
     from gsaj import rasterizer as C
     from oracle import oracle as orc
 
-    P, W, H, seed, deg, coeffs, zr, ls, orng, ortho = case
-    cam = hp.small_camera(W, H, f=0.8 * W, orthonormal=ortho)
-    sc = syn.make_scene(P, seed, cam, z_range=zr, log_scale_range=ls, opacity_range=orng, sh_coeffs=coeffs, margin=0.2)
-    bg = (0.3, 0.1, 0.7)
+    P, W, H, seed = case[:4]
+    cam, sc, deg = random_case_scene(case)
+    bg = RANDOM_BG
     (ref, st), kw = hp.oracle_forward(cam, sc, deg, bg=bg)
     out, args = hp.gpu_forward(cam, sc, deg, bg=bg, kw=kw)
     R, color, radii, geom, binning, img, depth, opacity, n_touched = out

@@ -30,9 +30,9 @@ def test_forward_and_backward_parity(torch_cuda, name, precomp):
     from gsaj import rasterizer as C
 
     cam, sc, deg = hp.make(name)
-    bg = (0.1, 0.2, 0.3)
-    (ref, st), kw = hp.oracle_forward(cam, sc, deg, bg=bg, precomp=precomp)
-    out, args = hp.gpu_forward(cam, sc, deg, bg=bg, kw=kw)
+    bg, mod = hp.PARITY_BG, hp.scale_modifier(name)
+    (ref, st), kw = hp.oracle_forward(cam, sc, deg, bg=bg, precomp=precomp, scale_modifier=mod)
+    out, args = hp.gpu_forward(cam, sc, deg, bg=bg, kw=kw, scale_modifier=mod)
     R, color, radii, geom, binning, img, depth, opacity, n_touched = out
     P, W, H = sc["means3D"].shape[0], cam["W"], cam["H"]
     assert R == ref["num_rendered"]
