@@ -468,9 +468,12 @@ int gsaj_rasterize_backward_batch(int K, int P, int D, int M, int capacity, cons
   if (rc != GSAJ_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+  // the whole window in one call: the chain kernel sums the reverse compositor's instance rows itself (no gather launch, no gsum
+  // round trip); the two halves called separately go through gsum as before
+  const int fused = (flags & (GSAJ_BWD_ONLY_COMPOSITE | GSAJ_BWD_ONLY_CHAIN)) ? 0 : 1;
   if (!(flags & GSAJ_BWD_ONLY_CHAIN)) {
     if ((rc = launch_render_backward(capacity, W, H, gx, gy, bg, g, b, im, dL_dpix, dL_dpix_depth, K, vs, s)) != GSAJ_OK) return rc;
-    if ((rc = launch_gather_sums(P, K, radii, g, b, im, vs, s)) != GSAJ_OK) return rc;
+    if (!fused && (rc = launch_gather_sums(P, K, radii, g, b, im, vs, s)) != GSAJ_OK) return rc;
   }
   if (flags & GSAJ_BWD_ONLY_COMPOSITE) return GSAJ_OK;
   BwdParams p;
@@ -487,7 +490,7 @@ int gsaj_rasterize_backward_batch(int K, int P, int D, int M, int capacity, cons
   p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
   p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
   (void)colors_precomp;
-  return launch_gaussian_backward_batch(p, K, g, b, im, vs, (flags & GSAJ_BWD_ACCUMULATE) ? 1 : 0, s);
+  return launch_gaussian_backward_batch(p, K, g, b, im, vs, (flags & GSAJ_BWD_ACCUMULATE) ? 1 : 0, fused, s);
 }
 
 static int backward_impl(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
@@ -632,6 +635,7 @@ int gsaj_debug_export(int P, int R, int W, int H, const void *geom_ws, const voi
   return GSAJ_OK;
 }
 
+// (valid only while gsum holds the view's sums: after a GSAJ_BWD_ONLY_COMPOSITE call; a whole-window backward does not write gsum)
 int gsaj_debug_export_view_sums(int P, const void *geom_ws, float *sums, void *stream) {
   if (P <= 0 || !geom_ws || !sums) {
     gsaj_set_error("gsaj_debug_export_view_sums: invalid argument");
@@ -639,6 +643,20 @@ int gsaj_debug_export_view_sums(int P, const void *geom_ws, float *sums, void *s
   }
   GeomWS g;
   geom_carve(align_base(const_cast<void *>(geom_ws)), (size_t)P, &g);
+  GSAJ_HIP_CHECK(hipMemcpyAsync(sums, g.gsum, sizeof(float4) * 3 * (size_t)P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return GSAJ_OK;
+}
+
+int gsaj_debug_export_view_sums_gather(int P, int capacity, int W, int H, void *geom_ws, void *binning_ws, void *image_ws, float *sums,
+                                       void *stream) {
+  if (P <= 0 || capacity <= 0 || W <= 0 || H <= 0 || !geom_ws || !binning_ws || !image_ws || !sums) {
+    gsaj_set_error("gsaj_debug_export_view_sums_gather: invalid argument");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  GeomWS g; BinWS b; ImageWS im; ViewStrides vs;
+  int rc = batch_workspaces(1, P, capacity, W, H, geom_ws, binning_ws, gsaj_binning_workspace_bytes(capacity), image_ws, &g, &b, &im, &vs);
+  if (rc != GSAJ_OK) return rc;
+  if ((rc = launch_gather_sums(P, 1, nullptr, g, b, im, vs, (hipStream_t)stream)) != GSAJ_OK) return rc;
   GSAJ_HIP_CHECK(hipMemcpyAsync(sums, g.gsum, sizeof(float4) * 3 * (size_t)P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return GSAJ_OK;
 }

@@ -547,11 +547,15 @@ int launch_gaussian_backward(const BwdParams &p, const GeomWS &g, const BinWS &b
 // ---- batched: K views of one map, per-Gaussian parameter gradients summed over the views IN-KERNEL --------------------
 // A mapping window renders every keyframe against the same Gaussians and back-propagates once, so the per-Gaussian
 // gradients accumulate over keyframes while every keyframe keeps its own dL/dtau (reference utils/slam_backend.py:168-232).
-// Three launches:
+// A whole window (gsaj_rasterize_backward_batch without GSAJ_BWD_ONLY_*): one launch per 8 views and one for dL/dtau,
+//  k_chain_window<SHW, true> + k_tau_sum: the chain kernel sums a Gaussian's per-instance partial-gradient rows ITSELF (the row
+//    walk of k_gather_sums, one wave per two views of 32 Gaussians, on k_gather_sums' own grid of 64-row groups: the same
+//    additions in the same order, the same bits) and runs the chain on the totals; gsum is neither written nor read.
+// The two halves of a window called separately (GSAJ_BWD_ONLY_COMPOSITE, then GSAJ_BWD_ONLY_CHAIN: two streams, tile bands):
 //  k_gather_sums (grid x K, HBM-streaming, many waves in flight): a Gaussian's per-instance partial-gradient rows -- one
 //    contiguous run by emission slot, a wave's 64 Gaussians one contiguous block -- are streamed with coalesced loads and
 //    added in emission order; 48 bytes per Gaussian and view out (gsum).
-//  k_chain_window + k_tau_sum: below.
+//  k_chain_window<SHW, false> + k_tau_sum: below; reads gsum.
 // one step of the keyed wave scan: lanes that receive a value through the DPP pattern CTRL (row mask ROWS) add it iff it comes from
 // the same owner; lanes the pattern does not reach see the key -1 and add nothing
 // Each value and step is ONE v_fmac_f32 with a DPP operand: v += dpp(v) * same, same = 1.0 where the incoming value is the lane's own
@@ -707,8 +711,98 @@ __global__ __launch_bounds__(256) void k_gather_sums(int P, const int *__restric
 #define CW_V 8    // views per pass
 GSAJ_TRACE_DEFINE(gbb)
 
-template <int SHW>
+// k_chain_window<., GATHER = true>: the ten sums of a (view, Gaussian) lane formed in the kernel.  The 32 lanes of half-wave `half` are
+// the 32 Gaussians of one view; their instance rows are one contiguous block [F, E), which the WHOLE wave walks with lane = row exactly
+// as k_gather_sums walks the block of its 64 Gaussians.  A run's total depends on where the 64-row group boundaries fall, so the walk
+// keeps k_gather_sums' grid: groups start at G + 64 k, G = first row of the enclosing block of 64 Gaussians.  A half-block that does
+// not start that block begins with the group of the grid that holds its first row; rows of the other half-block inside its first
+// and last group are foreign: never fetched, value 0, owner key -2 (a segment's scan result depends on its own lanes only, and
+// what the keyed fmac adds from another owner is x * 0 = +-0, which no non-zero value and no final sum -- sums start at +0 and
+// +0 + -0 = +0 -- can tell apart).  Every sum is bit-identical to what k_gather_sums leaves in gsum.
+// A wave runs its two views' walks as two streams side by side (start, then step by turns), so that two groups of rows are on
+// their way at any time.  endi: owners' end slots, non-decreasing inside each half-wave; first, cnt: the lane's own run; F32, E32,
+// G32: per half-wave (uniform inside a half) the half-block's rows and the grid's origin.
+struct ChainRowStream {
+  const float4 *__restrict__ inst_grad;
+  const uint8_t *__restrict__ reached;
+  uint32_t F, E, base;  // the half-block's rows [F, E); first row of the current group (uniform)
+  int src;              // first lane of the half-wave that owns these rows
+  bool active;          // uniform
+  float4 a0, a1, a2;
+  uint8_t fl, fl_a, fl_b;  // flags of the group in (a0, a1, a2), of the next group, of the one after
+
+  __device__ __forceinline__ uint8_t flags_of(uint32_t b, int lane) const {
+    const uint32_t r = b + (uint32_t)lane;
+    return r >= F && r < E ? reached[r] : (uint8_t)0;
+  }
+  __device__ __forceinline__ void rows_of(uint32_t b, int lane) {
+    const float4 *rp = inst_grad + (size_t)(b + lane) * REC_F4;
+    a0 = rp[0]; a1 = rp[1]; a2 = rp[2];
+  }
+  // requests the first group's flags and rows (the rows without waiting for their flags) and the flags of the next two groups
+  __device__ __forceinline__ void start(bool on, int half, int lane, uint32_t F32, uint32_t E32, uint32_t G32, const float4 *ig,
+                                        const uint8_t *rc) {
+    inst_grad = ig; reached = rc;
+    src = half * CW_G;
+    F = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)F32, src));
+    E = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)E32, src));
+    const uint32_t G = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)G32, src));
+    active = on && F != 0xffffffffu && F < E;
+    fl = fl_a = fl_b = 0;
+    base = 0;
+    if (active) {
+      base = G + ((F - G) & ~63u);
+      fl = flags_of(base, lane);
+      if (base + (uint32_t)lane >= F && base + (uint32_t)lane < E) rows_of(base, lane);
+      fl_a = flags_of(base + 64, lane);
+      fl_b = flags_of(base + 128, lane);
+    }
+  }
+  // one group of 64 rows: requests the next group's rows, reduces the current one, owners take their runs' totals
+  __device__ __forceinline__ void step(int lane, uint32_t endi, uint32_t first, uint32_t cnt, float (&sum)[10]) {
+    const uint32_t r = base + (uint32_t)lane;
+    const bool ok = fl != 0;
+    float v[10] = {ok ? a0.x : 0.f, ok ? a0.y : 0.f, ok ? a0.z : 0.f, ok ? a0.w : 0.f, ok ? a1.x : 0.f,
+                   ok ? a1.y : 0.f, ok ? a1.z : 0.f, ok ? a1.w : 0.f, ok ? a2.x : 0.f, ok ? a2.y : 0.f};
+    if (base + 64 < E) {
+      fl = fl_a;
+      if (fl) rows_of(base + 64, lane);
+      fl_a = fl_b;
+      fl_b = flags_of(base + 192, lane);
+    }
+    if (__builtin_amdgcn_ballot_w64(ok) != 0ull) {  // (a group none of whose rows was reached adds nothing)
+      // owner of row r among the half-wave's 32: number of owners whose end slot is <= r; foreign rows get a key no owner has
+      int own = 0;
+#pragma unroll
+      for (int st = CW_G / 2; st > 0; st >>= 1) {
+        const uint32_t e = (uint32_t)__shfl((int)endi, src + own + st - 1);
+        if (e <= r) own += st;
+      }
+      if (r < F || r >= E) own = -2;
+      scan_by_key_step<0x111, 0xF>(own, v);  // row_shr:1
+      scan_by_key_step<0x112, 0xF>(own, v);  // row_shr:2
+      scan_by_key_step<0x114, 0xF>(own, v);  // row_shr:4
+      scan_by_key_step<0x118, 0xF>(own, v);  // row_shr:8
+      scan_by_key_step<0x142, 0xA>(own, v);  // row_bcast:15 -> rows 1, 3
+      scan_by_key_step<0x143, 0xC>(own, v);  // row_bcast:31 -> rows 2, 3
+      // every owner of this view whose run meets this group takes the total at its run's last row inside the group
+      const uint32_t run_lo = max(first, base), run_hi = min(first + cnt, min(base + 64u, E));
+      const bool mine = (lane & CW_G) == src && cnt > 0 && run_lo < run_hi;
+      const int q = mine ? (int)(run_hi - 1u - base) : 0;
+#pragma unroll
+      for (int c = 0; c < 10; c++) {
+        const float t = __shfl(v[c], q);
+        sum[c] += mine ? t : 0.f;
+      }
+    }
+    base += 64;
+    active = base < E;
+  }
+};
+
+template <int SHW, bool GATHER>
 __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, int v0, int K, GeomWS g0, ImageWS im0, ViewStrides vs,
+                                                              const float4 *__restrict__ inst_grad0, const uint8_t *__restrict__ reached0,
                                                               float *__restrict__ pv_mean2D, float *__restrict__ pv_conic,
                                                               float *__restrict__ pv_color, float *__restrict__ pv_depth,
                                                               float *__restrict__ pv_tau, int accumulate) {
@@ -716,7 +810,7 @@ __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, in
   constexpr int NV = 13 + MC;           // values a (view, Gaussian) lane leaves for the sums
   constexpr int NE = 10 + SHW;          // summed outputs per Gaussian
   constexpr int EPT = (NE * CW_G + CW_G * CW_V - 1) / (CW_G * CW_V);  // elements per thread
-  __shared__ float rowv[CW_V * NV * CW_G];  // [view lane][value][Gaussian]
+  __shared__ __attribute__((aligned(16))) float rowv[CW_V * NV * CW_G];  // [view lane][value][Gaussian]
   __shared__ float outv[NE * CW_G];         // [element][Gaussian]: the sums, for the transposed store
   GSAJ_TRACE_BEGIN(gbb)
   const int tid = threadIdx.x, gl = tid & (CW_G - 1), vl = tid / CW_G;
@@ -725,8 +819,10 @@ __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, in
   // inputs that do not depend on the view: once
   const float3 mean = make_float3(p.means3D[3 * ii], p.means3D[3 * ii + 1], p.means3D[3 * ii + 2]);
   float c6[6];
+  if constexpr (!GATHER) {
 #pragma unroll
-  for (int k = 0; k < 6; k++) c6[k] = p.cov3Ds[6 * ii + k];  // (view 0's copy: Sigma = R S^2 R^T does not depend on the view)
+    for (int k = 0; k < 6; k++) c6[k] = p.cov3Ds[6 * ii + k];  // (view 0's copy: Sigma = R S^2 R^T does not depend on the view)
+  }
   const float *vm0 = p.viewmatrix, *pj0 = p.projmatrix;
   float acc[EPT];
 #pragma unroll
@@ -745,17 +841,84 @@ __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, in
 #pragma unroll
     for (int k = 0; k < MC; k++) w[k] = 0.f;
     float3 gmask = make_float3(0.f, 0.f, 0.f);
+    bool sh_left = false;
+    // GATHER: this lane's ten sums, formed here (the wave walks the instance rows of its two views' 32 Gaussians)
+    uint32_t aborted_w = 0u;
+    int rad_w = 0;
+    uint8_t cl_w[3] = {0, 0, 0};
+    if constexpr (GATHER) {
+      float sum[10];
+      const int lane = tid & 63, hl = lane & (CW_G - 1);
+      const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // this wave's views: v0 + 2 wv (lanes 0-31), v0 + 2 wv + 1 (lanes 32-63)
+      const size_t vc = (size_t)(v < K ? v : v0);  // (a lane past the window's last view reads view v0's and uses nothing of it)
+      const GeomWS gw = geom_view(g0, vc * vs.geom);
+      aborted_w = gsaj_shift(im0.counters, vc * vs.image)[4];
+      rad_w = p.radii[vc * p.P + ii];
+      if (SHW > 0) { cl_w[0] = gw.clamped[3 * ii]; cl_w[1] = gw.clamped[3 * ii + 1]; cl_w[2] = gw.clamped[3 * ii + 2]; }
+      const bool live = v < K && idx < p.P && aborted_w == 0u;  // (an aborted frame has no rows)
+      const uint32_t cnt = live ? gw.tiles_touched[ii] : 0u;
+      const uint32_t bs = live ? gw.block_sums[ii / PRE_BLOCK] : 0u;
+      const uint32_t endi_raw = live ? bs + gw.point_offsets[ii] : 0u;
+      // the grid's origin: first row of the enclosing block of 64 Gaussians = end slot of the Gaussian before it (same PRE_BLOCK)
+      const int i64 = ((int)blockIdx.x & ~1) * CW_G;
+      const uint32_t G32 = live ? bs + ((i64 % PRE_BLOCK) ? gw.point_offsets[i64 - 1] : 0u) : 0u;
+      uint32_t endi = endi_raw;  // non-decreasing over the half-wave (out-of-range owners repeat their predecessor's end)
+#pragma unroll
+      for (int o2 = 1; o2 < CW_G; o2 <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)endi, o2, CW_G);
+        if (hl >= o2) endi = max(endi, up);
+      }
+      const uint32_t first = live ? endi_raw - cnt : endi;
+      uint32_t F32 = (cnt > 0) ? first : 0xffffffffu;
+#pragma unroll
+      for (int o2 = CW_G / 2; o2 > 0; o2 >>= 1) F32 = min(F32, (uint32_t)__shfl_xor((int)F32, o2));
+      const uint32_t E32 = (uint32_t)__shfl((int)endi, CW_G - 1, CW_G);
+      const uint32_t G0 = (uint32_t)__shfl((int)G32, 0, CW_G);  // (lane 0 of a half is in range whenever the workgroup exists)
+#pragma unroll
+      for (int c = 0; c < 10; c++) sum[c] = 0.f;
+      // the wave's two views side by side: two independent row streams in flight (one after the other, a wave had one group of rows
+      // on its way at a time and the walk was bound by that round trip)
+      const int vA = v0 + 2 * wv;
+      ChainRowStream sa, sb;
+      sa.start(vA < K, 0, lane, F32, E32, G0, gsaj_shift(inst_grad0, (size_t)min(vA, K - 1) * vs.bin),
+               gsaj_shift(reached0, (size_t)min(vA, K - 1) * vs.bin));
+      sb.start(vA + 1 < K, 1, lane, F32, E32, G0, gsaj_shift(inst_grad0, (size_t)min(vA + 1, K - 1) * vs.bin),
+               gsaj_shift(reached0, (size_t)min(vA + 1, K - 1) * vs.bin));
+      while (sa.active || sb.active) {
+        if (sa.active) sa.step(lane, endi, first, cnt, sum);
+        if (sb.active) sb.step(lane, endi, first, cnt, sum);
+      }
+      // handed to the chain through LDS, in slots 0-9 of this view lane's part of rowv (320 floats: [32] float4 | [32] float4 | [32]
+      // float2; the chain writes those slots last, after every read; a lane reads what it wrote itself: no barrier).  The chain below
+      // then starts from 16-byte loads as it does on gsum and compiles to the same arithmetic -- contracting a * b + c into an fma
+      // is the compiler's choice and follows the form of the inputs: fed from scalar registers, dL/dtau came out 1 ulp different.
+      float *stage = rowv + vl * NV * CW_G;
+      reinterpret_cast<float4 *>(stage)[gl] = make_float4(sum[0], sum[1], sum[2], sum[3]);
+      reinterpret_cast<float4 *>(stage + 4 * CW_G)[gl] = make_float4(sum[4], sum[5], sum[6], sum[7]);
+      reinterpret_cast<float2 *>(stage + 8 * CW_G)[gl] = make_float2(sum[8], sum[9]);
+      asm volatile("" ::: "memory");  // (no store-to-load forwarding)
+    }
     if (v < K) {
       const GeomWS g = geom_view(g0, (size_t)v * vs.geom);
       const size_t iv = ii;
       const float3 mean_v = mean;
       const float (&c6v)[6] = c6;
       // every input of this (view, Gaussian) requested up front and unconditionally
-      const uint32_t aborted = gsaj_shift(im0.counters, (size_t)v * vs.image)[4];  // aborted async frame: contributes nothing
-      const int rad = p.radii[(size_t)v * p.P + ii];
-      const float4 s0 = g.gsum[3 * ii + 0], s1 = g.gsum[3 * ii + 1], s2 = g.gsum[3 * ii + 2];
+      const uint32_t aborted = GATHER ? aborted_w : gsaj_shift(im0.counters, (size_t)v * vs.image)[4];  // aborted async frame: contributes nothing
+      const int rad = GATHER ? rad_w : p.radii[(size_t)v * p.P + ii];
+      float4 s0, s1, s2;
+      if constexpr (GATHER) {
+        const float *stage = rowv + vl * NV * CW_G;
+        s0 = reinterpret_cast<const float4 *>(stage)[gl];
+        s1 = reinterpret_cast<const float4 *>(stage + 4 * CW_G)[gl];
+        const float2 s2h = reinterpret_cast<const float2 *>(stage + 8 * CW_G)[gl];
+        s2 = make_float4(s2h.x, s2h.y, 0.f, 0.f);
+      } else {
+        s0 = g.gsum[3 * ii + 0]; s1 = g.gsum[3 * ii + 1]; s2 = g.gsum[3 * ii + 2];
+      }
       uint8_t cl[3] = {0, 0, 0};
-      if (SHW > 0) { cl[0] = g.clamped[3 * ii]; cl[1] = g.clamped[3 * ii + 1]; cl[2] = g.clamped[3 * ii + 2]; }
+      if (SHW > 0 && GATHER) { cl[0] = cl_w[0]; cl[1] = cl_w[1]; cl[2] = cl_w[2]; }
+      else if (SHW > 0) { cl[0] = g.clamped[3 * ii]; cl[1] = g.clamped[3 * ii + 1]; cl[2] = g.clamped[3 * ii + 2]; }
       p.viewmatrix = vm0 + 16 * v;
       p.projmatrix = pj0 + 16 * v;
       const bool vis = idx < p.P && !aborted && rad > 0;
@@ -769,7 +932,30 @@ __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, in
           const float3 gcol = make_float3(s1.z, s1.w, s2.x);
           dmean = sh_backward<1>(min(p.D, DEG_MAX), p.M, mean_v, make_float3(cam[0], cam[1], cam[2]), p.shs + iv * SHW, w, cl, gcol);
           gmask = make_float3(cl[0] ? 0.f : gcol.x, cl[1] ? 0.f : gcol.y, cl[2] ? 0.f : gcol.z);
+          if constexpr (GATHER) {
+            // left in LDS at once, not carried through the geometric chain: 3 + M registers less at the kernel's register peak
+            // (slots 10 and up: clear of the staged sums in slots 0-9, which are read once more below)
+            float *mine = rowv + vl * NV * CW_G + gl;
+            mine[10 * CW_G] = gmask.x; mine[11 * CW_G] = gmask.y; mine[12 * CW_G] = gmask.z;
+#pragma unroll
+            for (int k = 0; k < MC; k++) mine[(13 + k) * CW_G] = w[k];
+            sh_left = true;
+          }
           __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (GATHER) {
+          // requested here, behind the view-direction term's register peak (the row walk is no place to hold them); the sums, of which
+          // that term needed the colour part only, are read from LDS again rather than carried through it
+#pragma unroll
+          for (int k = 0; k < 6; k++) c6[k] = p.cov3Ds[6 * ii + k];
+          if (SHW > 0) {
+            asm volatile("" ::: "memory");
+            const float *stage = rowv + vl * NV * CW_G;
+            s0 = reinterpret_cast<const float4 *>(stage)[gl];
+            s1 = reinterpret_cast<const float4 *>(stage + 4 * CW_G)[gl];
+            const float2 s2h = reinterpret_cast<const float2 *>(stage + 8 * CW_G)[gl];
+            s2 = make_float4(s2h.x, s2h.y, 0.f, 0.f);
+          }
         }
         gaussian_chain_geom(p, mean_v, c6v, s0, s1, s2, o, tau);
         if (SHW > 0) {
@@ -810,9 +996,17 @@ __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, in
     mine[0 * CW_G] = o.op; mine[1 * CW_G] = o.gm.x; mine[2 * CW_G] = o.gm.y; mine[3 * CW_G] = o.gm.z;
 #pragma unroll
     for (int k = 0; k < 6; k++) mine[(4 + k) * CW_G] = o.cov[k];
-    mine[10 * CW_G] = gmask.x; mine[11 * CW_G] = gmask.y; mine[12 * CW_G] = gmask.z;
+    if constexpr (GATHER && SHW > 0) {
+      if (!sh_left) {  // (a lane that ran the view-direction term has left these already; the others leave zeros)
+        mine[10 * CW_G] = 0.f; mine[11 * CW_G] = 0.f; mine[12 * CW_G] = 0.f;
 #pragma unroll
-    for (int k = 0; k < MC; k++) mine[(13 + k) * CW_G] = w[k];
+        for (int k = 0; k < MC; k++) mine[(13 + k) * CW_G] = 0.f;
+      }
+    } else {
+      mine[10 * CW_G] = gmask.x; mine[11 * CW_G] = gmask.y; mine[12 * CW_G] = gmask.z;
+#pragma unroll
+      for (int k = 0; k < MC; k++) mine[(13 + k) * CW_G] = w[k];
+    }
     __syncthreads();
     const int nv = min(CW_V, K - v0);
 #pragma unroll
@@ -894,11 +1088,13 @@ __global__ __launch_bounds__(256) void k_tau_sum(BwdParams p, GeomWS g0, ViewStr
   if (tid < 6 && p.dL_dtau_sum) p.dL_dtau_sum[6 * view + tid] = (float)red[tid * 256];
 }
 
-template <int SHW>
-static void launch_chain(const BwdParams &p, int K, const GeomWS &g, const ImageWS &im, ViewStrides vs, int accumulate, hipStream_t s) {
+template <int SHW, bool GATHER>
+static void launch_chain(const BwdParams &p, int K, const GeomWS &g, const BinWS &b, const ImageWS &im, ViewStrides vs, int accumulate,
+                         hipStream_t s) {
   for (int v0 = 0; v0 < K; v0 += CW_V)  // 8 views per launch; later launches add to the first one's sums (same stream: in view order)
-    hipLaunchKernelGGL(k_chain_window<SHW>, dim3((p.P + CW_G - 1) / CW_G), dim3(CW_G * CW_V), 0, s, p, v0, K, g, im, vs, p.dL_dmean2D,
-                       p.dL_dconic, p.dL_dcolor, p.dL_ddepth, p.dL_dtau, (accumulate || v0 > 0) ? 1 : 0);
+    hipLaunchKernelGGL((k_chain_window<SHW, GATHER>), dim3((p.P + CW_G - 1) / CW_G), dim3(CW_G * CW_V), 0, s, p, v0, K, g, im, vs,
+                       b.inst_grad, b.reached, p.dL_dmean2D, p.dL_dconic, p.dL_dcolor, p.dL_ddepth, p.dL_dtau,
+                       (accumulate || v0 > 0) ? 1 : 0);
   hipLaunchKernelGGL(k_tau_sum, dim3(K), dim3(256), 0, s, p, g, vs);
 }
 
@@ -909,20 +1105,26 @@ int launch_gather_sums(int P, int K, const int *radii, const GeomWS &g, const Bi
   return GSAJ_OK;
 }
 
+// gather != 0: the chain kernel sums the reverse compositor's instance rows itself (k_gather_sums has not run, gsum is not touched);
+// gather == 0: it reads the sums k_gather_sums left in gsum
 int launch_gaussian_backward_batch(const BwdParams &p, int K, const GeomWS &g, const BinWS &b, const ImageWS &im, ViewStrides vs,
-                                   int accumulate, hipStream_t s) {
-  (void)b;
+                                   int accumulate, int gather, hipStream_t s) {
   GsajProfScope ps(ST_GAUSSIAN_BWD, s);
+#define CHAIN(SHW)                                                       \
+  if (gather) launch_chain<SHW, true>(p, K, g, b, im, vs, accumulate, s); \
+  else launch_chain<SHW, false>(p, K, g, b, im, vs, accumulate, s);       \
+  break
   switch (p.shs ? p.M : 0) {
-    case 0: launch_chain<0>(p, K, g, im, vs, accumulate, s); break;
-    case 1: launch_chain<3>(p, K, g, im, vs, accumulate, s); break;
-    case 4: launch_chain<12>(p, K, g, im, vs, accumulate, s); break;
-    case 9: launch_chain<27>(p, K, g, im, vs, accumulate, s); break;
-    case 16: launch_chain<48>(p, K, g, im, vs, accumulate, s); break;
+    case 0: CHAIN(0);
+    case 1: CHAIN(3);
+    case 4: CHAIN(12);
+    case 9: CHAIN(27);
+    case 16: CHAIN(48);
     default:
       gsaj_set_error("batched backward: SH storage of %d coefficients is not supported (1, 4, 9 or 16)", p.M);
       return GSAJ_ERR_INVALID_ARGUMENT;
   }
+#undef CHAIN
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }

@@ -245,7 +245,7 @@ int launch_gaussian_backward(const BwdParams &p, const GeomWS &g, const BinWS &b
 // p.radii [K,P].
 int launch_gather_sums(int P, int K, const int *radii, const GeomWS &g, const BinWS &b, const ImageWS &im, ViewStrides vs, hipStream_t s);
 int launch_gaussian_backward_batch(const BwdParams &p, int K, const GeomWS &g, const BinWS &b, const ImageWS &im, ViewStrides vs,
-                                   int accumulate, hipStream_t s);
+                                   int accumulate, int gather, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 
 // ---- small device helpers -------------------------------------------------------------------

@@ -51,6 +51,7 @@ SIGNATURES = {
     "gsaj_mark_visible": (c_int, [c_int, P, P, P, P, P]),
     "gsaj_debug_export": (c_int, [c_int] * 4 + [P] * 3 + [P] * 11 + [P]),
     "gsaj_debug_export_view_sums": (c_int, [c_int, P, P, P]),
+    "gsaj_debug_export_view_sums_gather": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P]),
     "gsaj_profile_begin": (c_int, [c_int]),
     "gsaj_profile_end": (c_int, [P, P]),
     "gsaj_dense_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

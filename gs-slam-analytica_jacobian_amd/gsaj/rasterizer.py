@@ -681,7 +681,11 @@ class BatchContext:
         return st
 
     def backward(self, bg, means3D, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy, dL_dcolor, dL_ddepth,
-                 sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, scale_modifier=1.0, slot=0):
+                 sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, scale_modifier=1.0, slot=0,
+                 split=False):
+        """split=True (one stream): the window's two halves as two calls, GSAJ_BWD_ONLY_COMPOSITE then GSAJ_BWD_ONLY_CHAIN -- the
+        per-view sums go through the geometry workspace (k_gather_sums) instead of being formed inside the chain kernel; the
+        results are the same bits."""
         g = self.slots[slot]
         if g["tau_every_window"] is not None:
             g["tau_every_window"].zero_()  # rows of the other ranks' windows must be zero before the sum all-reduce
@@ -702,7 +706,11 @@ class BatchContext:
 
         cur = self._fork()
         if len(self.groups) == 1:
-            call(0, self.K, cur, 0)
+            if split:
+                call(0, self.K, cur, 2)
+                call(0, self.K, cur, 4)
+            else:
+                call(0, self.K, cur, 0)
             return g
         for v0, kv, st in self.groups:      # per-view halves: independent, one stream each
             call(v0, kv, cur if st is None else st, 2)
@@ -711,12 +719,21 @@ class BatchContext:
             call(v0, kv, cur, 4 | (1 if i > 0 else 0))
         return g
 
-    def view_sums(self, v):
-        """[P,12]: the reverse compositor's 10 sums per Gaussian of view v of the last backward (gsaj_debug_export_view_sums):
-        dL/dmean2D x, y | dL/dconic a, b, c | dL/dopacity | dL/dcolor r, g, b | dL/ddepth | 2 pads.  For parity tests."""
+    def view_sums(self, v, stored=False):
+        """[P,12]: the reverse compositor's 10 sums per Gaussian of view v of the last backward (gsaj_debug_export_view_sums_gather:
+        the whole-window backward never stores them, so they are summed again from the view's instance rows, which survive
+        until the next forward): dL/dmean2D x, y | dL/dconic a, b, c | dL/dopacity | dL/dcolor r, g, b | dL/ddepth | 2 pads.
+        stored=True: what the geometry workspace holds (gsaj_debug_export_view_sums) -- the sums a split or two-stream backward
+        left there for its chain.  For parity tests."""
         out = torch.zeros((self.P, 12), device=self.dev, dtype=_F32)
-        _lib.check(self.lib.gsaj_debug_export_view_sums(self.P, self.geom.data_ptr() + int(v) * self.geom_stride, out.data_ptr(),
-                                                        _stream(self.dev)), "gsaj_debug_export_view_sums")
+        v = int(v)
+        if stored:
+            _lib.check(self.lib.gsaj_debug_export_view_sums(self.P, self.geom.data_ptr() + v * self.geom_stride, out.data_ptr(),
+                                                            _stream(self.dev)), "gsaj_debug_export_view_sums")
+            return out
+        _lib.check(self.lib.gsaj_debug_export_view_sums_gather(
+            self.P, self.capacity, self.W, self.H, self.geom.data_ptr() + v * self.geom_stride, self.binning.data_ptr() + v * self.bin_stride,
+            self.img.data_ptr() + v * self.img_stride, out.data_ptr(), _stream(self.dev)), "gsaj_debug_export_view_sums_gather")
         return out
 
     def interactions(self):

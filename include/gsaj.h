@@ -246,7 +246,14 @@ int gsaj_debug_export(int P, int R, int W, int H, const void *geom_ws, const voi
 /* After gsaj_rasterize_backward_batch: the reverse compositor's 10 sums per Gaussian of ONE view of the window (that view's block
  * of the geometry workspace), sums [P,12] = (dL/dmean2D x, y | dL/dconic a, b, c | dL/dopacity | dL/dcolor r, g, b | dL/ddepth | 2
  * pads) -- the per-view quantities the batched backward does not return (it returns their sums over the views), for parity tests. */
+/* gsaj_debug_export_view_sums copies what the geometry workspace holds: valid only after a GSAJ_BWD_ONLY_COMPOSITE call, which
+ * leaves the sums there for the GSAJ_BWD_ONLY_CHAIN call.  A whole-window call (neither flag) forms the sums inside its chain kernel
+ * and never stores them: after it use gsaj_debug_export_view_sums_gather, which takes that view's blocks of all three workspaces
+ * (256-byte aligned, as the batched entry points take them), sums the view's instance rows again -- they and their `reached` flags
+ * survive until the next forward -- into the geometry workspace, and copies the result.  Same additions, same bits, either way. */
 int gsaj_debug_export_view_sums(int P, const void *geom_ws, float *sums /*dev [P,12]*/, void *stream);
+int gsaj_debug_export_view_sums_gather(int P, int capacity, int W, int H, void *geom_ws, void *binning_ws, void *image_ws,
+                                       float *sums /*dev [P,12]*/, void *stream);
 
 /* ---- per-kernel timing (bench.py's roofline leg) ----------------------------------------
  * Between gsaj_profile_begin and gsaj_profile_end every kernel launch of the library is
