@@ -247,6 +247,8 @@ int launch_gather_sums(int P, int K, const int *radii, const GeomWS &g, const Bi
 int launch_gaussian_backward_batch(const BwdParams &p, int K, const GeomWS &g, const BinWS &b, const ImageWS &im, ViewStrides vs,
                                    int accumulate, int gather, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
+// in-place exclusive scan of n counters by ONE workgroup (knn.hip; the radix sort's digit offsets, seed.hip's compaction offsets)
+void launch_exclusive_scan_u32(int n, uint32_t *v, hipStream_t s);
 
 // ---- small device helpers -------------------------------------------------------------------
 #ifdef __HIPCC__

@@ -215,6 +215,8 @@ __global__ __launch_bounds__(64) void k_rs_scatter(int P, int ntile, int shift, 
   }
 }
 
+void launch_exclusive_scan_u32(int n, uint32_t *v, hipStream_t s) { hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, s, n, v); }
+
 // Sorts the (codes, idx) pairs; the passes alternate between the two pairs of arrays, and w.codes_sorted / w.idx_sorted are
 // pointed at whichever pair holds the result.
 static int knn_radix_sort(int P, KnnWS &w, hipStream_t s) {
@@ -222,7 +224,7 @@ static int knn_radix_sort(int P, KnnWS &w, hipStream_t s) {
   uint32_t *ka = w.codes, *va = w.idx, *kb = w.codes_sorted, *vb = w.idx_sorted;
   for (int shift = 0; shift < 30; shift += RS_BITS) {
     hipLaunchKernelGGL(k_rs_hist, dim3(ntile), dim3(64), 0, s, P, ntile, shift, ka, w.hist);
-    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, s, RS_BUCKETS * ntile, w.hist);
+    launch_exclusive_scan_u32(RS_BUCKETS * ntile, w.hist, s);
     hipLaunchKernelGGL(k_rs_scatter, dim3(ntile), dim3(64), 0, s, P, ntile, shift, ka, va, kb, vb, w.hist);
     uint32_t *t = ka; ka = kb; kb = t;
     t = va; va = vb; vb = t;

@@ -4,8 +4,10 @@ get_xyz, get_features, get_opacity, get_scaling, get_rotation, get_covariance,
 active_sh_degree / max_sh_degree), plus what sits directly either side of it: the
 densification bookkeeping fed by a backward (add_densification_stats :767-771, max_radii2D, n_obs --
 one device launch, gsaj_densification_stats) and parameter I/O in the reference's formats
-(load_tensors :70-138, save_ply :402-436, load_ply :453-542; gsaj.model_io).  The densify / prune /
-optimiser-surgery logic itself (:281-765) stays the caller's.
+(load_tensors :70-138, save_ply :402-436, load_ply :453-542; gsaj.model_io), and map growth from a keyframe
+(create_pcd_from_image[_and_depth] :183-279, extend_from_pcd[_seq] :284-319: on the device, gsaj.seeding, where the reference
+goes through NumPy and Open3D).  The densify / prune / general optimiser-surgery logic (:321-765) stays the caller's; the one
+piece of it this path needs -- new rows enter an attached Adam with zero moments, cat_tensors_to_optimizer :599-631 -- is here.
 """
 import torch
 
@@ -25,6 +27,8 @@ class GaussianModel:
         self.covariance_activation = self.build_covariance_from_scaling_rotation
         self.config = config
         self.isotropic = False
+        self.optimizer = None
+        self.seed = 0  # seed of the next keyframe's down-sample (create_pcd_from_image_and_depth); advanced by every call
 
     @classmethod
     def from_activated(cls, xyz, scales, rotations, opacities, shs, sh_degree=3, active_sh_degree=None,
@@ -198,3 +202,89 @@ class GaussianModel:
         if n_obs is not None:
             self.n_obs = n_obs
         return n_obs
+
+    # ---- map growth from a keyframe (reference :183-319) ----------------------------------------------------------------
+    def init_lr(self, spatial_lr_scale):
+        self.spatial_lr_scale = spatial_lr_scale
+
+    def create_pcd_from_image(self, cam_info, init=False, scale=2.0, depthmap=None):
+        """Reference :183-207.  depthmap: [H,W] array or tensor (what add_new_keyframe returned); None: cam_info.depth, or, for
+        a monocular sensor, (1 + 0.05 (randn - 0.5)) * scale.  The colour is cam_info.original_image under the camera's
+        exposure, applied inside the kernel."""
+        cam = cam_info
+        dev = cam.original_image.device
+        if depthmap is None:
+            if self.config["Dataset"]["sensor_type"] == "monocular":
+                shape = (cam.image_height, cam.image_width)
+                depthmap = (torch.ones(shape) + (torch.randn(shape) - 0.5) * 0.05) * scale
+            else:
+                depthmap = cam.depth
+        depth = torch.as_tensor(depthmap, dtype=torch.float32).to(dev)
+        return self.create_pcd_from_image_and_depth(cam, cam.original_image, depth, init)
+
+    def create_pcd_from_image_and_depth(self, cam, rgb, depth, init=False):
+        """Reference :209-279 with tensors where it takes o3d.geometry.Image: rgb [3,H,W] fp32 in [0,1] BEFORE the exposure (the
+        kernel applies exp(a) rgb + b, clamps and quantises to 8 bits as :185-187 does), depth [H,W] fp32, both on the device.
+        Returns (xyz, features [m,3,M], scales, rots, opacities) like the reference.  The down-sample is a uniform subset
+        reproducible from self.seed (the reference's Open3D shuffle is unseeded); self.seed advances by one per call."""
+        from gsaj.seeding import seed_from_keyframe
+        from gaussian_splatting.utils.graphics_utils import getWorld2View2
+        ds = self.config["Dataset"]
+        factor = ds["pcd_downsample_init"] if init else ds["pcd_downsample"]
+        dev = depth.device
+        w2c = getWorld2View2(cam.R, cam.T).to(device=dev, dtype=torch.float32).contiguous()
+        ab = torch.cat([cam.exposure_a.detach().reshape(1), cam.exposure_b.detach().reshape(1)]).to(device=dev, dtype=torch.float32)
+        seed, self.seed = self.seed, self.seed + 1
+        return seed_from_keyframe(rgb, depth, w2c, cam.fx, cam.fy, cam.cx, cam.cy, factor, ds["point_size"],
+                                 sh_degree=self.max_sh_degree, adaptive_pointsize=bool(ds.get("adaptive_pointsize", False)),
+                                 isotropic=self.isotropic, exposure_ab=ab, seed=seed)
+
+    def extend_from_pcd(self, fused_point_cloud, features, scales, rots, opacities, kf_id):
+        """Reference :284-309 + densification_postfix :633-667: append the new Gaussians as new leaf tensors, reset max_radii2D /
+        xyz_gradient_accum / denom to zeros of the new size, extend unique_kfIDs with kf_id and n_obs with zeros.  With an
+        optimizer attached (torch.optim.Adam, one parameter per group, named xyz, f_dc, f_rest, opacity, scaling, rotation) the
+        new parameters replace the old ones in their groups and exp_avg / exp_avg_sq are padded with zeros (:599-631)."""
+        new = {"xyz": fused_point_cloud, "f_dc": features[:, :, 0:1].transpose(1, 2).contiguous(),
+               "f_rest": features[:, :, 1:].transpose(1, 2).contiguous(), "opacity": opacities, "scaling": scales, "rotation": rots}
+        old = {"xyz": self._xyz, "f_dc": self._features_dc, "f_rest": self._features_rest, "opacity": self._opacity,
+               "scaling": self._scaling, "rotation": self._rotation}
+        m = fused_point_cloud.shape[0]
+        grown = {}
+        with torch.no_grad():
+            for name, ext in new.items():
+                cur = old[name]
+                ext = ext.detach().to(dtype=torch.float32)
+                if cur.numel() == 0 and cur.dim() == 1:  # an empty model: the new rows are the map
+                    grown[name] = ext.clone().requires_grad_(True)
+                else:
+                    grown[name] = torch.cat((cur.detach(), ext.to(cur.device)), dim=0).requires_grad_(True)
+        if self.optimizer is not None:
+            for group in self.optimizer.param_groups:
+                assert len(group["params"]) == 1
+                name = group["name"]
+                prev = group["params"][0]
+                state = self.optimizer.state.pop(prev, None)
+                if state is not None and "exp_avg" in state:
+                    pad = torch.zeros((m,) + tuple(grown[name].shape[1:]), dtype=state["exp_avg"].dtype, device=state["exp_avg"].device)
+                    state["exp_avg"] = torch.cat((state["exp_avg"], pad), dim=0)
+                    state["exp_avg_sq"] = torch.cat((state["exp_avg_sq"], pad), dim=0)
+                group["params"][0] = grown[name]
+                if state is not None:
+                    self.optimizer.state[grown[name]] = state
+        self._xyz, self._features_dc, self._features_rest = grown["xyz"], grown["f_dc"], grown["f_rest"]
+        self._opacity, self._scaling, self._rotation = grown["opacity"], grown["scaling"], grown["rotation"]
+        n, dev = self._xyz.shape[0], self._xyz.device
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+        self.denom = torch.zeros((n, 1), device=dev)
+        self.max_radii2D = torch.zeros((n,), device=dev)
+
+        def host_ints(name):  # (a model built without them, e.g. from_activated, gets zeros for its old rows)
+            t = getattr(self, name, None)
+            return t.cpu().int() if t is not None and t.shape[0] == n - m else torch.zeros((n - m,)).int()
+
+        self.unique_kfIDs = torch.cat((host_ints("unique_kfIDs"), torch.ones((m,)).int() * kf_id)).int()
+        self.n_obs = torch.cat((host_ints("n_obs"), torch.zeros((m,)).int())).int()
+
+    def extend_from_pcd_seq(self, cam_info, kf_id=-1, init=False, scale=2.0, depthmap=None):
+        fused_point_cloud, features, scales, rots, opacities = self.create_pcd_from_image(cam_info, init, scale=scale, depthmap=depthmap)
+        self.extend_from_pcd(fused_point_cloud, features, scales, rots, opacities, kf_id)

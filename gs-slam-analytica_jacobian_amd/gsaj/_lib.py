@@ -79,6 +79,13 @@ SIGNATURES = {
     "gsaj_ssim_backward": (c_int, [c_int] * 4 + [P] * 6),
     "gsaj_refine_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gsaj_refine_loss_seeds": (c_int, [c_int, c_int, c_float] + [P] * 6),
+    "gsaj_seed_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsaj_depth_stats": (c_int, [c_int, c_int, P, P, c_float, P, P, c_float, P, P, P, P]),
+    "gsaj_keyframe_depth_prior": (c_int, [c_int, c_int, P, P, P, c_float, P, P, P, P, P]),
+    "gsaj_seed_select": (c_int, [c_int, c_int, P, P, c_float, c_float, c_double, ctypes.c_uint32, P, P]),
+    "gsaj_seed_count": (c_int, [P, P, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "gsaj_debug_seed_pixels": (c_int, [c_int, c_int, c_int, P, P, P]),
+    "gsaj_seed_gaussians": (c_int, [c_int, c_int, c_int, P, P, P, P] + [c_double] * 4 + [c_float, c_int, c_int, c_int] + [P] * 6 + [P, P, P]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 """Losses that seed the backward of the render path, with the reference's names and semantics
 (utils/slam_utils.py:56-128 get_loss_tracking* / get_loss_mapping*; compute_loss of
-Jacobian_test.py:155-196).  Device-agnostic restatement."""
+Jacobian_test.py:155-196), and get_median_depth (:131-142).  Device-agnostic restatement; get_median_depth hands device
+tensors to the kernels of gsaj.seeding."""
 import torch
 
 
@@ -74,3 +75,23 @@ def compute_loss(gaussian_model, color, depth, color_gt, depth_gt, mask, compute
         valid = (dgt > 0.0) & mask
         loss = loss + torch.nn.functional.l1_loss(depth.squeeze(0)[valid], dgt[valid])
     return loss
+
+
+def get_median_depth(depth, opacity=None, mask=None, return_std=False):
+    """Reference :131-142: the (lower) median of the depths with depth > 0, opacity > 0.95 and mask, optionally with their unbiased
+    standard deviation and the valid mask.  Device tensors go to gsaj.seeding.median_depth (one pass of kernels, no host
+    synchronisation; no valid pixel gives 0 there instead of an exception); CPU tensors take the torch statement below.  Unlike
+    the reference, opacity=None works."""
+    if depth.device.type == "cuda":  # (always the kernels: they refuse what they do not cover, nothing falls back to torch ops)
+        from gsaj.seeding import median_depth
+        return median_depth(depth, None if opacity is None else opacity.detach(), mask, return_std)
+    depth = depth.detach().clone()
+    valid = depth > 0
+    if opacity is not None:
+        valid = torch.logical_and(valid, opacity.detach() > 0.95)
+    if mask is not None:
+        valid = torch.logical_and(valid, mask)
+    valid_depth = depth[valid]
+    if return_std:
+        return valid_depth.median(), valid_depth.std(), valid
+    return valid_depth.median()

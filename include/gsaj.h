@@ -419,6 +419,57 @@ int gsaj_dist2(int P, const float *points, float *mean_dists, void *knn_ws, void
  * simple_knn.cu:211): ascending codes, equal codes in ascending index order. */
 int gsaj_debug_dist2_order(int P, void *knn_ws, uint32_t *codes_sorted, uint32_t *idx_sorted, void *stream);
 
+/* ---- new Gaussians from a keyframe (csrc/seed.hip) -------------------------------------------------------------------
+ * The reference grows its map from every keyframe through the host: slam_frontend.py:57-108 (add_new_keyframe: the depth to seed
+ * from), slam_utils.py:131-142 (get_median_depth), gaussian_model.py:183-279 (create_pcd_from_image[_and_depth]: Open3D RGBD image
+ * -> point cloud -> random_down_sample -> RGB2SH, distCUDA2 scales, unit rotations, opacity 0.5).  Here the same steps stay on the
+ * device; the only host read is the 8-byte gsaj_seed_count, which sizes the new tensors.  Images are [H,W] fp32 (depth, opacity,
+ * noise), [3,H,W] fp32 (gt_image / image), masks [H,W] bytes (non-zero = keep).  No float atomics: every result is bit-reproducible.
+ * seed_ws: gsaj_seed_workspace_bytes(W, H) bytes, no initialisation needed; it carries state from gsaj_seed_select to
+ * gsaj_seed_count / gsaj_seed_gaussians.
+ *
+ * gsaj_depth_stats = get_median_depth: valid = depth > 0 [and opacity > opacity_min] [and mask] [and (r + g) + b > rgb_threshold,
+ *   with gt_image]; out_stats (dev float[4]) = {median, std, n_valid, 0}; out_valid (dev bytes [H,W], may be NULL) = the valid mask.
+ *   median = torch.median = the LOWER median, order statistic (n_valid - 1) / 2, exact (integer radix select over order-preserving
+ *   keys); std = torch.std (unbiased, n - 1), summed in fp64 in a fixed order and rounded once.  n_valid == 0 (the reference
+ *   raises): median = std = 0.  n_valid == 1: std = NaN, as torch.std.
+ * gsaj_keyframe_depth_prior = the monocular branch of add_new_keyframe (:89-103): statistics as above with opacity > 0.95 and the
+ *   colour mask; invalid = depth > med + std or depth < med - std or not valid; out = (invalid ? med : depth) + noise * (invalid ?
+ *   0.5 std : 0.2 std); out = 0 where the colour mask fails.  noise: the caller's N(0,1) image or NULL for none.
+ * gsaj_seed_select: valid = 0 < depth < depth_trunc [and (r + g) + b > rgb_threshold] (Open3D create_from_color_and_depth(depth_scale
+ *   1, depth_trunc) + project_valid_depth_only); m = (size_t)(n_valid * (1.0 / downsample_factor)) in double (random_down_sample);
+ *   the chosen set is the m valid pixels with the smallest key, where, for pixel index i = v * W + u,
+ *       key(i) = mix(i XOR mix(seed)),   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *   in 32-bit unsigned arithmetic.  mix is a bijection, so no two pixels share a key and there is no tie-break rule.  The set is a
+ *   uniform m-subset of the valid pixels, reproducible from `seed`; it is NOT Open3D's subset (an unseeded mt19937 shuffle).  The
+ *   pixels are listed in ascending pixel order.  downsample_factor >= 1.
+ * gsaj_seed_count: blocking; n_valid and m of the last gsaj_seed_select on this workspace.
+ * gsaj_seed_gaussians: for the m chosen pixels, in pixel order: xyz [m,3] = inverse(W2C) (x, y, z, 1) with z = depth, x = (u - cx) z /
+ *   fx, y = (v - cy) z / fy, evaluated in fp64 on the fp32 inputs and rounded once (w2c: dev, 16 row-major floats, inverted as a general
+ *   affine map; the first 16 floats of a pose_state qualify); f_dc [m,3] = (q / 255 - 0.5) / C0 with q = (uint8)(clamp(exp(a) image + b, 0,
+ *   1) * 255), truncated (exposure_ab: dev {a, b} or NULL = {0, 0}; pose_state + 33 qualifies); f_rest [m, (sh_coeffs - 1) * 3] = 0;
+ *   scaling [m, isotropic ? 1 : 3] = log(sqrt(max(dist2, 1e-7) * point_size)), dist2 = gsaj_dist2 of the new points (knn_ws:
+ *   gsaj_dist2_workspace_bytes(m)); with adaptive != 0 point_size becomes min(0.05, point_size * median of ALL pixels of `depth`, zeros
+ *   included, the mean of the two middle values: np.median), found on the device; rotation [m,4] = (1, 0, 0, 0); opacity [m] = 0 =
+ *   inverse_sigmoid(0.5).  m must be the m of gsaj_seed_count; depth must be the image given to gsaj_seed_select.  m < 4 leaves
+ *   FLT_MAX terms in dist2 (see gsaj_dist2), hence huge or infinite scales, as in the reference; m == 0 is a successful no-op. */
+size_t gsaj_seed_workspace_bytes(int W, int H);
+int gsaj_depth_stats(int W, int H, const float *depth, const float *opacity /*or NULL*/, float opacity_min,
+                     const uint8_t *mask /*or NULL*/, const float *gt_image /*or NULL*/, float rgb_threshold,
+                     float *out_stats /*dev [4]*/, uint8_t *out_valid /*dev [H,W] or NULL*/, void *seed_ws, void *stream);
+int gsaj_keyframe_depth_prior(int W, int H, const float *depth, const float *opacity, const float *gt_image, float rgb_threshold,
+                              const float *noise /*or NULL*/, float *out_depth /*dev [H,W]*/, float *out_stats /*dev [4]*/,
+                              void *seed_ws, void *stream);
+int gsaj_seed_select(int W, int H, const float *depth, const float *gt_image /*or NULL*/, float rgb_threshold, float depth_trunc,
+                     double downsample_factor, uint32_t seed, void *seed_ws, void *stream);
+int gsaj_seed_count(const void *seed_ws, void *stream, int *n_valid /*host*/, int *m /*host*/);
+int gsaj_seed_gaussians(int m, int W, int H, const float *depth, const float *image, const float *exposure_ab /*dev [2] or NULL*/,
+                        const float *w2c /*dev [16]*/, double fx, double fy, double cx, double cy, float point_size, int adaptive,
+                        int sh_coeffs, int isotropic, float *xyz, float *f_dc, float *f_rest, float *scaling, float *rotation,
+                        float *opacity, void *seed_ws, void *knn_ws, void *stream);
+/* Tests only: the first m pixel indices (v * W + u, ascending) the last gsaj_seed_select left in the workspace -> pixels (dev [m]). */
+int gsaj_debug_seed_pixels(int W, int H, int m, const void *seed_ws, uint32_t *pixels, void *stream);
+
 /* ---- dense analytic path (NumPy-path semantics) ------------------ */
 size_t gsaj_dense_workspace_bytes(int N, int W, int H);
 /* N depth-sorted Gaussians: means2D [N,2] (pixels), covs2D [N,2,2], colors [N,3], depths [N], opac [N];
