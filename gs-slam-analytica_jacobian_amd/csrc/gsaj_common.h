@@ -249,6 +249,10 @@ int launch_gaussian_backward_batch(const BwdParams &p, int K, const GeomWS &g, c
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 // in-place exclusive scan of n counters by ONE workgroup (knn.hip; the radix sort's digit offsets, seed.hip's compaction offsets)
 void launch_exclusive_scan_u32(int n, uint32_t *v, hipStream_t s);
+// seed.hip's radix select (four 8-bit passes, integer histograms) over ALL W * H floats of `values` (device): leaves the key of the
+// order statistic `rank` (0-based, ascending) in *out_key (device).  The key of a float orders as an unsigned integer: a
+// non-negative float's bits with the sign bit set, a negative float's bits all flipped.  seed_ws: gsaj_seed_workspace_bytes(W, H).
+int launch_select_rank_f32(int W, int H, const float *values, uint32_t rank, uint32_t *out_key, void *seed_ws, hipStream_t s);
 
 // ---- small device helpers -------------------------------------------------------------------
 #ifdef __HIPCC__

@@ -538,6 +538,16 @@ extern "C" int gsaj_seed_select(int W, int H, const float *depth, const float *g
   return GSAJ_OK;
 }
 
+// the key (sd_float_key) of the order statistic `rank` of ALL W * H floats of `values`; for frame.hip, through gsaj_common.h
+int launch_select_rank_f32(int W, int H, const float *values, uint32_t rank, uint32_t *out_key, void *seed_ws, hipStream_t s) {
+  SeedWS w;
+  seed_carve(seed_ws, W, H, &w);
+  SdSrc src;
+  src.n = W * H; src.kind = SD_KIND_ALL; src.depth = values; src.opacity = nullptr; src.gt = nullptr; src.mask = nullptr;
+  src.opacity_min = 0.f; src.rgb_thr = 0.f; src.trunc = 0.f; src.seedmix = 0u; src.out_valid = nullptr;
+  return sd_run_select(src, SD_RANK_FIXED, rank, 0.0, 0, out_key, nullptr, nullptr, w, s);
+}
+
 extern "C" int gsaj_seed_count(const void *seed_ws, void *stream, int *n_valid, int *m) {
   if (!seed_ws || !n_valid || !m) {
     gsaj_set_error("gsaj_seed_count: invalid argument");
@@ -581,12 +591,9 @@ extern "C" int gsaj_seed_gaussians(int m, int W, int H, const float *depth, cons
   seed_carve(seed_ws, W, H, &w);
   const int n = W * H;
   if (adaptive) {  // the two middle order statistics of the whole depth image, zeros included (np.median)
-    SdSrc src;
-    src.n = n; src.kind = SD_KIND_ALL; src.depth = depth; src.opacity = nullptr; src.gt = nullptr; src.mask = nullptr;
-    src.opacity_min = 0.f; src.rgb_thr = 0.f; src.trunc = 0.f; src.seedmix = 0u; src.out_valid = nullptr;
-    int rc = sd_run_select(src, SD_RANK_FIXED, (uint32_t)((n - 1) / 2), 0.0, 0, w.res + RES_MED_LO, nullptr, nullptr, w, s);
+    int rc = launch_select_rank_f32(W, H, depth, (uint32_t)((n - 1) / 2), w.res + RES_MED_LO, seed_ws, s);
     if (rc != GSAJ_OK) return rc;
-    rc = sd_run_select(src, SD_RANK_FIXED, (uint32_t)(n / 2), 0.0, 0, w.res + RES_MED_HI, nullptr, nullptr, w, s);
+    rc = launch_select_rank_f32(W, H, depth, (uint32_t)(n / 2), w.res + RES_MED_HI, seed_ws, s);
     if (rc != GSAJ_OK) return rc;
   }
   SdInit a;

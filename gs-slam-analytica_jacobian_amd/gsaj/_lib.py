@@ -86,6 +86,9 @@ SIGNATURES = {
     "gsaj_seed_count": (c_int, [P, P, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "gsaj_debug_seed_pixels": (c_int, [c_int, c_int, c_int, P, P, P]),
     "gsaj_seed_gaussians": (c_int, [c_int, c_int, c_int, P, P, P, P] + [c_double] * 4 + [c_float, c_int, c_int, c_int] + [P] * 6 + [P, P, P]),
+    "gsaj_grad_mask_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsaj_grad_intensity": (c_int, [c_int, c_int, P, P, P]),
+    "gsaj_grad_mask": (c_int, [c_int, c_int, P, c_float, c_int, P, P, P, P]),
 }
 
 _lib = None

@@ -24,6 +24,7 @@ iterations and iterate() raises on every rank together.
 import torch
 
 from . import _lib, tile_band_shard as tbs
+from .grad_mask import GradMask
 from .losses import MONOCULAR, TRACKING, LossSeeds
 from .pose_step import PoseTracker
 from .rasterizer import FrameContext
@@ -63,6 +64,7 @@ class DeviceTracker:
         self._abort_ptr = self.ctx.abort_flag_ptr()
         self.gt_color = self.gt_depth = self.grad_mask = None
         self._graphs = None
+        self._grad_op = None  # gsaj.grad_mask.GradMask, made by the first set_frame(edge_threshold=...)
         self.iterations = 0
 
     # ---- one iteration, in the two halves a collective may sit between -------------------------------------------------
@@ -92,21 +94,33 @@ class DeviceTracker:
         skip = self.packed[tbs.ABORTED].data_ptr() if self._sharded() else self._abort_ptr
         self.pose.step(self.packed[tbs.TAU], self.packed[tbs.EXPOSURE_GRADS], skip=skip)
 
-    def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2c=None):
+    def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2c=None, edge_threshold=None, grad_blocks=False):
         """New frame: ground truth (device, [3,H,W] / [H,W]; grad_mask [1,H,W] or None) and optionally a new initial pose.
-        Everything is copied into buffers the tracker owns, so a captured graph stays valid from frame to frame."""
+        Everything is copied into buffers the tracker owns, so a captured graph stays valid from frame to frame.
+        edge_threshold (with grad_mask None): the tracker computes the frame's gradient mask itself (gsaj.grad_mask: the reference's
+        Camera.compute_grad_mask; grad_blocks=True: its "replica" block form) from its own copy of gt_color into its own mask
+        buffer, on the current stream.  A mask, given or computed, is there for every frame of a tracker or for none."""
+        masked = grad_mask is not None or edge_threshold is not None
         if self.gt_color is None:
             self.gt_color = gt_color.to(self.dev, torch.float32).contiguous().clone()
             self.gt_depth = None if gt_depth is None else gt_depth.to(self.dev, torch.float32).contiguous().clone()
-            self.grad_mask = None if grad_mask is None else grad_mask.to(self.dev, torch.uint8).contiguous().view(-1).clone()
+            if grad_mask is not None:
+                self.grad_mask = grad_mask.to(self.dev, torch.uint8).contiguous().view(-1).clone()
+            elif masked:
+                self.grad_mask = torch.empty(self.gt_color[0].numel(), dtype=torch.uint8, device=self.dev)
         else:
-            if (gt_depth is None) != (self.gt_depth is None) or (grad_mask is None) != (self.grad_mask is None):
+            if (gt_depth is None) != (self.gt_depth is None) or masked != (self.grad_mask is not None):
                 raise _lib.GsajError("set_frame: depth / mask must be given for every frame of a tracker or for none")
             self.gt_color.copy_(gt_color)
             if gt_depth is not None:
                 self.gt_depth.copy_(gt_depth)
             if grad_mask is not None:
                 self.grad_mask.copy_(grad_mask.to(self.dev, torch.uint8).view(-1))
+        if grad_mask is None and masked:
+            if self._grad_op is None:
+                _, H, W = self.gt_color.shape
+                self._grad_op = GradMask(W, H, self.dev)
+            self._grad_op(self.gt_color, edge_threshold, blocks=grad_blocks, out=self.grad_mask)
         if w2c is not None:
             self.pose.reset(w2c)
 

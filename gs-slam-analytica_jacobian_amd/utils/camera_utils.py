@@ -1,6 +1,6 @@
 """Camera with the matrix properties `render()` consumes (reference: utils/camera_utils.py:8-109).
 Only what the render / pose-update path reads is kept: R, T, pose deltas, exposure a/b,
-intrinsics, and the derived world_view_transform (= W2C^T), full_proj_transform (= W2C^T P^T),
+intrinsics, compute_grad_mask (:115-144, on the device), and the derived world_view_transform (= W2C^T), full_proj_transform (= W2C^T P^T),
 camera_center (= inv(W2C^T)[3,:3], a true inverse: W2C may be a similarity transform)."""
 import torch
 from torch import nn
@@ -54,6 +54,20 @@ class Camera(nn.Module):
     def update_RT(self, R, t):
         self.R = R.to(device=self.device)
         self.T = t.to(device=self.device)
+
+    def compute_grad_mask(self, config):
+        """Reference :115-144 on the device (gsaj.grad_mask, csrc/frame.hip): self.grad_mask = the pixels of original_image whose
+        gradient intensity exceeds Training.edge_threshold times the median -- bool [1,H,W]; with Dataset.type "replica" the float
+        [1,H,W] the reference's 32 x 32 block loop leaves.  original_image must be a device tensor (there is no CPU path)."""
+        from gsaj.grad_mask import GradMask
+
+        _, h, w = self.original_image.shape
+        op = getattr(self, "_grad_mask_op", None)
+        if op is None or (op.W, op.H, op.dev) != (w, h, self.original_image.device):
+            op = GradMask(w, h, self.original_image.device)
+            self._grad_mask_op = op
+        op(self.original_image, config["Training"]["edge_threshold"], blocks=config["Dataset"]["type"] == "replica")
+        self.grad_mask = op.reference_tensor().clone()
 
     def clean(self):
         self.original_image = self.depth = self.grad_mask = None

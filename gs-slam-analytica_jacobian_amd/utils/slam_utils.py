@@ -1,8 +1,48 @@
 """Losses that seed the backward of the render path, with the reference's names and semantics
 (utils/slam_utils.py:56-128 get_loss_tracking* / get_loss_mapping*; compute_loss of
-Jacobian_test.py:155-196), and get_median_depth (:131-142).  Device-agnostic restatement; get_median_depth hands device
-tensors to the kernels of gsaj.seeding."""
+Jacobian_test.py:155-196), get_median_depth (:131-142) and the image-gradient helpers (:4-53 image_gradient,
+image_gradient_mask, depth_reg).  Device-agnostic restatement; get_median_depth hands device tensors to the kernels of
+gsaj.seeding.  The gradient helpers are plain torch on the input's device: the product's gradient mask is gsaj.grad_mask
+(Camera.compute_grad_mask), these are the module's surface and what tools time it against."""
 import torch
+import torch.nn.functional as F
+
+_SCHARR = ((3.0, 10.0, 3.0), (0.0, 0.0, 0.0), (-3.0, -10.0, -3.0))  # rows above minus rows below; transposed: left minus right
+
+
+def _reflect_padded(image):
+    return F.pad(image[None], (1, 1, 1, 1), mode="reflect")
+
+
+def image_gradient(image):
+    """Scharr gradients of a [C,H,W] image, each channel on its own, normalised by the filter's absolute sum (32), on the image
+    reflect-padded by one pixel -> (vertical [C,H,W], horizontal [C,H,W]).  Reference :4-21."""
+    c = image.shape[0]
+    kv = torch.tensor(_SCHARR, dtype=torch.float32, device=image.device)
+    norm = 1.0 / kv.abs().sum()
+    p = _reflect_padded(image)
+    gv = F.conv2d(p, kv.expand(c, 1, 3, 3).contiguous(), groups=c)
+    gh = F.conv2d(p, kv.t().expand(c, 1, 3, 3).contiguous(), groups=c)
+    return (norm * gv)[0], (norm * gh)[0]
+
+
+def image_gradient_mask(image, eps=0.01):
+    """Where all nine reflect-padded neighbours have |value| > eps -> the same bool [C,H,W] twice (the reference computes it once
+    per filter).  Reference :24-38."""
+    small = (torch.abs(_reflect_padded(image)) > eps).logical_not().float()
+    valid = (F.max_pool2d(small, 3, stride=1) == 0)[0]
+    return valid, valid.clone()
+
+
+def depth_reg(depth, gt_image, huber_eps=0.1, mask=None):
+    """Edge-aware depth smoothness (reference :41-53; the reference never calls it, huber_eps and mask are unused there too): the
+    depth gradients weighted by exp(-10 gray_gradient^2), averaged over the pixels whose depth neighbourhood is valid."""
+    valid_v, valid_h = image_gradient_mask(depth)
+    gray_v, gray_h = image_gradient(gt_image.mean(dim=0, keepdim=True))
+    depth_v, depth_h = image_gradient(depth)
+    term_v = torch.exp(-10 * gray_v[valid_v] ** 2) * torch.abs(depth_v[valid_v])
+    term_h = torch.exp(-10 * gray_h[valid_h] ** 2) * torch.abs(depth_h[valid_h])
+    return term_h.mean() + term_v.mean()
 
 
 def _as_depth_tensor(d, like):

@@ -470,6 +470,35 @@ int gsaj_seed_gaussians(int m, int W, int H, const float *depth, const float *im
 /* Tests only: the first m pixel indices (v * W + u, ascending) the last gsaj_seed_select left in the workspace -> pixels (dev [m]). */
 int gsaj_debug_seed_pixels(int W, int H, int m, const void *seed_ws, uint32_t *pixels, void *stream);
 
+/* ---- the tracking gradient mask of a frame (frame.hip) -------------------------------------------------------------------------
+ * The per-pixel grad_mask the tracking loss reads, computed from the frame's colour image on the device (reference
+ * utils/camera_utils.py:115-144 Camera.compute_grad_mask on utils/slam_utils.py:4-38 image_gradient / image_gradient_mask).
+ * image: dev [3,H,W] fp32, W, H >= 2.  One fp32 rounding per operation, no fused multiply-add:
+ *   gray = ((r + g) + b) / 3 (a true division); p = gray reflect-padded by one pixel (the edge pixel is not repeated);
+ *   gv = ((3 p[-1,-1] + 10 p[-1,0]) + 3 p[-1,+1]) - ((3 p[+1,-1] + 10 p[+1,0]) + 3 p[+1,+1])) / 32  (p[row, column]),
+ *   gh = ((3 p[-1,-1] + 10 p[0,-1]) + 3 p[+1,-1]) - ((3 p[-1,+1] + 10 p[0,+1]) + 3 p[+1,+1])) / 32;
+ *   a pixel is valid iff all nine padded neighbours have |p| > 0.01, otherwise gv = gh = 0;
+ *   intensity I = sqrt(gv gv + gh gh), correctly rounded.  (The reference's conv2d sums the nine taps in an order of its own; any
+ *   order is within 16 * 2^-24 * max|gray| of this one.)
+ * gsaj_grad_intensity: out_intensity [H,W] = I.
+ * gsaj_grad_mask, blocks == 0 (every dataset type but "replica"): t = med * edge_threshold with med the LOWER median of all H W
+ *   intensities, zeros included (order statistic (H W - 1) / 2, torch.median); mask = I > t.  out_mask_u8 [H,W] = 0 / 1;
+ *   out_mask_f32 [H,W] (may be NULL) = 0.0 / 1.0.  An intensity pass, a radix select and one threshold kernel that reads the
+ *   selected value from device memory: no host read, no synchronisation.  ws: gsaj_grad_mask_workspace_bytes(W, H).
+ * blocks != 0 ("replica"): a 32 x 32 grid of blocks of bh = H / 32 rows and bw = W / 32 columns (integer division) anchored at
+ *   (0, 0); per block t = med * edge_threshold with med the lower median of the block's bh bw intensities; out_mask_f32 is what the
+ *   reference leaves in Camera.grad_mask, a FLOAT image: 1 where I > t and t < 1 (the reference writes the ones first and then
+ *   zeroes everything <= t, the ones included), else 0; rows >= 32 bh and columns >= 32 bw are never visited and keep I.
+ *   out_mask_u8 = (uint8)out_mask_f32, truncated: the byte the loss kernels read when handed that float image.  One kernel, one
+ *   workgroup per block; ws may be NULL.  W < 32 or H < 32 (empty blocks: the reference raises) and blocks of more than 4096 pixels,
+ *   or 4608 with their one-pixel halo (what a workgroup holds in LDS; 1920 x 1080 has 1980), return GSAJ_ERR_INVALID_ARGUMENT
+ *   before anything is launched.
+ * Integer counters only: results are bit-reproducible. */
+size_t gsaj_grad_mask_workspace_bytes(int W, int H);
+int gsaj_grad_intensity(int W, int H, const float *image, float *out_intensity /*dev [H,W]*/, void *stream);
+int gsaj_grad_mask(int W, int H, const float *image, float edge_threshold, int blocks, uint8_t *out_mask_u8 /*dev [H,W]*/,
+                   float *out_mask_f32 /*dev [H,W] or NULL*/, void *ws, void *stream);
+
 /* ---- dense analytic path (NumPy-path semantics) ------------------ */
 size_t gsaj_dense_workspace_bytes(int N, int W, int H);
 /* N depth-sorted Gaussians: means2D [N,2] (pixels), covs2D [N,2,2], colors [N,3], depths [N], opac [N];
