@@ -89,6 +89,9 @@ SIGNATURES = {
     "gsaj_grad_mask_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gsaj_grad_intensity": (c_int, [c_int, c_int, P, P, P]),
     "gsaj_grad_mask": (c_int, [c_int, c_int, P, c_float, c_int, P, P, P, P]),
+    "gsaj_covis_pack": (c_int, [c_int, c_int, P, ctypes.POINTER(c_int), ctypes.c_uint32, P, P]),
+    "gsaj_covis_query": (c_int, [c_int, P, P, c_int, ctypes.c_uint32, P, P]),
+    "gsaj_covis_prune_mask": (c_int, [c_int, P, ctypes.c_uint32, P, c_int, c_int, P, P, P, P]),
 }
 
 _lib = None

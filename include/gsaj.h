@@ -499,6 +499,37 @@ int gsaj_grad_intensity(int W, int H, const float *image, float *out_intensity /
 int gsaj_grad_mask(int W, int H, const float *image, float edge_threshold, int blocks, uint8_t *out_mask_u8 /*dev [H,W]*/,
                    float *out_mask_f32 /*dev [H,W] or NULL*/, void *ws, void *stream);
 
+/* ---- covisibility of the keyframe window (csrc/covis.hip) ------------------------------
+ * What the reference keeps as occ_aware_visibility[kf] = (n_touched > 0).long(), one int64 [P] vector per keyframe
+ * (utils/slam_backend.py:236-240), is ONE uint32 word per Gaussian here: bit s of words[i] = "Gaussian i was touched
+ * (n_touched > 0) in the view held in slot s".  At most GSAJ_COVIS_MAX_SLOTS views; which keyframe sits in which slot is
+ * the caller's book-keeping.  All results are exact integers, independent of the launch geometry; nothing below
+ * synchronises with the host.
+ *
+ * gsaj_covis_pack: K rows n_touched [K,P] (device int32) go to the K DISTINCT slots `slots` (host [K], each 0..31):
+ *   words[i] = (words[i] & ~(clear_mask | bits of slots)) | (bit slots[k] where n_touched[k][i] > 0).
+ *   clear_mask = 0xFFFFFFFF rebuilds every word from the rows (the old words are not read); K = 1 updates one slot;
+ *   a clear_mask bit also wipes a slot that is not written (a dropped keyframe).
+ * gsaj_covis_query: one pass over the P words.  The query set is {i : cur_n_touched[i] > 0} when cur_n_touched is given
+ *   (device int32 [P]; query_slot is ignored), else {i : bit query_slot of words[i]}.  out (device int32 [65]), for
+ *   every slot s in slot_mask:  out[s] = |query & slot s|,  out[32 + s] = |slot s|;  out[64] = |query|;  entries of
+ *   slots outside slot_mask are 0.  out is overwritten whatever it held.  A union is |a| + |b| - |a & b|.
+ * gsaj_covis_prune_mask: n_obs[i] = popcount(words[i] & window_mask) (written when n_obs is given);
+ *   to_prune[i] = n_obs[i] <= max_obs && (unique_kfIDs == NULL || unique_kfIDs[i] >= kf_id_min); *n_pruned = number of
+ *   ones in to_prune.  The reference's two modes (utils/slam_backend.py:252-263): "odometry" max_obs = 2, no ids
+ *   (n_obs < 3); "slam" max_obs = 3, kf_id_min = the third-newest keyframe of the window, or 0 while not initialised.
+ *   Only the mask and its count are produced; no row of the map is removed.
+ * GSAJ_ERR_INVALID_ARGUMENT: P <= 0, K outside 1..32, a slot outside 0..31 or repeated, a null pointer (cur_n_touched,
+ *   unique_kfIDs and n_obs may be NULL). */
+#define GSAJ_COVIS_MAX_SLOTS 32
+int gsaj_covis_pack(int K, int P, const int *n_touched /*dev [K,P]*/, const int *slots /*host [K]*/, uint32_t clear_mask,
+                    uint32_t *words /*dev [P]*/, void *stream);
+int gsaj_covis_query(int P, const uint32_t *words, const int *cur_n_touched /*dev [P] or NULL*/, int query_slot,
+                     uint32_t slot_mask, int *out /*dev int32 [65]*/, void *stream);
+int gsaj_covis_prune_mask(int P, const uint32_t *words, uint32_t window_mask, const int *unique_kfIDs /*dev [P] or NULL*/,
+                          int kf_id_min, int max_obs, uint8_t *to_prune /*dev [P]*/, int *n_obs /*dev [P] or NULL*/,
+                          int *n_pruned /*dev [1]*/, void *stream);
+
 /* ---- dense analytic path (NumPy-path semantics) ------------------ */
 size_t gsaj_dense_workspace_bytes(int N, int W, int H);
 /* N depth-sorted Gaussians: means2D [N,2] (pixels), covs2D [N,2,2], colors [N,3], depths [N], opac [N];
