@@ -635,6 +635,22 @@ int gsaj_debug_export(int P, int R, int W, int H, const void *geom_ws, const voi
   return GSAJ_OK;
 }
 
+int gsaj_debug_export_taken(int R, int W, int H, const void *binning_ws, const void *image_ws, uint32_t *taken, uint8_t *reached,
+                            void *stream) {
+  if (R <= 0 || W <= 0 || H <= 0 || !binning_ws || !image_ws) {
+    gsaj_set_error("gsaj_debug_export_taken: invalid argument");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  BinWS b;
+  bin_carve(align_base(const_cast<void *>(binning_ws)), (size_t)R, &b);
+  ImageWS im;
+  image_carve(align_base(const_cast<void *>(image_ws)), W, H, &im);
+  if (reached) GSAJ_HIP_CHECK(hipMemcpyAsync(reached, b.reached, (size_t)R, hipMemcpyDeviceToDevice, s));
+  if (taken) return launch_export_taken(W, H, (W + TILE - 1) / TILE, (H + TILE - 1) / TILE, b, im, taken, s);
+  return GSAJ_OK;
+}
+
 // (valid only while gsum holds the view's sums: after a GSAJ_BWD_ONLY_COMPOSITE call; a whole-window backward does not write gsum)
 int gsaj_debug_export_view_sums(int P, const void *geom_ws, float *sums, void *stream) {
   if (P <= 0 || !geom_ws || !sums) {

@@ -116,11 +116,16 @@ static inline __host__ __device__ size_t image_carve(char *base, int W, int H, I
 
 struct BinWS {  // reference: BinningState, rasterizer_impl.h:55-66
   uint64_t *keys_unsorted;  // [R] the two key buffers of tile lists longer than the LDS sort capacity (chunk sort -> merge passes);
-  uint64_t *keys;           // [R]   keys are (depth bits << 32 | id)
+  uint64_t *keys;           // [R]   keys are (depth bits << 32 | id).  Idle once the lists are sorted: the reverse compositor keeps
+                            //   each tile's compacted list of LIVE entries in the tile's segment of `keys` (render_bwd.hip)
   uint32_t *point_list;     // [R] Gaussian ids grouped by tile: as scattered (k_scatter_instances), then sorted in place (k_tile_sort)
   float4 *inst_grad;        // [R*3] per-instance partial gradients (backward), indexed by emission slot
   uint8_t *reached;         // [R] by emission slot: 1 = the reverse compositor wrote that row, 0 = no pixel of the tile got that far
                             //   (zeroed by the tile sort, set by the reverse compositor)
+  uint32_t *taken;          // [R] by list position: byte q = 1 if some pixel of quadrant q of the position's tile composited the
+                            //   entry (written by the forward compositor, one byte per quadrant wave; a wave writes the bytes of
+                            //   the 64-entry chunks it processed and no others, so bytes at or beyond a quadrant's furthest last
+                            //   contributor may be stale and are ignored by every reader)
 };
 
 // ---- batched multi-view launches (gsaj_rasterize_*_batch): K views of ONE Gaussian map -------------------------------
@@ -164,6 +169,7 @@ static inline size_t bin_carve(char *base, size_t R, BinWS *g) {
   CARVE(point_list, uint32_t, Rn);
   CARVE(inst_grad, float4, Rn * REC_F4);
   CARVE(reached, uint8_t, Rn);
+  CARVE(taken, uint32_t, Rn);
   return off;
 }
 #undef CARVE
@@ -228,6 +234,9 @@ int launch_loss_finalize(const FusedLoss &fl, int nslots, int W, int H, const ui
 int launch_render_backward(int R, int W, int H, int grid_x, int grid_y, const float *bg, const GeomWS &g, const BinWS &b,
                            const ImageWS &im, const float *dL_dpix, const float *dL_dpix_depth, int views, ViewStrides vs,
                            hipStream_t s, const FusedLoss *fl = nullptr);
+// debug: the `taken` words of one view as the reverse compositor reads them (bytes at or beyond a quadrant's furthest last
+// contributor cleared), out [R] by list position
+int launch_export_taken(int W, int H, int grid_x, int grid_y, const BinWS &b, const ImageWS &im, uint32_t *out, hipStream_t s);
 struct BwdParams {
   int P, D, M, W, H;
   const float *means3D, *shs, *scales, *rotations, *cov3Ds;
@@ -355,6 +364,13 @@ __device__ __forceinline__ float4 gsaj_load_f4_unaligned(const void *src) {
 }
 __device__ __forceinline__ uint32_t gsaj_load_u32_global(const uint32_t *src) {
   return *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>((unsigned long long)src);
+}
+// Eight bytes written earlier in this kernel (by this workgroup, made visible by a barrier): a device-scope load, which is served
+// by the L2 -- never by a line this CU's L1 took before the store -- and, unlike the coherent load below, is not waited for here.
+__device__ __forceinline__ uint2 gsaj_load_u64_device(const uint2 *src) {
+  const unsigned long long v = __hip_atomic_load(reinterpret_cast<const __attribute__((address_space(1))) unsigned long long *>((unsigned long long)src),
+                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
 }
 __device__ __forceinline__ uint4 gsaj_coherent_load_x4(const void *src) {
   uint4 v;

@@ -10,8 +10,8 @@
 // backward.cu:633-644) and then issues 10 global float atomics.  Here a wave64 owns an 8x8 pixel
 // quadrant and works in two phases per batch of 8 accepted entries:
 //
-//  phase 1 (lane = pixel):  the sequential part only.  For an entry the quadrant can see
-//    (lane-parallel culling, see wave_reduce.h) each lane advances T and accum_rec and produces
+//  phase 1 (lane = pixel):  the sequential part only.  For an entry some pixel of the quadrant took in the
+//    forward (BinWS.taken, see "the live entries of the tile" below) each lane advances T and accum_rec and produces
 //    just TWO scalars: w = dL/dG * G and u = alpha * T.  All 10 partials are linear in (w, u):
 //      d/dmean2D ~ w * (conic . d),  d/dconic ~ w * d d^T,  d/dopacity = w / o,  d/dcolour = u * dL/dC,
 //      d/ddepth = u * dL/dD.        (w, u) go to LDS, one 64-pixel row per entry.
@@ -27,11 +27,11 @@
 //  after each round the workgroup stores one 48-byte partial-gradient row per (tile, Gaussian)
 //  instance at the instance's emission slot.  The per-Gaussian kernel (gaussian_bwd.hip) sums a
 //  Gaussian's rows in a fixed order, so gradients are bit-reproducible run to run (the reference's
-//  float atomics are not).  Entries beyond the quadrant's / tile's furthest last-contributor are
-//  never visited -- not even fetched: the list is a list of Gaussian ids, and the 48-byte rows they name
-//  (GeomWS.splat) are gathered per round of 48 entries -- one 16-byte piece per wave and entry, a round ahead of their use, the
-//  ids two rounds ahead (see the staging below).  Rows beyond the tile's furthest
-//  last contributor keep the one-byte `reached = 0` flag the tile sort gave them instead of a zero row.
+//  float atomics are not).  Entries beyond the quadrant's / tile's furthest last-contributor, and entries no pixel of the
+//  tile took, are never visited -- not even fetched: the list is a list of Gaussian ids, and the 48-byte rows they name
+//  (GeomWS.splat) are gathered per round of 48 LIVE entries -- one 16-byte piece per wave and entry, a round ahead of their use,
+//  the live-list records two rounds ahead (see the staging below).  Rows of entries that are never staged keep the one-byte
+//  `reached = 0` flag the tile sort gave them instead of a zero row.
 //  Workgroups take tiles longest list first (ImageWS.tile_order, written by the preprocess kernel's frame scan).
 #include "gsaj_common.h"
 #include "loss_terms.h"
@@ -58,7 +58,8 @@ GSAJ_TRACE_DEFINE(bwdph)  // per-wave phase times of the rounds (trace build; to
 // bits) instead of being read from a seed image -- that image is never materialised.
 template <bool LOSS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_render_bwd(int W, int H, int gx, ImageWS im,
-                                                    const uint32_t *__restrict__ point_list, GeomWS g,
+                                                    const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ taken,
+                                                    uint2 *__restrict__ live, GeomWS g,
                                                     const float *__restrict__ bg,
                                                     const float *__restrict__ dL_dpix,
                                                     const float *__restrict__ dL_dpix_depth,
@@ -68,6 +69,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
     const size_t view = blockIdx.y, HWv = (size_t)H * W;
     im = image_view(im, view * vs.image);
     point_list = gsaj_shift(point_list, view * vs.bin);
+    taken = gsaj_shift(taken, view * vs.bin);
+    live = gsaj_shift(live, view * vs.bin);
     g = geom_view(g, view * vs.geom);
     inst_grad = gsaj_shift(inst_grad, view * vs.bin);
     reached = gsaj_shift(reached, view * vs.bin);
@@ -84,6 +87,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   __shared__ float4 seed_all[4 * 64];                  // [wave][pixel] (dL/dC rgb, dL/dD)
   __shared__ uint32_t wave_max[4];
   __shared__ uint32_t blk_first[BWD_ROUND];
+  __shared__ uint32_t ent_pos[2][BWD_ROUND];  // per staged entry: list index << 4 | quadrant bits; [round parity] (written a round ahead)
+  __shared__ uint32_t sweep_cnt[2][4];        // live entries per wave of a sweep iteration; [iteration parity]
   if (counters[4]) return;  // aborted async frame
   GSAJ_TRACE_BEGIN(bwd)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -104,6 +109,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   const float T_final = inside ? final_T[pid] : 0.f;
   float T = T_final;
   const uint32_t last = inside ? n_contrib[pid] : 0u;
+  const uint32_t last4 = last << 4;  // (compared with ent_pos words: index << 4 | quadrant bits < last << 4  <=>  index < last)
   float gC0 = 0.f, gC1 = 0.f, gC2 = 0.f, gD = 0.f;
   if (inside) {
     if (LOSS) {
@@ -130,7 +136,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, o));
   if (lane == 0) wave_max[wave] = wmax;
   __syncthreads();
-  const uint32_t bmax = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
+  const uint32_t wm0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max[0]), wm1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max[1]);
+  const uint32_t wm2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max[2]), wm3 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max[3]);
+  // (a last contributor is a position of the tile's own list: the clamp only keeps a stale image workspace inside the tile's segment)
+  const uint32_t bmax = min(max(max(wm0, wm1), max(wm2, wm3)), range.y - range.x);
+
+  // ---- the live entries of the tile ----
+  // The forward left, per list position and quadrant, whether ANY pixel of the quadrant composited the entry (BinWS.taken).  Per
+  // pixel the test below (`valid`) is the forward's `ok` on the same bits, so an entry no quadrant took adds exactly nothing:
+  // it is not staged, gets no row and keeps reached = 0.  One sweep over positions [0, bmax), all 256 threads, compacts the
+  // entries live in at least one quadrant, in list order, into the tile's own segment of the idle sort-key buffer: 8 bytes per
+  // entry, (Gaussian id, list index << 4 | quadrant bits).  A quadrant's byte counts only below the quadrant's furthest last
+  // contributor: every position below it was processed by the quadrant's forward wave in THIS frame, bytes at or beyond it
+  // may be stale (earlier frames, chunks behind the forward's early exit, quadrants outside the image).  The sweep reads
+  // nothing the backward writes but its own output: a second backward after the same forward forms the same list.
+  // (list index < 2^28: a tile list that long needs a 20 GB binning workspace per view)
+  uint2 *__restrict__ seg = live + range.x;
+  uint32_t nlive = 0u;  // workgroup-uniform
+  for (uint32_t p0 = 0u, it = 0u; p0 < bmax; p0 += 256u, it ^= 1u) {
+    const uint32_t p = p0 + (uint32_t)tid;
+    const bool in = p < bmax;
+    const uint32_t word = gsaj_load_u32_global(taken + range.x + (in ? p : 0u));
+    const uint32_t id = gsaj_load_u32_global(point_list + range.x + (in ? p : 0u));
+    const uint32_t keep = (p < wm0 ? 0x1u : 0u) | (p < wm1 ? 0x100u : 0u) | (p < wm2 ? 0x10000u : 0u) | (p < wm3 ? 0x1000000u : 0u);
+    const uint32_t qb = (((word & keep) * 0x00204081u) >> 21) & 0xfu;  // bits 0, 8, 16, 24 -> bits 0..3
+    const unsigned long long bal = __builtin_amdgcn_ballot_w64(in && qb != 0u);
+    if (lane == 0) sweep_cnt[it][wave] = (uint32_t)__popcll(bal);
+    __syncthreads();  // (one per iteration: the counts alternate between two sets)
+    const uint32_t c0 = sweep_cnt[it][0], c1 = sweep_cnt[it][1], c2 = sweep_cnt[it][2], c3 = sweep_cnt[it][3];
+    if (in && qb != 0u) {
+      const uint32_t before = (wave > 0 ? c0 : 0u) + (wave > 1 ? c1 : 0u) + (wave > 2 ? c2 : 0u);
+      const uint32_t at = nlive + before + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+      seg[at] = make_uint2(id, (p << 4) | qb);
+    }
+    nlive = (uint32_t)__builtin_amdgcn_readfirstlane((int)(nlive + c0 + c1 + c2 + c3));
+  }
+  // the records are read back below by other waves of this workgroup: every wave's stores have reached the L2 before it
+  // arrives at the barrier (the wait is explicit: a workgroup-scope release alone does not wait for stores on this target),
+  // and the loads are device-scope ones, served by that L2 -- never by a line this CU's L1 holds from before the stores
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
 
   float accS = 0.f;  // (accum_rec, accum_rec_depth) . (dL/dC, dL/dD) of this pixel: the only form the recurrences are needed in
 
@@ -138,12 +183,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   const int p2_slot = lane & (SLOTS - 1), p2_row = lane >> 3;
   const float p2_py = qy0 + (float)p2_row;
 
-  uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(range.x + bmax));  // exclusive sorted position (workgroup-uniform: kept in scalar registers)
-  // entries [hi, range.y) were never reached by any pixel of the tile: their partials are zero, and their `reached` flags
-  // stay as the tile sort left them (opaque scenes leave most of a long list unreached: neither their ids nor their rows
-  // are ever fetched)
+  uint32_t hi = nlive;  // exclusive index into the live list (workgroup-uniform: kept in scalar registers)
+  // entries beyond bmax were never reached by any pixel of the tile, the others left out no pixel took: their partials are
+  // zero, and their `reached` flags stay as the tile sort left them (opaque scenes leave most of a long list unreached:
+  // neither their ids nor their rows are ever fetched)
   const bool rec16 = counters[7] != 0u;  // fp16-storage rows (gsaj_common.h)
-  // Staging, software-pipelined over the rounds.  A round's 48 rows are gathered through two dependent loads (id, then the row
+  // Staging, software-pipelined over the rounds of 48 LIVE entries.  A round's 48 rows are gathered through two dependent loads (live-list record, then the row
   // it names): waited for at the round's start, that latency was a tenth of a wave's life (per-round phase times of the
   // trace build, tools/batch_trace.py).  Now thread (part, e) = (tid / 48, tid % 48), part < 4, owns ONE 16-byte piece of entry e
   // -- the row's three float4s and the Gaussian's block offset -- requests round r+1's piece at the start of round r (its id
@@ -151,13 +196,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   // of a whole row, and nothing is waited for but the very first round.  (part = wave: which array a wave reads is decided by
   // scalar code; every wave issues ONE 16-byte load per round from base(part) + offset(lane).)
   const int part = __builtin_amdgcn_readfirstlane(wave), e = lane;
-  auto round_lo = [&](uint32_t h) { return (h - range.x > BWD_ROUND) ? h - BWD_ROUND : range.x; };
-  auto load_id = [&](uint32_t l, uint32_t h) -> uint32_t {  // id of entry e of the round [l, h)
-    // (no branch around the load: a lane without an entry reads the tile's first id -- the value a load leaves in its
+  auto round_lo = [&](uint32_t h) { return h > BWD_ROUND ? h - BWD_ROUND : 0u; };
+  auto load_ent = [&](uint32_t l, uint32_t h) -> uint2 {  // (id, index << 4 | quadrant bits) of entry e of the round [l, h)
+    // (no branch around the load: a lane without an entry reads the tile's first record -- the value a load leaves in its
     // registers can stay in flight across the loop's back edge only if no copy merges it with another definition)
     const bool has = e < BWD_ROUND && l + (uint32_t)e < h;
-    const uint32_t v = gsaj_load_u32_global(point_list + (has ? l + (uint32_t)e : range.x));
-    return has ? v : 0xffffffffu;
+    const uint2 v = gsaj_load_u64_device(seg + (has ? l + (uint32_t)e : 0u));
+    return has ? v : make_uint2(0xffffffffu, 0u);
   };
   // base and stride of this wave's piece (wave-uniform).  The 16-byte load of the 4-byte block offset / the 8-byte rectangle reads
   // on into the next elements of the same workspace array (its last element: into the carve's alignment gap / the next array).
@@ -172,13 +217,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
     const size_t off = piece_stride ? (size_t)i * piece_stride : (size_t)(i / PRE_BLOCK) * 4u;
     return gsaj_load_f4_unaligned(piece_base + off);
   };
-  uint32_t id_cur = 0xffffffffu, id_nxt = 0xffffffffu;  // ids of entry e in the round being staged next / the one after
+  uint2 ent_nxt = make_uint2(0xffffffffu, 0u);  // record of entry e in the round after the one being staged next
   float4 piece = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (hi > range.x) {
+  uint32_t par = 0u;  // parity of the round (scalar): which half of ent_pos it reads
+  if (hi > 0u) {
     const uint32_t lo0 = round_lo(hi);
-    id_cur = load_id(lo0, hi);
-    id_nxt = load_id(round_lo(lo0), lo0);
-    piece = load_piece(id_cur);
+    const uint2 ent = load_ent(lo0, hi);
+    ent_nxt = load_ent(round_lo(lo0), lo0);
+    if (part == 2 && e < BWD_ROUND) ent_pos[0][e] = ent.y;
+    piece = load_piece(ent.x);
   }
 
 #ifdef GSAJ_BLOCK_TRACE
@@ -186,7 +233,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   unsigned tr_flushes = 0u, tr_slots = 0u;  // phase-2 batches of this wave, and the accepted entries in them
   unsigned long long pht_ = wall_clock64();
 #endif
-  while (hi > range.x) {
+  while (hi > 0u) {
     BWD_PH(6)
     const uint32_t lo = round_lo(hi);
     const int n = (int)(hi - lo);
@@ -222,11 +269,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
         }
       }
     }
-    {  // the next round's pieces, and the ids of the round after it (unconditional: past the list's head the rounds are empty)
+    {  // the next round's pieces and list indices, and the records of the round after it (unconditional: past the list's head the
+       // rounds are empty)
       const uint32_t lo2 = round_lo(lo);
-      id_cur = id_nxt;
-      id_nxt = load_id(round_lo(lo2), lo2);
-      piece = load_piece(id_cur);
+      const uint2 ent = ent_nxt;
+      ent_nxt = load_ent(round_lo(lo2), lo2);
+      if (part == 2 && e < BWD_ROUND) ent_pos[par ^ 1u][e] = ent.y;  // (its last readers finished before the previous round's final barrier)
+      piece = load_piece(ent.x);
     }
     {
       float4 *z = reinterpret_cast<float4 *>(acc);
@@ -236,16 +285,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
     __syncthreads();
     BWD_PH(1)
 
-    const uint32_t first_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lo - range.x));  // list index (0-based) of rec[0]; workgroup-uniform -> scalar
-    if (wmax > first_idx) {
-      // lane l tests entry l against this wave's quadrant (and its furthest last contributor)
-      bool rel = false;
-      if (lane < n && first_idx + (uint32_t)lane < wmax) {
-        const float4 q0 = rec[lane * REC_F4 + 0];
-        const float4 q1 = rec[lane * REC_F4 + 1];
-        // (conic back from its pre-scaled form: a = -2/log2e kx, b = -1/log2e ky, c = -2/log2e kz)
-        rel = quadrant_relevant(q0.x, q0.y, (-2.0f / GSAJ_LOG2E) * q1.x, (-1.0f / GSAJ_LOG2E) * q1.y, (-2.0f / GSAJ_LOG2E) * q1.z, q1.w, qx0, qy0);
-      }
+    const uint32_t *pos_r = ent_pos[par];
+    {
+      // lane l: did some pixel of this wave's quadrant take entry l?  (the forward's answer: no test of the entry here)
+      const bool rel = lane < n && ((pos_r[min(lane, BWD_ROUND - 1)] >> wave) & 1u) != 0u;
       unsigned long long todo = __builtin_amdgcn_ballot_w64(rel);
       int nslot = 0;      // accepted entries waiting in wu[] (wave-uniform)
       unsigned long long slot_pack = 0ull;  // byte s: round-local index j of the entry in slot s (wave-uniform: scalar registers)
@@ -324,7 +367,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
         float4 k = rec[jj * REC_F4 + 1], c = rec[jj * REC_F4 + 2];
         while (true) {
           const int j = jj;
-          const uint32_t idx = first_idx + (uint32_t)j;
+          const uint32_t idx4 = pos_r[j];  // the entry's list index << 4 | quadrant bits (wave-uniform; used far below)
           const bool more = todo != 0ull;
           if (more) {
             jj = 63 - __builtin_clzll(todo);
@@ -340,7 +383,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
           k = rec[jj * REC_F4 + 1];
           // alpha = min(0.99, o G) >= 1/255  <=>  o G >= 1/255: the clamp is applied after the mask (one select fewer); the
           // decision is the forward's bit for bit
-          const bool valid = idx < last && p2 <= 0.0f && oG >= (1.0f / 255.0f);
+          const bool valid = idx4 < last4 && p2 <= 0.0f && oG >= (1.0f / 255.0f);
           // (a chain of plain fmas: paired into v_pk_mul_f32 + adds -- what the compiler makes of the sum of products -- it costs more
           // cycles, a packed operation being worth 1.2 plain ones here, and needs its operands moved into register pairs)
           float cg = __builtin_fmaf(c.x, gC0, __builtin_fmaf(c.y, gC1, __builtin_fmaf(c.z, gC2, c.w * gD)));
@@ -399,6 +442,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
     __syncthreads();
     BWD_PH(5)
     hi = lo;
+    par ^= 1u;
   }
 #ifdef GSAJ_BLOCK_TRACE
   {
@@ -421,12 +465,40 @@ int launch_render_backward(int R, int W, int H, int grid_x, int grid_y, const fl
   {
     GsajProfScope ps(ST_RENDER_BWD, s);
     if (fl)
-      hipLaunchKernelGGL(k_render_bwd<true>, dim3(grid_x * grid_y, 1), dim3(256), 0, s, W, H, grid_x, im, b.point_list, g, bg, dL_dpix,
-                         dL_dpix_depth, b.inst_grad, b.reached, vs, *fl);
+      hipLaunchKernelGGL(k_render_bwd<true>, dim3(grid_x * grid_y, 1), dim3(256), 0, s, W, H, grid_x, im, b.point_list, b.taken, reinterpret_cast<uint2 *>(b.keys), g, bg,
+                         dL_dpix, dL_dpix_depth, b.inst_grad, b.reached, vs, *fl);
     else
-      hipLaunchKernelGGL(k_render_bwd<false>, dim3(grid_x * grid_y, views), dim3(256), 0, s, W, H, grid_x, im, b.point_list, g, bg, dL_dpix,
-                         dL_dpix_depth, b.inst_grad, b.reached, vs, FusedLoss{});
+      hipLaunchKernelGGL(k_render_bwd<false>, dim3(grid_x * grid_y, views), dim3(256), 0, s, W, H, grid_x, im, b.point_list, b.taken, reinterpret_cast<uint2 *>(b.keys), g, bg,
+                         dL_dpix, dL_dpix_depth, b.inst_grad, b.reached, vs, FusedLoss{});
   }
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}
+
+// debug (gsaj_debug_export_taken): the `taken` words of a view as the reverse compositor reads them -- byte q of a position
+// counts only below quadrant q's furthest last contributor (see the sweep above) -- for the whole of every tile list
+__global__ __launch_bounds__(256) void k_export_taken(int W, int H, int gx, ImageWS im, const uint32_t *__restrict__ taken,
+                                                      uint32_t *__restrict__ out) {
+  __shared__ uint32_t wave_max[4];
+  if (im.counters[4]) return;  // aborted async frame
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tile = blockIdx.x, ty = tile / gx, tx = tile - ty * gx;
+  const int px = tx * TILE + (wave & 1) * 8 + (lane & 7), py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
+  uint32_t wmax = (px < W && py < H) ? im.n_contrib[(size_t)py * W + px] : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, o));
+  if (lane == 0) wave_max[wave] = wmax;
+  __syncthreads();
+  const uint2 range = im.ranges[tile];
+  for (uint32_t p = (uint32_t)tid; p < range.y - range.x; p += 256u) {
+    const uint32_t keep = (p < wave_max[0] ? 0x1u : 0u) | (p < wave_max[1] ? 0x100u : 0u) | (p < wave_max[2] ? 0x10000u : 0u) |
+                          (p < wave_max[3] ? 0x1000000u : 0u);
+    out[range.x + p] = taken[range.x + p] & keep;
+  }
+}
+
+int launch_export_taken(int W, int H, int grid_x, int grid_y, const BinWS &b, const ImageWS &im, uint32_t *out, hipStream_t s) {
+  hipLaunchKernelGGL(k_export_taken, dim3(grid_x * grid_y), dim3(256), 0, s, W, H, grid_x, im, b.taken, out);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }

@@ -16,6 +16,8 @@
 // stops), not the reference's block-wide votes.  n_touched: lane l counts packed entry l, only while some pixel of the
 // quadrant still has T > 0.5, and ONE atomic wave-instruction per 64 entries flushes it (the reference issues one
 // atomic per pixel per entry, forward.cu:512-514).  Tiles are taken longest list first (ImageWS.tile_order).
+// Per list position and quadrant the wave also records whether ANY of its pixels took the entry (BinWS.taken, one byte store per
+// chunk): the reverse compositor stages only those entries.
 #include "gsaj_common.h"
 #include "loss_terms.h"
 #include "wave_reduce.h"
@@ -41,18 +43,20 @@ GSAJ_TRACE_DEFINE(fwd)
 // L1 terms of its pixels against the ground truth (loss_terms.h) and leaves the workgroup's four sums in fl.partials -- the loss
 // value without a pass of its own over the images.
 template <bool LOSS>
-__global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_render_fwd(int W, int H, int gx, int tiles, int P, ImageWS im,
+__global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_render_fwd(int W, int H, int gx, int tiles, int P, ImageWS im,
                                                     const float4 *__restrict__ splat, const float4 *__restrict__ splat16,
                                                     const float *__restrict__ bg,
                                                     float *__restrict__ out_color, float *__restrict__ out_depth,
                                                     float *__restrict__ out_opacity, int *__restrict__ n_touched,
-                                                    const uint32_t *__restrict__ point_list, ViewStrides vs, FusedLoss fl) {
+                                                    const uint32_t *__restrict__ point_list, uint32_t *__restrict__ taken,
+                                                    ViewStrides vs, FusedLoss fl) {
   {  // batched launch: blockIdx.y = view
     const size_t view = blockIdx.y, HWv = (size_t)H * W;
     im = image_view(im, view * vs.image);
     splat = gsaj_shift(splat, view * vs.geom);
     splat16 = gsaj_shift(splat16, view * vs.geom);
     point_list = gsaj_shift(point_list, view * vs.bin);
+    taken = gsaj_shift(taken, view * vs.bin);
     out_color += view * 3 * HWv;
     out_depth += view * HWv;
     out_opacity += view * HWv;
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
   const float qx0 = (float)(tx * TILE + (wave & 1) * 8), qy0 = (float)(ty * TILE + (wave >> 1) * 8);
   const uint2 range = ranges[tile];
 
-  bool done = !inside;
+  unsigned long long done_m = __builtin_amdgcn_ballot_w64(!inside);  // pixels that have stopped (wave-uniform mask)
   float T = 1.0f;
   uint32_t last = 0;
   bool counting = true;  // wave-uniform: some pixel of the quadrant still has T > 0.5 (only those can "touch")
@@ -106,10 +110,26 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
   // scalar, A before B; colour + depth accumulate as two packed pairs.  A pixel that skips an entry runs the same arithmetic
   // with weight 0: T, C, D come out unchanged.  Every operation is the one gsaj_power2 / the reverse compositor use (IEEE
   // mul / fma, packed or not): both passes decide on identical bits.
+  // The per-pixel decisions are kept as LANE MASKS in scalar registers, written out as such: `done_m` (pixels that have stopped),
+  // and per entry ok = (power <= 0) & (alpha >= 1/255) & ~done & ~saturated -- each term the ballot of one plain compare (one
+  // v_cmp writing a scalar pair), combined by scalar code.  Whether ANY pixel took an entry (BinWS.taken), how many took it with
+  // T > 0.5 (n_touched) and whether the whole quadrant has stopped are then scalar tests of masks that exist anyway.  The three
+  // selects an entry needs take the mask as it is (v_cndmask_b32 with a scalar-pair operand; the compiler offers no way to say
+  // "select by this mask" that does not first turn the mask into a per-lane value and compare it again).
+  auto sel = [](unsigned long long m, float a, float b) -> float {  // lane in m ? a : b
+    float r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
+    return r;
+  };
+  auto sel0 = [](unsigned long long m, float a) -> float {  // lane in m ? a : 0
+    float r;
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(a), "s"(m));
+    return r;
+  };
   v2f Crg = {0.f, 0.f}, Cbd = {0.f, 0.f};
   const v2f px2 = {pxf, pxf}, py2 = {pyf, pyf};
   auto composite2 = [&](const float4 p0, const float4 p1, const float4 p2, const float4 cA, const float4 cB, const float2 pos,
-                        float &T_afterA) {
+                        float &T_afterA, unsigned long long &okA, unsigned long long &okB) {
     const v2f dx = v2f{p0.x, p0.y} - px2, dy = v2f{p0.z, p0.w} - py2;
     const v2f t = v2f{p1.z, p1.w} * dy;
     const v2f u = v2f{p2.x, p2.y} * dy;
@@ -117,36 +137,36 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
     const v2f oe = v2f{p2.z, p2.w} * v2f{__builtin_amdgcn_exp2f(pw.x), __builtin_amdgcn_exp2f(pw.y)};
     {
       const float alpha0 = fminf(0.99f, oe.x);
-      bool ok = !done && pw.x <= 0.0f && alpha0 >= (1.0f / 255.0f);
       const float tA = __builtin_fmaf(-alpha0, T, T);
-      const bool sat = ok && tA < 0.0001f;  // this pixel is saturated: stop before this entry
-      done = done || sat;
-      ok = ok && !sat;
-      const float w = ok ? alpha0 * T : 0.f;
+      const unsigned long long pre = __builtin_amdgcn_ballot_w64(pw.x <= 0.0f) & __builtin_amdgcn_ballot_w64(alpha0 >= (1.0f / 255.0f)) & ~done_m;
+      const unsigned long long sat = pre & __builtin_amdgcn_ballot_w64(tA < 0.0001f);  // these pixels are saturated: they stop before this entry
+      done_m |= sat;
+      okA = pre & ~sat;
+      const float w = sel0(okA, alpha0 * T);
       const v2f w2 = {w, w};
       Crg = __builtin_elementwise_fma(v2f{cA.x, cA.y}, w2, Crg);
       Cbd = __builtin_elementwise_fma(v2f{cA.z, cA.w}, w2, Cbd);
-      T = ok ? tA : T;
-      last = ok ? __float_as_uint(pos.x) : last;
+      T = sel(okA, tA, T);
+      last = __float_as_uint(sel(okA, pos.x, __uint_as_float(last)));
       T_afterA = T;
     }
     {
       const float alpha0 = fminf(0.99f, oe.y);
-      bool ok = !done && pw.y <= 0.0f && alpha0 >= (1.0f / 255.0f);
       const float tB = __builtin_fmaf(-alpha0, T, T);
-      const bool sat = ok && tB < 0.0001f;
-      done = done || sat;
-      ok = ok && !sat;
-      const float w = ok ? alpha0 * T : 0.f;
+      const unsigned long long pre = __builtin_amdgcn_ballot_w64(pw.y <= 0.0f) & __builtin_amdgcn_ballot_w64(alpha0 >= (1.0f / 255.0f)) & ~done_m;
+      const unsigned long long sat = pre & __builtin_amdgcn_ballot_w64(tB < 0.0001f);
+      done_m |= sat;
+      okB = pre & ~sat;
+      const float w = sel0(okB, alpha0 * T);
       const v2f w2 = {w, w};
       Crg = __builtin_elementwise_fma(v2f{cB.x, cB.y}, w2, Crg);
       Cbd = __builtin_elementwise_fma(v2f{cB.z, cB.w}, w2, Cbd);
-      T = ok ? tB : T;
-      last = ok ? __float_as_uint(pos.y) : last;
+      T = sel(okB, tB, T);
+      last = __float_as_uint(sel(okB, pos.y, __uint_as_float(last)));
     }
   };
 
-  if (__builtin_amdgcn_ballot_w64(!done) != 0ull && range.x < range.y) {
+  if (~done_m != 0ull && range.x < range.y) {
     // two loads in a row per entry (id, then the row it names): ids are requested two chunks ahead and rows one chunk ahead,
     // so that neither round trip is waited for behind the other
     float4 q0, q1, q2;
@@ -197,7 +217,10 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       // lane l: #pixels of this wave that count packed entry l as "touched".  The four counts of a step (each <= 64) travel as
       // the bytes of ONE scalar word to the four lanes of the step (one compare + select per FOUR entries instead of per entry);
-      // every lane takes its byte after the loop
+      // every lane takes its byte after the loop.  Bit 7 of each byte: SOME pixel of the quadrant took the entry -- the reverse
+      // compositor's per-pixel test is this same decision on the same bits, so it stages only the entries some quadrant took
+      // (BinWS.taken, stored below).  The flag rides in the
+      // word that travels anyway: scalar code on the entry's `ok` mask.
       uint32_t cnt4 = 0u;
       bool wave_done = false;
       // two pairs per step; the pair of the next half-step is requested from LDS before this half-step's arithmetic
@@ -208,21 +231,19 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
         const int pb = (i >> 1) * FWD_PAIR_F4;
         const float4 c0 = rec[pb + 6], c1 = rec[pb + 7], c2 = rec[pb + 8], c3 = rec[pb + 9], c4 = rec[pb + 10];
         const float2 c5 = rec2[(pb + 11) * 2];
-        uint32_t pack = 0u;  // (scalar)
-        // "touched" (forward.cu:512-514): the pixel took the entry and is left with T > 0.5.  A pixel that takes an entry leaves
-        // with a strictly smaller T (alpha >= 1/255), one that does not keeps its T: "took it" is T_after < T_before -- two
-        // compares on registers, and T_after > 0.5 of the second entry is the "anyone still counting" test as well (a ballot of the
-        // accept flag itself -- or of any `a && b` -- is first materialised as 0 / 1 and compared again; the AND of two ballots of plain
-        // compares is two v_cmp and a scalar AND).
+        uint32_t pack;  // (scalar)
+        // "touched" (forward.cu:512-514): the pixel took the entry and is left with T > 0.5 -- the entry's `ok` mask and one
+        // compare; T_after > 0.5 of the second entry is the "anyone still counting" test as well.
         {
-          const float T0 = T;
           float Ta;
-          composite2(a0, a1, a2, a3, a4, a5, Ta);
+          unsigned long long okA, okB;
+          composite2(a0, a1, a2, a3, a4, a5, Ta, okA, okB);
+          pack = (okA != 0ull ? 0x80u : 0u) | (okB != 0ull ? 0x8000u : 0u);
           if (counting) {
             const unsigned long long hB = __builtin_amdgcn_ballot_w64(T > 0.5f);
-            const uint32_t nA = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(Ta > 0.5f) & __builtin_amdgcn_ballot_w64(Ta < T0));
-            const uint32_t nB = (uint32_t)__popcll(hB & __builtin_amdgcn_ballot_w64(T < Ta));
-            pack = nA | (nB << 8);
+            const uint32_t nA = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(Ta > 0.5f) & okA);
+            const uint32_t nB = (uint32_t)__popcll(hB & okB);
+            pack |= nA | (nB << 8);
             counting = hB != 0ull;
           }
         }
@@ -232,27 +253,38 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
         a0 = rec[pb + 12], a1 = rec[pb + 13], a2 = rec[pb + 14], a3 = rec[pb + 15], a4 = rec[pb + 16];
         a5 = rec2[(pb + 17) * 2];
         {
-          const float T0 = T;
           float Tc;
-          composite2(c0, c1, c2, c3, c4, c5, Tc);
+          unsigned long long okC, okD;
+          composite2(c0, c1, c2, c3, c4, c5, Tc, okC, okD);
+          pack |= (okC != 0ull ? 0x800000u : 0u) | (okD != 0ull ? 0x80000000u : 0u);
           if (counting) {
             const unsigned long long hD = __builtin_amdgcn_ballot_w64(T > 0.5f);
-            const uint32_t nC = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(Tc > 0.5f) & __builtin_amdgcn_ballot_w64(Tc < T0));
-            const uint32_t nD = (uint32_t)__popcll(hD & __builtin_amdgcn_ballot_w64(T < Tc));
+            const uint32_t nC = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(Tc > 0.5f) & okC);
+            const uint32_t nD = (uint32_t)__popcll(hD & okD);
             pack |= (nC << 16) | (nD << 24);
             counting = hD != 0ull;
           }
         }
         cnt4 = ((lane >> 2) == (i >> 2)) ? pack : cnt4;
-        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) {
+        if (~done_m == 0ull) {
           wave_done = true;
           break;
         }
       }
-      const int cnt = (int)((cnt4 >> (8 * (lane & 3))) & 0xffu);
+      const uint32_t mine = (cnt4 >> (8 * (lane & 3))) & 0xffu;  // of packed slot `lane`: touched count | took << 7
+      const int cnt = (int)(mine & 0x7fu);
       if (lane < nrel && cnt > 0) {
         const uint32_t id = __float_as_uint(recf[(lane >> 1) * FWD_PAIR_F4 * 4 + 22 + (lane & 1)]);
         atomicAdd(&n_touched[id], cnt);
+      }
+      // lane l: was list entry base + l taken by any pixel of this quadrant?  (the flag of its packed slot, fetched from the lane
+      // that holds it.)  One byte store per wave and chunk -- also for the chunk the wave breaks out of (the slots it never ran
+      // have flag 0); the four quadrant waves of a tile write the four bytes of a word and never touch each other's
+      const int slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(todo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)todo, 0u));
+      const uint32_t took = (uint32_t)__shfl((int)mine, slot) >> 7;
+      if (lane < m) {
+        // (address = scalar base of the chunk + a 32-bit lane offset: nothing per-lane is carried around the loop for it)
+        reinterpret_cast<uint8_t *>(taken + base)[(uint32_t)(lane * 4 + wave)] = rel ? (uint8_t)took : (uint8_t)0;
       }
       __builtin_amdgcn_wave_barrier();
       if (wave_done) break;  // whole quadrant saturated
@@ -260,8 +292,12 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
   }
 
   const float Cr = Crg.x, Cg = Crg.y, Cb = Cbd.x, Dp = Cbd.y;
+  // (the pixel's coordinates are formed again from the lane id: carried from the prologue they cost registers the whole walk long)
+  int lane_e = lane;
+  asm volatile("" : "+v"(lane_e));
+  const int px_e = tx * TILE + (wave & 1) * 8 + (lane_e & 7), py_e = ty * TILE + (wave >> 1) * 8 + (lane_e >> 3);
   if (inside) {
-    const size_t pid = (size_t)py * W + px;
+    const size_t pid = (size_t)py_e * W + px_e;
     const size_t HW = (size_t)H * W;
     final_T[pid] = T;
     n_contrib[pid] = last;
@@ -274,7 +310,7 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
   if (LOSS) {  // the loss terms of this quadrant's pixels, from the very values just stored
     float s4[4] = {0.f, 0.f, 0.f, 0.f};
     if (inside) {
-      const size_t pid = (size_t)py * W + px, HW = (size_t)H * W;
+      const size_t pid = (size_t)py_e * W + px_e, HW = (size_t)H * W;
       const LossConsts L = loss_consts(fl.flags, fl.alpha, fl.rgb_thr, fl.exp_a, fl.exp_b, HW, 1.f);
       const bool mask = fl.grad_mask ? fl.grad_mask[pid] != 0 : true;
       const float gd = L.mono ? 0.f : fl.gt_depth[pid];
@@ -307,10 +343,10 @@ int launch_render_forward(int P, int W, int H, int grid_x, int grid_y, const flo
     const unsigned nblk = FWD_WAVES == 1 ? (unsigned)((tiles + 7) / 8) * 32u : (unsigned)tiles;
     if (fl)
       hipLaunchKernelGGL(k_render_fwd<true>, dim3(nblk, 1), dim3(GSAJ_FWD_THREADS), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg,
-                         out_color, out_depth, out_opacity, n_touched, b.point_list, vs, *fl);
+                         out_color, out_depth, out_opacity, n_touched, b.point_list, b.taken, vs, *fl);
     else
       hipLaunchKernelGGL(k_render_fwd<false>, dim3(nblk, views), dim3(GSAJ_FWD_THREADS), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16,
-                         bg, out_color, out_depth, out_opacity, n_touched, b.point_list, vs, FusedLoss{});
+                         bg, out_color, out_depth, out_opacity, n_touched, b.point_list, b.taken, vs, FusedLoss{});
   }
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;

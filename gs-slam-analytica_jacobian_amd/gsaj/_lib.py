@@ -50,6 +50,7 @@ SIGNATURES = {
                                         c_float, c_float, P, P, P, P, P, P] + [P] * 12 + [P]),
     "gsaj_mark_visible": (c_int, [c_int, P, P, P, P, P]),
     "gsaj_debug_export": (c_int, [c_int] * 4 + [P] * 3 + [P] * 11 + [P]),
+    "gsaj_debug_export_taken": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
     "gsaj_debug_export_view_sums": (c_int, [c_int, P, P, P]),
     "gsaj_debug_export_view_sums_gather": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P]),
     "gsaj_profile_begin": (c_int, [c_int]),

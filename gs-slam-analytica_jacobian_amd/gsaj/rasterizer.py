@@ -212,6 +212,20 @@ def debug_export(P, R, W, H, geomBuffer, binningBuffer, imageBuffer):
     return out
 
 
+def debug_export_taken(R, W, H, binningBuffer, imageBuffer):
+    """(taken [R] int32 by list position, reached [R] uint8 by emission slot) of one view: which entries the forward compositor
+    took per quadrant (byte q of a word), cleared beyond each quadrant's furthest last contributor as the reverse compositor
+    reads them, and which instance rows the last backward wrote.  binningBuffer / imageBuffer: the view's own blocks."""
+    lib = _lib.load()
+    dev = binningBuffer.device
+    taken = torch.zeros((max(R, 1),), device=dev, dtype=torch.int32)
+    reached = torch.zeros((max(R, 1),), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gsaj_debug_export_taken(R, W, H, binningBuffer.data_ptr(), imageBuffer.data_ptr(), taken.data_ptr(),
+                                               reached.data_ptr(), _stream(dev)), "gsaj_debug_export_taken")
+    return taken[:R], reached[:R]
+
+
 STAGE_NAMES = ("preprocess,scan_blocks,emit_keys,sort,ranges_records,render_fwd,render_bwd,gaussian_bwd,tau_finalize,"
                "dense_bwd,dense_reduce,scatter_instances,tile_sort_records,gather_sums").split(",")
 

@@ -59,6 +59,10 @@ int gsaj_version(void);
 /* ---- workspace sizes (bytes) -------------------------------------------------------- */
 size_t gsaj_geom_workspace_bytes(int P);
 size_t gsaj_image_workspace_bytes(int W, int H);
+/* The binning workspace holds, per instance (one Gaussian in one tile's list): two 8-byte sort keys, the 4-byte list entry, a
+ * 48-byte partial-gradient row with its one-byte `reached` flag, and a 4-byte `taken` word -- one byte per 8x8 pixel quadrant of
+ * the tile, set by the forward compositor when some pixel of the quadrant composited the entry.  The reverse compositor stages only
+ * entries taken by some quadrant, and keeps their compacted list in the (by then idle) first sort-key buffer. */
 size_t gsaj_binning_workspace_bytes(int R);
 
 /* ---- per-call flags of the forward entry points (the library keeps NO process-wide mode: two threads may render
@@ -242,6 +246,15 @@ int gsaj_debug_export(int P, int R, int W, int H, const void *geom_ws, const voi
                       float *means2D, float *depths, float *cov3D, float *conic_opacity, float *rgb, uint8_t *clamped,
                       uint32_t *tiles_touched, uint32_t *point_list, uint32_t *ranges, float *final_T,
                       uint32_t *n_contrib, void *stream);
+
+/* What the forward compositor took, and what the reverse compositor wrote, of one view (its blocks of the binning and image
+ * workspaces; R = the capacity the binning workspace was carved for).  taken [R] u32, by position in point_list: byte q = 1 if
+ * some pixel of quadrant q (8x8 pixels; q = 2 * (lower half) + (right half)) of the position's tile composited that entry, as the
+ * reverse compositor reads it: bytes at or beyond the quadrant's furthest last contributor are cleared (they may be stale in the
+ * workspace); positions outside every tile list are left as the caller initialised them.  reached [R] u8, by emission slot: 1 = the
+ * last backward wrote that instance's row.  Either may be NULL. */
+int gsaj_debug_export_taken(int R, int W, int H, const void *binning_ws, const void *image_ws, uint32_t *taken /*dev [R]*/,
+                            uint8_t *reached /*dev [R]*/, void *stream);
 
 /* After gsaj_rasterize_backward_batch: the reverse compositor's 10 sums per Gaussian of ONE view of the window (that view's block
  * of the geometry workspace), sums [P,12] = (dL/dmean2D x, y | dL/dconic a, b, c | dL/dopacity | dL/dcolor r, g, b | dL/ddepth | 2

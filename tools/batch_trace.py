@@ -47,6 +47,8 @@ def main():
         assert fn(buf.ctypes.data, n) == 0
         s, e = buf[:, 0].astype(np.int64), buf[:, 1].astype(np.int64)
         ok = (s > 0) & (e >= s)
+        if not ok.any():  # (a kernel the window does not launch)
+            continue
         s, e = s[ok], e[ok]
         t0 = s.min()
         life = (e - s) * 0.01
@@ -67,6 +69,36 @@ def main():
             print("      phases (us, mean): %s = %s" % (labels, " / ".join("%.1f" % (x.astype(np.int64).mean() * 0.01) for x in ph)))
         if name == "bwd":
             bwd_phases(lib, n)
+    bwd_rounds(bc, K, P, W, H)
+
+
+def bwd_rounds(bc, K, P, W, H):
+    """Rounds of 48 entries per tile of the reverse compositor, from the forward state of the last window (any build): over the
+    tile's furthest last contributor (what a walk of consecutive entries stages) and over the entries some quadrant took (what
+    the kernel stages: gsaj_debug_export_taken)."""
+    from gsaj import rasterizer as C
+
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    tiles = lists = last = live = r_last = r_live = 0
+    for v in range(K):
+        blk = lambda buf, stride: buf[v * stride:(v + 1) * stride]  # noqa: E731
+        dbg = C.debug_export(P, bc.capacity, W, H, blk(bc.geom, bc.geom_stride), blk(bc.binning, bc.bin_stride), blk(bc.img, bc.img_stride))
+        taken, _ = C.debug_export_taken(bc.capacity, W, H, blk(bc.binning, bc.bin_stride), blk(bc.img, bc.img_stride))
+        nc = np.zeros((gy * 16, gx * 16), np.int64)
+        nc[:H, :W] = dbg["n_contrib"].cpu().numpy()
+        bmax = nc.reshape(gy, 16, gx, 16).max(axis=(1, 3)).reshape(-1)
+        rg = dbg["ranges"].cpu().numpy().astype(np.int64)
+        csum = np.concatenate([[0], np.cumsum(taken.cpu().numpy() != 0)])
+        nl = csum[rg[:, 1]] - csum[rg[:, 0]]
+        tiles += len(bmax)
+        lists += int((rg[:, 1] - rg[:, 0]).sum())
+        last += int(bmax.sum())
+        live += int(nl.sum())
+        r_last += int((-(-bmax // 48)).sum())
+        r_live += int((-(-nl // 48)).sum())
+    print("      bwd per tile (mean over %d tiles): list %.1f, furthest last contributor %.1f, live in some quadrant %.1f (%.0f %%); rounds of 48 "
+          "over the last contributor %.2f, over the live entries %.2f"
+          % (tiles, lists / tiles, last / tiles, live / tiles, 100.0 * live / max(last, 1), r_last / tiles, r_live / tiles))
 
 
 def bwd_phases(lib, n):
