@@ -6,8 +6,9 @@ densification bookkeeping fed by a backward (add_densification_stats :767-771, m
 one device launch, gsaj_densification_stats) and parameter I/O in the reference's formats
 (load_tensors :70-138, save_ply :402-436, load_ply :453-542; gsaj.model_io), and map growth from a keyframe
 (create_pcd_from_image[_and_depth] :183-279, extend_from_pcd[_seq] :284-319: on the device, gsaj.seeding, where the reference
-goes through NumPy and Open3D).  The densify / prune / general optimiser-surgery logic (:321-765) stays the caller's; the one
-piece of it this path needs -- new rows enter an attached Adam with zero moments, cat_tensors_to_optimizer :599-631 -- is here.
+goes through NumPy and Open3D).  The densify / general optimiser-surgery logic (:321-765) stays the caller's; the two pieces of
+it this path needs are here: new rows enter an attached Adam with zero moments (cat_tensors_to_optimizer :599-631), and rows
+leave the map and the Adam state under a mask (prune_points, _prune_optimizer :559-597: one device launch, gsaj.pruning).
 """
 import torch
 
@@ -288,3 +289,59 @@ class GaussianModel:
     def extend_from_pcd_seq(self, cam_info, kf_id=-1, init=False, scale=2.0, depthmap=None):
         fused_point_cloud, features, scales, rots, opacities = self.create_pcd_from_image(cam_info, init, scale=scale, depthmap=depthmap)
         self.extend_from_pcd(fused_point_cloud, features, scales, rots, opacities, kf_id)
+
+    # ---- map pruning (reference :559-597) ---------------------------------------------------------------------------------
+    def prune_points(self, mask, n_kept=None):
+        """Reference prune_points + _prune_optimizer (:559-597): remove the rows where mask (bool or uint8 [P] on the device) is
+        set.  One plan and one launch (gsaj.pruning.CompactPlan) move the six parameters, exp_avg / exp_avg_sq of every group of
+        an attached optimizer that has state, xyz_gradient_accum, denom and max_radii2D, and unique_kfIDs / n_obs where those
+        live on the device; host-resident ones are indexed on the host with the mask copied once (the reference's .cpu(),
+        :596-597).  The new parameters are leaf tensors that replace the old ones in their optimizer groups; a group's state
+        moves to the new key with every other entry (step) untouched, as in extend_from_pcd.  n_kept: the number of rows that
+        stay, when the caller has it (P minus the n_pruned of CovisibilityWindow.prune_mask, read with its other scalars):
+        then nothing is read here.  Returns the plan, for CovisibilityWindow.compact_plan.  A rasteriser context is sized for a
+        fixed P: build a new one afterwards."""
+        from gsaj.pruning import CompactPlan
+        plan = CompactPlan(mask, remove=True, n_kept=n_kept)
+        names = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
+        old = dict(zip(names, (self._xyz, self._features_dc, self._features_rest, self._opacity, self._scaling, self._rotation)))
+        moved = [(("param", n), old[n].detach().contiguous()) for n in names]
+        states = {}
+        if self.optimizer is not None:
+            for group in self.optimizer.param_groups:
+                assert len(group["params"]) == 1
+                name = group["name"]
+                if group["params"][0] is not old[name]:
+                    from gsaj._lib import GsajError
+                    raise GsajError("prune_points: optimizer group %r does not hold the model's parameter of that name" % name)
+                state = self.optimizer.state.get(old[name], None)
+                if state is not None and "exp_avg" in state:
+                    states[name] = state
+                    moved += [((key, name), state[key].contiguous()) for key in ("exp_avg", "exp_avg_sq")]
+        aux = [a for a in ("xyz_gradient_accum", "denom", "max_radii2D") if getattr(self, a, None) is not None]
+        ids = [a for a in ("unique_kfIDs", "n_obs") if getattr(self, a, None) is not None]
+        dev = plan.dev
+        moved += [(("aux", a), getattr(self, a).contiguous()) for a in aux + ids if getattr(self, a).device == dev]
+        out = dict(zip([k for k, _ in moved], plan.apply(*[t for _, t in moved])))
+
+        new = {n: out[("param", n)].requires_grad_(True) for n in names}
+        if self.optimizer is not None:
+            for group in self.optimizer.param_groups:
+                name = group["name"]
+                state = self.optimizer.state.pop(old[name], None)
+                if name in states:
+                    state["exp_avg"], state["exp_avg_sq"] = out[("exp_avg", name)], out[("exp_avg_sq", name)]
+                group["params"][0] = new[name]
+                if state is not None:
+                    self.optimizer.state[new[name]] = state
+        self._xyz, self._features_dc, self._features_rest = new["xyz"], new["f_dc"], new["f_rest"]
+        self._opacity, self._scaling, self._rotation = new["opacity"], new["scaling"], new["rotation"]
+        keep_host = None
+        for a in aux + ids:
+            if ("aux", a) in out:
+                setattr(self, a, out[("aux", a)])
+            else:
+                if keep_host is None:
+                    keep_host = plan.keep_mask().cpu()
+                setattr(self, a, getattr(self, a)[keep_host.to(getattr(self, a).device)])
+        return plan

@@ -93,6 +93,10 @@ SIGNATURES = {
     "gsaj_covis_pack": (c_int, [c_int, c_int, P, ctypes.POINTER(c_int), ctypes.c_uint32, P, P]),
     "gsaj_covis_query": (c_int, [c_int, P, P, c_int, ctypes.c_uint32, P, P]),
     "gsaj_covis_prune_mask": (c_int, [c_int, P, ctypes.c_uint32, P, c_int, c_int, P, P, P, P]),
+    "gsaj_compact_workspace_bytes": (c_size_t, [c_int]),
+    "gsaj_compact_plan": (c_int, [c_int, P, c_int, P, P]),
+    "gsaj_compact_count": (c_int, [P, P, ctypes.POINTER(c_int)]),
+    "gsaj_compact_rows": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), P, P]),
 }
 
 _lib = None

@@ -127,7 +127,8 @@ class CovisibilityWindow:
         """The reference's to_prune (utils/slam_backend.py:246-263) over the keyframes `window` (ids this object holds):
         -> (to_prune uint8 [P], n_pruned int32 [1]), both on the device; self.n_obs [P] holds the observation counts.
         mode "odometry": n_obs < 3.  mode "slam": n_obs <= 3 and unique_kfIDs (int32 [P]) >= the third-newest id of the window, or
-        >= 0 while not initialised.  Only the mask is produced: removing the rows is the caller's, then compact(~to_prune)."""
+        >= 0 while not initialised.  Only the mask is produced: GaussianModel.prune_points(to_prune) removes the rows and returns the plan for compact_plan(); a
+        caller who removes them another way follows with compact(~to_prune)."""
         if mode not in PRUNE_MODES:
             raise _lib.GsajError("prune_mask: mode must be one of %s (got %r)" % (sorted(PRUNE_MODES), mode))
         window = list(window)
@@ -157,6 +158,19 @@ class CovisibilityWindow:
         if words.numel() == 0:
             raise _lib.GsajError("compact: no row is kept")
         self.words, self.P = words.contiguous(), int(words.numel())
+        self._alloc_rows()
+
+    def compact_plan(self, plan):
+        """compact() through the plan the map was pruned with (gsaj.pruning.CompactPlan, what GaussianModel.prune_points returns):
+        the words go through the same device compaction, with no further host read.  Leaves the window exactly as
+        compact(keep) would.  (A plan made from this object's to_prune keeps that tensor: the new buffers are new tensors.)"""
+        from .pruning import CompactPlan
+        if not isinstance(plan, CompactPlan) or plan.dev != self.words.device or plan.P != self.P:
+            raise _lib.GsajError("compact_plan: needs a CompactPlan of %d rows on %s" % (self.P, self.words.device))
+        if plan.n_kept == 0:
+            raise _lib.GsajError("compact: no row is kept")
+        self.words = plan.apply(self.words)[0]
+        self.P = int(self.words.numel())
         self._alloc_rows()
 
     # ---- the reference's form ---------------------------------------------------------------------------------------

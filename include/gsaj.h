@@ -543,6 +543,31 @@ int gsaj_covis_prune_mask(int P, const uint32_t *words, uint32_t window_mask, co
                           int kf_id_min, int max_obs, uint8_t *to_prune /*dev [P]*/, int *n_obs /*dev [P] or NULL*/,
                           int *n_pruned /*dev [1]*/, void *stream);
 
+/* ---- removing rows of the map under a mask (csrc/compact.hip) ---------------------------
+ * The reference's prune_points (gaussian_splatting/scene/gaussian_model.py:559-597) indexes every parameter, Adam moment and
+ * bookkeeping vector with one boolean mask, t[mask] each.  Here ONE pass over the mask plans the move and ONE launch moves the
+ * kept rows of up to GSAJ_COMPACT_MAX_TENSORS tensors.  keep(i) = (mask[i] != 0) != (mask_is_remove != 0) -- any non-zero byte
+ * is set; P' = number of kept rows.
+ *
+ * gsaj_compact_plan: counts the kept rows per block of 256 and scans the counts into block offsets.  No host read.
+ *   compact_ws: gsaj_compact_workspace_bytes(P) bytes, P / 256 + O(1) words.  The plan remembers the mask's ADDRESS: the mask
+ *   must stay where it is, unchanged, until the last gsaj_compact_rows of the plan has run.
+ * gsaj_compact_count: *n_kept = P' (host).  The one blocking read, 4 bytes; a caller who knows P' already need not call it.
+ * gsaj_compact_rows: for every t < n_tensors, dst[t] = the kept rows of src[t], row_bytes[t] bytes each, in the STABLE order
+ *   (what t[keep] gives, bit for bit).  dst[t] holds P' rows; nothing outside those rows is written; src and mask are not
+ *   modified.  P is the plan's P: with any other value nothing is read or written.  With P' = 0 nothing is written either
+ *   (every workgroup returns at once); a caller who knows P' = 0 launches nothing, as gsaj.pruning does.  A plan stays valid
+ *   until its workspace is reused; several gsaj_compact_rows calls may follow one plan.  src[t] and dst[t] must not overlap:
+ *   destinations precede sources in a stable compaction, so an in-place form would race between workgroups.
+ * GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: P <= 0, a null pointer (in src / dst too), n_tensors outside
+ *   1..GSAJ_COMPACT_MAX_TENSORS, a row size that is not a positive multiple of 4 or exceeds 4096, src[t] == dst[t]. */
+#define GSAJ_COMPACT_MAX_TENSORS 32
+size_t gsaj_compact_workspace_bytes(int P);
+int gsaj_compact_plan(int P, const uint8_t *mask /*dev [P]*/, int mask_is_remove, void *compact_ws, void *stream);
+int gsaj_compact_count(const void *compact_ws, void *stream, int *n_kept /*host*/);
+int gsaj_compact_rows(int P, int n_tensors, const void *const *src /*host [n] of dev*/, void *const *dst /*host [n] of dev*/,
+                      const int *row_bytes /*host [n]*/, const void *compact_ws, void *stream);
+
 /* ---- dense analytic path (NumPy-path semantics) ------------------ */
 size_t gsaj_dense_workspace_bytes(int N, int W, int H);
 /* N depth-sorted Gaussians: means2D [N,2] (pixels), covs2D [N,2,2], colors [N,3], depths [N], opac [N];
