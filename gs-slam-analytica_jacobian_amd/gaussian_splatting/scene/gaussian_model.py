@@ -6,9 +6,11 @@ densification bookkeeping fed by a backward (add_densification_stats :767-771, m
 one device launch, gsaj_densification_stats) and parameter I/O in the reference's formats
 (load_tensors :70-138, save_ply :402-436, load_ply :453-542; gsaj.model_io), and map growth from a keyframe
 (create_pcd_from_image[_and_depth] :183-279, extend_from_pcd[_seq] :284-319: on the device, gsaj.seeding, where the reference
-goes through NumPy and Open3D).  The densify / general optimiser-surgery logic (:321-765) stays the caller's; the two pieces of
-it this path needs are here: new rows enter an attached Adam with zero moments (cat_tensors_to_optimizer :599-631), and rows
-leave the map and the Adam state under a mask (prune_points, _prune_optimizer :559-597: one device launch, gsaj.pruning).
+goes through NumPy and Open3D).  The optimiser surgery of the mapping loop is here too: training_setup (:321-370, plain torch),
+new rows enter an attached Adam with zero moments (cat_tensors_to_optimizer :599-631), rows leave the map and the Adam state
+under a mask (prune_points, _prune_optimizer :559-597: one device launch, gsaj.pruning), and the consumer of the densification
+statistics, densify_and_prune / densify_and_clone / densify_and_split (:669-765), is one plan, one 16-byte read, one launch that
+moves every tensor and one that computes the children (gsaj.densify).  reset_opacity* and update_learning_rate stay the caller's.
 """
 import torch
 
@@ -29,7 +31,9 @@ class GaussianModel:
         self.config = config
         self.isotropic = False
         self.optimizer = None
-        self.seed = 0  # seed of the next keyframe's down-sample (create_pcd_from_image_and_depth); advanced by every call
+        self.seed = 0  # seed of the next keyframe's down-sample (create_pcd_from_image_and_depth) or split; advanced by every call
+        self.percent_dense = 0.01  # (training_setup takes it from the training arguments)
+        self.spatial_lr_scale = 0
 
     @classmethod
     def from_activated(cls, xyz, scales, rotations, opacities, shs, sh_degree=3, active_sh_degree=None,
@@ -345,3 +349,119 @@ class GaussianModel:
                     keep_host = plan.keep_mask().cpu()
                 setattr(self, a, getattr(self, a)[keep_host.to(getattr(self, a).device)])
         return plan
+
+    # ---- optimiser + densification (reference :321-370, :599-765) ---------------------------------------------------------
+    def training_setup(self, training_args):
+        """Reference :321-370 on the parameters' own device: percent_dense, zeroed xyz_gradient_accum / denom, and an Adam
+        (lr=0.0, eps=1e-15) of six one-parameter groups named xyz, f_dc, f_rest, opacity, scaling, rotation with the reference's
+        learning rates.  The schedule's numbers are kept (lr_init, lr_final, lr_delay_mult, max_steps); applying it,
+        update_learning_rate, stays the caller's."""
+        a = training_args
+        self.percent_dense = a.percent_dense
+        n, dev = self._xyz.shape[0], self._xyz.device
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+        self.denom = torch.zeros((n, 1), device=dev)
+        groups = [{"params": [self._xyz], "lr": a.position_lr_init * self.spatial_lr_scale, "name": "xyz"},
+                  {"params": [self._features_dc], "lr": a.feature_lr, "name": "f_dc"},
+                  {"params": [self._features_rest], "lr": a.feature_lr / 20.0, "name": "f_rest"},
+                  {"params": [self._opacity], "lr": a.opacity_lr, "name": "opacity"},
+                  {"params": [self._scaling], "lr": a.scaling_lr * self.spatial_lr_scale, "name": "scaling"},
+                  {"params": [self._rotation], "lr": a.rotation_lr, "name": "rotation"}]
+        self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        self.lr_init = a.position_lr_init * self.spatial_lr_scale
+        self.lr_final = a.position_lr_final * self.spatial_lr_scale
+        self.lr_delay_mult = a.position_lr_delay_mult
+        self.max_steps = a.position_lr_max_steps
+
+    def _densify(self, plan, seed, noise, who):
+        """Send the model through a gsaj.densify.DensifyPlan: the six parameters (a new row gets its parent's), exp_avg /
+        exp_avg_sq of every optimizer group that has state (a new row gets zeros; step and every other entry untouched),
+        unique_kfIDs / n_obs (the parent's, int32; host-resident ones are indexed with plan.source_rows() after one copy), all in
+        one rows launch; then the children's xyz and _scaling; xyz_gradient_accum, denom, max_radii2D become zeros of the new size."""
+        from gsaj._lib import GsajError
+        names = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
+        old = dict(zip(names, (self._xyz, self._features_dc, self._features_rest, self._opacity, self._scaling, self._rotation)))
+        src = {n: old[n].detach().contiguous() for n in names}
+        moved = [(("param", n), src[n], "parent") for n in names]
+        states = {}
+        if self.optimizer is not None:
+            for group in self.optimizer.param_groups:
+                assert len(group["params"]) == 1
+                name = group["name"]
+                if group["params"][0] is not old[name]:
+                    raise GsajError("%s: optimizer group %r does not hold the model's parameter of that name" % (who, name))
+                state = self.optimizer.state.get(old[name], None)
+                if state is not None and "exp_avg" in state:
+                    states[name] = state
+                    moved += [((key, name), state[key].contiguous(), "zeros") for key in ("exp_avg", "exp_avg_sq")]
+        dev = plan.dev
+        ids = [a for a in ("unique_kfIDs", "n_obs") if getattr(self, a, None) is not None]
+        on_host = [a for a in ids if getattr(self, a).device != dev]
+        moved += [(("aux", a), getattr(self, a).int().contiguous(), "parent") for a in ids if a not in on_host]
+        if on_host:
+            moved.append((("rows", None), torch.arange(plan.P, dtype=torch.int32, device=dev), "parent"))
+        out = dict(zip([k for k, _, _ in moved], plan.apply([t for _, t, _ in moved], new_rows=[m for _, _, m in moved])))
+        plan.children(src["xyz"], src["scaling"], src["rotation"], out[("param", "xyz")], out[("param", "scaling")], noise=noise, seed=seed)
+
+        new = {n: out[("param", n)].requires_grad_(True) for n in names}
+        if self.optimizer is not None:
+            for group in self.optimizer.param_groups:
+                name = group["name"]
+                state = self.optimizer.state.pop(old[name], None)
+                if name in states:
+                    state["exp_avg"], state["exp_avg_sq"] = out[("exp_avg", name)], out[("exp_avg_sq", name)]
+                group["params"][0] = new[name]
+                if state is not None:
+                    self.optimizer.state[new[name]] = state
+        self._xyz, self._features_dc, self._features_rest = new["xyz"], new["f_dc"], new["f_rest"]
+        self._opacity, self._scaling, self._rotation = new["opacity"], new["scaling"], new["rotation"]
+        n = plan.n_out
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+        self.denom = torch.zeros((n, 1), device=dev)
+        self.max_radii2D = torch.zeros((n,), device=dev)
+        rows_host = None
+        for a in ids:
+            if a in on_host:
+                if rows_host is None:
+                    rows_host = out[("rows", None)].cpu().long()
+                setattr(self, a, getattr(self, a)[rows_host.to(getattr(self, a).device)].int())
+            else:
+                setattr(self, a, out[("aux", a)])
+        return plan
+
+    def _densify_seed(self, seed, noise):
+        if noise is None and seed is None:
+            seed, self.seed = self.seed, self.seed + 1
+        return 0 if seed is None else seed
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, seed=None, noise=None, counts=None):
+        """Reference densify_and_prune (:750-765) with its densify_and_clone, densify_and_split (N = 2) and final prune_points, from
+        the statistics xyz_gradient_accum / denom: one plan, one 16-byte read (none with counts = the plan's four), one rows
+        launch, one children launch, three torch.zeros.  Output order and every copied bit are the reference's (include/gsaj.h
+        has the rules and the kept quirks).  The children's positions are drawn from noise [2,P,3] (standard normal, indexed by
+        source row) or, noise=None, from the counter-based generator under seed; seed=None takes and advances self.seed.
+        Returns the plan, for CovisibilityWindow.densify_plan.  A rasteriser context is sized for a fixed P: build a new one."""
+        from gsaj.densify import DensifyPlan
+        plan = DensifyPlan(self.xyz_gradient_accum, self.denom, self._scaling, self._opacity, max_grad, min_opacity, extent,
+                           max_screen_size, percent_dense=self.percent_dense, N=2, counts=counts)
+        return self._densify(plan, self._densify_seed(seed, noise), noise, "densify_and_prune")
+
+    def densify_and_clone(self, grads, grad_threshold, scene_extent, counts=None):
+        """Reference densify_and_clone (:719-748): grads [P,1] or [P]; rows with |grads| >= grad_threshold and largest scale
+        <= percent_dense * scene_extent are appended behind the map.  Nothing is pruned."""
+        from gsaj.densify import CLONE, DensifyPlan
+        if grads.numel() != self._xyz.shape[0]:
+            from gsaj._lib import GsajError
+            raise GsajError("densify_and_clone: grads must have one value per Gaussian (%d), got %s" % (self._xyz.shape[0], list(grads.shape)))
+        plan = DensifyPlan(grads, None, self._scaling, self._opacity, grad_threshold, 0.0, scene_extent, None,
+                           percent_dense=self.percent_dense, N=1, stages=CLONE, counts=counts)
+        return self._densify(plan, 0, None, "densify_and_clone")
+
+    def densify_and_split(self, grads, grad_threshold, scene_extent, N=2, seed=None, noise=None, counts=None):
+        """Reference densify_and_split (:669-717): grads of at most P values (the rows behind them have gradient 0); rows with
+        grads >= grad_threshold and largest scale > percent_dense * scene_extent leave the map and N children each are appended,
+        copy by copy.  noise [N,P,3] / seed as in densify_and_prune."""
+        from gsaj.densify import SPLIT, DensifyPlan
+        plan = DensifyPlan(grads, None, self._scaling, self._opacity, grad_threshold, 0.0, scene_extent, None,
+                           percent_dense=self.percent_dense, N=N, stages=SPLIT, counts=counts)
+        return self._densify(plan, self._densify_seed(seed, noise), noise, "densify_and_split")

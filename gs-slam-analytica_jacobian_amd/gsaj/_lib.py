@@ -97,6 +97,13 @@ SIGNATURES = {
     "gsaj_compact_plan": (c_int, [c_int, P, c_int, P, P]),
     "gsaj_compact_count": (c_int, [P, P, ctypes.POINTER(c_int)]),
     "gsaj_compact_rows": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), P, P]),
+    "gsaj_densify_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsaj_densify_plan": (c_int, [c_int] * 4 + [P, P, c_int, P, P] + [c_float] * 4 + [c_int, c_int, P, P, P]),
+    "gsaj_densify_counts": (c_int, [P, P, ctypes.POINTER(c_int)]),
+    "gsaj_densify_rows": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_int),
+                                  ctypes.POINTER(c_int), P, P, P]),
+    "gsaj_densify_children": (c_int, [c_int, c_int, c_int, P, P, P, P, ctypes.c_uint64, P, P, P, P, P]),
+    "gsaj_densify_noise": (c_int, [c_int, c_int, ctypes.c_uint64, P, P]),
 }
 
 _lib = None

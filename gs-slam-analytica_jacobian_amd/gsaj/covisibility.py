@@ -173,6 +173,19 @@ class CovisibilityWindow:
         self.P = int(self.words.numel())
         self._alloc_rows()
 
+    def densify_plan(self, plan):
+        """Follow a map update (gsaj.densify.DensifyPlan, what GaussianModel.densify_and_prune returns): a surviving original keeps
+        its word, a new row (clone or child) starts with 0, it has been seen from no keyframe yet.  The words go through the
+        plan's rows launch, with no further host read."""
+        from .densify import DensifyPlan
+        if not isinstance(plan, DensifyPlan) or plan.dev != self.words.device or plan.P != self.P:
+            raise _lib.GsajError("densify_plan: needs a DensifyPlan of %d rows on %s" % (self.P, self.words.device))
+        if plan.n_out == 0:
+            raise _lib.GsajError("densify_plan: no row is left")
+        self.words = plan.apply([self.words], new_rows="zeros")[0]
+        self.P = int(self.words.numel())
+        self._alloc_rows()
+
     # ---- the reference's form ---------------------------------------------------------------------------------------
     def as_reference_dict(self):
         """{kf_id: int64 [P] of 0 / 1}, what the reference calls occ_aware_visibility (new tensors)."""

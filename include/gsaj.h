@@ -568,6 +568,56 @@ int gsaj_compact_count(const void *compact_ws, void *stream, int *n_kept /*host*
 int gsaj_compact_rows(int P, int n_tensors, const void *const *src /*host [n] of dev*/, void *const *dst /*host [n] of dev*/,
                       const int *row_bytes /*host [n]*/, const void *compact_ws, void *stream);
 
+/* ---- map densification: clone, split and prune from one plan (csrc/densify_prune.hip) --------------------------------------------
+ * The reference's densify_and_prune (gaussian_splatting/scene/gaussian_model.py:599-765: densify_and_clone, densify_and_split with
+ * its prune of the parents, and the final prune_points) as one classification of the P source rows and one move of every tensor.
+ * All comparisons are fp32; the caller rounds every threshold to fp32 once: t_dense = fl32(percent_dense * extent),
+ * t_big = fl32(0.1 * extent), grad_threshold, min_opacity.  Per row i: g = accum[i] / denom[i] with NaN -> 0 (denom == NULL:
+ * g = accum[i] for i < n_grads, else 0 -- the padded_grad of densify_and_split), m = max_j exp(scaling[i][j]), o = sigmoid(opacity[i]).
+ *   clone  (stage GSAJ_DENSIFY_CLONE):  |g| >= grad_threshold and m <= t_dense
+ *   split  (stage GSAJ_DENSIFY_SPLIT):  g >= grad_threshold and m > t_dense; the parent leaves, N children enter
+ *   prune  (stage GSAJ_DENSIFY_PRUNE):  a row goes if o < min_opacity, or if size_rule and (size_all or m > t_big); a clone
+ *          stands or falls with its original; a child uses its parent's opacity and its own m = max_j exp(log(exp(s_ij) / d)),
+ *          d = fl32(0.8 N), and the N children of a parent stand or fall together.
+ * Kept quirks of the reference: size_rule is bool(max_screen_size), so None and 0 switch the size terms off; size_all is
+ * 0 > max_screen_size, the reference's max_radii2D > max_screen_size evaluated on the zeros densification_postfix has just
+ * written (true only for a negative size); the clone test takes |g| and the split test g; a zero quaternion gives NaN children.
+ * grad_threshold must be greater than 0 (at or below 0 the reference would split the clones it has just appended).
+ * code [P]: bit 0 the original is emitted, bit 1 a clone, bit 2 the children.  Output order (the reference's cat, prune, prune):
+ * kept originals not split, kept clones, then the kept children of copy 0, copy 1, ... copy N - 1, each in source-row order.
+ * gsaj_densify_counts: the one blocking read, 16 bytes: {originals, clones, children per copy, P''}, P'' = originals + clones +
+ *   N children.
+ * gsaj_densify_rows: dst[t] [P'', row_bytes[t]] from src[t] [P, row_bytes[t]]: an original keeps its row; a new row (clone,
+ *   child) gets its parent's row, or zeros where zero_new[t] is set (Adam moments).  src[t] != dst[t].  Several calls may follow one plan.
+ * gsaj_densify_children: overwrites the child rows of dst_xyz [P'',3] and dst_scaling [P'',S] with
+ *   R(q_i) (exp(s_i) o z_{i,n}) + xyz_i (R: the reference's build_rotation, normalised by the fp32 norm; S = 1: the one scale
+ *   multiplies the three components) and log(exp(s_i) / d).  noise [N,P,3] is indexed by SOURCE row; NULL: Philox4x32-10 with
+ *   key (seed low, seed high) and counter (i, n, 0, 0): u1 = ((x0 >> 9) + 0.5) 2^-23, u2 = (x1 >> 8) 2^-24, r = sqrt(-2 ln u1),
+ *   z0 = r cos(2 pi u2), z1 = r sin(2 pi u2), z2 from (x2, x3) the same way, cosine branch.  gsaj_densify_noise writes exactly
+ *   those draws for every (n, i).  They depend on (seed, i, n) only.
+ * GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: P <= 0 or P (N + 1) > INT_MAX, S not 1 or 3, N outside
+ *   1..GSAJ_DENSIFY_MAX_SPLIT, grad_threshold not greater than 0, stages outside the mask, n_grads outside 0..P without denom,
+ *   a null pointer (noise and denom excepted), n_tensors outside 1..GSAJ_DENSIFY_MAX_TENSORS, a row size that is not a positive
+ *   multiple of 4 or exceeds 4096, a source equal to its destination. */
+#define GSAJ_DENSIFY_MAX_TENSORS 32
+#define GSAJ_DENSIFY_MAX_SPLIT 4
+#define GSAJ_DENSIFY_CLONE 1
+#define GSAJ_DENSIFY_SPLIT 2
+#define GSAJ_DENSIFY_PRUNE 4
+size_t gsaj_densify_workspace_bytes(int P, int N);
+int gsaj_densify_plan(int P, int S, int N, int stages, const float *accum /*dev [P]*/, const float *denom /*dev [P] or NULL*/,
+                      int n_grads, const float *scaling /*dev [P,S]*/, const float *opacity /*dev [P]*/, float grad_threshold,
+                      float t_dense, float t_big, float min_opacity, int size_rule, int size_all, uint8_t *code /*dev [P]*/,
+                      void *densify_ws, void *stream);
+int gsaj_densify_counts(const void *densify_ws, void *stream, int *counts /*host [4]*/);
+int gsaj_densify_rows(int P, int N, int n_tensors, const void *const *src /*host [n] of dev*/, void *const *dst /*host [n] of dev*/,
+                      const int *row_bytes /*host [n]*/, const int *zero_new /*host [n]*/, const uint8_t *code, const void *densify_ws,
+                      void *stream);
+int gsaj_densify_children(int P, int S, int N, const float *xyz, const float *scaling, const float *rotation,
+                          const float *noise /*dev [N,P,3] or NULL*/, uint64_t seed, const uint8_t *code, const void *densify_ws,
+                          float *dst_xyz /*dev [P'',3]*/, float *dst_scaling /*dev [P'',S]*/, void *stream);
+int gsaj_densify_noise(int P, int N, uint64_t seed, float *out /*dev [N,P,3]*/, void *stream);
+
 /* ---- dense analytic path (NumPy-path semantics) ------------------ */
 size_t gsaj_dense_workspace_bytes(int N, int W, int H);
 /* N depth-sorted Gaussians: means2D [N,2] (pixels), covs2D [N,2,2], colors [N,3], depths [N], opac [N];
