@@ -4,50 +4,30 @@
 // twenty boolean-mask gathers and three torch.cat reallocations of the six parameters and their twelve Adam moments) is one pass
 // over the rows that classifies each (a code byte and three block counts), one exclusive scan that turns the counts into the
 // destination offsets of the 2 + N output segments, one launch that writes every segment of a whole table of tensors, and one
-// launch that overwrites the children's positions and log-scales.  Structure as compact.hip: no atomics, no tickets, the result
-// does not depend on the launch geometry.  Built with -ffp-contract=off: the decisions and the child values restate fp32 tensor
-// operations one rounding at a time.
-#include "gsaj_common.h"
+// launch that overwrites the children's positions and log-scales.  Structure as compact.hip, the block counts and the row mover
+// from the header the two share (row_move.h): no atomics, no tickets, the result does not depend on the launch geometry.  Built
+// with -ffp-contract=off: the decisions and the child values restate fp32 tensor operations one rounding at a time.
+#include "row_move.h"
 
-#define DN_BLOCK 256   // rows per workgroup, one lane per row: the unit of the block counts and of a destination slice
 #define DN_HDR 8       // words in front of the counters: [0] kept originals [1] clones [2] children per copy [3] P'' [4] P [5] N
-#define DN_UNROLL 8    // dwords a lane has in flight in the gather loop
-#define DN_SHIFT 30    // row = (j * ceil(2^30 / w)) >> 30, exact for j < 2^18 and w <= 1024 (compact.hip has the argument)
 
 #define DN_ORIGINAL 1u  // code bits: what a source row emits
 #define DN_CLONE 2u
 #define DN_CHILDREN 4u
-
-struct DensifyTable {
-  const void *src[GSAJ_DENSIFY_MAX_TENSORS];
-  void *dst[GSAJ_DENSIFY_MAX_TENSORS];
-  uint32_t w[GSAJ_DENSIFY_MAX_TENSORS];      // row size in dwords
-  uint32_t magic[GSAJ_DENSIFY_MAX_TENSORS];  // ceil(2^30 / w)
-  uint32_t zero_new;                         // bit t: new rows (clones, children) of tensor t are zeros, not the parent's row
-};
 
 struct DensifyRule {  // every threshold already rounded to fp32 on the host
   float grad_threshold, t_dense, t_big, min_opacity, divisor;
   int size_rule, size_all, stages, S, N;
 };
 
-typedef const __attribute__((address_space(1))) uint32_t *dn_src32;
-typedef __attribute__((address_space(1))) uint32_t *dn_dst32;
-typedef uint32_t dn_u4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) dn_u4 *dn_src128;
-typedef __attribute__((address_space(1))) dn_u4 *dn_dst128;
-typedef const __attribute__((address_space(1))) uint8_t *dn_code;
-
-static inline size_t dn_blocks(int P) { return ((size_t)P + DN_BLOCK - 1) / DN_BLOCK; }
-
 __device__ __forceinline__ float dn_max(float m, float e) { return (e > m || e != e) ? e : m; }  // torch.max: a NaN wins
 
 // The code byte of row i and the block's three counts.  counters: [nb] originals, [nb] clones, N x [nb] children, one zero.
-__global__ void __launch_bounds__(DN_BLOCK) k_dn_plan(int P, DensifyRule r, const float *__restrict__ accum, const float *__restrict__ denom,
-                                                      int n_grads, const float *__restrict__ scaling, const float *__restrict__ opacity,
-                                                      uint8_t *__restrict__ code, uint32_t *__restrict__ ws) {
-  __shared__ uint32_t wcnt[3][DN_BLOCK / GSAJ_WAVE];
-  const size_t i = (size_t)blockIdx.x * DN_BLOCK + threadIdx.x;
+__global__ void __launch_bounds__(ROW_BLOCK) k_dn_plan(int P, DensifyRule r, const float *__restrict__ accum, const float *__restrict__ denom,
+                                                       int n_grads, const float *__restrict__ scaling, const float *__restrict__ opacity,
+                                                       uint8_t *__restrict__ code, uint32_t *__restrict__ ws) {
+  __shared__ uint32_t wcnt[3][ROW_BLOCK / GSAJ_WAVE];
+  const size_t i = (size_t)blockIdx.x * ROW_BLOCK + threadIdx.x;
   uint32_t c = 0u;
   if (i < (size_t)P) {
     float g;
@@ -82,21 +62,16 @@ __global__ void __launch_bounds__(DN_BLOCK) k_dn_plan(int P, DensifyRule r, cons
     if (split && !child_gone) c |= DN_CHILDREN;
     code[i] = (uint8_t)c;
   }
-  const unsigned long long b0 = __ballot((c & DN_ORIGINAL) != 0u), b1 = __ballot((c & DN_CLONE) != 0u),
-                           b2 = __ballot((c & DN_CHILDREN) != 0u);
-  if ((threadIdx.x & (GSAJ_WAVE - 1)) == 0) {
-    const int wv = threadIdx.x / GSAJ_WAVE;
-    wcnt[0][wv] = (uint32_t)__popcll(b0);
-    wcnt[1][wv] = (uint32_t)__popcll(b1);
-    wcnt[2][wv] = (uint32_t)__popcll(b2);
-  }
+  row_post((c & DN_ORIGINAL) != 0u, wcnt[0]);
+  row_post((c & DN_CLONE) != 0u, wcnt[1]);
+  row_post((c & DN_CHILDREN) != 0u, wcnt[2]);
   __syncthreads();
   if (threadIdx.x == 0) {
     uint32_t *counts = gsaj_shift(ws, sizeof(uint32_t) * DN_HDR);
     const size_t nb = gridDim.x;
-    const uint32_t k2 = wcnt[2][0] + wcnt[2][1] + wcnt[2][2] + wcnt[2][3];
-    counts[blockIdx.x] = wcnt[0][0] + wcnt[0][1] + wcnt[0][2] + wcnt[0][3];
-    counts[nb + blockIdx.x] = wcnt[1][0] + wcnt[1][1] + wcnt[1][2] + wcnt[1][3];
+    const uint32_t k2 = row_total(wcnt[2]);
+    counts[blockIdx.x] = row_total(wcnt[0]);
+    counts[nb + blockIdx.x] = row_total(wcnt[1]);
     for (int n = 0; n < r.N; ++n) counts[(size_t)(2 + n) * nb + blockIdx.x] = k2;
     if (blockIdx.x == 0) {
       counts[(size_t)(2 + r.N) * nb] = 0u;
@@ -116,93 +91,29 @@ __global__ void __launch_bounds__(GSAJ_WAVE) k_dn_totals(uint32_t nb, uint32_t N
   }
 }
 
-// rank of this lane among the workgroup's lanes with `has` set, through four wave counts in LDS (every lane must call)
-__device__ __forceinline__ uint32_t dn_rank(bool has, uint32_t *wcnt) {
-  const unsigned long long set = __ballot(has);
-  const int lane = threadIdx.x & (GSAJ_WAVE - 1), wave = threadIdx.x / GSAJ_WAVE;
-  if (lane == 0) wcnt[wave] = (uint32_t)__popcll(set);
-  __syncthreads();
-  uint32_t before = 0u;
-  for (int k = 0; k < wave; ++k) before += wcnt[k];
-  return before + (uint32_t)__popcll(set & ((1ull << lane) - 1ull));
-}
-
 // Workgroup (b, t, seg) writes rows [offs[seg][b], offs[seg][b + 1]) of tensor t: the rows source block b emits into segment seg
 // (0 originals, 1 clones, 2 + n the children of copy n), in order.
-__global__ void __launch_bounds__(DN_BLOCK) k_dn_rows(int P, int N, DensifyTable tb, const uint8_t *__restrict__ code_,
-                                                      const uint32_t *__restrict__ ws) {
-  __shared__ uint8_t list[DN_BLOCK];  // the emitted local rows, ascending
-  __shared__ uint32_t wcnt[DN_BLOCK / GSAJ_WAVE];
+__global__ void __launch_bounds__(ROW_BLOCK) k_dn_rows(int P, int N, RowTable tb, const uint8_t *__restrict__ code_,
+                                                       const uint32_t *__restrict__ ws) {
   if (ws[4] != (uint32_t)P || ws[5] != (uint32_t)N) return;  // not the plan of these tensors: nothing is read or written
   const uint32_t *offs = gsaj_shift(ws, sizeof(uint32_t) * DN_HDR);
   const uint32_t seg = blockIdx.z;
   const size_t slot = (size_t)seg * gridDim.x + blockIdx.x;
   const uint32_t off = offs[slot], count = offs[slot + 1] - off;
-  if (count == 0u || count > DN_BLOCK) return;  // (more than a block's rows: the counters are not this plan's)
-
-  const uint32_t w = tb.w[blockIdx.y], magic = tb.magic[blockIdx.y];
-  const size_t row0 = (size_t)blockIdx.x * DN_BLOCK;
-  const dn_src32 s32 = (dn_src32)((unsigned long long)tb.src[blockIdx.y]) + row0 * w;
-  const dn_dst32 d32 = (dn_dst32)((unsigned long long)tb.dst[blockIdx.y]) + (size_t)off * w;
-  const uint32_t n = count * w;  // dwords of the slice, at most 2^18
+  if (!row_count_ok(count)) return;  // (the mover refuses the same; here for the zero fill below, and before the table is read)
+  const uint32_t w = tb.w[blockIdx.y];
+  const size_t row0 = (size_t)blockIdx.x * ROW_BLOCK;
+  const row_src32 s32 = (row_src32)((unsigned long long)tb.src[blockIdx.y]) + row0 * w;
+  const row_dst32 d32 = (row_dst32)((unsigned long long)tb.dst[blockIdx.y]) + (size_t)off * w;
 
   if (seg != 0u && ((tb.zero_new >> blockIdx.y) & 1u)) {  // new rows of an Adam moment
-    for (uint32_t j = threadIdx.x; j < n; j += DN_BLOCK) d32[j] = 0u;
+    for (uint32_t j = threadIdx.x; j < count * w; j += ROW_BLOCK) d32[j] = 0u;
     return;
   }
-
-  if (count == DN_BLOCK) {  // every row of the block goes to this segment: a straight copy, 16 bytes per lane where both addresses allow
-    if ((((unsigned long long)s32 | (unsigned long long)d32) & 15ull) == 0ull) {
-      const dn_src128 s128 = (dn_src128)s32;
-      const dn_dst128 d128 = (dn_dst128)d32;
-      const uint32_t n4 = n / 4u;  // (256 w dwords: a multiple of 4)
-      for (uint32_t j0 = threadIdx.x; j0 < n4; j0 += DN_BLOCK * 4) {
-        dn_u4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = j0 + u * DN_BLOCK < n4 ? s128[j0 + u * DN_BLOCK] : dn_u4{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (j0 + u * DN_BLOCK < n4) d128[j0 + u * DN_BLOCK] = v[u];
-      }
-    } else {
-      for (uint32_t j0 = threadIdx.x; j0 < n; j0 += DN_BLOCK * DN_UNROLL) {
-        uint32_t v[DN_UNROLL];
-#pragma unroll
-        for (int u = 0; u < DN_UNROLL; ++u) v[u] = j0 + u * DN_BLOCK < n ? s32[j0 + u * DN_BLOCK] : 0u;
-#pragma unroll
-        for (int u = 0; u < DN_UNROLL; ++u)
-          if (j0 + u * DN_BLOCK < n) d32[j0 + u * DN_BLOCK] = v[u];
-      }
-    }
-    return;
-  }
-
-  // the list of emitted rows: ballot, position among the wave's emitting lanes, prefix over the four waves
-  const dn_code code = (dn_code)((unsigned long long)code_);
+  const row_bytes_t code = (row_bytes_t)((unsigned long long)code_);
   const uint32_t bit = seg == 0u ? DN_ORIGINAL : seg == 1u ? DN_CLONE : DN_CHILDREN;
-  const size_t i = row0 + threadIdx.x;
-  const bool emit = i < (size_t)P && ((uint32_t)code[i] & bit) != 0u;
-  list[threadIdx.x] = 0;  // (codes changed since the plan leave slots unwritten: they name the block's first row, which exists)
-  const uint32_t rank = dn_rank(emit, wcnt);  // (the barrier inside orders the line above before the writes below)
-  if (emit) list[rank] = (uint8_t)threadIdx.x;
-  __syncthreads();
-
-  // consecutive lanes write consecutive dwords of the slice; dword j is column j % w of the (j / w)-th emitted row
-  for (uint32_t j0 = threadIdx.x; j0 < n; j0 += DN_BLOCK * DN_UNROLL) {
-    uint32_t v[DN_UNROLL];
-#pragma unroll
-    for (int u = 0; u < DN_UNROLL; ++u) {
-      const uint32_t j = j0 + u * DN_BLOCK;
-      v[u] = 0u;
-      if (j < n) {
-        const uint32_t q = (uint32_t)(((unsigned long long)j * magic) >> DN_SHIFT);
-        v[u] = s32[(uint32_t)list[q] * w + (j - q * w)];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < DN_UNROLL; ++u)
-      if (j0 + u * DN_BLOCK < n) d32[j0 + u * DN_BLOCK] = v[u];
-  }
+  row_move_segment(s32, d32, w, tb.magic[blockIdx.y], count,
+                   [=](uint32_t r) { return row0 + r < (size_t)P && ((uint32_t)code[row0 + r] & bit) != 0u; });
 }
 
 // ---- Philox4x32-10 and the normal draws of (row i, copy n) -------------------------------------------------------------------
@@ -234,8 +145,8 @@ __device__ __forceinline__ dn_z3 dn_draw(uint32_t i, uint32_t n, uint32_t k0, ui
   return z;
 }
 
-__global__ void __launch_bounds__(DN_BLOCK) k_dn_noise(int P, uint32_t k0, uint32_t k1, float *__restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * DN_BLOCK + threadIdx.x;
+__global__ void __launch_bounds__(ROW_BLOCK) k_dn_noise(int P, uint32_t k0, uint32_t k1, float *__restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * ROW_BLOCK + threadIdx.x;
   if (i >= (size_t)P) return;
   const dn_z3 z = dn_draw((uint32_t)i, blockIdx.y, k0, k1);
   float *o = out + ((size_t)blockIdx.y * (size_t)P + i) * 3;
@@ -243,21 +154,21 @@ __global__ void __launch_bounds__(DN_BLOCK) k_dn_noise(int P, uint32_t k0, uint3
 }
 
 // Lane (i, n) with children emitted: xyz = R(q_i) (exp(s_i) o z_{i,n}) + xyz_i and log(exp(s_i) / d) into the child's row.
-__global__ void __launch_bounds__(DN_BLOCK) k_dn_children(int P, int S, int N, float divisor, const float *__restrict__ xyz,
-                                                          const float *__restrict__ scaling, const float *__restrict__ rotation,
-                                                          const float *__restrict__ noise, uint32_t k0, uint32_t k1,
-                                                          const uint8_t *__restrict__ code, const uint32_t *__restrict__ ws,
-                                                          float *__restrict__ dst_xyz, float *__restrict__ dst_scaling) {
-  __shared__ uint32_t wcnt[DN_BLOCK / GSAJ_WAVE];
+__global__ void __launch_bounds__(ROW_BLOCK) k_dn_children(int P, int S, int N, float divisor, const float *__restrict__ xyz,
+                                                           const float *__restrict__ scaling, const float *__restrict__ rotation,
+                                                           const float *__restrict__ noise, uint32_t k0, uint32_t k1,
+                                                           const uint8_t *__restrict__ code, const uint32_t *__restrict__ ws,
+                                                           float *__restrict__ dst_xyz, float *__restrict__ dst_scaling) {
+  __shared__ uint32_t wcnt[ROW_BLOCK / GSAJ_WAVE];
   if (ws[4] != (uint32_t)P || ws[5] != (uint32_t)N) return;
   const uint32_t *offs = gsaj_shift(ws, sizeof(uint32_t) * DN_HDR);
   const uint32_t n = blockIdx.y;
   const size_t slot = (size_t)(2u + n) * gridDim.x + blockIdx.x;
   const uint32_t off = offs[slot], count = offs[slot + 1] - off;
-  if (count == 0u || count > DN_BLOCK) return;
-  const size_t i = (size_t)blockIdx.x * DN_BLOCK + threadIdx.x;
+  if (!row_count_ok(count)) return;
+  const size_t i = (size_t)blockIdx.x * ROW_BLOCK + threadIdx.x;
   const bool emit = i < (size_t)P && (code[i] & DN_CHILDREN) != 0u;
-  const uint32_t rank = dn_rank(emit, wcnt);
+  const uint32_t rank = row_rank(emit, wcnt);
   if (!emit || rank >= count) return;
   const size_t row = (size_t)off + rank;
 
@@ -299,7 +210,7 @@ static bool dn_bad_pn(int P, int N) { return P <= 0 || N < 1 || N > GSAJ_DENSIFY
 
 extern "C" size_t gsaj_densify_workspace_bytes(int P, int N) {
   if (dn_bad_pn(P, N)) return 0;
-  return gsaj_align(sizeof(uint32_t) * (DN_HDR + (size_t)(2 + N) * dn_blocks(P) + 1));
+  return gsaj_align(sizeof(uint32_t) * (DN_HDR + (size_t)(2 + N) * row_blocks(P) + 1));
 }
 
 extern "C" int gsaj_densify_plan(int P, int S, int N, int stages, const float *accum, const float *denom, int n_grads, const float *scaling,
@@ -314,12 +225,12 @@ extern "C" int gsaj_densify_plan(int P, int S, int N, int stages, const float *a
   }
   hipStream_t s = (hipStream_t)stream;
   uint32_t *ws = static_cast<uint32_t *>(densify_ws);
-  const size_t nb = dn_blocks(P);
+  const size_t nb = row_blocks(P);
   DensifyRule r;
   r.grad_threshold = grad_threshold; r.t_dense = t_dense; r.t_big = t_big; r.min_opacity = min_opacity;
   r.divisor = (float)(0.8 * N);
   r.size_rule = size_rule ? 1 : 0; r.size_all = size_all ? 1 : 0; r.stages = stages; r.S = S; r.N = N;
-  hipLaunchKernelGGL(k_dn_plan, dim3((unsigned)nb), dim3(DN_BLOCK), 0, s, P, r, accum, denom, n_grads, scaling, opacity, code, ws);
+  hipLaunchKernelGGL(k_dn_plan, dim3((unsigned)nb), dim3(ROW_BLOCK), 0, s, P, r, accum, denom, n_grads, scaling, opacity, code, ws);
   launch_exclusive_scan_u32((int)((size_t)(2 + N) * nb + 1), ws + DN_HDR, s);
   hipLaunchKernelGGL(k_dn_totals, dim3(1), dim3(GSAJ_WAVE), 0, s, (uint32_t)nb, (uint32_t)N, ws);
   GSAJ_HIP_CHECK(hipGetLastError());
@@ -346,23 +257,9 @@ extern "C" int gsaj_densify_rows(int P, int N, int n_tensors, const void *const 
                    P, N, n_tensors, GSAJ_DENSIFY_MAX_SPLIT, GSAJ_DENSIFY_MAX_TENSORS);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  DensifyTable tb = {};
-  for (int t = 0; t < n_tensors; ++t) {
-    if (!src[t] || !dst[t] || src[t] == dst[t]) {
-      gsaj_set_error("gsaj_densify_rows: tensor %d: src and dst must be two different non-null pointers (no in-place form)", t);
-      return GSAJ_ERR_INVALID_ARGUMENT;
-    }
-    if (row_bytes[t] <= 0 || row_bytes[t] % 4 != 0 || row_bytes[t] > 4096) {
-      gsaj_set_error("gsaj_densify_rows: tensor %d: row size %d is not a positive multiple of 4 bytes of at most 4096", t, row_bytes[t]);
-      return GSAJ_ERR_INVALID_ARGUMENT;
-    }
-    tb.src[t] = src[t];
-    tb.dst[t] = dst[t];
-    tb.w[t] = (uint32_t)row_bytes[t] / 4u;
-    tb.magic[t] = (uint32_t)(((1ull << DN_SHIFT) + tb.w[t] - 1u) / tb.w[t]);
-    if (zero_new[t]) tb.zero_new |= 1u << t;
-  }
-  hipLaunchKernelGGL(k_dn_rows, dim3((unsigned)dn_blocks(P), (unsigned)n_tensors, (unsigned)(2 + N)), dim3(DN_BLOCK), 0, (hipStream_t)stream,
+  RowTable tb;
+  if (int rc = row_table_fill("gsaj_densify_rows", &tb, n_tensors, src, dst, row_bytes, zero_new)) return rc;
+  hipLaunchKernelGGL(k_dn_rows, dim3((unsigned)row_blocks(P), (unsigned)n_tensors, (unsigned)(2 + N)), dim3(ROW_BLOCK), 0, (hipStream_t)stream,
                      P, N, tb, code, static_cast<const uint32_t *>(densify_ws));
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
@@ -377,7 +274,7 @@ extern "C" int gsaj_densify_children(int P, int S, int N, const float *xyz, cons
                    "destinations different from the sources)", P, S, N, GSAJ_DENSIFY_MAX_SPLIT);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  hipLaunchKernelGGL(k_dn_children, dim3((unsigned)dn_blocks(P), (unsigned)N), dim3(DN_BLOCK), 0, (hipStream_t)stream, P, S, N,
+  hipLaunchKernelGGL(k_dn_children, dim3((unsigned)row_blocks(P), (unsigned)N), dim3(ROW_BLOCK), 0, (hipStream_t)stream, P, S, N,
                      (float)(0.8 * N), xyz, scaling, rotation, noise, (uint32_t)seed, (uint32_t)(seed >> 32), code,
                      static_cast<const uint32_t *>(densify_ws), dst_xyz, dst_scaling);
   GSAJ_HIP_CHECK(hipGetLastError());
@@ -389,7 +286,7 @@ extern "C" int gsaj_densify_noise(int P, int N, uint64_t seed, float *out, void 
     gsaj_set_error("gsaj_densify_noise: invalid argument (P=%d N=%d; P must be positive, N 1..%d, no null pointer)", P, N, GSAJ_DENSIFY_MAX_SPLIT);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  hipLaunchKernelGGL(k_dn_noise, dim3((unsigned)dn_blocks(P), (unsigned)N), dim3(DN_BLOCK), 0, (hipStream_t)stream, P, (uint32_t)seed,
+  hipLaunchKernelGGL(k_dn_noise, dim3((unsigned)row_blocks(P), (unsigned)N), dim3(ROW_BLOCK), 0, (hipStream_t)stream, P, (uint32_t)seed,
                      (uint32_t)(seed >> 32), out);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;

@@ -263,21 +263,15 @@ class GaussianModel:
                     grown[name] = ext.clone().requires_grad_(True)
                 else:
                     grown[name] = torch.cat((cur.detach(), ext.to(cur.device)), dim=0).requires_grad_(True)
+        moments = {}
         if self.optimizer is not None:
             for group in self.optimizer.param_groups:
-                assert len(group["params"]) == 1
                 name = group["name"]
-                prev = group["params"][0]
-                state = self.optimizer.state.pop(prev, None)
+                state = self.optimizer.state.get(group["params"][0], None)
                 if state is not None and "exp_avg" in state:
                     pad = torch.zeros((m,) + tuple(grown[name].shape[1:]), dtype=state["exp_avg"].dtype, device=state["exp_avg"].device)
-                    state["exp_avg"] = torch.cat((state["exp_avg"], pad), dim=0)
-                    state["exp_avg_sq"] = torch.cat((state["exp_avg_sq"], pad), dim=0)
-                group["params"][0] = grown[name]
-                if state is not None:
-                    self.optimizer.state[grown[name]] = state
-        self._xyz, self._features_dc, self._features_rest = grown["xyz"], grown["f_dc"], grown["f_rest"]
-        self._opacity, self._scaling, self._rotation = grown["opacity"], grown["scaling"], grown["rotation"]
+                    moments[name] = (torch.cat((state["exp_avg"], pad), dim=0), torch.cat((state["exp_avg_sq"], pad), dim=0))
+        self._install(grown, moments)
         n, dev = self._xyz.shape[0], self._xyz.device
         self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
         self.denom = torch.zeros((n, 1), device=dev)
@@ -307,41 +301,13 @@ class GaussianModel:
         fixed P: build a new one afterwards."""
         from gsaj.pruning import CompactPlan
         plan = CompactPlan(mask, remove=True, n_kept=n_kept)
-        names = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
-        old = dict(zip(names, (self._xyz, self._features_dc, self._features_rest, self._opacity, self._scaling, self._rotation)))
-        moved = [(("param", n), old[n].detach().contiguous()) for n in names]
-        states = {}
-        if self.optimizer is not None:
-            for group in self.optimizer.param_groups:
-                assert len(group["params"]) == 1
-                name = group["name"]
-                if group["params"][0] is not old[name]:
-                    from gsaj._lib import GsajError
-                    raise GsajError("prune_points: optimizer group %r does not hold the model's parameter of that name" % name)
-                state = self.optimizer.state.get(old[name], None)
-                if state is not None and "exp_avg" in state:
-                    states[name] = state
-                    moved += [((key, name), state[key].contiguous()) for key in ("exp_avg", "exp_avg_sq")]
-        aux = [a for a in ("xyz_gradient_accum", "denom", "max_radii2D") if getattr(self, a, None) is not None]
-        ids = [a for a in ("unique_kfIDs", "n_obs") if getattr(self, a, None) is not None]
-        dev = plan.dev
-        moved += [(("aux", a), getattr(self, a).contiguous()) for a in aux + ids if getattr(self, a).device == dev]
-        out = dict(zip([k for k, _ in moved], plan.apply(*[t for _, t in moved])))
-
-        new = {n: out[("param", n)].requires_grad_(True) for n in names}
-        if self.optimizer is not None:
-            for group in self.optimizer.param_groups:
-                name = group["name"]
-                state = self.optimizer.state.pop(old[name], None)
-                if name in states:
-                    state["exp_avg"], state["exp_avg_sq"] = out[("exp_avg", name)], out[("exp_avg_sq", name)]
-                group["params"][0] = new[name]
-                if state is not None:
-                    self.optimizer.state[new[name]] = state
-        self._xyz, self._features_dc, self._features_rest = new["xyz"], new["f_dc"], new["f_rest"]
-        self._opacity, self._scaling, self._rotation = new["opacity"], new["scaling"], new["rotation"]
+        moved, ids = self._gather("prune_points", plan.dev)
+        stats = [a for a in ("xyz_gradient_accum", "denom", "max_radii2D") if getattr(self, a, None) is not None]
+        moved += [(("aux", a), getattr(self, a).contiguous(), "parent") for a in stats if getattr(self, a).device == plan.dev]
+        out = dict(zip([k for k, _, _ in moved], plan.apply(*[t for _, t, _ in moved])))
+        self._install_moved(out)
         keep_host = None
-        for a in aux + ids:
+        for a in stats + ids:
             if ("aux", a) in out:
                 setattr(self, a, out[("aux", a)])
             else:
@@ -349,6 +315,56 @@ class GaussianModel:
                     keep_host = plan.keep_mask().cpu()
                 setattr(self, a, getattr(self, a)[keep_host.to(getattr(self, a).device)])
         return plan
+
+    # ---- what prune_points, _densify and extend_from_pcd share: the tensors of the map, and putting new ones in their place -----
+    _NAMES = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
+
+    def _gather(self, who, dev, id_dtype=None):
+        """The tensors whose rows follow the map's, as a list of (key, tensor, new-row mode): the six parameters ("param", name;
+        a new row gets its parent's), exp_avg / exp_avg_sq of every optimizer group that has state ((moment, name); zeros), and
+        unique_kfIDs / n_obs where they live on dev (("aux", attribute); the parent's; cast to id_dtype if given).  Beside it the
+        names of the id vectors the model has, on dev or not.  who: the caller, for the message about a foreign optimizer."""
+        old = dict(zip(self._NAMES, self.parameters()))
+        moved = [(("param", n), old[n].detach().contiguous(), "parent") for n in self._NAMES]
+        if self.optimizer is not None:
+            for group in self.optimizer.param_groups:
+                assert len(group["params"]) == 1
+                name = group["name"]
+                if group["params"][0] is not old[name]:
+                    from gsaj._lib import GsajError
+                    raise GsajError("%s: optimizer group %r does not hold the model's parameter of that name" % (who, name))
+                state = self.optimizer.state.get(old[name], None)
+                if state is not None and "exp_avg" in state:
+                    moved += [((key, name), state[key].contiguous(), "zeros") for key in ("exp_avg", "exp_avg_sq")]
+        ids = [a for a in ("unique_kfIDs", "n_obs") if getattr(self, a, None) is not None]
+        for a in ids:
+            t = getattr(self, a)
+            if t.device == dev:
+                moved.append((("aux", a), (t if id_dtype is None else t.to(id_dtype)).contiguous(), "parent"))
+        return moved, ids
+
+    def _install(self, new, moments):
+        """new: the six parameters by name; they become the model's leaves and replace the old ones in the groups of an attached
+        optimizer (one parameter per group, named as the parameters).  A group's state moves to the new key with step and every
+        other entry untouched; moments: (exp_avg, exp_avg_sq) by name, for the groups whose state gets new ones."""
+        new = {n: t.requires_grad_(True) for n, t in new.items()}
+        if self.optimizer is not None:
+            for group in self.optimizer.param_groups:
+                assert len(group["params"]) == 1
+                name = group["name"]
+                state = self.optimizer.state.pop(group["params"][0], None)
+                if name in moments:
+                    state["exp_avg"], state["exp_avg_sq"] = moments[name]
+                group["params"][0] = new[name]
+                if state is not None:
+                    self.optimizer.state[new[name]] = state
+        self._xyz, self._features_dc, self._features_rest = new["xyz"], new["f_dc"], new["f_rest"]
+        self._opacity, self._scaling, self._rotation = new["opacity"], new["scaling"], new["rotation"]
+
+    def _install_moved(self, out):
+        """_install from the outputs of a plan, keyed as _gather keys its list."""
+        self._install({n: out[("param", n)] for n in self._NAMES},
+                      {n: (out[("exp_avg", n)], out[("exp_avg_sq", n)]) for n in self._NAMES if ("exp_avg", n) in out})
 
     # ---- optimiser + densification (reference :321-370, :599-765) ---------------------------------------------------------
     def training_setup(self, training_args):
@@ -378,43 +394,15 @@ class GaussianModel:
         exp_avg_sq of every optimizer group that has state (a new row gets zeros; step and every other entry untouched),
         unique_kfIDs / n_obs (the parent's, int32; host-resident ones are indexed with plan.source_rows() after one copy), all in
         one rows launch; then the children's xyz and _scaling; xyz_gradient_accum, denom, max_radii2D become zeros of the new size."""
-        from gsaj._lib import GsajError
-        names = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
-        old = dict(zip(names, (self._xyz, self._features_dc, self._features_rest, self._opacity, self._scaling, self._rotation)))
-        src = {n: old[n].detach().contiguous() for n in names}
-        moved = [(("param", n), src[n], "parent") for n in names]
-        states = {}
-        if self.optimizer is not None:
-            for group in self.optimizer.param_groups:
-                assert len(group["params"]) == 1
-                name = group["name"]
-                if group["params"][0] is not old[name]:
-                    raise GsajError("%s: optimizer group %r does not hold the model's parameter of that name" % (who, name))
-                state = self.optimizer.state.get(old[name], None)
-                if state is not None and "exp_avg" in state:
-                    states[name] = state
-                    moved += [((key, name), state[key].contiguous(), "zeros") for key in ("exp_avg", "exp_avg_sq")]
         dev = plan.dev
-        ids = [a for a in ("unique_kfIDs", "n_obs") if getattr(self, a, None) is not None]
+        moved, ids = self._gather(who, dev, id_dtype=torch.int32)
+        src = {k[1]: t for k, t, _ in moved if k[0] == "param"}
         on_host = [a for a in ids if getattr(self, a).device != dev]
-        moved += [(("aux", a), getattr(self, a).int().contiguous(), "parent") for a in ids if a not in on_host]
         if on_host:
             moved.append((("rows", None), torch.arange(plan.P, dtype=torch.int32, device=dev), "parent"))
         out = dict(zip([k for k, _, _ in moved], plan.apply([t for _, t, _ in moved], new_rows=[m for _, _, m in moved])))
         plan.children(src["xyz"], src["scaling"], src["rotation"], out[("param", "xyz")], out[("param", "scaling")], noise=noise, seed=seed)
-
-        new = {n: out[("param", n)].requires_grad_(True) for n in names}
-        if self.optimizer is not None:
-            for group in self.optimizer.param_groups:
-                name = group["name"]
-                state = self.optimizer.state.pop(old[name], None)
-                if name in states:
-                    state["exp_avg"], state["exp_avg_sq"] = out[("exp_avg", name)], out[("exp_avg_sq", name)]
-                group["params"][0] = new[name]
-                if state is not None:
-                    self.optimizer.state[new[name]] = state
-        self._xyz, self._features_dc, self._features_rest = new["xyz"], new["f_dc"], new["f_rest"]
-        self._opacity, self._scaling, self._rotation = new["opacity"], new["scaling"], new["rotation"]
+        self._install_moved(out)
         n = plan.n_out
         self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
         self.denom = torch.zeros((n, 1), device=dev)

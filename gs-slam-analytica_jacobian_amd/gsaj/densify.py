@@ -13,10 +13,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
-
-MAX_TENSORS = 32      # GSAJ_DENSIFY_MAX_TENSORS
-MAX_ROW_BYTES = 4096
+from . import _lib, _rows
+from ._rows import MAX_ROW_BYTES, MAX_TENSORS  # noqa: F401 -- GSAJ_DENSIFY_MAX_TENSORS; the largest row
 MAX_SPLIT = 4         # GSAJ_DENSIFY_MAX_SPLIT
 CLONE, SPLIT, PRUNE = 1, 2, 4
 ALL = CLONE | SPLIT | PRUNE
@@ -102,44 +100,22 @@ class DensifyPlan:
     def n_out(self):
         return self.counts[3]
 
-    def _row_bytes(self, k, t):
-        if not torch.is_tensor(t) or t.device != self.dev:
-            raise _lib.GsajError("apply: tensor %d must be a tensor on %s (there is no CPU path)" % (k, self.dev))
-        if t.dim() < 1 or t.shape[0] != self.P:
-            raise _lib.GsajError("apply: tensor %d must have %d rows (got shape %s)" % (k, self.P, list(t.shape)))
-        if not t.is_contiguous():
-            raise _lib.GsajError("apply: tensor %d is not contiguous" % k)
-        rb = (t.numel() // self.P) * t.element_size()
-        if rb % 4 != 0 or rb > MAX_ROW_BYTES:
-            raise _lib.GsajError("apply: tensor %d has rows of %d bytes; a row must be a multiple of 4 bytes, at most %d" % (k, rb, MAX_ROW_BYTES))
-        return rb
-
     def apply(self, tensors, new_rows="parent"):
         """Every tensor ([P, ...], contiguous, on the plan's device, rows a multiple of 4 bytes) through the plan, as new tensors
         [P'', ...].  new_rows: "parent" (a clone or child gets its parent's row) or "zeros" (Adam moments), one word for all or one
         per tensor.  A tensor with zero-width rows is not sent to the kernel.  One launch per 32 tensors."""
-        srcs = [t.detach() if torch.is_tensor(t) else t for t in tensors]
-        modes = [new_rows] * len(srcs) if isinstance(new_rows, str) else list(new_rows)
-        if len(modes) != len(srcs) or any(m not in ("parent", "zeros") for m in modes):
+        tensors = list(tensors)
+        modes = [new_rows] * len(tensors) if isinstance(new_rows, str) else list(new_rows)
+        if len(modes) != len(tensors) or any(m not in ("parent", "zeros") for m in modes):
             raise _lib.GsajError("apply: new_rows must be 'parent' or 'zeros', once or once per tensor")
-        rbs = [self._row_bytes(k, t) for k, t in enumerate(srcs)]
-        n = self.n_out
-        outs = [torch.empty((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.dev) for t in srcs]
-        live = [k for k, rb in enumerate(rbs) if rb > 0]
-        if n == 0 or not live:
-            return outs
-        with torch.cuda.device(self.dev):
-            for k0 in range(0, len(live), MAX_TENSORS):
-                ks = live[k0:k0 + MAX_TENSORS]
-                cnt = len(ks)
-                src = (ctypes.c_void_p * cnt)(*[srcs[k].data_ptr() for k in ks])
-                dst = (ctypes.c_void_p * cnt)(*[outs[k].data_ptr() for k in ks])
-                rb = (ctypes.c_int * cnt)(*[rbs[k] for k in ks])
-                zn = (ctypes.c_int * cnt)(*[int(modes[k] == "zeros") for k in ks])
-                _lib.check(self.lib.gsaj_densify_rows(self.P, self.N, cnt, src, dst, rb, zn, self.code.data_ptr(), self.ws.data_ptr(),
-                                                      _stream(self.dev)), "gsaj_densify_rows")
-                self.launches += 1
-        return outs
+        srcs, rbs = _rows.check(self, tensors, zero_width=True)
+
+        def rows(cnt, src, dst, rb, ks):
+            zn = (ctypes.c_int * cnt)(*[int(modes[k] == "zeros") for k in ks])
+            _lib.check(self.lib.gsaj_densify_rows(self.P, self.N, cnt, src, dst, rb, zn, self.code.data_ptr(), self.ws.data_ptr(),
+                                                  _stream(self.dev)), "gsaj_densify_rows")
+
+        return _rows.move(self, srcs, rbs, self.n_out, rows)
 
     def children(self, xyz, scaling, rotation, dst_xyz, dst_scaling, noise=None, seed=0):
         """Overwrite the child rows of dst_xyz [P'',3] and dst_scaling [P'',S] (outputs of apply()) with the sampled positions and

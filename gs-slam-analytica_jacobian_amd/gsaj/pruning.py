@@ -10,10 +10,8 @@ import ctypes
 
 import torch
 
-from . import _lib
-
-MAX_TENSORS = 32      # GSAJ_COMPACT_MAX_TENSORS: tensors one launch moves
-MAX_ROW_BYTES = 4096
+from . import _lib, _rows
+from ._rows import MAX_ROW_BYTES, MAX_TENSORS  # noqa: F401 -- GSAJ_COMPACT_MAX_TENSORS: tensors one launch moves; the largest row
 
 
 def _stream(dev):
@@ -58,35 +56,12 @@ class CompactPlan:
         """bool [P] on the device: True where the row stays (a new tensor)."""
         return (self.mask != 0) != self.remove
 
-    def _row_bytes(self, k, t):
-        if not torch.is_tensor(t) or t.device != self.dev:
-            raise _lib.GsajError("apply: tensor %d must be a tensor on %s (there is no CPU path)" % (k, self.dev))
-        if t.dim() < 1 or t.shape[0] != self.P:
-            raise _lib.GsajError("apply: tensor %d must have %d rows (got shape %s)" % (k, self.P, list(t.shape)))
-        if not t.is_contiguous():
-            raise _lib.GsajError("apply: tensor %d is not contiguous" % k)
-        rb = (t.numel() // self.P) * t.element_size()
-        if rb <= 0 or rb % 4 != 0 or rb > MAX_ROW_BYTES:
-            raise _lib.GsajError("apply: tensor %d has rows of %d bytes; a row must be a non-zero multiple of 4 bytes, at most %d"
-                                 % (k, rb, MAX_ROW_BYTES))
-        return rb
-
     def apply(self, *tensors):
         """The kept rows of every tensor ([P, ...], contiguous, on the mask's device, any dtype whose row is a non-zero multiple of
         4 bytes) as new tensors [P', ...], in the same order: what t[keep] gives.  One launch per 32 tensors."""
-        srcs = [t.detach() if torch.is_tensor(t) else t for t in tensors]
-        rbs = [self._row_bytes(k, t) for k, t in enumerate(srcs)]
-        n = self.n_kept
-        outs = [torch.empty((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.dev) for t in srcs]
-        if n == 0:
-            return outs
-        with torch.cuda.device(self.dev):
-            for k0 in range(0, len(srcs), MAX_TENSORS):
-                k1 = min(len(srcs), k0 + MAX_TENSORS)
-                cnt = k1 - k0
-                src = (ctypes.c_void_p * cnt)(*[t.data_ptr() for t in srcs[k0:k1]])
-                dst = (ctypes.c_void_p * cnt)(*[t.data_ptr() for t in outs[k0:k1]])
-                rb = (ctypes.c_int * cnt)(*rbs[k0:k1])
-                _lib.check(self.lib.gsaj_compact_rows(self.P, cnt, src, dst, rb, self.ws.data_ptr(), _stream(self.dev)), "gsaj_compact_rows")
-                self.launches += 1
-        return outs
+        srcs, rbs = _rows.check(self, tensors, zero_width=False)
+
+        def rows(cnt, src, dst, rb, ks):
+            _lib.check(self.lib.gsaj_compact_rows(self.P, cnt, src, dst, rb, self.ws.data_ptr(), _stream(self.dev)), "gsaj_compact_rows")
+
+        return _rows.move(self, srcs, rbs, self.n_kept, rows)

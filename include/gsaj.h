@@ -544,6 +544,7 @@ int gsaj_covis_prune_mask(int P, const uint32_t *words, uint32_t window_mask, co
                           int *n_pruned /*dev [1]*/, void *stream);
 
 /* ---- removing rows of the map under a mask (csrc/compact.hip) ---------------------------
+ * The rows are moved by the one mover of csrc/row_move.h, which gsaj_densify_rows below calls too.
  * The reference's prune_points (gaussian_splatting/scene/gaussian_model.py:559-597) indexes every parameter, Adam moment and
  * bookkeeping vector with one boolean mask, t[mask] each.  Here ONE pass over the mask plans the move and ONE launch moves the
  * kept rows of up to GSAJ_COMPACT_MAX_TENSORS tensors.  keep(i) = (mask[i] != 0) != (mask_is_remove != 0) -- any non-zero byte
@@ -558,7 +559,9 @@ int gsaj_covis_prune_mask(int P, const uint32_t *words, uint32_t window_mask, co
  *   modified.  P is the plan's P: with any other value nothing is read or written.  With P' = 0 nothing is written either
  *   (every workgroup returns at once); a caller who knows P' = 0 launches nothing, as gsaj.pruning does.  A plan stays valid
  *   until its workspace is reused; several gsaj_compact_rows calls may follow one plan.  src[t] and dst[t] must not overlap:
- *   destinations precede sources in a stable compaction, so an in-place form would race between workgroups.
+ *   destinations precede sources in a stable compaction, so an in-place form would race between workgroups.  A workspace
+ *   that is no plan's is harmless as far as the mover goes: a block whose offsets differ by more than 256 rows, which no plan
+ *   produces, moves nothing (as in gsaj_densify_rows; not observable with a valid plan).
  * GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: P <= 0, a null pointer (in src / dst too), n_tensors outside
  *   1..GSAJ_COMPACT_MAX_TENSORS, a row size that is not a positive multiple of 4 or exceeds 4096, src[t] == dst[t]. */
 #define GSAJ_COMPACT_MAX_TENSORS 32
@@ -569,6 +572,7 @@ int gsaj_compact_rows(int P, int n_tensors, const void *const *src /*host [n] of
                       const int *row_bytes /*host [n]*/, const void *compact_ws, void *stream);
 
 /* ---- map densification: clone, split and prune from one plan (csrc/densify_prune.hip) --------------------------------------------
+ * The rows are moved by the one mover of csrc/row_move.h, as in gsaj_compact_rows above: the two tables have one size and one set of limits.
  * The reference's densify_and_prune (gaussian_splatting/scene/gaussian_model.py:599-765: densify_and_clone, densify_and_split with
  * its prune of the parents, and the final prune_points) as one classification of the P source rows and one move of every tensor.
  * All comparisons are fp32; the caller rounds every threshold to fp32 once: t_dense = fl32(percent_dense * extent),

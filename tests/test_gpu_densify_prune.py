@@ -1,10 +1,11 @@
 """GPU: clone, split and prune of the map from one plan (csrc/densify_prune.hip, gsaj.densify.DensifyPlan) against the NumPy
 restatement of the reference (tests/densify_restated.py) on generated inputs that keep a 1e-4 margin from every threshold, the
-exact ties, the overlay GaussianModel.densify_and_prune against the outcome recorded from the reference
-(tests/golden/densify_prune_P150.npz) and against a twin densified with the reference's statement in torch, the counter-based
-noise, the covisibility window and a densified model through the rasteriser.  Everything copied, zeroed or counted is compared
-with torch.equal on int32 views; the children's xyz and _scaling against the fp64 restatement within the bounds derived there.
-The worst err / bound of each goes into profiles/r08_densify_parity.json when GSAJ_WRITE_PARITY is set."""
+exact ties, a prune-only plan against gsaj.pruning.CompactPlan (one row mover under both), the overlay
+GaussianModel.densify_and_prune against the outcome recorded from the reference (tests/golden/densify_prune_P150.npz) and against
+a twin densified with the reference's statement in torch, the counter-based noise, the covisibility window and a densified model
+through the rasteriser.  Everything copied, zeroed or counted is compared with torch.equal on int32 views; the children's xyz and
+_scaling against the fp64 restatement within the bounds derived there.  The worst err / bound of each goes into
+profiles/r08_densify_parity.json when GSAJ_WRITE_PARITY is set."""
 import ctypes
 import json
 import os
@@ -264,6 +265,40 @@ def test_stage_subsets(P):
         if stages == 0:
             assert counts == (P, 0, 0, P), tag
         check_rows(P, N, table, [False, True, False, True], _t(src), _t(kind > 0), code, ws, tag)
+
+
+@pytest.mark.parametrize("P", [255, 256, 257, 1000])
+def test_a_prune_only_plan_moves_what_the_compact_plan_moves(P):
+    """The two wrappers over the one mover (csrc/row_move.h) agree.  Opacity logits of +2 / -2 against min_opacity = 0.3 make the
+    prune rule keep a known set: with two blocks or more the first block whole (the straight copy), with three or more the second
+    block not at all, and two rows of three everywhere else, the ragged last block included.  A DensifyPlan of the PRUNE stage
+    alone (no gradients, no size rule) then has to give the tensors CompactPlan gives for that set, which are t[keep], bit for
+    bit, for rows of 4, 12, 180 and 4096 bytes, and counts of (kept, 0, 0, kept)."""
+    import torch
+    from gsaj.densify import PRUNE, DensifyPlan
+    from gsaj.pruning import CompactPlan
+    r = torch.arange(P, device=_dev())
+    nb = (P + 255) // 256
+    keep = r % 3 != 1  # (P = 257: the one row of the last block goes)
+    if nb >= 2:
+        keep[:256] = True
+    if nb >= 3:
+        keep[256:512] = False
+    n_kept = int(keep.sum())
+    assert 0 < n_kept < P
+    opacity = torch.where(keep, 2.0, -2.0).to(torch.float32).view(P, 1)
+    scaling = torch.full((P, 3), -3.0, device=_dev())
+    tensors = [pattern(t, P, w) for t, w in enumerate((1, 3, 45, 1024))]
+    dn = DensifyPlan(torch.empty(0, dtype=torch.float32, device=_dev()), None, scaling, opacity, MAX_GRAD, MIN_OPACITY, EXTENT, None,
+                     percent_dense=PERCENT_DENSE, stages=PRUNE)
+    assert dn.counts == (n_kept, 0, 0, n_kept), (P, dn.counts)
+    cp = CompactPlan(keep, remove=False)
+    assert cp.n_kept == n_kept
+    got_dn, got_cp = dn.apply(tensors), cp.apply(*tensors)
+    assert dn.launches == 1 and cp.launches == 1
+    for t, a, b in zip(tensors, got_dn, got_cp):
+        assert same_bits(a, b), "P=%d: rows of %d bytes differ between the two plans" % (P, 4 * t.shape[1])
+        assert same_bits(a, t[keep]), "P=%d: rows of %d bytes are not t[keep]" % (P, 4 * t.shape[1])
 
 
 def test_exact_ties():
