@@ -8,11 +8,13 @@
 //   k_dense_tau      <- the dL/dtau chain-rule loop (:1587-1695) incl. compute_sh_backward_single
 //                       (:452-532) and dnormvdv (:434-449)
 //
-// One pixel per lane; the Gaussian list is staged through LDS in chunks.  Pass 1 composites
-// front-to-back for the per-pixel totals; pass 2 repeats the walk, forms S_i (the sum over the
-// Gaussians behind i) as total - prefix in fp64, and reduces the 10 per-pixel partials of each
-// Gaussian with the same register-only wave reduction as the tiled backward.  Workgroup partials
-// go to a [workgroup][N][12] slab that a second kernel sums in workgroup order: no float atomics,
+// One pixel per lane; the Gaussian list is staged through LDS in chunks.  Pass 1 composites front-to-back and keeps every
+// Gaussian's transmittance T_i of the pixel in a [N][pixel] plane.  Pass 2 walks back-to-front: it carries R_i, what the Gaussians
+// behind i composite to on their own (R_{i-1} = val_i alpha_i + (1 - alpha_i) R_i, fp64: a sum of like-signed terms, nothing
+// cancels), forms S_i (the sum over the Gaussians behind i) as T_i (1 - alpha_i) R_i, and reduces the 10 per-pixel partials of
+// each Gaussian with the same register-only wave reduction as the tiled backward.  (S_i as total - prefix, even in fp64, is
+// rounded at the size of the total: behind a stack with T < 1e-11 it is the whole of dL/dalpha and had no correct digit.)
+// Workgroup partials go to a [workgroup][N][12] slab that a second kernel sums in workgroup order: no float atomics,
 // bit-reproducible.
 #include "gsaj_common.h"
 #include "wave_reduce.h"
@@ -54,8 +56,8 @@ __global__ __launch_bounds__(256) void k_dense_bwd(int N, int W, int H, const fl
                                                    const float *__restrict__ covs2D, const float *__restrict__ colors,
                                                    const float *__restrict__ depths, const float *__restrict__ opac,
                                                    const float *__restrict__ seed_color,
-                                                   const float *__restrict__ seed_depth, float *__restrict__ slab, int naive,
-                                                   DensePixelMap pm) {
+                                                   const float *__restrict__ seed_depth, float *__restrict__ slab,
+                                                   float *__restrict__ Tplane, int naive, DensePixelMap pm) {
   __shared__ float par[DCHUNK * DPAR];
   __shared__ float acc[DCHUNK * 4 * IGRAD_F];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -73,8 +75,8 @@ __global__ __launch_bounds__(256) void k_dense_bwd(int N, int W, int H, const fl
     gC[0] = seed_color[3 * pid]; gC[1] = seed_color[3 * pid + 1]; gC[2] = seed_color[3 * pid + 2];
     gD = seed_depth[pid];
   }
-  // ---- pass 1: per-pixel totals sum_i (c_i, z_i) alpha_i T_i ----
-  double tot[4] = {0.0, 0.0, 0.0, 0.0};
+  // ---- pass 1: T_i of this pixel for every Gaussian (plane stride = the padded pixel count: every lane owns a column) ----
+  const size_t plane = (size_t)gridDim.x * 256;
   {
     float T = 1.0f;
     for (int base = 0; base < N; base += DCHUNK) {
@@ -86,26 +88,25 @@ __global__ __launch_bounds__(256) void k_dense_bwd(int N, int W, int H, const fl
         const float *p = par + j * DPAR;
         float dx, dy, qx, qy, rx, ry;
         const float alpha = dense_alpha(p, u, v, dx, dy, qx, qy, rx, ry);
-        const float aT = alpha * T;
-        tot[0] += (double)(p[6] * aT); tot[1] += (double)(p[7] * aT); tot[2] += (double)(p[8] * aT);
-        tot[3] += (double)(p[9] * aT);
+        Tplane[(size_t)(base + j) * plane + pid] = T;
         T = T * (1.0f - alpha);
       }
     }
   }
-  // ---- pass 2: gradients ----
-  double pre[4] = {0.0, 0.0, 0.0, 0.0};
-  float T = 1.0f;
-  for (int base = 0; base < N; base += DCHUNK) {
+  // ---- pass 2: gradients, back to front ----
+  double R[4] = {0.0, 0.0, 0.0, 0.0};  // what the Gaussians behind the current one composite to, from T = 1
+  for (int base = ((N - 1) / DCHUNK) * DCHUNK; base >= 0; base -= DCHUNK) {
     const int n = min(DCHUNK, N - base);
     __syncthreads();
     stage_chunk(par, tid, base, n, means2D, covs2D, colors, depths, opac);
     __syncthreads();
-    for (int j = 0; j < n; j++) {
+    for (int j = n - 1; j >= 0; j--) {
       const float *p = par + j * DPAR;
       float dx, dy, qx, qy, rx, ry;
       const float alpha = dense_alpha(p, u, v, dx, dy, qx, qy, rx, ry);
+      const float T = Tplane[(size_t)(base + j) * plane + pid];
       const float aT = alpha * T;
+      const float Tn = T * (1.0f - alpha);  // the transmittance behind this Gaussian
       const float den = alpha < 0.999f ? 1.0f - alpha : 1.0f;
       // naive-loop semantics (GSAJ_DENSE_NAIVE_GUARDS): at alpha >= 0.999 the suffix term is dropped, not divided by 1
       const float keep = (naive && !(alpha < 0.999f)) ? 0.0f : 1.0f;
@@ -113,10 +114,10 @@ __global__ __launch_bounds__(256) void k_dense_bwd(int N, int W, int H, const fl
 #pragma unroll
       for (int ch = 0; ch < 4; ch++) {
         const float val = p[6 + ch];
-        pre[ch] += (double)(val * aT);
-        const float after = (float)(tot[ch] - pre[ch]);
+        const float after = (float)((double)Tn * R[ch]);
         const float g = ch < 3 ? gC[ch] : gD;
         dLda += g * (val * T - keep * (after / den));
+        R[ch] = (double)(val * alpha) + (double)(1.0f - alpha) * R[ch];
       }
       // (naive loop: an entry with abs(alpha) < 1e-8 adds nothing to dL/dmu, dL/dSigma)
       const float w = (inside && !(naive && fabsf(alpha) < 1e-8f)) ? dLda * alpha : 0.f;
@@ -127,7 +128,6 @@ __global__ __launch_bounds__(256) void k_dense_bwd(int N, int W, int H, const fl
       vals[4] = 0.5f * w * qy * rx; vals[5] = 0.5f * w * qy * ry;  //           [1][0], [1][1]
       vals[6] = m * gD;                                            // dL/dz
       vals[7] = m * gC[0]; vals[8] = m * gC[1]; vals[9] = m * gC[2];  // dL/dc
-      T = T * (1.0f - alpha);
       float x0, x1, x2;
       reduce10(vals, x0, x1, x2);
       store10(acc + (j * 4 + wave) * IGRAD_F, lane, x0, x1, x2);
@@ -466,7 +466,8 @@ extern "C" {
 
 size_t gsaj_dense_workspace_bytes(int N, int W, int H) {
   const size_t nblk = ((size_t)W * H + 255) / 256;
-  return nblk * (size_t)(N > 0 ? N : 1) * IGRAD_F * sizeof(float) + 256;
+  // the workgroup slab [nblk][N][IGRAD_F] and the transmittance plane [N][nblk * 256]
+  return nblk * (size_t)(N > 0 ? N : 1) * (IGRAD_F + 256) * sizeof(float) + 256;
 }
 
 int gsaj_dense_backward(int N, int W, int H, const float *means2D, const float *covs2D, const float *colors,
@@ -489,10 +490,11 @@ int gsaj_dense_backward(int N, int W, int H, const float *means2D, const float *
   hipStream_t s = (hipStream_t)stream;
   const int nblk = (int)(((size_t)W * H + 255) / 256);
   float *slab = reinterpret_cast<float *>(gsaj_align(reinterpret_cast<size_t>(dense_ws)));
+  float *Tplane = slab + (size_t)nblk * N * IGRAD_F;
   {
     GsajProfScope ps(ST_DENSE_BWD, s);
     hipLaunchKernelGGL(k_dense_bwd, dim3(nblk), dim3(256), 0, s, N, W, H, means2D, covs2D, colors, depths, opac, seed_color,
-                       seed_depth, slab, (flags & GSAJ_DENSE_NAIVE_GUARDS) ? 1 : 0, pm);
+                       seed_depth, slab, Tplane, (flags & GSAJ_DENSE_NAIVE_GUARDS) ? 1 : 0, pm);
   }
   GsajProfScope ps(ST_DENSE_REDUCE, s);
   hipLaunchKernelGGL(k_dense_reduce, dim3((N * 10 + 255) / 256), dim3(256), 0, s, N, nblk, slab, grad_mu, grad_Sigma,
