@@ -195,6 +195,115 @@ def test_loss_fused_into_the_compositors_gives_the_unfused_gradients_bit_for_bit
     assert float((scalars - want_scalars).abs().max()) <= 2e-6 * float(want_scalars.abs().max()), (scalars, want_scalars)
 
 
+FUSED_MODES = [(fl, m) for fl in (1, 1 | 2, 1 | 4, 1 | 2 | 4) for m in (False, True)] + [(0, False), (0, True), (2, False), (4, False), (2 | 4, False)]
+
+
+def _fused_pair(W, H, bg_rgb, P=300):
+    """A small scene rendered twice from one pose: context `a` for forward -> gsaj_loss_seeds -> backward, `b` for the fused calls."""
+    import torch
+    from gsaj.rasterizer import FrameContext
+
+    dev, cam, g, _, _, _, _, M, praw = _setup(P=P, W=W, H=H)
+    t = lambda x: torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32, device=dev)  # noqa: E731
+    bg = t(np.array(bg_rgb, np.float32))
+    view, proj, cp = t(cam["viewmatrix"]), t(cam["projmatrix"]), t(cam["campos"])
+    kw = dict(sh_degree=3, shs=g["shs"], scales=g["scales"], rotations=g["rotations"])
+    fwd = (bg, g["means3D"], g["opacities"], view, proj, cp, cam["tanfovx"], cam["tanfovy"])
+    bwd = (bg, g["means3D"], view, proj, praw, cp, cam["tanfovx"], cam["tanfovy"])
+    a, b = (FrameContext(P, W, H, M, dev, per_gaussian_tau=True) for _ in range(2))
+    for ctx in (a, b):
+        ctx.forward(*fwd, sync=True, **kw)
+    return dev, t, a, b, fwd, bwd, kw
+
+
+@pytest.mark.parametrize("W,H,bg_rgb", [(37, 29, (0, 0, 0)), (37, 29, (0.1, 0.2, 0.3)), (160, 120, (0, 0, 0)), (160, 120, (0.1, 0.2, 0.3))])
+def test_loss_fused_in_every_mode_size_and_background_against_the_unfused_path_and_the_restatement(W, H, bg_rgb):
+    """The fused pair in every flag combination the compositors accept (tracking and mapping, RGB-D and monocular, with and without
+    exposure, a mask where tracking reads one and one that mapping must ignore), on 160x120 (80 tiles) and 37x29 (6 tiles: not a multiple
+    of 8, so workgroups with rank >= tiles run and must zero their partial slot; the last tile column's right quadrants lie wholly
+    outside; the last tile row is ragged), over a zero and a non-zero background.  The ground truth is built on the images the device
+    rendered (loss_restated.gt_for_render), so the gates occur on rendered values: gt sums and gt depths on the threshold and an ulp
+    to either side, residuals exactly 0.  Every gradient output equals the unfused path bit for bit; the five scalars of both paths are
+    within SUM_K eps sum|term| + eps |value| of the float64 restatement evaluated on the rendered images.  A rendered opacity within
+    4 ulp of 0.95 would hold the depth sums to the unfused path only (asserted not to occur in these scenes)."""
+    import torch
+    import loss_restated as lr
+    from gsaj.losses import MONOCULAR, NO_EXPOSURE, LossSeeds
+
+    dev, t, a, b, fwd, bwd, kw = _fused_pair(W, H, bg_rgb)
+    ea, eb = t(np.array([0.07], np.float32)), t(np.array([0.02], np.float32))
+    mask_np = np.random.default_rng(5).choice(np.array([0, 1, 255], np.uint8), size=H * W, p=[0.3, 0.5, 0.2])
+    ls = LossSeeds(W, H, dev)
+    reached = set()
+    for flags, masked in FUSED_MODES:
+        tag = "%dx%d bg %s flags %d%s" % (W, H, bg_rgb, flags, " masked" if masked else "")
+        a.forward(*fwd, sync=False, **kw)
+        color, depth, opacity = (x.cpu().numpy() for x in (a.color, a.depth, a.opacity))
+        near = np.abs(opacity.astype(np.float64) - float(np.float32(0.95))) <= lr.OPACITY_ULPS * 2.0 ** -24
+        assert not near.any(), (tag, "a rendered opacity within 4 ulp of 0.95")
+        noexp = bool(flags & NO_EXPOSURE)
+        gtd = lr.gt_for_render(color, depth, flags, 0.07, 0.02, 0.01, seed=flags + 16 * masked)
+        reached |= set(gtd["planted"])
+        want = lr.restate(flags, 0.9, 0.01, color, depth, opacity, gtd["gt"], gtd["gt_depth"], mask_np if masked else None, 0.07, 0.02)
+        lr.check_guards(gtd, tag, want, gtd["zero_c"], gtd["zero_d"])
+        gt_c, gt_d = t(gtd["gt"]), None if flags & MONOCULAR else t(gtd["gt_depth"])
+        mask = torch.as_tensor(mask_np, device=dev) if masked else None
+        L = ls(flags, 0.9, 0.01, a.color, a.depth, a.opacity, gt_c, gt_d, mask, None if noexp else ea, None if noexp else eb)
+        lr.note("device_mi355x", "unfused_on_render", lr.assert_loss_close(L, want, tag + " (gsaj_loss_seeds)"))
+        ga = a.backward(*bwd, L["dL_dcolor"], L["dL_ddepth"], **kw)
+        ref = {n: x.clone() for n, x in ga.items() if torch.is_tensor(x)}
+        assert float(ref["tau_sum"].abs().max()) > 0.0, tag
+
+        scalars = torch.zeros(5, device=dev)
+        FL = dict(flags=flags, alpha=0.9, rgb_boundary_threshold=0.01, gt_color=gt_c, gt_depth=gt_d, grad_mask=mask, exposure_a=None if noexp else ea,
+                  exposure_b=None if noexp else eb, scalars=scalars)
+        b.forward_loss(FL, *fwd, **kw)
+        gb = b.backward_loss(FL, *bwd, **kw)
+        assert torch.equal(a.color, b.color) and torch.equal(a.depth, b.depth) and torch.equal(a.opacity, b.opacity), tag
+        for n, x in ref.items():
+            assert torch.equal(gb[n], x), "%s: dL/d%s of the fused path differs from the unfused path" % (tag, n)
+        got = dict(zip(lr.SCALARS, scalars.cpu().numpy()))
+        ratios = lr.assert_loss_close(got, want, tag + " (fused)", lr.SCALARS)
+        print(tag, {k: round(v, 4) for k, v in ratios.items()})
+        lr.note("device_mi355x", "fused_%dx%d" % (W, H), ratios)
+    assert {"rgb_thr", "gt_depth", "zero_depth", "zero_color"} <= reached, reached
+
+
+def test_fused_forward_is_not_reached_by_stale_partials():
+    """37x29 is 6 tiles: the forward launches 32 workgroups for 8 tile ranks, and the 8 whose rank >= tiles own partial slots that no
+    pixel feeds -- they must be zeroed on every launch, or k_loss_finalize adds what was there.  A first frame with large loss terms
+    (gt = render + 100), then the whole workspace overwritten with 1e6, then a frame whose loss is small (residuals of 1e-3) on the same
+    context and workspace: its five scalars must meet the bound."""
+    import torch
+    import loss_restated as lr
+
+    W, H = 37, 29
+    dev, t, a, b, fwd, bwd, kw = _fused_pair(W, H, (0, 0, 0))
+    ea, eb = t(np.array([0.07], np.float32)), t(np.array([0.02], np.float32))
+    a.forward(*fwd, sync=False, **kw)
+    color, depth, opacity = (x.cpu().numpy() for x in (a.color, a.depth, a.opacity))
+    fm = float(np.exp(np.float64(np.float32(0.07)))) * color.astype(np.float64) + float(np.float32(0.02))
+    rng = np.random.default_rng(9)
+    frames = [((fm + 100.0).astype(np.float32), (depth[0] + np.float32(50.0)).astype(np.float32)),
+              ((fm + rng.choice([-1.0, 1.0], fm.shape) * 1e-3).astype(np.float32),
+               (depth[0] + rng.choice([-1.0, 1.0], depth[0].shape) * 1e-3).astype(np.float32))]
+    values = []
+    for i, (gt, gtd) in enumerate(frames):
+        want = lr.restate(0, 0.9, 0.01, color, depth, opacity, gt, gtd, None, 0.07, 0.02)
+        lr.check_guards(dict(gt_depth=gtd), "frame %d" % i, want, np.zeros((3, H * W), bool), np.zeros(H * W, bool))
+        scalars = torch.zeros(5, device=dev)
+        FL = dict(flags=0, alpha=0.9, rgb_boundary_threshold=0.01, gt_color=t(gt), gt_depth=t(gtd), grad_mask=None, exposure_a=ea, exposure_b=eb,
+                  scalars=scalars)
+        b.forward_loss(FL, *fwd, **kw)
+        torch.cuda.synchronize()
+        got = dict(zip(lr.SCALARS, scalars.cpu().numpy()))
+        lr.note("device_mi355x", "fused_after_stale", lr.assert_loss_close(got, want, "frame %d" % i, lr.SCALARS))
+        values.append(want["value"]["loss"])
+        n = b.loss_ws.numel() // 4 * 4
+        b.loss_ws[:n].view(torch.float32).fill_(1e6)   # what another frame, or another owner of the memory, could have left
+    assert values[0] > 1e4 * values[1] > 0
+
+
 def test_fused_tracker_follows_the_unfused_tracker_bit_for_bit():
     """DeviceTracker(fused=True), the default: an iteration is forward_loss -> backward_loss -> pose step, with no dL/dpix buffers;
     the pose after 10 iterations equals the unfused tracker's bit for bit (the pose step consumes dL/dtau and dL/d(exposure), both

@@ -100,3 +100,97 @@ def test_batched_loss_seeds_equal_the_single_view_calls_bit_for_bit(flags_name):
         assert torch.equal(lb.scalars[k], ls.scalars)
     with pytest.raises(Exception, match="gsaj_loss_seeds_batch"):
         lb(8, 0.9, 0.01, image, depth, opacity, gt_image, gt_depth)  # COMPUTE_LOSS has no batched form
+
+
+# ---- per-pixel / per-scalar parity against the float64 restatement (tests/loss_restated.py) ------------------------------------------
+# Every pixel of the three seed images is held to ROUND_K eps x its own mass (exactly 0 behind a closed gate or on a residual that is
+# exactly 0), every scalar to SUM_K eps sum|term| + eps |value|, on frames that sit ON each gate of loss_pixel (gt sum, gt depth,
+# opacity: the threshold and an ulp to either side; mask bytes 0, 1, 255; residuals exactly 0; ea c + eb < 0), at image sizes around
+# the workgroup's 1024 pixels, in every flag combination.  No pixel is exempted: the cases assert their own guard margins.  The worst
+# err / bound per output goes into profiles/r10_loss_parity.json when GSAJ_WRITE_PARITY is set.
+import loss_restated as lr  # noqa: E402
+
+
+def _t(a, dtype=None):
+    import torch
+    return None if a is None else torch.as_tensor(np.array(a), dtype=dtype, device="cuda:0")
+
+
+def _frame_args(fr):
+    import torch
+    f = torch.float32
+    return (int(fr["flags"]), float(fr["alpha"]), float(fr["rgb_thr"]), _t(fr["image"], f), _t(fr["depth"], f), _t(fr["opacity"], f),
+            _t(fr["gt"], f), _t(fr["gt_depth"], f), _t(fr["mask"], torch.uint8), None if fr["a"] is None else _t([fr["a"]], f),
+            None if fr["b"] is None else _t([fr["b"]], f))
+
+
+@pytest.mark.parametrize("name", lr.cases())
+def test_loss_seeds_every_pixel_and_scalar_against_the_restatement(name):
+    import torch
+    from gsaj import losses
+
+    fr = lr.make_case(name)
+    ls = losses.LossSeeds(fr["W"], fr["H"], torch.device("cuda:0"))
+    args = _frame_args(fr)
+    first = {k: v.clone() for k, v in ls(*args, want_opacity_grad=True).items()}
+    out = ls(*args, want_opacity_grad=True)
+    for k in out:  # second launch reuses the ticket: identical bits
+        assert torch.equal(out[k], first[k]), (name, k)
+    ratios = lr.assert_loss_close(out, fr["want"], name)
+    print(name, {k: round(v, 4) for k, v in ratios.items()})
+    lr.note("device_mi355x", "loss_seeds/" + name.rsplit("-", 1)[0], ratios)
+    if name == "cl-no-valid-pixel-37x29":
+        # no pixel with gt_depth > 0 inside the mask: max(n_valid, 1) makes the depth term a finite 0 (torch's mean over the empty
+        # selection in compute_loss, Jacobian_test.py:155-196, is NaN); the loss is the colour term alone
+        assert float(out["l1_depth"]) == 0.0 and float(out["loss"]) == float(out["l1_rgb"]) and not bool(out["dL_ddepth"].any())
+
+
+@pytest.mark.parametrize("K,W,H", [(1, 1, 1), (3, 1, 1), (1, 37, 29), (3, 37, 29)])
+@pytest.mark.parametrize("flags,masked", [(1, True), (0, False), (2, False), (1 | 4, True)], ids=["track-mask", "map", "map-mono", "track-noexp-mask"])
+def test_batched_loss_seeds_every_view_against_the_restatement(K, W, H, flags, masked):
+    """Each view has its own exposure (a = -0.05, 0, 0.1; b = 0.01, 1/64, -0.5), its own mask and its own planted gates; the per-view
+    workspace stride is the rounded-up minimum, which at 1x1 and 37x29 is one and two workgroups' worth."""
+    import torch
+    from gsaj.losses import LossSeedsBatch
+
+    frames = [lr.make_frame(W, H, flags, masked, 60 + k, exposure=("ab", "a0", "negb")[k], plant=W * H > 1 or k == 0) for k in range(K)]
+    f = torch.float32
+    stack = lambda key, dt: None if frames[0][key] is None else _t(np.stack([fr[key] for fr in frames]), dt)  # noqa: E731
+    ea = None if frames[0]["a"] is None else _t([fr["a"] for fr in frames], f)
+    eb = None if frames[0]["b"] is None else _t([fr["b"] for fr in frames], f)
+    lb = LossSeedsBatch(K, W, H, torch.device("cuda:0"))
+    for _ in range(2):  # twice: the tickets must have been reset
+        ob = lb(flags, 0.9, 0.01, stack("image", f), stack("depth", f), stack("opacity", f), stack("gt", f), stack("gt_depth", f),
+                stack("mask", torch.uint8), ea, eb)
+    for k, fr in enumerate(frames):
+        got = {n: ob[n][k] for n in ("dL_dcolor", "dL_ddepth") + lr.SCALARS}
+        lr.note("device_mi355x", "loss_seeds_batch", lr.assert_loss_close(got, fr["want"], "view %d of %d, %dx%d flags %d" % (k, K, W, H, flags)))
+
+
+@pytest.mark.parametrize("P", lr.ISO_P)
+@pytest.mark.parametrize("C", lr.ISO_C)
+def test_isotropic_loss_every_row_against_the_restatement(P, C):
+    """Rows of three equal scales (what gsaj_seed_gaussians makes; fp32 sees d = +-1 ulp on one row in seven) must give a gradient of
+    exactly 0, (1/8, 2/8, 3/8) exactly k (-1, 0, +1); P around the workgroup's 256 rows, C = 1, 2, 3; two calls on one workspace give
+    equal bits (ticket reset); accumulate on and off."""
+    import torch
+    from gsaj.losses import IsotropicLoss
+
+    c = lr.make_iso_case(P, C)
+    iso = IsotropicLoss(P, torch.device("cuda:0"))
+    s = _t(c["scales"], torch.float32)
+    loss, g = iso(s, weight=lr.ISO_WEIGHT)
+    loss0, g0 = loss.clone(), g.clone()
+    loss, g = iso(s, weight=lr.ISO_WEIGHT)
+    assert torch.equal(loss, loss0) and torch.equal(g, g0)
+    lr.note("device_mi355x", "isotropic", lr.assert_iso_close(loss, g, c["want"], "isotropic P %d C %d" % (P, C)))
+    gn = g.cpu().numpy()
+    assert not gn[c["equal_rows"]].any()
+    if c["ramp_rows"].size:
+        k = np.float32(lr.ISO_WEIGHT) / (np.float32(P) * np.float32(C))
+        assert (gn[c["ramp_rows"]] == np.array([-k, 0, k], np.float32)).all()
+    acc = _t(c["grad_in"], torch.float32)
+    loss, g = iso(s, weight=lr.ISO_WEIGHT, grad_out=acc, accumulate=True)
+    assert torch.equal(loss, loss0)
+    lr.note("device_mi355x", "isotropic", lr.assert_iso_close(loss, g, c["want_acc"], "isotropic P %d C %d accumulate" % (P, C)))
+    assert torch.equal(g[torch.as_tensor(c["equal_rows"], device=g.device)], _t(c["grad_in"][c["equal_rows"]], torch.float32))
