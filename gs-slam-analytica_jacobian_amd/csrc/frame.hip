@@ -21,6 +21,7 @@
 // Built with -ffp-contract=off (csrc/Makefile): each tensor operation of the reference rounds once in fp32, and so does each
 // operator here; division and square root are correctly rounded (hipcc's default for fp32).
 #include "gsaj_common.h"
+#include "wave_reduce.h"
 #include <cmath>
 
 #define GM_THREADS 256
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(GM_THREADS) void k_gm_blocks(int W, int H, int bw, 
   __shared__ uint32_t hist[256];
   __shared__ uint32_t wsum[4];
   __shared__ uint32_t s_prefix, s_rank;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int x0 = blockIdx.x * bw, y0 = blockIdx.y * bh, n = bw * bh, ld = bw + 2;
   gm_stage_tile(image, W, H, x0, y0, bw, bh, tile);
   if (tid == 0) {
@@ -148,17 +149,7 @@ __global__ __launch_bounds__(GM_THREADS) void k_gm_blocks(int W, int H, int bw, 
     }
     __syncthreads();
     const uint32_t c = hist[tid];
-    uint32_t x = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = (uint32_t)__shfl_up((int)x, o);
-      if (lane >= o) x += up;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    uint32_t before = 0u;
-    for (int k = 0; k < wave; k++) before += wsum[k];
-    const uint32_t excl = before + x - c;
+    const uint32_t excl = block_excl_scan_add<GM_THREADS / 64>(c, wsum);
     if (rank >= excl && rank < excl + c) {  // exactly one thread: the counts add up to more than the rank
       s_prefix = prefix | ((uint32_t)tid << shift);
       s_rank = rank - excl;

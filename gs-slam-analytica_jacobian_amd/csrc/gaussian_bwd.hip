@@ -14,6 +14,7 @@
 // contiguous run (emission-slot order), and the [64][M*3] SH blocks are staged through LDS so that the
 // global loads / stores of dL_dsh are fully coalesced (padded LDS rows, conflict-free per-lane reads).
 #include "gsaj_common.h"
+#include "wave_reduce.h"
 
 __constant__ float bSH_C0 = 0.28209479177387814f;
 __constant__ float bSH_C1 = 0.4886025119029199f;
@@ -353,9 +354,7 @@ __global__ __launch_bounds__(GB_BLOCK) void k_gaussian_bwd(BwdParams p, GeomWS g
   // The wave's rows [F, E) of inst_grad are gathered in trips of 256; the first trip's flag and row loads (two dependent
   // round trips) are issued NOW, so that they overlap the input loads and the SH staging below.
   const uint32_t F = (uint32_t)__shfl((int)first, 0);
-  uint32_t E = endi;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) E = max(E, (uint32_t)__shfl_xor((int)E, o));
+  const uint32_t E = wave_max(endi);
   float4 a[4][3];
   auto load_trip = [&](uint32_t lo, uint32_t hi) {
 #pragma unroll
@@ -449,9 +448,7 @@ __global__ __launch_bounds__(GB_BLOCK) void k_gaussian_bwd(BwdParams p, GeomWS g
   // ---- 7. wave partial of dL/dtau (fixed butterfly) ----
 #pragma unroll
   for (int k = 0; k < 6; k++) {
-    float v = tau[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const float v = wave_sum(tau[k]);
     if (tid == 0)  // write-through (sc1) store: part of the fence-free hand-off below
       __hip_atomic_store(&g.tau_partials[(size_t)blockIdx.x * 8 + k], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -474,9 +471,7 @@ __global__ __launch_bounds__(GB_BLOCK) void k_gaussian_bwd(BwdParams p, GeomWS g
   gsaj_sum_partials(g.tau_partials, nblk, tid, acc6);
 #pragma unroll
   for (int k = 0; k < 6; k++) {
-    double v = acc6[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const double v = wave_sum(acc6[k]);
     if (tid == 0) p.dL_dtau_sum[k] = (float)v;
   }
   if (tid == 0) counters[3] = 0u;  // ready for the next backward over this workspace
@@ -611,16 +606,9 @@ __global__ __launch_bounds__(256) void k_gather_sums(int P, const int *__restric
   const uint32_t cnt = live ? g.tiles_touched[ii] : 0u;
   const uint32_t endi_raw = live ? g.block_sums[ii / PRE_BLOCK] + g.point_offsets[ii] : 0u;  // (block-local scan + the block's offset)
   // owners' end slots, made non-decreasing over the lanes (culled / out-of-range owners repeat their predecessor's end)
-  uint32_t endi = endi_raw;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t up = (uint32_t)__shfl_up((int)endi, o);
-    if (lane >= o) endi = max(endi, up);
-  }
+  const uint32_t endi = wave_incl_scan_max(endi_raw);
   const uint32_t first = live ? endi_raw - cnt : endi;
-  uint32_t F = (cnt > 0) ? first : 0xffffffffu;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) F = min(F, (uint32_t)__shfl_xor((int)F, o));
+  const uint32_t F = wave_min((cnt > 0) ? first : 0xffffffffu);
   const uint32_t E = (uint32_t)__shfl((int)endi, 63);
   float sum[10];
 #pragma unroll
@@ -848,7 +836,7 @@ __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, in
     uint8_t cl_w[3] = {0, 0, 0};
     if constexpr (GATHER) {
       float sum[10];
-      const int lane = tid & 63, hl = lane & (CW_G - 1);
+      const int lane = tid & 63;
       const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // this wave's views: v0 + 2 wv (lanes 0-31), v0 + 2 wv + 1 (lanes 32-63)
       const size_t vc = (size_t)(v < K ? v : v0);  // (a lane past the window's last view reads view v0's and uses nothing of it)
       const GeomWS gw = geom_view(g0, vc * vs.geom);
@@ -862,16 +850,10 @@ __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, in
       // the grid's origin: first row of the enclosing block of 64 Gaussians = end slot of the Gaussian before it (same PRE_BLOCK)
       const int i64 = ((int)blockIdx.x & ~1) * CW_G;
       const uint32_t G32 = live ? bs + ((i64 % PRE_BLOCK) ? gw.point_offsets[i64 - 1] : 0u) : 0u;
-      uint32_t endi = endi_raw;  // non-decreasing over the half-wave (out-of-range owners repeat their predecessor's end)
-#pragma unroll
-      for (int o2 = 1; o2 < CW_G; o2 <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)endi, o2, CW_G);
-        if (hl >= o2) endi = max(endi, up);
-      }
+      // non-decreasing over the half-wave (out-of-range owners repeat their predecessor's end)
+      const uint32_t endi = wave_incl_scan_max<CW_G>(endi_raw);
       const uint32_t first = live ? endi_raw - cnt : endi;
-      uint32_t F32 = (cnt > 0) ? first : 0xffffffffu;
-#pragma unroll
-      for (int o2 = CW_G / 2; o2 > 0; o2 >>= 1) F32 = min(F32, (uint32_t)__shfl_xor((int)F32, o2));
+      const uint32_t F32 = wave_min<CW_G>((cnt > 0) ? first : 0xffffffffu);
       const uint32_t E32 = (uint32_t)__shfl((int)endi, CW_G - 1, CW_G);
       const uint32_t G0 = (uint32_t)__shfl((int)G32, 0, CW_G);  // (lane 0 of a half is in range whenever the workgroup exists)
 #pragma unroll
@@ -980,10 +962,7 @@ __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, in
       float t6[6];
 #pragma unroll
       for (int k = 0; k < 6; k++) {
-        float t = tau[k];
-#pragma unroll
-        for (int o2 = CW_G / 2; o2 > 0; o2 >>= 1) t += __shfl_xor(t, o2);
-        t6[k] = t;
+        t6[k] = wave_sum<CW_G>(tau[k]);
       }
       if (gl == 0) {
         float4 *tp = reinterpret_cast<float4 *>(g.tau_partials + (size_t)blockIdx.x * 8);

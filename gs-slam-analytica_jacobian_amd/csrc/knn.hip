@@ -12,6 +12,7 @@
 // points = spatial neighbours) scans the UNION of the boxes its lanes accept, so a box's points are fetched once per
 // wave through LDS and every lane tests them (a superset of candidates keeps the result exact).
 #include "gsaj_common.h"
+#include "wave_reduce.h"
 #include <cfloat>
 #include <cstring>
 
@@ -59,12 +60,7 @@ __global__ __launch_bounds__(256) void k_knn_bbox(int P, const float *__restrict
     v[3] = fmaxf(0.f, x); v[4] = fmaxf(0.f, y); v[5] = fmaxf(0.f, z);
   }
 #pragma unroll
-  for (int c = 0; c < 6; c++)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float t = __shfl_xor(v[c], o);
-      v[c] = c < 3 ? fminf(v[c], t) : fmaxf(v[c], t);
-    }
+  for (int c = 0; c < 6; c++) v[c] = c < 3 ? wave_min(v[c]) : wave_max(v[c]);
   if ((threadIdx.x & 63) == 0)
 #pragma unroll
     for (int c = 0; c < 6; c++) red[c][threadIdx.x >> 6] = v[c];
@@ -89,12 +85,7 @@ __global__ __launch_bounds__(256) void k_knn_bbox(int P, const float *__restrict
       a[c] = c < 3 ? fminf(a[c], t) : fmaxf(a[c], t);
     }
 #pragma unroll
-  for (int c = 0; c < 6; c++)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float t = __shfl_xor(a[c], o);
-      a[c] = c < 3 ? fminf(a[c], t) : fmaxf(a[c], t);
-    }
+  for (int c = 0; c < 6; c++) a[c] = c < 3 ? wave_min(a[c]) : wave_max(a[c]);
   __syncthreads();
   if ((threadIdx.x & 63) == 0)
 #pragma unroll
@@ -163,25 +154,16 @@ __global__ __launch_bounds__(64) void k_rs_hist(int P, int ntile, int shift, con
 __global__ __launch_bounds__(1024) void k_rs_scan(int n, uint32_t *__restrict__ hist) {  // exclusive scan, one workgroup
   __shared__ uint32_t wsum[16];
   __shared__ uint32_t carry;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid == 0) carry = 0u;
   __syncthreads();
   for (int base = 0; base < n; base += 1024) {
     const int i = base + tid;
     const uint32_t v = i < n ? hist[i] : 0u;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t = (uint32_t)__shfl_up((int)x, o);
-      if (lane >= o) x += t;
-    }
-    if (lane == 63) wsum[wave] = x;
+    const uint32_t excl = block_excl_scan_add<16>(v, wsum) + carry;  // (carry: read behind the scan's barrier)
+    if (i < n) hist[i] = excl;
     __syncthreads();
-    uint32_t before = carry;
-    for (int k = 0; k < wave; k++) before += wsum[k];
-    if (i < n) hist[i] = before + x - v;
-    __syncthreads();
-    if (tid == 1023) carry = before + x;
+    if (tid == 1023) carry = excl + v;
     __syncthreads();
   }
 }
@@ -247,12 +229,7 @@ __global__ __launch_bounds__(KNN_BOX) void k_knn_boxes(int P, const float *__res
     v[0] = x; v[1] = y; v[2] = z; v[3] = x; v[4] = y; v[5] = z;
   }
 #pragma unroll
-  for (int c = 0; c < 6; c++)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float t = __shfl_xor(v[c], o);
-      v[c] = c < 3 ? fminf(v[c], t) : fmaxf(v[c], t);
-    }
+  for (int c = 0; c < 6; c++) v[c] = c < 3 ? wave_min(v[c]) : wave_max(v[c]);
   if ((threadIdx.x & 63) == 0)
 #pragma unroll
     for (int c = 0; c < 6; c++) red[c][threadIdx.x >> 6] = v[c];

@@ -11,6 +11,7 @@
 // workgroup (ticket; no float atomics).
 #include "gsaj_common.h"
 #include "loss_terms.h"
+#include "wave_reduce.h"
 
 #define LOSS_BLOCK 256
 #define LOSS_PPT 4  // pixels per thread (strided by the workgroup size: coalesced, 4x the loads in flight, 4x fewer partials)
@@ -77,10 +78,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_loss_seeds(LossParams p) {
   // workgroup partials: wave butterfly, then the four waves in order
   float v[4] = {s_rgb, s_d, s_a, s_b};
 #pragma unroll
-  for (int c = 0; c < 4; c++) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o);
-  }
+  for (int c = 0; c < 4; c++) v[c] = wave_sum(v[c]);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (lane == 0) {
 #pragma unroll
@@ -113,10 +111,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_loss_seeds(LossParams p) {
     acc[3] += (double)__uint_as_float(u.w);
   }
 #pragma unroll
-  for (int c = 0; c < 4; c++) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
-  }
+  for (int c = 0; c < 4; c++) acc[c] = wave_sum(acc[c]);
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < 4; c++) fin[c][wave] = acc[c];
@@ -185,8 +180,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_count_valid(size_t HW, const flo
   uint32_t c = 0;
   for (size_t i = (size_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < HW; i += (size_t)gridDim.x * LOSS_BLOCK)
     c += (gt_depth[i] > 0.0f && (!mask || mask[i])) ? 1u : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
 }
 
@@ -287,8 +281,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_isotropic(int P, int C, float we
         dL_dscales[(size_t)i * C + c] = accumulate ? dL_dscales[(size_t)i * C + c] + gq : gq;
       }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -250,33 +250,15 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_preprocess(FwdParams p, int *__re
     g.splat[3 * (size_t)idx + 2] = make_float4(rgb.x, rgb.y, rgb.z, depth);
   }
   TRP(0)
-  // block-local inclusive scan of tiles_touched: wave scans (shuffles) + one LDS hop for the four wave totals
-  uint32_t incl = touched;
-  {
-    const int lane = tid & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t v = (uint32_t)__shfl_up((int)incl, o);
-      if (lane >= o) incl += v;
-    }
-    if (lane == 63) scan[tid >> 6] = incl;
-  }
-  __syncthreads();
-  uint32_t block_total = 0;
-#pragma unroll
-  for (int w = 0; w < PRE_BLOCK / 64; w++) {
-    const uint32_t v = scan[w];
-    if (w < (tid >> 6)) incl += v;
-    block_total += v;
-  }
+  // block-local scan of tiles_touched
+  const uint32_t first = block_excl_scan_add<PRE_BLOCK / 64>(touched, scan);
   if (idx < p.P) {
     // emission slots are counted inside the block; + block_sums[block] (its exclusive offset once the frame scan below has run)
-    const uint32_t first = incl - touched;
-    g.point_offsets[idx] = incl;
+    g.point_offsets[idx] = first + touched;
     reinterpret_cast<float *>(g.splat)[12 * (size_t)idx + 3] = __uint_as_float(first);
     g.scat[idx] = make_uint2(rect_x, rect_y);
   }
-  if (tid == 0) g.block_sums[blk] = block_total;  // block totals -> exclusive offsets: k_frame_scan
+  if (tid == 0) g.block_sums[blk] = block_scan_total<PRE_BLOCK / 64>(scan);  // block totals -> exclusive offsets: k_frame_scan
   __syncthreads();  // (scan[] is written again by the next block; after the last one: every thread's LDS histogram atomics are done)
   }
   if (use_lds)
@@ -295,50 +277,6 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_preprocess(FwdParams p, int *__re
 #endif
 }
 
-// Exclusive scan of n items by ONE workgroup of PRE_BLOCK lanes: each lane sums a contiguous run, the
-// run totals are scanned with wave shuffles + one LDS hop, then each lane rewrites its run.  Returns the total.
-__device__ uint32_t tail_exclusive_scan(const uint32_t *in, uint32_t *out, int n, uint32_t *run_max) {
-  __shared__ uint32_t wsum[PRE_BLOCK / 64];
-  __shared__ uint32_t wmax[PRE_BLOCK / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int per = (n + PRE_BLOCK - 1) / PRE_BLOCK;
-  const int b0 = min(n, tid * per), b1 = min(n, b0 + per);
-  uint32_t s = 0, mx = 0;
-  for (int i = b0; i < b1; i++) {
-    const uint32_t v = in[i];
-    s += v;
-    mx = max(mx, v);
-  }
-  uint32_t incl = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t v = __shfl_up((int)incl, o);
-    if (lane >= o) incl += v;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-  if (lane == 63) wsum[wave] = incl;
-  if (lane == 0) wmax[wave] = mx;
-  __syncthreads();
-  uint32_t woff = 0, total = 0, m = 0;
-#pragma unroll
-  for (int w = 0; w < PRE_BLOCK / 64; w++) {
-    const uint32_t v = wsum[w];
-    if (w < wave) woff += v;
-    total += v;
-    m = max(m, wmax[w]);
-  }
-  if (run_max) *run_max = m;
-  uint32_t run = woff + incl - s;
-  for (int i = b0; i < b1; i++) {
-    const uint32_t v = in[i];
-    out[i] = run;
-    run += v;
-  }
-  __syncthreads();
-  return total;
-}
-
 // The per-tile histogram the other workgroups flushed -> (1) its exclusive scan (tile_offset), (2) the longest list, (3) the order
 // in which both compositors take their tiles: longest list first (64 length classes, counting sort in LDS).  A launch that
 // oversubscribes the chip (a batched window: 9600 tiles for 1280 workgroup slots) then ends on its short tiles instead of waiting
@@ -347,7 +285,7 @@ __device__ uint32_t tail_exclusive_scan(const uint32_t *in, uint32_t *out, int n
 // ([tiles], the dead workgroup-local histogram area) with wide coherent loads; every later pass reads LDS.
 __device__ uint32_t tile_scan_and_schedule(int tiles, ImageWS im, uint32_t *len, uint32_t *longest_out) {
   __shared__ uint32_t wsum[PRE_BLOCK / 64], wmax[PRE_BLOCK / 64], cls[64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   for (int c = tid; 4 * c < tiles; c += PRE_BLOCK) {  // (reads up to 3 words past `tiles`: still inside the zeroed counter block)
     const uint4 v = *reinterpret_cast<const uint4 *>(im.tile_count + 4 * c);
     len[4 * c] = v.x;
@@ -357,51 +295,16 @@ __device__ uint32_t tile_scan_and_schedule(int tiles, ImageWS im, uint32_t *len,
   }
   if (tid < 64) cls[tid] = 0u;
   __syncthreads();
-  // (1) + (2): each lane owns a contiguous run, run totals scanned with wave shuffles + one LDS hop
-  const int per = (tiles + PRE_BLOCK - 1) / PRE_BLOCK;
-  const int b0 = min(tiles, tid * per), b1 = min(tiles, b0 + per);
-  uint32_t s = 0, mx = 0;
-  for (int i = b0; i < b1; i++) {
-    s += len[i];
-    mx = max(mx, len[i]);
-  }
-  uint32_t incl = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t v = __shfl_up((int)incl, o);
-    if (lane >= o) incl += v;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-  if (lane == 63) wsum[wave] = incl;
-  if (lane == 0) wmax[wave] = mx;
-  __syncthreads();
-  uint32_t woff = 0, total = 0, longest = 0;
-#pragma unroll
-  for (int w = 0; w < PRE_BLOCK / 64; w++) {
-    const uint32_t v = wsum[w];
-    if (w < wave) woff += v;
-    total += v;
-    longest = max(longest, wmax[w]);
-  }
-  uint32_t run = woff + incl - s;
-  for (int i = b0; i < b1; i++) {
-    im.tile_offset[i] = run;
-    run += len[i];
-  }
+  // (1) + (2)
+  uint32_t longest;
+  const uint32_t total = block_excl_scan_runs<PRE_BLOCK / 64>(len, im.tile_offset, tiles, wsum, wmax, longest);
   // (3)
   const int shift = longest >= 64u ? (32 - __builtin_clz(longest)) - 6 : 0;  // longest >> shift <= 63
   for (int t = tid; t < tiles; t += PRE_BLOCK) atomicAdd(&cls[63u - min(63u, len[t] >> shift)], 1u);
   __syncthreads();
   if (tid < 64) {  // exclusive scan of the 64 class sizes by one wave
     const uint32_t v = cls[tid];
-    uint32_t in2 = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t u = (uint32_t)__shfl_up((int)in2, o);
-      if (tid >= o) in2 += u;
-    }
-    cls[tid] = in2 - v;
+    cls[tid] = wave_incl_scan_add(v) - v;
   }
   __syncthreads();
   for (int t = tid; t < tiles; t += PRE_BLOCK) im.tile_order[atomicAdd(&cls[63u - min(63u, len[t] >> shift)], 1u)] = (uint32_t)t;
@@ -420,13 +323,15 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_frame_scan(int nblk, int tiles, i
   extern __shared__ uint32_t lds_len[];  // [tiles] when tiles <= LDS_TILES_MAX
   g = geom_view(g, (size_t)blockIdx.y * vs.geom);
   im = image_view(im, (size_t)blockIdx.y * vs.image);
+  __shared__ uint32_t wsum[PRE_BLOCK / 64], wmax[PRE_BLOCK / 64];
   uint32_t *block_sums = g.block_sums;
-  const uint32_t R = tail_exclusive_scan(block_sums, block_sums, nblk, nullptr);
-  uint32_t m = 0, R2;
+  uint32_t m, R2;  // (m: the largest block total first -- not wanted --, then the longest tile list)
+  const uint32_t R = block_excl_scan_runs<PRE_BLOCK / 64>(block_sums, block_sums, nblk, wsum, wmax, m);
+  __syncthreads();  // (wsum / wmax are used again below)
   if (tiles <= LDS_TILES_MAX) {
     R2 = tile_scan_and_schedule(tiles, im, lds_len, &m);
   } else {  // more tiles than the LDS copy holds (> 8192: beyond 2048 x 1024 pixels): scan from memory, tiles in index order
-    R2 = tail_exclusive_scan(im.tile_count, im.tile_offset, tiles, &m);
+    R2 = block_excl_scan_runs<PRE_BLOCK / 64>(im.tile_count, im.tile_offset, tiles, wsum, wmax, m);
     for (int t = threadIdx.x; t < tiles; t += PRE_BLOCK) im.tile_order[t] = (uint32_t)t;
   }
   if (threadIdx.x == 0) {
@@ -541,7 +446,7 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_scatter_instances(int P, int gx, 
   // overlapping across the lanes) and lay the tiles' runs out back to back in the staging area: 256 tiles per step, exclusive
   // scan of their counts by wave shuffles + one LDS hop, carry from step to step
   for (int l0 = 0; l0 < ltiles; l0 += PRE_BLOCK) {
-    const int lt = l0 + tid, lane = tid & 63;
+    const int lt = l0 + tid;
     uint32_t c = 0u, off = 0u, base = 0u;
     if (lt < ltiles) {
       const int j = lt / gx;
@@ -550,24 +455,13 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_scatter_instances(int P, int gx, 
       off = im.tile_offset[t];  // in flight together with the atomic
       if (c) base = atomicAdd(&im.tile_cursor[t], c);
     }
-    uint32_t incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t v = (uint32_t)__shfl_up((int)incl, o);
-      if (lane >= o) incl += v;
-    }
-    if (lane == 63) s_wave[tid >> 6] = incl;
-    __syncthreads();
-    uint32_t before = s_carry;
-#pragma unroll
-    for (int w = 0; w < PRE_BLOCK / 64; w++)
-      if (w < (tid >> 6)) before += s_wave[w];
+    const uint32_t first = block_excl_scan_add<PRE_BLOCK / 64>(c, s_wave) + s_carry;  // (s_carry: read behind the scan's barrier)
     if (lt < ltiles) {
       cnt[lt] = off + base;
-      lbase[lt] = before + incl - c;
+      lbase[lt] = first;
     }
     __syncthreads();
-    if (tid == PRE_BLOCK - 1) s_carry = before + incl;
+    if (tid == PRE_BLOCK - 1) s_carry = first + c;
   }
   __syncthreads();
   const uint32_t total = s_carry;  // this workgroup's instances

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   __shared__ __attribute__((aligned(16))) float acc[4 * ACC_C * ACC_STRIDE];  // [wave][partial][entry]
   __shared__ float2 wu_all[4 * SLOTS * WU_STRIDE];     // [wave][slot][pixel] (w, u)
   __shared__ float4 seed_all[4 * 64];                  // [wave][pixel] (dL/dC rgb, dL/dD)
-  __shared__ uint32_t wave_max[4];
+  __shared__ uint32_t quad_last[4];
   __shared__ uint32_t blk_first[BWD_ROUND];
   __shared__ uint32_t ent_pos[2][BWD_ROUND];  // per staged entry: list index << 4 | quadrant bits; [round parity] (written a round ahead)
   __shared__ uint32_t sweep_cnt[2][4];        // live entries per wave of a sweep iteration; [iteration parity]
@@ -132,12 +132,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
 
   // furthest last-contributor of this quadrant and of the tile
   uint32_t wmax = last;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, o));
-  if (lane == 0) wave_max[wave] = wmax;
+  wmax = wave_max(wmax);
+  if (lane == 0) quad_last[wave] = wmax;
   __syncthreads();
-  const uint32_t wm0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max[0]), wm1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max[1]);
-  const uint32_t wm2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max[2]), wm3 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max[3]);
+  const uint32_t wm0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)quad_last[0]), wm1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)quad_last[1]);
+  const uint32_t wm2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)quad_last[2]), wm3 = (uint32_t)__builtin_amdgcn_readfirstlane((int)quad_last[3]);
   // (a last contributor is a position of the tile's own list: the clamp only keeps a stale image workspace inside the tile's segment)
   const uint32_t bmax = min(max(max(wm0, wm1), max(wm2, wm3)), range.y - range.x);
 
@@ -479,20 +478,19 @@ int launch_render_backward(int R, int W, int H, int grid_x, int grid_y, const fl
 // counts only below quadrant q's furthest last contributor (see the sweep above) -- for the whole of every tile list
 __global__ __launch_bounds__(256) void k_export_taken(int W, int H, int gx, ImageWS im, const uint32_t *__restrict__ taken,
                                                       uint32_t *__restrict__ out) {
-  __shared__ uint32_t wave_max[4];
+  __shared__ uint32_t quad_last[4];
   if (im.counters[4]) return;  // aborted async frame
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int tile = blockIdx.x, ty = tile / gx, tx = tile - ty * gx;
   const int px = tx * TILE + (wave & 1) * 8 + (lane & 7), py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
   uint32_t wmax = (px < W && py < H) ? im.n_contrib[(size_t)py * W + px] : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, o));
-  if (lane == 0) wave_max[wave] = wmax;
+  wmax = wave_max(wmax);
+  if (lane == 0) quad_last[wave] = wmax;
   __syncthreads();
   const uint2 range = im.ranges[tile];
   for (uint32_t p = (uint32_t)tid; p < range.y - range.x; p += 256u) {
-    const uint32_t keep = (p < wave_max[0] ? 0x1u : 0u) | (p < wave_max[1] ? 0x100u : 0u) | (p < wave_max[2] ? 0x10000u : 0u) |
-                          (p < wave_max[3] ? 0x1000000u : 0u);
+    const uint32_t keep = (p < quad_last[0] ? 0x1u : 0u) | (p < quad_last[1] ? 0x100u : 0u) | (p < quad_last[2] ? 0x10000u : 0u) |
+                          (p < quad_last[3] ? 0x1000000u : 0u);
     out[range.x + p] = taken[range.x + p] & keep;
   }
 }

@@ -7,7 +7,7 @@
 // pixel per lane) and walking the tile list on its own -- no workgroup barrier in the loop.  Per 64 sorted list
 // entries: lane l takes entry l -- its Gaussian id from point_list (coalesced; requested TWO chunks ahead) and that
 // Gaussian's 48-byte row gathered from GeomWS.splat (requested ONE chunk ahead; the rows of a frame live in L2) -- a
-// lane-parallel test of the entry against the quadrant box (wave_reduce.h), and the survivors PACKED in list order into
+// lane-parallel test of the entry against the quadrant box (quadrant_relevant, gsaj_common.h), and the survivors PACKED in list order into
 // the wave's LDS area with the conic pre-scaled for v_exp_f32 -- PAIR-INTERLEAVED (x_A x_B y_A y_B | kx_A kx_B ky_A ky_B | ...), so that
 // ds_read_b128 delivers the register pairs the packed fp32 instructions take: the compiler paired entries before, but paid 31
 // v_mov shuffles per four entries for it (120 -> 96 VALU instructions per four entries, 231 -> 219 us per cfg2 window).  The
@@ -319,10 +319,7 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
       s4[0] = o.s_rgb; s4[1] = o.s_d; s4[2] = o.s_a; s4[3] = o.s_b;
     }
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
-#pragma unroll
-      for (int o2 = 32; o2 > 0; o2 >>= 1) s4[c] += __shfl_xor(s4[c], o2);
-    }
+    for (int c = 0; c < 4; c++) s4[c] = wave_sum(s4[c]);
     if (lane == 0) reinterpret_cast<float4 *>(fl.partials)[blockIdx.x] = make_float4(s4[0], s4[1], s4[2], s4[3]);
   }
   GSAJ_TRACE_END(fwd)

@@ -22,6 +22,7 @@
 // Built with -ffp-contract=off (csrc/Makefile): where the reference is a chain of fp32 tensor operations (the depth prior, the
 // colour quantisation, the scales) each operation here rounds once, like its tensor counterpart; a fused multiply-add would not.
 #include "gsaj_common.h"
+#include "wave_reduce.h"
 #include <cfloat>
 #include <cmath>
 
@@ -98,8 +99,7 @@ __device__ __forceinline__ void sd_load4(const float *__restrict__ p, size_t i, 
 }
 
 __device__ __forceinline__ double sd_block_sum(double v, double *red /*[4] LDS*/) {  // fixed tree; the total in every thread
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void k_sd_pick(SdPick a, SeedWS w) {
   __shared__ uint32_t wsum[4];
   __shared__ double red[4];
   __shared__ uint32_t s_rank, s_none, s_prefix, s_final;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int shift = 24 - 8 * a.pass;
   double psum = 0.0;
   if (a.stats && a.pass < 2) {
@@ -252,20 +252,11 @@ __global__ __launch_bounds__(256) void k_sd_pick(SdPick a, SeedWS w) {
     psum = sd_block_sum(psum, red);
   }
   const uint32_t c = w.hist[a.pass * 256 + tid];
-  uint32_t x = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = (uint32_t)__shfl_up((int)x, o);
-    if (lane >= o) x += t;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  uint32_t before = 0u;
-  for (int k = 0; k < wave; k++) before += wsum[k];
+  const uint32_t excl = block_excl_scan_add<4>(c, wsum);
   if (tid == 0) {
     uint32_t none, rank;
     if (a.pass == 0) {
-      const uint32_t nv = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+      const uint32_t nv = block_scan_total<4>(wsum);  // pass 0's histogram counts every valid pixel
       uint32_t m = 0u;
       none = nv == 0u;
       rank = 0u;
@@ -298,7 +289,6 @@ __global__ __launch_bounds__(256) void k_sd_pick(SdPick a, SeedWS w) {
   }
   __syncthreads();
   if (!s_none) {
-    const uint32_t excl = before + x - c;
     if (s_rank >= excl && s_rank < excl + c) {  // exactly one thread: the counts of the matching keys add up to more than the rank
       const uint32_t np = s_prefix | ((uint32_t)tid << shift);
       w.st[ST_PREFIX] = np;
@@ -348,8 +338,7 @@ __global__ __launch_bounds__(64) void k_sd_count(int n, SeedWS w) {
   const uint32_t thr = w.res[RES_THRESHOLD];
   uint32_t cnt = 0u;
   for (int i = beg + lane; i < end; i += 64) cnt += (any && w.flags[i] && w.keys[i] <= thr) ? 1u : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, o);
+  cnt = wave_sum(cnt);
   if (lane == 0) w.tcount[blockIdx.x] = cnt;
 }
 

@@ -17,6 +17,7 @@
 // LDS: lane = column in every pass, so each 32-lane half of a wave reads 32 consecutive dwords of one row: conflict-free
 // without padding (ds_read_b32 banks are dword % 32, serviced per 32-lane half).
 #include "gsaj_common.h"
+#include "wave_reduce.h"
 
 #define SSIM_TW 32           // output tile width (= the 32 lanes of a wave half)
 #define SSIM_TH 16           // output tile height
@@ -165,11 +166,8 @@ __global__ __launch_bounds__(SSIM_BLOCK) void k_ssim_fwd(SsimFwdParams p) {
     s_l1 += fabsf(sx[r + SSIM_R][c + SSIM_R] - sy[r + SSIM_R][c + SSIM_R]);
   }
   // workgroup partials: wave butterfly, then the four waves in order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s_ssim += __shfl_xor(s_ssim, o);
-    s_l1 += __shfl_xor(s_l1, o);
-  }
+  s_ssim = wave_sum(s_ssim);
+  s_l1 = wave_sum(s_l1);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (lane == 0) { red[0][wave] = s_ssim; red[1][wave] = s_l1; }
   __syncthreads();
@@ -196,11 +194,8 @@ __global__ __launch_bounds__(SSIM_BLOCK) void k_ssim_fwd(SsimFwdParams p) {
       acc[0] += (double)__uint_as_float(u.x);
       acc[1] += (double)__uint_as_float(u.y);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      acc[0] += __shfl_xor(acc[0], o);
-      acc[1] += __shfl_xor(acc[1], o);
-    }
+    acc[0] = wave_sum(acc[0]);
+    acc[1] = wave_sum(acc[1]);
     if (lane == 0) { fin[0][wave] = acc[0]; fin[1][wave] = acc[1]; }
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -1,4 +1,16 @@
-// wave_reduce.h -- register-only wave64 reduction of 10 per-lane partials on gfx950.
+// wave_reduce.h -- the only home of lane scans and reductions: every kernel's __shfl_xor butterfly and __shfl_up ladder is one of these.
+//
+// All of it is register-only and force-inlined; nothing here owns LDS.  Where a workgroup form needs one slot per wave the
+// caller passes the array (as row_rank() in row_move.h does), so a kernel's LDS is what the kernel declares.  Workgroups are
+// one-dimensional and a multiple of 64 lanes wide: lane = threadIdx.x & 63, wave = threadIdx.x >> 6.
+//
+//   wave_sum / wave_min / wave_max   xor butterfly over WIDTH lanes (64, or a half-wave), steps WIDTH/2 ... 1, the result in
+//                                    every lane.  Floating-point sums are compared bit for bit elsewhere: this tree is fixed.
+//   wave_incl_scan_add / _max        the __shfl_up ladder (steps 1 ... WIDTH/2) over uint32_t
+//   block_excl_scan_add              workgroup exclusive scan: wave scans + one LDS hop for the wave totals, ONE barrier;
+//   block_scan_total                 the workgroup's total from the same LDS words
+//   block_excl_scan_runs             the same over n items, a contiguous run per lane, with the largest item
+//   reduce10 / store10               ten per-lane partials at once, register-only:
 //
 // v_permlane32_swap / v_permlane16_swap exchange half-waves / odd-even rows between two
 // registers, so ONE swap + ONE add both halves the number of live registers and folds one
@@ -7,6 +19,121 @@
 //                    x2 -> v[{8,8,9,9}[r]]   in every lane of the row.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// The value parameter of every wave primitive, as the __shfl_* it is handed to declare theirs: the compiler then treats the argument
+// exactly as it treats the operand of a shuffle written at the call site (a plain by-value parameter is `noundef`, which changes
+// the code around the call: up to 10 VGPRs in k_chain_window).
+#define WAVE_MAYBE_UNDEF __attribute__((maybe_undef))
+
+// ---- xor butterfly: all-reduce over each aligned group of WIDTH lanes -------------------------------------------------------
+struct lane_add {
+  template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct lane_min {
+  template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return min(a, b); }
+};
+struct lane_max {
+  template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return max(a, b); }
+};
+template <int WIDTH = 64, typename T, typename Op>
+__device__ __forceinline__ T wave_allreduce(WAVE_MAYBE_UNDEF T v, Op op) {
+#pragma unroll
+  for (int o = WIDTH / 2; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
+  return v;
+}
+template <int WIDTH = 64, typename T>
+__device__ __forceinline__ T wave_sum(WAVE_MAYBE_UNDEF T v) {
+  return wave_allreduce<WIDTH>(v, lane_add());
+}
+template <int WIDTH = 64, typename T>
+__device__ __forceinline__ T wave_min(WAVE_MAYBE_UNDEF T v) {
+  return wave_allreduce<WIDTH>(v, lane_min());
+}
+template <int WIDTH = 64, typename T>
+__device__ __forceinline__ T wave_max(WAVE_MAYBE_UNDEF T v) {
+  return wave_allreduce<WIDTH>(v, lane_max());
+}
+
+// ---- __shfl_up ladder: inclusive scan over each aligned group of WIDTH lanes ------------------------------------------------
+template <int WIDTH = 64, typename Op>
+__device__ __forceinline__ uint32_t wave_incl_scan(WAVE_MAYBE_UNDEF uint32_t x, Op op) {
+  const int lane = threadIdx.x & (WIDTH - 1);
+#pragma unroll
+  for (int o = 1; o < WIDTH; o <<= 1) {
+    const uint32_t up = __shfl_up(x, o, WIDTH);
+    if (lane >= o) x = op(x, up);
+  }
+  return x;
+}
+template <int WIDTH = 64>
+__device__ __forceinline__ uint32_t wave_incl_scan_add(WAVE_MAYBE_UNDEF uint32_t x) {
+  return wave_incl_scan<WIDTH>(x, lane_add());
+}
+template <int WIDTH = 64>
+__device__ __forceinline__ uint32_t wave_incl_scan_max(WAVE_MAYBE_UNDEF uint32_t x) {
+  return wave_incl_scan<WIDTH>(x, lane_max());
+}
+
+// ---- workgroup exclusive scan of one value per lane, NWAVES waves (every lane must call) ------------------------------------
+// wsum: NWAVES words of the caller's LDS; they hold the wave totals until the caller reuses them, and block_scan_total is
+// their sum, the workgroup's total (as row_total() in row_move.h).  A running offset across several calls stays with the caller
+// (k_scatter_instances, k_rs_scan): this has ONE barrier.
+template <int NWAVES>
+__device__ __forceinline__ uint32_t block_excl_scan_add(uint32_t x, uint32_t *wsum) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t incl = wave_incl_scan_add(x);
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  uint32_t before = 0u;
+#pragma unroll 4  // (four totals in flight at a time: the sixteen of a 1024-lane workgroup at once cost k_rs_scan 5 VGPRs)
+  for (int w = 0; w < NWAVES; w++) {
+    const uint32_t v = wsum[w];
+    if (w < wave) before += v;
+  }
+  // the same in every lane of a wave: a scalar register, formed HERE (left as a vector value the compiler moved the sum behind
+  // k_sd_pick's bookkeeping branch and kept the wave totals alive across it: 4 VGPRs)
+  before = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);
+  return before + incl - x;
+}
+template <int NWAVES>
+__device__ __forceinline__ uint32_t block_scan_total(const uint32_t *wsum) {
+  uint32_t total = 0u;
+#pragma unroll
+  for (int w = 0; w < NWAVES; w++) total += wsum[w];
+  return total;
+}
+
+// ---- workgroup exclusive scan of n items: each lane sums a contiguous run, the run totals go through block_excl_scan_add, then
+// each lane rewrites its run (out may be in).  Returns the total; largest = the largest item.  wsum, wmax: NWAVES words each of
+// the caller's LDS.  In: the input's pointer type -- force-inlined, so an LDS array is still read as LDS.
+template <int NWAVES, typename In>
+__device__ __forceinline__ uint32_t block_excl_scan_runs(In in, uint32_t *out, int n, uint32_t *wsum, uint32_t *wmax, uint32_t &largest) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int per = (n + NWAVES * 64 - 1) / (NWAVES * 64);
+  const int b0 = min(n, tid * per), b1 = min(n, b0 + per);
+  uint32_t s = 0, mx = 0;
+  for (int i = b0; i < b1; i++) {
+    const uint32_t v = in[i];
+    s += v;
+    mx = max(mx, v);
+  }
+  mx = wave_max(mx);
+  if (lane == 0) wmax[wave] = mx;
+  uint32_t run = block_excl_scan_add<NWAVES>(s, wsum);
+  const uint32_t total = block_scan_total<NWAVES>(wsum);
+  largest = 0u;
+#pragma unroll
+  for (int w = 0; w < NWAVES; w++) largest = max(largest, wmax[w]);
+  for (int i = b0; i < b1; i++) {
+    const uint32_t v = in[i];
+    out[i] = run;
+    run += v;
+  }
+  return total;
+}
+
+// ---- ten values at once -----------------------------------------------------------------------------------------------------
 
 typedef unsigned gsaj_u32x2 __attribute__((ext_vector_type(2)));
 
@@ -47,35 +174,4 @@ __device__ __forceinline__ void store10(float *a, int lane, float x0, float x1, 
     a[4 + k] = x1;
     if ((r & 1) == 0) a[8 + (r >> 1)] = x2;
   }
-}
-
-// ---- lane-parallel relevance test of one list entry against an 8x8 pixel quadrant -----------------
-// Returns false only if NO pixel of the quadrant [X0, X0+7] x [Y0, Y0+7] can pass the compositor's
-// per-pixel tests (power <= 0 and alpha = o * exp(power) >= 1/255): the quadratic form
-// q = a dx^2 + 2 b dx dy + c dy^2 (power = -q/2) is minimised over the continuous box, and the
-// entry is dropped when o * exp(-q_min / 2) stays below 1/255 by a safety factor that covers the
-// fp32 / v_exp_f32 rounding of the per-pixel evaluation.  Non positive-definite conics are kept.
-// This only removes work whose result is "skip" for all 64 lanes -- results are unchanged.
-__device__ __forceinline__ bool quadrant_relevant(float mx, float my, float a, float b, float c, float o, float X0,
-                                                  float Y0) {
-  const float dxl = mx - (X0 + 7.0f), dxh = mx - X0;
-  const float dyl = my - (Y0 + 7.0f), dyh = my - Y0;
-  const bool pd = a > 0.f && c > 0.f && (a * c - b * b) > 0.f;
-  const bool inside = dxl <= 0.f && dxh >= 0.f && dyl <= 0.f && dyh >= 0.f;
-  const float ic = __builtin_amdgcn_rcpf(c), ia = __builtin_amdgcn_rcpf(a);
-  float q = 3.0e38f;
-  {
-    const float y0 = fminf(fmaxf(-b * dxl * ic, dyl), dyh);
-    q = fminf(q, a * dxl * dxl + 2.f * b * dxl * y0 + c * y0 * y0);
-    const float y1 = fminf(fmaxf(-b * dxh * ic, dyl), dyh);
-    q = fminf(q, a * dxh * dxh + 2.f * b * dxh * y1 + c * y1 * y1);
-    const float x0 = fminf(fmaxf(-b * dyl * ia, dxl), dxh);
-    q = fminf(q, a * x0 * x0 + 2.f * b * x0 * dyl + c * dyl * dyl);
-    const float x1 = fminf(fmaxf(-b * dyh * ia, dxl), dxh);
-    q = fminf(q, a * x1 * x1 + 2.f * b * x1 * dyh + c * dyh * dyh);
-  }
-  // keep if o * exp(-q/2) >= (1/255) * 0.99, evaluated conservatively (q shrunk by a relative 1e-3 and 1e-3 absolute)
-  const float qs = fmaxf(q * 0.999f - 1.0e-3f, 0.f);
-  const bool reach = o * __expf(-0.5f * qs) >= (0.99f / 255.0f);
-  return !pd || inside || reach;
 }

@@ -35,6 +35,33 @@ def test_more_tiles_than_the_lds_histogram_holds(case):
     g, gref = hp.check_backward(cam, 1, out, args, st, dLc, dLd, "large_image")
 
 
+# The carried and the two-items-per-lane forms of the binning scans, at the smallest shape that reaches all three: 258 blocks of 256
+# Gaussians (the scan of block_sums: 258 items over 256 lanes), 258 x 2 tiles (the tile scan likewise), and 258 class-local tiles in
+# the scatter classes of tile rows 0 and 1 (the 256-tiles-per-step carry loop of k_scatter_instances takes a second step).
+CASES_CARRIED_SCANS = [(66000, 4128, 32, 11)]
+
+
+@pytest.mark.parametrize("case", CASES_CARRIED_SCANS, ids=["P66000_4128x32"])
+def test_scans_that_carry_and_take_two_items_per_lane(case):
+    from gsaj import rasterizer as C
+
+    P, W, H, seed = case
+    assert (P + 255) // 256 > 256 and ((W + 15) // 16) * ((H + 15) // 16) > 256 and (W + 15) // 16 > 256
+    cam = hp.small_camera(W, H, f=0.9 * W, orthonormal=True)
+    sc = syn.make_scene(P, seed, cam, z_range=(1.0, 4.0), log_scale_range=(math.log(0.002), math.log(0.01)), sh_coeffs=1, margin=0.1)
+    (ref, st), kw = hp.oracle_forward(cam, sc, 0)
+    gx = (W + 15) // 16
+    assert all(int((st["ranges"][r * gx:(r + 1) * gx, 1] - st["ranges"][r * gx:(r + 1) * gx, 0]).sum()) > 0 for r in (0, 1))
+    out, args = hp.gpu_forward(cam, sc, 0, kw=kw)
+    R, color, radii, geom, binning, img, depth, opacity, n_touched = out
+    assert R == ref["num_rendered"]
+    np.testing.assert_array_equal(radii.cpu().numpy(), ref["radii"])
+    dbg = {k: v.cpu().numpy() for k, v in C.debug_export(P, R, W, H, geom, binning, img).items()}
+    np.testing.assert_array_equal(dbg["point_list"].astype(np.uint32), st["point_list"])
+    np.testing.assert_array_equal(dbg["ranges"], st["ranges"])
+    hp.assert_image_close(color.cpu().numpy(), ref["color"], hp.IMG_TOL, st=st, tag="carried_scans/color")
+
+
 CASES = [
     # P, W, H, seed, deg, coeffs, z_range, log_scale_range, opacity_range, orthonormal
     (1, 33, 17, 1, 0, 1, (1.0, 1.5), (math.log(0.05), math.log(0.1)), (0.5, 0.9), True),
