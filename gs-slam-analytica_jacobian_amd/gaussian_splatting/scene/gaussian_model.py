@@ -10,11 +10,13 @@ goes through NumPy and Open3D).  The optimiser surgery of the mapping loop is he
 new rows enter an attached Adam with zero moments (cat_tensors_to_optimizer :599-631), rows leave the map and the Adam state
 under a mask (prune_points, _prune_optimizer :559-597: one device launch, gsaj.pruning), and the consumer of the densification
 statistics, densify_and_prune / densify_and_clone / densify_and_split (:669-765), is one plan, one 16-byte read, one launch that
-moves every tensor and one that computes the children (gsaj.densify).  reset_opacity* and update_learning_rate stay the caller's.
+moves every tensor and one that computes the children (gsaj.densify).  The step itself is one launch as well (map_step: the chain
+rule through the activations, Adam, and reset_opacity / reset_opacity_nonvisible :438-451 fused or on their own; gsaj.map_step), and
+update_learning_rate (:372-386) is host arithmetic.
 """
 import torch
 
-from gaussian_splatting.utils.general_utils import build_scaling_rotation, inverse_sigmoid, strip_symmetric
+from gaussian_splatting.utils.general_utils import build_scaling_rotation, helper, inverse_sigmoid, strip_symmetric
 
 
 class GaussianModel:
@@ -370,8 +372,8 @@ class GaussianModel:
     def training_setup(self, training_args):
         """Reference :321-370 on the parameters' own device: percent_dense, zeroed xyz_gradient_accum / denom, and an Adam
         (lr=0.0, eps=1e-15) of six one-parameter groups named xyz, f_dc, f_rest, opacity, scaling, rotation with the reference's
-        learning rates.  The schedule's numbers are kept (lr_init, lr_final, lr_delay_mult, max_steps); applying it,
-        update_learning_rate, stays the caller's."""
+        learning rates.  The schedule's numbers are kept (lr_init, lr_final, lr_delay_mult, max_steps); update_learning_rate
+        applies it, and map_step (or optimizer.step() after assign_bucket_gradients) takes the step."""
         a = training_args
         self.percent_dense = a.percent_dense
         n, dev = self._xyz.shape[0], self._xyz.device
@@ -388,6 +390,43 @@ class GaussianModel:
         self.lr_final = a.position_lr_final * self.spatial_lr_scale
         self.lr_delay_mult = a.position_lr_delay_mult
         self.max_steps = a.position_lr_max_steps
+
+    def update_learning_rate(self, iteration):
+        """Reference :372-386: the xyz group's learning rate of this iteration, set in the optimizer and returned."""
+        for group in self.optimizer.param_groups:
+            if group["name"] == "xyz":
+                group["lr"] = helper(iteration, lr_init=self.lr_init, lr_final=self.lr_final, lr_delay_mult=self.lr_delay_mult,
+                                     max_steps=self.max_steps)
+                return group["lr"]
+
+    def map_step(self, g, reset=None, radii=None, freeze=()):
+        """optimizer.step() of the reference's mapping loop (slam_backend.py:299-311) from the gradients a backward left in its
+        context's slot g (ctx.g: mean3D, sh, opacity, scale, rot w.r.t. the ACTIVATED quantities, after any
+        gsaj_isotropic_loss(accumulate=1) into g["scale"]), in ONE launch: the chain rule of assign_bucket_gradients, then Adam on
+        the six raw parameters and on exp_avg / exp_avg_sq of the attached torch.optim.Adam, in place.  The optimizer keeps owning
+        the state: absent state is created as torch creates it, each group's host `step` advances by one, learning rates and betas
+        are read from param_groups at every call, and map_step and optimizer.step() may alternate.  .grad is not touched (it stays
+        None) and g is only read.  freeze: names of groups that are not stepped, as if their .grad were None (no state created, no
+        step counted), e.g. freeze=("xyz", "scaling", "rotation") for a colour refinement.
+        reset: None, or the opacity reset the reference runs BEFORE the step in that iteration, fused: "all" (reset_opacity),
+        "nonvisible" (reset_opacity_nonvisible; radii = int32 [K,P] or a list of bool [P] filters), "nonvisible_keep" (the same
+        without the reference's quirk: visible rows keep their raw opacity instead of getting sigmoid(opacity)).  As in the
+        reference the opacity group is then not stepped, its step count stays, its moments become zeros, and _opacity is a new leaf.
+        An optimizer the kernel cannot reproduce raises GsajError with the reason."""
+        from gsaj.map_step import map_step
+        map_step(self, g, reset=reset, radii=radii, freeze=freeze)
+
+    def reset_opacity(self):
+        """Reference :438-441: every raw opacity becomes inverse_sigmoid(0.01), the opacity group's moments zeros (one launch)."""
+        from gsaj.map_step import map_step
+        map_step(self, None, reset="all")
+
+    def reset_opacity_nonvisible(self, visibility_filters):
+        """Reference :443-451: inverse_sigmoid(0.4) for the Gaussians no view sees, the opacity group's moments zeros (one
+        launch).  visibility_filters: a list of bool [P] tensors (radii > 0 per view) or one int32 [K,P] radii tensor.  A visible
+        Gaussian's raw opacity becomes sigmoid(raw), as in the reference (include/gsaj.h: kept quirk)."""
+        from gsaj.map_step import map_step
+        map_step(self, None, reset="nonvisible", radii=visibility_filters)
 
     def _densify(self, plan, seed, noise, who):
         """Send the model through a gsaj.densify.DensifyPlan: the six parameters (a new row gets its parent's), exp_avg /

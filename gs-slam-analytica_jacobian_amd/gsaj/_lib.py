@@ -104,6 +104,7 @@ SIGNATURES = {
                                   ctypes.POINTER(c_int), P, P, P]),
     "gsaj_densify_children": (c_int, [c_int, c_int, c_int, P, P, P, P, ctypes.c_uint64, P, P, P, P, P]),
     "gsaj_densify_noise": (c_int, [c_int, c_int, ctypes.c_uint64, P, P]),
+    "gsaj_map_step": (c_int, [c_int, c_int, c_int, c_int, P, P]),
 }
 
 _lib = None

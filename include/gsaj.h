@@ -622,6 +622,56 @@ int gsaj_densify_children(int P, int S, int N, const float *xyz, const float *sc
                           float *dst_xyz /*dev [P'',3]*/, float *dst_scaling /*dev [P'',S]*/, void *stream);
 int gsaj_densify_noise(int P, int N, uint64_t seed, float *out /*dev [N,P,3]*/, void *stream);
 
+/* ---- map step: activation gradients, Adam and the opacity resets in one launch (csrc/map_step.hip) ------------------------------
+ * The step of a mapping iteration on the Gaussian map (utils/slam_backend.py:299-311: the opacity reset, optimizer.step) over the six
+ * raw parameters of gaussian_model.py, groups in the order xyz [P,3], f_dc [P,1,3], f_rest [P,M-1,3] (empty for M = 1), opacity [P,1],
+ * scaling [P,scale_cols], rotation [P,4], each with exp_avg / exp_avg_sq of its shape, all updated IN PLACE.  One launch; every
+ * element of every tensor is read once and written once; fp32 throughout, one rounding per operation (no contraction).
+ * (a) The gradients arrive w.r.t. the ACTIVATED quantities, as the backwards leave them in the bucket: g_mean3D [P,3], g_sh [P,M,3],
+ *   g_opacity [P], g_scale [P,3], g_rot [P,4].  The chain rule through the activations is closed form: xyz and SH identity (coefficient
+ *   0 of a g_sh row is f_dc's, the rest f_rest's); opacity g s (1 - s), s = 1 / (1 + expf(-o)); scaling g_j expf(s_j), with
+ *   scale_cols = 1 the three products summed, ((0 + 1) + 2), into the one column; rotation (g - qh (g . qh)) / n, n = max(|q|, 1e-12),
+ *   qh = q / n, the dot product summed ((0 + 1) + 2) + 3.
+ * (b) Per group with skip == 0, torch.optim.Adam without weight decay / amsgrad / maximize, eps outside the root:
+ *   m = b1 m + c1 g;  v = b2 v + (c2 g) g;  p = p + (-step_size (m / (sqrtf(v) / bc2_sqrt + eps))),
+ *   with b = (float)beta and c = (float)(1.0 - beta) formed from the doubles, the factors torch's fp32 kernels get from its Python
+ *   floats ((float)(1.0 - 0.999) is not 1.0f - 0.999f), and step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) computed by
+ *   the caller, who also owns t.  A zero gradient with non-zero moments moves the parameter; zero gradient and zero moments leave
+ *   all three bit-identical.
+ * (c) flags & (GSAJ_MAP_RESET_ALL | GSAJ_MAP_RESET_NONVISIBLE): the opacity group is NOT stepped whatever its skip says (the caller
+ *   must not advance its t either), its moments become zeros and its raw values are rewritten -- what the reference's
+ *   replace_tensor_to_optimizer leaves behind when the reset precedes optimizer.step (gaussian_model.py:438-451, 544-557):
+ *   GSAJ_MAP_RESET_ALL: reset_value everywhere (the caller passes inverse_sigmoid(0.01)); it wins over the other two bits.
+ *   GSAJ_MAP_RESET_NONVISIBLE: reset_value (inverse_sigmoid(0.4)) where radii[k][i] <= 0 for every k < K_vis.  A row visible in any
+ *     view gets s = sigmoid(o), the ACTIVATED value, as its raw value.  Kept quirk of the reference (opacities_new[filter] =
+ *     self.get_opacity[filter]): every such reset squashes the visible opacities once more.
+ *   GSAJ_MAP_RESET_KEEP_VISIBLE (with _NONVISIBLE): visible rows keep their raw value instead; their moments are zeroed all the same.
+ *   A reset bit with every skip set is the stand-alone reset.  Without a reset bit radii, K_vis and reset_value are not read.
+ * Pointers of a group that is neither stepped nor reset, and gradients no stepped group reads, may be NULL.  No pointer needs more
+ * than 4-byte alignment (the bucket's field views have no more when P is odd): gradients are always read a dword at a time, and
+ * a group's parameter and moments 16 bytes at a time only where the three addresses allow it, checked per launch.
+ * P = 0: GSAJ_OK, nothing launched.  GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: P < 0, M < 1, P * 3 * M > INT_MAX,
+ * scale_cols not 1 or 3, args NULL, a NULL pointer that the launch would read or write, flags outside the three bits,
+ * GSAJ_MAP_RESET_NONVISIBLE (without _ALL) with radii NULL or K_vis < 1. */
+#define GSAJ_MAP_GROUPS 6
+#define GSAJ_MAP_RESET_ALL 1
+#define GSAJ_MAP_RESET_NONVISIBLE 2
+#define GSAJ_MAP_RESET_KEEP_VISIBLE 4
+typedef struct GsajMapStepArgs {
+  float *param[GSAJ_MAP_GROUPS];      /* dev, in place; xyz, f_dc, f_rest, opacity, scaling, rotation */
+  float *exp_avg[GSAJ_MAP_GROUPS];    /* dev, in place */
+  float *exp_avg_sq[GSAJ_MAP_GROUPS]; /* dev, in place */
+  const float *g_mean3D, *g_sh, *g_opacity, *g_scale, *g_rot; /* dev */
+  float step_size[GSAJ_MAP_GROUPS];
+  float bc2_sqrt[GSAJ_MAP_GROUPS];
+  int skip[GSAJ_MAP_GROUPS];
+  double beta1, beta2, eps; /* as the optimizer holds them: the kernel's four factors are (float)beta, (float)(1.0 - beta) */
+  int flags;
+  const int *radii; /* dev [K_vis,P] or NULL */
+  float reset_value;
+} GsajMapStepArgs;
+int gsaj_map_step(int P, int M, int scale_cols /*3 or 1*/, int K_vis, const GsajMapStepArgs *args /*host*/, void *stream);
+
 /* ---- dense analytic path (NumPy-path semantics) ------------------ */
 size_t gsaj_dense_workspace_bytes(int N, int W, int H);
 /* N depth-sorted Gaussians: means2D [N,2] (pixels), covs2D [N,2,2], colors [N,3], depths [N], opac [N];
