@@ -105,6 +105,8 @@ SIGNATURES = {
     "gsaj_densify_children": (c_int, [c_int, c_int, c_int, P, P, P, P, ctypes.c_uint64, P, P, P, P, P]),
     "gsaj_densify_noise": (c_int, [c_int, c_int, ctypes.c_uint64, P, P]),
     "gsaj_map_step": (c_int, [c_int, c_int, c_int, c_int, P, P]),
+    "gsaj_eval_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gsaj_eval_frame": (c_int, [c_int, c_int, c_int, c_int] + [P] * 7),
 }
 
 _lib = None

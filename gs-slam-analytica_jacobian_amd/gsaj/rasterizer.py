@@ -83,7 +83,9 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     M = 0 if sh is None else sh.shape[1]
 
     geom = torch.empty(lib.gsaj_geom_workspace_bytes(P), **byte)
-    img = torch.empty(lib.gsaj_image_workspace_bytes(W, H), **byte)
+    # zeroed, as the contexts' are: a block the allocator hands back may be a freed context's image workspace of the same size, with
+    # its tile band and the complement that validates it still in place, and this frame would then render that band only
+    img = torch.zeros(lib.gsaj_image_workspace_bytes(W, H), **byte)
     st = _stream(dev)
     with torch.cuda.device(dev):
         _lib.check(lib.gsaj_forward_preprocess(

@@ -672,6 +672,34 @@ typedef struct GsajMapStepArgs {
 } GsajMapStepArgs;
 int gsaj_map_step(int P, int M, int scale_cols /*3 or 1*/, int K_vis, const GsajMapStepArgs *args /*host*/, void *stream);
 
+/* ---- rendering quality of one frame: masked PSNR, SSIM, the 8-bit picture (csrc/eval.hip) ----------------------------------------
+ * What eval_rendering forms per frame (utils/eval_utils.py:141-160) from image (the render) and gt, both [C,H,W] fp32, contiguous,
+ * 4-byte aligned (16 bytes at a time where both are 16-byte aligned, checked per call).  One fp32 rounding per tensor operation
+ * of the reference (no contraction):
+ *   x = clamp(image, 0, 1)                      a NaN stays a NaN, as torch.clamp leaves it
+ *   m = gt > 0                                  per ELEMENT (per channel value), not per pixel: image[mask] gathers elements
+ *   d = x - gt;  q = d * d                      fp32, two roundings
+ *   n = sum m, an exact integer;  sse = sum over m of q, in fp64 in a fixed order (the reference sums the gathered q in fp32)
+ *   mse = (float)(sse / n);  psnr = 20 * log10f(1.0f / sqrtf(mse))        (gaussian_splatting/utils/image_utils.py:19-21)
+ *   ssim = the size_average=True value of gsaj_ssim_forward(1, C, W, H, x, gt, ...): of the CLAMPED image and NOT masked (:155)
+ *   out_row [4] (dev) = {psnr, ssim, mse, n / (C * H * W)};  out_count [1] (dev) = n.
+ * Kept as the reference has them: n = 0 (a black gt) gives mse = psnr = NaN; mse = 0 gives psnr = +inf; a NaN in image gives a NaN
+ * psnr (and SSIM), and the byte of that element is 0.
+ * image_u8 [H,W,C] (dev, may be NULL): the picture the reference appends to img_pred (:144-148), byte (h, w, c) =
+ *   (uint8)(x[c', h, w] * 255.0f), one fp32 multiply and then truncation; c' = C - 1 - c with GSAJ_EVAL_REVERSE_CHANNELS (what
+ *   cv2.COLOR_BGR2RGB does to the three channels), else c' = c.
+ * Three launches on `stream` (the element pass, gsaj_ssim_forward, a one-workgroup tail), no host read, no float atomics:
+ * bit-reproducible.  Nothing but out_row, out_count, image_u8 and eval_ws is written.
+ * eval_ws: gsaj_eval_workspace_bytes(C, W, H) bytes, ZEROED ONCE by the caller when allocated (its SSIM slice holds a ticket).  From
+ *   its first 256-byte-aligned address it holds x [C,H,W] (readable after the call: what a perceptual metric wants), then the
+ *   per-workgroup partials and the SSIM workspace.  gsaj_eval_workspace_bytes returns 0 for dimensions the call would refuse.
+ * GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: C, W or H < 1, C * W * H > INT_MAX, a NULL image / gt / out_row /
+ * out_count / eval_ws, flags outside GSAJ_EVAL_REVERSE_CHANNELS. */
+#define GSAJ_EVAL_REVERSE_CHANNELS 1
+size_t gsaj_eval_workspace_bytes(int C, int W, int H);
+int gsaj_eval_frame(int C, int W, int H, int flags, const float *image, const float *gt, float *out_row /*[4] dev*/,
+                    uint32_t *out_count /*[1] dev*/, uint8_t *image_u8 /*[H,W,C] dev or NULL*/, void *eval_ws, void *stream);
+
 /* ---- dense analytic path (NumPy-path semantics) ------------------ */
 size_t gsaj_dense_workspace_bytes(int N, int W, int H);
 /* N depth-sorted Gaussians: means2D [N,2] (pixels), covs2D [N,2,2], colors [N,3], depths [N], opac [N];
