@@ -95,7 +95,7 @@ int gsaj_profile_end(float *stage_ms, int *stage_launches) {
 }
 
 const char *gsaj_last_error(void) { return g_err; }
-int gsaj_version(void) { return 106; }
+int gsaj_version(void) { return 107; }
 
 size_t gsaj_geom_workspace_bytes(int P) { return geom_carve(nullptr, (size_t)(P > 0 ? P : 0), nullptr) + 256; }
 size_t gsaj_image_workspace_bytes(int W, int H) { return image_carve(nullptr, W, H, nullptr) + 256; }
@@ -339,10 +339,12 @@ int gsaj_rasterize_forward_async(int P, int D, int M, const float *bg, int W, in
 }
 
 static int fused_loss_args(const char *who, int loss_flags, const float *gt_color, const float *gt_depth, const float *exposure_a,
-                           const float *exposure_b) {
+                           const float *exposure_b, int exposure_stride = 1) {
   const bool mono = loss_flags & GSAJ_LOSS_MONOCULAR, noexp = loss_flags & GSAJ_LOSS_NO_EXPOSURE;
-  if ((loss_flags & GSAJ_LOSS_COMPUTE_LOSS) || !gt_color || (!mono && !gt_depth) || (!noexp && (!exposure_a || !exposure_b))) {
-    gsaj_set_error("%s: invalid loss arguments (flags=%d; GSAJ_LOSS_COMPUTE_LOSS has no fused form)", who, loss_flags);
+  if ((loss_flags & GSAJ_LOSS_COMPUTE_LOSS) || !gt_color || (!mono && !gt_depth) || (!noexp && (!exposure_a || !exposure_b)) ||
+      exposure_stride < 1) {
+    gsaj_set_error("%s: invalid loss arguments (flags=%d, exposure stride %d; GSAJ_LOSS_COMPUTE_LOSS has no fused form)", who, loss_flags,
+                   exposure_stride);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   return GSAJ_OK;
@@ -395,13 +397,14 @@ static int batch_workspaces(int K, int P, int capacity, int W, int H, void *geom
   return GSAJ_OK;
 }
 
-int gsaj_rasterize_forward_batch(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
-                                 const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
-                                 const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
-                                 const float *projmatrices, const float *campos, float tanfovx, float tanfovy, int prefiltered,
-                                 float *out_color, float *out_depth, float *out_opacity, int *radii, int *n_touched, void *geom_ws,
-                                 void *binning_ws, size_t binning_ws_bytes, int capacity, int tile_list_capacity, void *image_ws,
-                                 int flags, void *stream) {
+// fl != NULL: the loss-fused form (view 0's pointers; partials = the aligned loss workspace)
+static int forward_batch_impl(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
+                              const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
+                              const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                              const float *projmatrices, const float *campos, float tanfovx, float tanfovy, int prefiltered,
+                              float *out_color, float *out_depth, float *out_opacity, int *radii, int *n_touched, void *geom_ws,
+                              void *binning_ws, size_t binning_ws_bytes, int capacity, int tile_list_capacity, void *image_ws,
+                              int flags, void *stream, const FusedLoss *fl, float *out_scalars, float *out_dexposure) {
   if (K <= 0 || P <= 0 || W <= 0 || H <= 0 || capacity <= 0 || !means3D || !opacities || !viewmatrices || !projmatrices || !bg ||
       !out_color || !out_depth || !out_opacity || !radii || !n_touched || !geom_ws || !binning_ws || !image_ws) {
     gsaj_set_error("gsaj_rasterize_forward_batch: invalid argument (K=%d P=%d W=%d H=%d capacity=%d)", K, P, W, H, capacity);
@@ -440,20 +443,82 @@ int gsaj_rasterize_forward_batch(int K, int P, int D, int M, const float *bg, in
   if ((rc = launch_preprocess(p, radii, n_touched, g, im, vs, s)) != GSAJ_OK) return rc;
   if ((rc = launch_tile_binning(P, p.sort_cap, (flags & GSAJ_FWD_RECORDS_FP16) ? 1 : 0, p.grid_x, p.grid_y, g, b, im, K, vs, s)) != GSAJ_OK)
     return rc;
-  return launch_render_forward(P, W, H, p.grid_x, p.grid_y, bg, g, b, im, out_color, out_depth, out_opacity, n_touched, K, vs, s);
+  if ((rc = launch_render_forward(P, W, H, p.grid_x, p.grid_y, bg, g, b, im, out_color, out_depth, out_opacity, n_touched, K, vs, s, fl)) != GSAJ_OK)
+    return rc;
+  if (fl) return launch_loss_finalize(*fl, gsaj_fwd_loss_slots(W, H), W, H, im.counters + 4, out_scalars, s, K, vs.image, out_dexposure);
+  return GSAJ_OK;
 }
 
-int gsaj_rasterize_backward_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
-                                  const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
-                                  const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
-                                  const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
-                                  float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
-                                  const float *dL_dpix, const float *dL_dpix_depth, float *dL_dmean2D, float *dL_dconic,
-                                  float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D, float *dL_dcov3D,
-                                  float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau, float *dL_dtau_sum, int flags,
-                                  void *stream) {
+int gsaj_rasterize_forward_batch(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
+                                 const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
+                                 const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                 const float *projmatrices, const float *campos, float tanfovx, float tanfovy, int prefiltered,
+                                 float *out_color, float *out_depth, float *out_opacity, int *radii, int *n_touched, void *geom_ws,
+                                 void *binning_ws, size_t binning_ws_bytes, int capacity, int tile_list_capacity, void *image_ws,
+                                 int flags, void *stream) {
+  return forward_batch_impl(K, P, D, M, bg, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                            viewmatrices, projmatrices, campos, tanfovx, tanfovy, prefiltered, out_color, out_depth, out_opacity, radii,
+                            n_touched, geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws, flags, stream,
+                            nullptr, nullptr, nullptr);
+}
+
+static size_t fused_loss_view_bytes(int W, int H) { return (gsaj_fused_loss_workspace_bytes(W, H) + 255) & ~(size_t)255; }
+
+size_t gsaj_fused_loss_batch_workspace_bytes(int K, int W, int H) { return (size_t)(K > 0 ? K : 0) * fused_loss_view_bytes(W, H); }
+
+// the loss arguments of the two batched fused entry points, checked before anything is launched
+static int fused_loss_batch_args(const char *who, int K, int loss_flags, const float *gt_color, const float *gt_depth,
+                                 const float *exposure_a, const float *exposure_b, int exposure_stride, FusedLoss *fl, float alpha,
+                                 float rgb_boundary_threshold, const uint8_t *grad_mask) {
+  if (K <= 0) {
+    gsaj_set_error("%s: invalid argument (K=%d)", who, K);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  int rc = fused_loss_args(who, loss_flags, gt_color, gt_depth, exposure_a, exposure_b, exposure_stride);
+  if (rc != GSAJ_OK) return rc;
+  const bool noexp = loss_flags & GSAJ_LOSS_NO_EXPOSURE;
+  fl->flags = loss_flags; fl->alpha = alpha; fl->rgb_thr = rgb_boundary_threshold;
+  fl->gt_color = gt_color; fl->gt_depth = (loss_flags & GSAJ_LOSS_MONOCULAR) ? nullptr : gt_depth; fl->grad_mask = grad_mask;
+  fl->exp_a = noexp ? nullptr : exposure_a; fl->exp_b = noexp ? nullptr : exposure_b; fl->exp_stride = exposure_stride;
+  return GSAJ_OK;
+}
+
+int gsaj_rasterize_forward_loss_batch(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
+                                      const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
+                                      const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                      const float *projmatrices, const float *campos, float tanfovx, float tanfovy, int prefiltered,
+                                      float *out_color, float *out_depth, float *out_opacity, int *radii, int *n_touched, void *geom_ws,
+                                      void *binning_ws, size_t binning_ws_bytes, int capacity, int tile_list_capacity, void *image_ws,
+                                      int flags, int loss_flags, float alpha, float rgb_boundary_threshold, const float *gt_color,
+                                      const float *gt_depth, const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b,
+                                      int exposure_stride, float *out_scalars, float *out_dexposure, void *loss_ws, void *stream) {
+  FusedLoss fl{};
+  int rc = fused_loss_batch_args("gsaj_rasterize_forward_loss_batch", K, loss_flags, gt_color, gt_depth, exposure_a, exposure_b,
+                                 exposure_stride, &fl, alpha, rgb_boundary_threshold, grad_mask);
+  if (rc != GSAJ_OK) return rc;
+  if (!out_scalars || !loss_ws) {
+    gsaj_set_error("gsaj_rasterize_forward_loss_batch: out_scalars and loss_ws are required");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  fl.partials = reinterpret_cast<float *>(align_base(loss_ws));  // [K][slots][4], dense: K x 255 bytes of the workspace are slack
+  return forward_batch_impl(K, P, D, M, bg, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                            viewmatrices, projmatrices, campos, tanfovx, tanfovy, prefiltered, out_color, out_depth, out_opacity, radii,
+                            n_touched, geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws, flags, stream, &fl,
+                            out_scalars, out_dexposure);
+}
+
+// fl != NULL: the loss-fused form (view 0's pointers); dL_dpix / dL_dpix_depth are not read then
+static int backward_batch_impl(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
+                               const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                               const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                               const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
+                               float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
+                               const float *dL_dpix, const float *dL_dpix_depth, float *dL_dmean2D, float *dL_dconic,
+                               float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D, float *dL_dcov3D,
+                               float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau, float *dL_dtau_sum, int flags,
+                               void *stream, const FusedLoss *fl) {
   if (K <= 0 || P <= 0 || capacity <= 0 || W <= 0 || H <= 0 || !bg || !means3D || !viewmatrices || !projmatrices || !projmatrix_raw ||
-      !radii || !geom_ws || !binning_ws || !image_ws || !dL_dpix || !dL_dpix_depth || !dL_dopacity || !dL_dmean3D || !dL_dcov3D ||
+      !radii || !geom_ws || !binning_ws || !image_ws || (!fl && (!dL_dpix || !dL_dpix_depth)) || !dL_dopacity || !dL_dmean3D || !dL_dcov3D ||
       !dL_dtau_sum) {
     gsaj_set_error("gsaj_rasterize_backward_batch: invalid argument");
     return GSAJ_ERR_INVALID_ARGUMENT;
@@ -472,7 +537,7 @@ int gsaj_rasterize_backward_batch(int K, int P, int D, int M, int capacity, cons
   // round trip); the two halves called separately go through gsum as before
   const int fused = (flags & (GSAJ_BWD_ONLY_COMPOSITE | GSAJ_BWD_ONLY_CHAIN)) ? 0 : 1;
   if (!(flags & GSAJ_BWD_ONLY_CHAIN)) {
-    if ((rc = launch_render_backward(capacity, W, H, gx, gy, bg, g, b, im, dL_dpix, dL_dpix_depth, K, vs, s)) != GSAJ_OK) return rc;
+    if ((rc = launch_render_backward(capacity, W, H, gx, gy, bg, g, b, im, dL_dpix, dL_dpix_depth, K, vs, s, fl)) != GSAJ_OK) return rc;
     if (!fused && (rc = launch_gather_sums(P, K, radii, g, b, im, vs, s)) != GSAJ_OK) return rc;
   }
   if (flags & GSAJ_BWD_ONLY_COMPOSITE) return GSAJ_OK;
@@ -491,6 +556,49 @@ int gsaj_rasterize_backward_batch(int K, int P, int D, int M, int capacity, cons
   p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
   (void)colors_precomp;
   return launch_gaussian_backward_batch(p, K, g, b, im, vs, (flags & GSAJ_BWD_ACCUMULATE) ? 1 : 0, fused, s);
+}
+
+int gsaj_rasterize_backward_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
+                                  const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                  const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                  const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                  float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
+                                  const float *dL_dpix, const float *dL_dpix_depth, float *dL_dmean2D, float *dL_dconic,
+                                  float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D, float *dL_dcov3D,
+                                  float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau, float *dL_dtau_sum, int flags,
+                                  void *stream) {
+  return backward_batch_impl(K, P, D, M, capacity, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
+                             cov3D_precomp, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws,
+                             binning_ws, image_ws, dL_dpix, dL_dpix_depth, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth,
+                             dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dtau, dL_dtau_sum, flags, stream, nullptr);
+}
+
+int gsaj_rasterize_backward_loss_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
+                                       const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                       const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                       const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                       float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws, int loss_flags,
+                                       float alpha, float rgb_boundary_threshold, const float *color, const float *depth,
+                                       const float *opacity, const float *gt_color, const float *gt_depth, const uint8_t *grad_mask,
+                                       const float *exposure_a, const float *exposure_b, int exposure_stride, float *dL_dmean2D,
+                                       float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D,
+                                       float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau,
+                                       float *dL_dtau_sum, int flags, void *stream) {
+  FusedLoss fl{};
+  if (!(flags & GSAJ_BWD_ONLY_CHAIN)) {  // (the chain half reads no image: its loss arguments are ignored)
+    int rc = fused_loss_batch_args("gsaj_rasterize_backward_loss_batch", K, loss_flags, gt_color, gt_depth, exposure_a, exposure_b,
+                                   exposure_stride, &fl, alpha, rgb_boundary_threshold, grad_mask);
+    if (rc != GSAJ_OK) return rc;
+    if (!color || !opacity || (!(loss_flags & GSAJ_LOSS_MONOCULAR) && !depth)) {
+      gsaj_set_error("gsaj_rasterize_backward_loss_batch: the forward's color / depth / opacity images are required");
+      return GSAJ_ERR_INVALID_ARGUMENT;
+    }
+    fl.color = color; fl.depth = (loss_flags & GSAJ_LOSS_MONOCULAR) ? nullptr : depth; fl.opacity = opacity;
+  }
+  return backward_batch_impl(K, P, D, M, capacity, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
+                             cov3D_precomp, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws,
+                             binning_ws, image_ws, nullptr, nullptr, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth,
+                             dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dtau, dL_dtau_sum, flags, stream, &fl);
 }
 
 static int backward_impl(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,

@@ -222,15 +222,18 @@ int launch_tile_binning(int P, int sort_cap, int rec16, int grid_x, int grid_y, 
                         int views, ViewStrides vs, hipStream_t s);
 // out_color [views,3,H,W], out_depth / out_opacity [views,1,H,W], n_touched [views,P]
 struct FusedLoss;  // loss_terms.h
-// fl != NULL (single view only): the forward's epilogue also sums the loss terms of its pixels into fl->partials
-// [gsaj_fwd_loss_slots(W, H)][4]
+// fl != NULL: the forward's epilogue also sums the loss terms of its pixels into fl->partials
+// [views][gsaj_fwd_loss_slots(W, H)][4]; *fl holds view 0's pointers (loss_terms.h: fused_loss_view)
 int launch_render_forward(int P, int W, int H, int grid_x, int grid_y, const float *bg, const GeomWS &g, const BinWS &b,
                           const ImageWS &im, float *out_color, float *out_depth, float *out_opacity, int *n_touched, int views,
                           ViewStrides vs, hipStream_t s, const FusedLoss *fl = nullptr);
 int gsaj_fwd_loss_slots(int W, int H);  // workgroups of the forward compositor = loss partial slots
-int launch_loss_finalize(const FusedLoss &fl, int nslots, int W, int H, const uint32_t *aborted, float *out_scalars, hipStream_t s);
+// one workgroup per view: out_scalars [views,5], out_dexposure [views,2] or NULL; view v's abort word is v * abort_stride bytes
+// after `aborted`
+int launch_loss_finalize(const FusedLoss &fl, int nslots, int W, int H, const uint32_t *aborted, float *out_scalars, hipStream_t s,
+                         int views = 1, size_t abort_stride = 0, float *out_dexposure = nullptr);
 // dL_dpix [views,3,H,W], dL_dpix_depth [views,1,H,W]
-// fl != NULL (single view only): the pixel seeds are derived from fl's images + ground truth instead of read from dL_dpix
+// fl != NULL: the pixel seeds are derived from fl's images + ground truth (view 0's pointers) instead of read from dL_dpix
 int launch_render_backward(int R, int W, int H, int grid_x, int grid_y, const float *bg, const GeomWS &g, const BinWS &b,
                            const ImageWS &im, const float *dL_dpix, const float *dL_dpix_depth, int views, ViewStrides vs,
                            hipStream_t s, const FusedLoss *fl = nullptr);

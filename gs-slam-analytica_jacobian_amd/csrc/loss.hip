@@ -136,10 +136,19 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_loss_seeds(LossParams p) {
 
 // The loss value and dL/d(exposure) of a frame whose forward compositor summed the per-pixel terms itself (render_fwd.hip,
 // loss-fused form): one workgroup adds the per-workgroup partials in slot order (fp64, fixed tree) -- the tail of k_loss_seeds
-// without its pass over the image.
+// without its pass over the image.  Batched (gsaj_rasterize_forward_loss_batch): workgroup k does this for view k -- its own block of
+// partials, its own abort word (abort_stride bytes after the previous view's: the image workspace stride), row k of out [K,5] and,
+// if asked for, of dexp [K,2] = (dL/da, dL/db), the contiguous form gsaj_pose_adam_step_batch reads.
 __global__ __launch_bounds__(LOSS_BLOCK) void k_loss_finalize(FusedLoss fl, int nslots, size_t HW, const uint32_t *__restrict__ aborted,
-                                                              float *__restrict__ out) {
+                                                              size_t abort_stride, float *__restrict__ out, float *__restrict__ dexp) {
   __shared__ double red[4][LOSS_BLOCK];
+  {
+    const size_t view = blockIdx.x;
+    fused_loss_view(fl, view, HW, (size_t)nslots);
+    if (aborted) aborted = gsaj_shift(aborted, view * abort_stride);
+    out += view * 5;
+    if (dexp) dexp += view * 2;
+  }
   if (aborted && aborted[0]) return;  // aborted asynchronous frame: no partials were written; the scalars stay the last frame's
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int b = threadIdx.x; b < nslots; b += LOSS_BLOCK) {
@@ -165,11 +174,14 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_loss_finalize(FusedLoss fl, int 
     out[2] = (float)l_d;
     out[3] = noexp ? 0.f : (float)((double)L.k_rgb * red[2][0]);
     out[4] = noexp ? 0.f : (float)((double)L.k_rgb * red[3][0]);
+    if (dexp) { dexp[0] = out[3]; dexp[1] = out[4]; }
   }
 }
 
-int launch_loss_finalize(const FusedLoss &fl, int nslots, int W, int H, const uint32_t *aborted, float *out_scalars, hipStream_t s) {
-  hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(LOSS_BLOCK), 0, s, fl, nslots, (size_t)W * H, aborted, out_scalars);
+int launch_loss_finalize(const FusedLoss &fl, int nslots, int W, int H, const uint32_t *aborted, float *out_scalars, hipStream_t s,
+                         int views, size_t abort_stride, float *out_dexposure) {
+  hipLaunchKernelGGL(k_loss_finalize, dim3((unsigned)views), dim3(LOSS_BLOCK), 0, s, fl, nslots, (size_t)W * H, aborted, abort_stride,
+                     out_scalars, out_dexposure);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }

@@ -14,7 +14,8 @@ struct LossConsts {
 };
 
 // Loss terms fused into the compositors (gsaj_rasterize_forward_loss / gsaj_rasterize_backward_loss): what the stand-alone
-// kernel takes as arguments, by value in the compositors' kernel arguments.
+// kernel takes as arguments, by value in the compositors' kernel arguments.  The batched forms (gsaj_rasterize_forward_loss_batch /
+// _backward_loss_batch) hand over view 0's pointers; view v's are fused_loss_view(fl, v, ...).
 struct FusedLoss {
   int flags;
   float alpha, rgb_thr;
@@ -23,9 +24,25 @@ struct FusedLoss {
   const float *exp_a, *exp_b;          // device scalars (NULL with GSAJ_LOSS_NO_EXPOSURE)
   const float *color, *depth, *opacity;  // backward: the images the forward wrote
   float *partials;                     // forward: [workgroups][4] sums of (colour term, depth term, d/da term, d/db term)
+  int exp_stride;                      // batched: floats between two views' exp_a (and exp_b) scalars
 };
 
 #ifdef __HIPCC__
+// View `view` of a batched launch: every per-view member moved on (images by the image size, the exposure scalars by exp_stride,
+// the partials by `slots` workgroups).  `view` is workgroup-uniform (blockIdx), so these are scalar adds; view 0 changes nothing.
+// Pointers that may be NULL stay NULL (grad_mask's NULL is tested per pixel; the others are never read when NULL).
+__device__ __forceinline__ void fused_loss_view(FusedLoss &fl, size_t view, size_t HW, size_t slots) {
+  fl.gt_color += view * 3 * HW;
+  fl.color += view * 3 * HW;
+  if (fl.gt_depth) fl.gt_depth += view * HW;
+  if (fl.grad_mask) fl.grad_mask += view * HW;
+  if (fl.depth) fl.depth += view * HW;
+  fl.opacity += view * HW;
+  if (fl.exp_a) fl.exp_a += view * (size_t)fl.exp_stride;
+  if (fl.exp_b) fl.exp_b += view * (size_t)fl.exp_stride;
+  fl.partials += view * slots * 4;
+}
+
 __device__ __forceinline__ float loss_sgn(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
 
 __device__ __forceinline__ LossConsts loss_consts(int flags, float alpha, float rgb_thr, const float *exp_a, const float *exp_b,

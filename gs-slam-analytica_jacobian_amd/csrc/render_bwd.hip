@@ -76,6 +76,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
     reached = gsaj_shift(reached, view * vs.bin);
     dL_dpix += view * 3 * HWv;
     dL_dpix_depth += view * HWv;
+    if (LOSS) fused_loss_view(fl, view, HWv, 0);  // (the partials are the forward's)
   }
   const uint2 *__restrict__ ranges = im.ranges;
   const float *__restrict__ final_T = im.final_T;
@@ -464,7 +465,7 @@ int launch_render_backward(int R, int W, int H, int grid_x, int grid_y, const fl
   {
     GsajProfScope ps(ST_RENDER_BWD, s);
     if (fl)
-      hipLaunchKernelGGL(k_render_bwd<true>, dim3(grid_x * grid_y, 1), dim3(256), 0, s, W, H, grid_x, im, b.point_list, b.taken, reinterpret_cast<uint2 *>(b.keys), g, bg,
+      hipLaunchKernelGGL(k_render_bwd<true>, dim3(grid_x * grid_y, views), dim3(256), 0, s, W, H, grid_x, im, b.point_list, b.taken, reinterpret_cast<uint2 *>(b.keys), g, bg,
                          dL_dpix, dL_dpix_depth, b.inst_grad, b.reached, vs, *fl);
     else
       hipLaunchKernelGGL(k_render_bwd<false>, dim3(grid_x * grid_y, views), dim3(256), 0, s, W, H, grid_x, im, b.point_list, b.taken, reinterpret_cast<uint2 *>(b.keys), g, bg,

@@ -61,6 +61,7 @@ __global__ __launch_bounds__(GSAJ_FWD_THREADS) __attribute__((amdgpu_waves_per_e
     out_depth += view * HWv;
     out_opacity += view * HWv;
     n_touched += view * (size_t)P;
+    if (LOSS) fused_loss_view(fl, view, HWv, gridDim.x);  // (each view has gridDim.x partial slots)
   }
   const uint2 *__restrict__ ranges = im.ranges;
   float *__restrict__ final_T = im.final_T;
@@ -339,7 +340,7 @@ int launch_render_forward(int P, int W, int H, int grid_x, int grid_y, const flo
     const int tiles = grid_x * grid_y;
     const unsigned nblk = FWD_WAVES == 1 ? (unsigned)((tiles + 7) / 8) * 32u : (unsigned)tiles;
     if (fl)
-      hipLaunchKernelGGL(k_render_fwd<true>, dim3(nblk, 1), dim3(GSAJ_FWD_THREADS), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg,
+      hipLaunchKernelGGL(k_render_fwd<true>, dim3(nblk, views), dim3(GSAJ_FWD_THREADS), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg,
                          out_color, out_depth, out_opacity, n_touched, b.point_list, b.taken, vs, *fl);
     else
       hipLaunchKernelGGL(k_render_fwd<false>, dim3(nblk, views), dim3(GSAJ_FWD_THREADS), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16,

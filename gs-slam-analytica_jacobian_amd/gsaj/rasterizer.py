@@ -735,6 +735,112 @@ class BatchContext:
             call(v0, kv, cur, 4 | (1 if i > 0 else 0))
         return g
 
+    # ---- the loss fused into the batched compositors (gsaj_rasterize_forward_loss_batch / _backward_loss_batch) ---------------
+    def _loss_args(self, L, v0):
+        """The loss arguments both fused calls share, for the view group that starts at view v0: (flags, alpha, threshold), then the
+        ground-truth pointers and the exposure pair moved on to view v0."""
+        HW, es = self.H * self.W, int(L.get("exposure_stride", 1))
+        K = self.K
+        for name, n in (("gt_color", 3 * K * HW), ("gt_depth", K * HW), ("grad_mask", K * HW)):
+            t = L.get(name)
+            if t is not None and (t.device.type != "cuda" or not t.is_contiguous() or t.numel() != n or
+                                  t.dtype != (torch.uint8 if name == "grad_mask" else _F32)):
+                raise _lib.GsajError("forward_loss / backward_loss: %s must be a contiguous device tensor of %d elements" % (name, n))
+        for name in ("exposure_a", "exposure_b"):
+            t = L.get(name)
+            if t is not None and (t.device.type != "cuda" or t.dtype != _F32 or t.dim() != 1 or t.shape[0] != K or
+                                  (K > 1 and t.stride(0) != es)):
+                raise _lib.GsajError("forward_loss / backward_loss: %s must be a float32 device tensor [K] whose stride is "
+                                     "exposure_stride = %d floats" % (name, es))
+        off = lambda t, b: None if t is None else t.data_ptr() + b * v0  # noqa: E731
+        return ((int(L["flags"]), float(L["alpha"]), float(L["rgb_boundary_threshold"])),
+                (off(L["gt_color"], 12 * HW), off(L.get("gt_depth"), 4 * HW), off(L.get("grad_mask"), HW),
+                 off(L.get("exposure_a"), 4 * es), off(L.get("exposure_b"), 4 * es), es))
+
+    def forward_loss(self, L, bg, means3D, opacities, viewmatrices, projmatrices, campos, tanfovx, tanfovy, sh_degree=0, shs=None,
+                     colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, scale_modifier=1.0):
+        """forward(sync=False) whose compositor also sums every view's loss: L is the dict FrameContext.forward_loss takes with
+        [K,...] tensors -- flags, alpha, rgb_boundary_threshold, gt_color [K,3,H,W], gt_depth [K,H,W] or None, grad_mask (uint8
+        [K*H*W]) or None, exposure_a / exposure_b ([K] views with stride exposure_stride floats, default 1; e.g. columns 33 / 34 of
+        PoseTrackerBatch.state with exposure_stride=80, read in place) or None, scalars (float32 [K,5]: loss, L_rgb, L_depth,
+        dL/da, dL/db per view) and optionally dexposure (float32 [K,2]: the last two again, contiguous, what PoseTrackerBatch.step
+        takes).  Asynchronous only: the arena must have been sized by an earlier forward(sync=True).  An aborted view leaves its
+        rows of scalars / dexposure as they were."""
+        if self.capacity <= 0:
+            raise _lib.GsajError("forward_loss: size the arena with one synchronous forward() first")
+        K, HW, P = self.K, self.H * self.W, self.P
+        sc, dx = L["scalars"], L.get("dexposure")
+        for t, shape in ((sc, (K, 5)), (dx, (K, 2))):
+            if t is not None and (t.device.type != "cuda" or t.dtype != _F32 or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise _lib.GsajError("forward_loss: scalars / dexposure must be contiguous float32 device tensors [K,5] / [K,2]")
+        if not hasattr(self, "loss_ws"):
+            self.loss_ws_stride = self.lib.gsaj_fused_loss_batch_workspace_bytes(1, self.W, self.H)
+            self.loss_ws = torch.empty(self.lib.gsaj_fused_loss_batch_workspace_bytes(K, self.W, self.H), device=self.dev, dtype=torch.uint8)
+        if self.auto_grow:
+            seen = self.watch.poll()
+            if seen is not None:
+                if seen[0] > self.watch.grow_at * self.capacity:
+                    self._size(int(1.5 * seen[0]) + 1024)
+                    self.watch.grown += 1
+                if seen[1] > self.tile_list_capacity > 0:
+                    self.tile_list_capacity = min(SORT_CAP, int(1.1 * seen[1]) + 1)
+        cur = self._fork()
+        for v0, kv, st in self.groups:
+            stream = cur if st is None else st
+            head, loss = self._loss_args(L, v0)
+            _lib.check(self.lib.gsaj_rasterize_forward_loss_batch(
+                kv, P, int(sh_degree), self.M, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
+                _ptr(opacities), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
+                viewmatrices.data_ptr() + 64 * v0, projmatrices.data_ptr() + 64 * v0, None if campos is None else campos.data_ptr() + 12 * v0,
+                float(tanfovx), float(tanfovy), 0, self.color.data_ptr() + 12 * HW * v0, self.depth.data_ptr() + 4 * HW * v0,
+                self.opacity.data_ptr() + 4 * HW * v0, self.radii.data_ptr() + 4 * P * v0, self.n_touched.data_ptr() + 4 * P * v0,
+                self.geom.data_ptr() + self.geom_stride * v0, self.binning.data_ptr() + self.bin_stride * v0, self.bin_stride * kv,
+                self.capacity, self.tile_list_capacity, self.img.data_ptr() + self.img_stride * v0, self.flags, *head, *loss,
+                sc.data_ptr() + 20 * v0, None if dx is None else dx.data_ptr() + 8 * v0, self.loss_ws.data_ptr() + self.loss_ws_stride * v0,
+                stream.cuda_stream), "gsaj_rasterize_forward_loss_batch")
+        self._join(cur)
+        if self.auto_grow:
+            self.watch.post()
+
+    def backward_loss(self, L, bg, means3D, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy, sh_degree=0, shs=None,
+                      colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, scale_modifier=1.0, slot=0, split=False):
+        """backward() with every view's pixel seeds derived inside the reverse compositor from this context's color / depth / opacity
+        and the ground truth of L (same dict as forward_loss): no [K,3,H,W] / [K,1,H,W] seed images exist.  The gradients are those
+        of forward -> LossSeedsBatch -> backward bit for bit; split and the view groups work as in backward()."""
+        g = self.slots[slot]
+        if g["tau_every_window"] is not None:
+            g["tau_every_window"].zero_()
+        HW, P = self.H * self.W, self.P
+
+        def call(v0, kv, stream, flags):
+            head, loss = self._loss_args(L, v0)
+            _lib.check(self.lib.gsaj_rasterize_backward_loss_batch(
+                kv, P, int(sh_degree), self.M, self.capacity, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs),
+                _ptr(colors_precomp), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
+                viewmatrices.data_ptr() + 64 * v0, projmatrices.data_ptr() + 64 * v0, _ptr(projmatrix_raw),
+                None if campos is None else campos.data_ptr() + 12 * v0, float(tanfovx), float(tanfovy), self.radii.data_ptr() + 4 * P * v0,
+                self.geom.data_ptr() + self.geom_stride * v0, self.binning.data_ptr() + self.bin_stride * v0,
+                self.img.data_ptr() + self.img_stride * v0, *head, self.color.data_ptr() + 12 * HW * v0, self.depth.data_ptr() + 4 * HW * v0,
+                self.opacity.data_ptr() + 4 * HW * v0, *loss, g["mean2D"].data_ptr() + 12 * P * v0, None, g["opacity"].data_ptr(), None,
+                None, g["mean3D"].data_ptr(), g["cov3D"].data_ptr(), _ptr(g["sh"]), _ptr(g["scale"]), _ptr(g["rot"]),
+                None if g["tau"] is None else g["tau"].data_ptr() + 24 * P * v0, g["tau_all"].data_ptr() + 24 * v0, flags,
+                stream.cuda_stream), "gsaj_rasterize_backward_loss_batch")
+
+        cur = self._fork()
+        if len(self.groups) == 1:
+            if split:
+                call(0, self.K, cur, 2)
+                call(0, self.K, cur, 4)
+            else:
+                call(0, self.K, cur, 0)
+            return g
+        for v0, kv, st in self.groups:      # per-view halves: independent, one stream each
+            call(v0, kv, cur if st is None else st, 2)
+        self._join(cur)                      # the accumulating per-Gaussian chains: in group order on the caller's stream
+        for i, (v0, kv, st) in enumerate(self.groups):
+            call(v0, kv, cur, 4 | (1 if i > 0 else 0))
+        return g
+
     def view_sums(self, v, stored=False):
         """[P,12]: the reverse compositor's 10 sums per Gaussian of view v of the last backward (gsaj_debug_export_view_sums_gather:
         the whole-window backward never stores them, so they are summed again from the view's instance rows, which survive

@@ -336,6 +336,48 @@ int gsaj_rasterize_backward_loss(int P, int D, int M, int R, const float *bg, in
                                  float *dL_ddepth, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscale,
                                  float *dL_drot, float *dL_dtau, float *dL_dtau_sum, void *stream);
 
+/* ---- the fused losses for the K views of a mapping window ---------------------------------------------------------------------
+ * gsaj_rasterize_forward_loss_batch = gsaj_rasterize_forward_batch whose compositor also sums each view's loss terms, followed by
+ * one finalize workgroup per view: out_scalars [K,5] row k = {loss, L_rgb, L_depth, dL/da, dL/db} of view k, and, if
+ * out_dexposure is given, out_dexposure [K,2] row k = {dL/da, dL/db} (the contiguous form gsaj_pose_adam_step_batch reads).
+ * gsaj_rasterize_backward_loss_batch = gsaj_rasterize_backward_batch whose reverse compositor derives the pixel seeds of view k from
+ * color / depth / opacity [K,.,H,W] as the forward wrote them; no [K,3,H,W] / [K,1,H,W] seed images exist.  gt_color [K,3,H,W],
+ * gt_depth / grad_mask [K,H,W]; exposure_a / exposure_b point at view 0's scalars, view k's are exposure_stride floats further on
+ * (1: contiguous [K]; 80: columns 33 and 34 of the gsaj_pose_adam_step_batch state, read in place).
+ * Bit for bit: every image, n_touched and every gradient equals gsaj_rasterize_forward_batch -> gsaj_loss_seeds_batch ->
+ * gsaj_rasterize_backward_batch on the same inputs, and row k of out_scalars equals what gsaj_rasterize_forward_loss gives for view
+ * k alone (same partial grid, same summation order); with K = 1 both calls are the single-view pair above.  The scalars differ
+ * from gsaj_loss_seeds_batch's only by the order of their sums.  A view aborted on the device (binning arena too small) leaves its
+ * rows of out_scalars / out_dexposure as they were and contributes nothing to any gradient.
+ * loss_ws: gsaj_fused_loss_batch_workspace_bytes(K, W, H) = K blocks of gsaj_fused_loss_workspace_bytes(W, H) rounded up to 256
+ * bytes; no initialisation needed.  The GSAJ_BWD_* flags keep their meaning (GSAJ_BWD_ONLY_CHAIN reads no image and ignores the loss
+ * arguments).  Invalid arguments are reported before anything is launched. */
+size_t gsaj_fused_loss_batch_workspace_bytes(int K, int W, int H);
+int gsaj_rasterize_forward_loss_batch(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
+                                      const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
+                                      const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                      const float *projmatrices, const float *campos, float tanfovx, float tanfovy, int prefiltered,
+                                      float *out_color, float *out_depth, float *out_opacity, int *radii, int *n_touched, void *geom_ws,
+                                      void *binning_ws, size_t binning_ws_bytes, int capacity, int tile_list_capacity, void *image_ws,
+                                      int flags /* GSAJ_FWD_* */, int loss_flags /* GSAJ_LOSS_* */, float alpha,
+                                      float rgb_boundary_threshold, const float *gt_color /*dev [K,3,H,W]*/,
+                                      const float *gt_depth /*dev [K,H,W] or NULL (monocular)*/,
+                                      const uint8_t *grad_mask /*dev [K,H,W] or NULL*/, const float *exposure_a, const float *exposure_b,
+                                      int exposure_stride /*floats between views, >= 1; pointers NULL with NO_EXPOSURE*/,
+                                      float *out_scalars /*dev [K,5]*/, float *out_dexposure /*dev [K,2] or NULL*/, void *loss_ws,
+                                      void *stream);
+int gsaj_rasterize_backward_loss_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
+                                       const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                       const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                       const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                       float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws, int loss_flags,
+                                       float alpha, float rgb_boundary_threshold, const float *color, const float *depth,
+                                       const float *opacity, const float *gt_color, const float *gt_depth, const uint8_t *grad_mask,
+                                       const float *exposure_a, const float *exposure_b, int exposure_stride, float *dL_dmean2D,
+                                       float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D,
+                                       float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau,
+                                       float *dL_dtau_sum, int flags /* GSAJ_BWD_* */, void *stream);
+
 /* The same for the K views of a mapping window in ONE launch (utils/slam_backend.py:168-232 sums get_loss_mapping over the
  * keyframes of the window): color / gt_color / dL_dcolor [K,3,H,W], depth / opacity / dL_ddepth / dL_dopacity [K,1,H,W], gt_depth /
  * grad_mask [K,H,W], exposure_a / exposure_b [K] (one pair per keyframe, camera_utils.py:43-48), out_scalars [K,5]; view k gets
