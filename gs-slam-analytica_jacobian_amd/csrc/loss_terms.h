@@ -98,4 +98,46 @@ __device__ __forceinline__ LossPixel loss_pixel(const LossConsts &L, float g0, f
   }
   return o;
 }
+
+// The same pixel for a Gauss-Newton solver (pose_jac.hip): the L1 terms as iteratively reweighted least squares.  With the
+// residuals r_ch = m (ea c_ch + eb - g_ch), r_d = dm (d - gd) of loss_pixel (the same explicitly rounded operations, the same
+// bits) and the per-pixel coefficients kappa_rgb = k_rgb wrgb, kappa_d = k_d:
+//   seed       s = kappa (dr/dC) clamp(r / delta, -1, 1)     delta == 0: loss_pixel's gC / gD, bit for bit
+//   curvature  h = kappa (dr/dC)^2 / max(|r|, delta)         0 where the gate is closed, or r == 0 with delta == 0
+// o: loss_pixel's result for the same arguments.
+struct LossGN {
+  float s[4], h[4];  // r, g, b, depth
+};
+__device__ __forceinline__ LossGN loss_pixel_gn(const LossConsts &L, const LossPixel &o, float g0, float g1, float g2, float c0, float c1,
+                                                float c2, float op, bool mask, float gd, float d, float delta) {
+  LossGN q;
+  float m = (L.cl || __fadd_rn(__fadd_rn(g0, g1), g2) > L.rgb_thr) ? 1.f : 0.f;
+  if (L.tracking || L.cl) m = mask ? m : 0.f;
+  const float wrgb = L.tracking ? op : 1.f;
+  const float r[3] = {__fsub_rn(__fmul_rn(__builtin_fmaf(L.ea, c0, L.eb), m), __fmul_rn(g0, m)),
+                      __fsub_rn(__fmul_rn(__builtin_fmaf(L.ea, c1, L.eb), m), __fmul_rn(g1, m)),
+                      __fsub_rn(__fmul_rn(__builtin_fmaf(L.ea, c2, L.eb), m), __fmul_rn(g2, m))};
+  const float gC[3] = {o.gC0, o.gC1, o.gC2};
+  const float kw = __fmul_rn(__fmul_rn(L.k_rgb, L.ea), __fmul_rn(wrgb, m));  // kappa dr/dC = (k_rgb ea) (wrgb m): loss_pixel's ke, wm
+  const float drdc = __fmul_rn(m, L.ea);
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) {
+    const float den = fmaxf(fabsf(r[ch]), delta);
+    q.s[ch] = delta > 0.f ? __fmul_rn(kw, fminf(1.f, fmaxf(-1.f, __fdiv_rn(r[ch], delta)))) : gC[ch];
+    q.h[ch] = den > 0.f ? __fdiv_rn(__fmul_rn(kw, drdc), den) : 0.f;
+  }
+  q.s[3] = 0.f;
+  q.h[3] = 0.f;
+  if (!L.mono) {
+    float dm = (gd > (L.cl ? 0.0f : 0.01f)) ? 1.f : 0.f;
+    if (L.tracking) dm = (op > 0.95f) ? dm : 0.f;
+    if (L.cl) dm *= m;
+    const float rd = __fsub_rn(__fmul_rn(d, dm), __fmul_rn(gd, dm));
+    const float kd = __fmul_rn(L.k_d, dm);
+    const float den = fmaxf(fabsf(rd), delta);
+    q.s[3] = delta > 0.f ? __fmul_rn(kd, fminf(1.f, fmaxf(-1.f, __fdiv_rn(rd, delta)))) : o.gD;
+    q.h[3] = den > 0.f ? __fdiv_rn(kd, den) : 0.f;  // (dm is 0 or 1: dm^2 = dm)
+  }
+  return q;
+}
 #endif

@@ -8,19 +8,7 @@
 // W2C^T * projection_matrix, camera_center = -R^-1 t (camera_utils.py:95-109).  The reference does this with ~60 tiny
 // torch kernels and one host read-back per iteration; here it is one single-lane kernel and no read-back.
 #include "gsaj_common.h"
-
-// pose_state layout (floats): see include/gsaj.h
-#define PS_W2C 0
-#define PS_M 16
-#define PS_V 24
-#define PS_STEP 32
-#define PS_EXP 33
-#define PS_VIEW 35
-#define PS_PROJ 51
-#define PS_CAMPOS 67
-#define PS_TAU 70
-#define PS_NORM 76
-#define PS_CONV 77
+#include "pose_se3.h"
 
 struct PoseStepParams {
   const float *g_tau, *g_exp, *projection;
@@ -31,29 +19,6 @@ struct PoseStepParams {
   const uint32_t *skip;   // (may be NULL) a non-zero word makes the step a no-op: the frame's abort flag (gsaj_forward_abort_flag),
   size_t skip_stride;     //   pose k's word `skip_stride` bytes after pose k - 1's
 };
-
-__device__ void so3_exp_and_v(const float *th, float R[9], float V[9]) {
-  const float W[9] = {0.f, -th[2], th[1], th[2], 0.f, -th[0], -th[1], th[0], 0.f};
-  float W2[9];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) W2[i * 3 + j] = W[i * 3 + 0] * W[0 * 3 + j] + W[i * 3 + 1] * W[1 * 3 + j] + W[i * 3 + 2] * W[2 * 3 + j];
-  const float angle = sqrtf(th[0] * th[0] + th[1] * th[1] + th[2] * th[2]);
-  float a, b, c, d;  // R = I + a W + b W2;  V = I + c W + d W2
-  if (angle < 1e-5f) {
-    a = 1.f; b = 0.5f; c = 0.5f; d = 1.0f / 6.0f;
-  } else {
-    const float s = sinf(angle), co = cosf(angle), a2 = angle * angle;
-    a = s / angle;
-    b = (1.f - co) / a2;
-    c = b;
-    d = (angle - s) / (a2 * angle);
-  }
-  for (int i = 0; i < 9; i++) {
-    const float id = (i % 4 == 0) ? 1.f : 0.f;
-    R[i] = id + a * W[i] + b * W2[i];
-    V[i] = id + c * W[i] + d * W2[i];
-  }
-}
 
 __global__ void k_pose_adam_step(PoseStepParams p) {
   if (threadIdx.x != 0) return;

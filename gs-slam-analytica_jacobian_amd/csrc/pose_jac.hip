@@ -1,0 +1,501 @@
+// pose_jac.hip -- the per-pixel pose Jacobian d(C, D)/dtau in forward mode, the 6x6 normal equations of the tracking loss
+// formed from it, and a Levenberg-Marquardt pose step on the device (gfx950).
+//
+// tau = [rho(3), theta(3)] is the left increment W2C <- Exp(tau) W2C.  J_p in R^{4x6} (rows r, g, b, depth) is the exact
+// transpose of the linear map the backward implements: sum_p sum_ch s[ch, p] J_p[ch, :] == dL_dtau_sum of
+// gsaj_rasterize_backward(seeds = s) in real arithmetic, gate for gate (DESIGN.md "Gauss-Newton tracking").
+//
+//  k_splat_jac     one lane per visible Gaussian: the rows d(mean2D, conic, depth, colour)/dtau -- gaussian_chain_geom /
+//                  sh_backward (gaussian_chain.h: the backward's own chain) applied to unit sums, 45 floats in a 48-float row.
+//  k_render_jac    the forward-mode compositor: k_render_fwd's work decomposition (one wave64 per 8x8 quadrant, private LDS
+//                  staging, no workgroup barrier, tiles in tile_order with the XCD-aware block mapping) over the state of a
+//                  FINISHED forward: only the entries the quadrant's forward wave took (BinWS.taken) are staged, each pixel
+//                  stops at its n_contrib, and power / G / alpha come from gsaj_power2 / gsaj_load_row -- every gate decides
+//                  on the forward's bits.  Per pixel, walking front to back (dalpha, dc, dz are 6-vectors):
+//                      J_ch += T (alpha dc[ch] + c[ch] (dalpha - alpha S));   S += dalpha / (1 - alpha);   T *= 1 - alpha
+//                  and J_ch -= bg[ch] T_final S_final for the colour rows.  dalpha = o G dpower: the 0.99 cap is no gradient gate.
+//                  With seeds s and curvatures h (given as images, or derived from the tracking loss: loss_terms.h) the pixel's
+//                  g = sum s J and H = sum h J^T J are reduced over the wave and stored as ONE 32-float row per workgroup
+//                  -- no atomics anywhere, so the results are the same bits run to run.
+//  k_gn_reduce     the explicit form's tail: the rows summed in slot order (fp64) -> H [21], g [6].
+//  k_gn_step       the fused form's tail: the same sum, then accept / reject, damping, a 6x6 Cholesky solve in fp64 and
+//                  Exp(tau) W2C with the Adam pose step's own device functions (pose_se3.h).  One launch, no host read.
+#include "gsaj_common.h"
+#include "gaussian_chain.h"
+#include "loss_terms.h"
+#include "pose_se3.h"
+#include "wave_reduce.h"
+
+#define JROW_F 48      // floats per derivative row: m2x[6] m2y[6] conic a[6] b[6] c[6] depth[6] colour r[3] g[3] b[3], 3 unused
+#define JROW_F4 (JROW_F / 4)
+#define JAC_CHUNK 32   // list positions examined (and at most that many entries staged) per wave and trip: 1.5 KB of splat rows + 6 KB
+                       // of derivative rows + the ids = 7.8 KB of LDS per wave
+#define GN_ROW GSAJ_GN_PARTIAL_FLOATS  // H (21, upper triangle by rows), g (6), loss, L_rgb, L_depth, d/da, d/db partials
+
+// gn_state fields behind the pose state (include/gsaj.h)
+#define GN_LAMBDA 80
+#define GN_ACC_LOSS 81
+#define GN_HAS 82
+#define GN_ACCEPTED 83
+#define GN_REJECTED 84
+#define GN_LAST 85      // loss, L_rgb, L_depth of the last call
+#define GN_ACC_W2C 88
+#define GN_H 104
+#define GN_G 125
+static_assert(GN_G + 6 <= GSAJ_GN_STATE_FLOATS, "gn_state layout");
+
+// ---- per-Gaussian derivative rows ----------------------------------------------------------------------------------------
+// The chain is linear in the ten sums the reverse compositor hands it, so its transpose is the chain applied to unit sums:
+// row j of d(.)/dtau = the tau the chain returns for sum j = 1, all others 0.  Opacity does not depend on tau.  The colour
+// rows are the view-direction term of the SH colour (rho columns only, masked by the clamp flags: sh_backward).
+__global__ __launch_bounds__(64) void k_splat_jac(BwdParams p, const uint8_t *__restrict__ clamped, const uint32_t *__restrict__ counters,
+                                                  float *__restrict__ rows) {
+  if (counters[4]) return;  // aborted async frame
+  const int idx = blockIdx.x * 64 + threadIdx.x;
+  if (idx >= p.P) return;
+  // every input of this Gaussian is requested up front (streaming kernel)
+  const size_t ii = (size_t)idx;
+  const int radius = p.radii[ii];
+  const float3 mean = make_float3(p.means3D[3 * ii], p.means3D[3 * ii + 1], p.means3D[3 * ii + 2]);
+  float c6[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) c6[k] = p.cov3Ds[6 * ii + k];
+  uint8_t cl[3] = {0, 0, 0};
+  if (p.shs) {
+    cl[0] = clamped[3 * ii]; cl[1] = clamped[3 * ii + 1]; cl[2] = clamped[3 * ii + 2];
+  }
+  if (radius <= 0) return;  // rows of culled Gaussians are never read: no tile list names them
+  float *row = rows + ii * JROW_F;
+#pragma unroll 1
+  for (int u = 0; u < 6; u++) {  // mean2D x, y, conic a, b, c, depth
+    const float4 s0 = make_float4(u == 0 ? 1.f : 0.f, u == 1 ? 1.f : 0.f, u == 2 ? 1.f : 0.f, u == 3 ? 1.f : 0.f);
+    const float4 s1 = make_float4(u == 4 ? 1.f : 0.f, 0.f, 0.f, 0.f);
+    const float4 s2 = make_float4(0.f, u == 5 ? 1.f : 0.f, 0.f, 0.f);
+    GaussianGrads o;
+    float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    gaussian_chain_geom(p, mean, c6, s0, s1, s2, o, tau);
+#pragma unroll
+    for (int k = 0; k < 6; k++) row[6 * u + k] = tau[k];
+  }
+  float col[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (p.shs) {
+    const float3 cam = make_float3(p.campos[0], p.campos[1], p.campos[2]);
+    const float *sh_row = p.shs + ii * 3 * (size_t)p.M;
+    float w_unused[16];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      const float3 unit = make_float3(ch == 0 ? 1.f : 0.f, ch == 1 ? 1.f : 0.f, ch == 2 ? 1.f : 0.f);
+      const float3 dmean = sh_backward<1>(p.D, p.M, mean, cam, sh_row, w_unused, cl, unit);
+      col[3 * ch] = -dmean.x; col[3 * ch + 1] = -dmean.y; col[3 * ch + 2] = -dmean.z;  // (gaussian_chain: tau[0..2] -= dmean)
+    }
+  }
+  float4 *row4 = reinterpret_cast<float4 *>(row + 36);
+  row4[0] = make_float4(col[0], col[1], col[2], col[3]);
+  row4[1] = make_float4(col[4], col[5], col[6], col[7]);
+  row4[2] = make_float4(col[8], 0.f, 0.f, 0.f);
+}
+
+// ---- forward-mode compositor ----------------------------------------------------------------------------------------------
+struct JacOut {
+  float *jac;                       // [H,W,4,6] or NULL
+  float *color, *depth;             // re-derived images [3,H,W], [H,W] or NULL
+  const float *seed_c, *seed_d;     // explicit form: seed images [3,H,W], [H,W] (NULL: no g)
+  const float *curv_c, *curv_d;     // explicit form: curvature images (NULL: no H)
+  float *partials;                  // [workgroups][GN_ROW] or NULL
+  float delta;                      // fused form: the IRLS delta
+};
+
+template <bool LOSS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_render_jac(
+    int W, int H, int gx, int tiles, int P, ImageWS im, const float4 *__restrict__ splat, const float4 *__restrict__ splat16,
+    const float *__restrict__ bg, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ taken,
+    const float4 *__restrict__ rows, JacOut jo, FusedLoss fl) {
+  __shared__ float4 srow[JAC_CHUNK * 3];         // (x, y, kx, ky) (kz, o, 1-based list position, -) (r, g, b, depth)
+  __shared__ float4 drow[JAC_CHUNK * JROW_F4];   // the entries' derivative rows
+  __shared__ uint32_t sid[JAC_CHUNK];
+  const uint32_t *__restrict__ counters = im.counters;
+  if (counters[4]) return;  // aborted async frame: the partial rows stay the previous frame's (k_gn_step is handed the abort word)
+  const int lane = threadIdx.x;
+  // 32 consecutive workgroups = 8 tiles x 4 quadrants; tile slot = blockIdx.x & 7 (the XCD the workgroup lands on): k_render_fwd's mapping
+  const int wave = ((int)blockIdx.x >> 3) & 3;
+  const int rank = ((int)blockIdx.x >> 5) * 8 + ((int)blockIdx.x & 7);
+  if (rank >= tiles) {
+    if (jo.partials && lane < GN_ROW) jo.partials[(size_t)blockIdx.x * GN_ROW + lane] = 0.f;
+    return;
+  }
+  const int tile = (int)min(im.tile_order[rank], (uint32_t)(tiles - 1));
+  const int ty = tile / gx, tx = tile - ty * gx;
+  const int px = tx * TILE + (wave & 1) * 8 + (lane & 7);
+  const int py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
+  const bool inside = px < W && py < H;
+  const float pxf = (float)px, pyf = (float)py;
+  const size_t pid = (size_t)py * W + px, HW = (size_t)H * W;
+  const uint2 range = im.ranges[tile];
+  const uint32_t last = inside ? im.n_contrib[pid] : 0u;
+  // furthest last contributor of the quadrant (a position of the tile's own list: the clamp only keeps a stale workspace inside it)
+  const uint32_t wmax = min(wave_max(last), range.y - range.x);
+  const bool rec16 = counters[7] != 0u;
+  const float half_w = 0.5f * W, half_h = 0.5f * H;
+
+  float T = 1.f;
+  float C[4] = {0.f, 0.f, 0.f, 0.f};
+  float J[4][6], S[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    S[k] = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 4; ch++) J[ch][k] = 0.f;
+  }
+
+  for (uint32_t base = 0u; base < wmax; base += JAC_CHUNK) {
+    // lane l < 32: did some pixel of this quadrant take list entry base + l?  (the forward's answer: no test of the entry here)
+    const uint32_t pos = base + (uint32_t)lane;
+    bool rel = false;
+    uint32_t id = 0u;
+    if (lane < JAC_CHUNK && pos < wmax) {
+      rel = ((taken[range.x + pos] >> (8 * wave)) & 0xffu) != 0u;
+      if (rel) id = min(point_list[range.x + pos], (uint32_t)(P - 1));  // (clamped: a stale list must not name a row outside the workspace)
+    }
+    const unsigned long long todo = __builtin_amdgcn_ballot_w64(rel);
+    const int nrel = __popcll(todo);
+    if (nrel == 0) continue;  // (wave-uniform)
+    if (rel) {
+      const int slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(todo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)todo, 0u));
+      float4 q0, q1, q2;
+      gsaj_load_row(splat, splat16, id, rec16, q0, q1, q2);
+      const float3 k = gsaj_prescale_conic(q1.x, q1.y, q1.z);
+      srow[slot * 3 + 0] = make_float4(q0.x, q0.y, k.x, k.y);
+      srow[slot * 3 + 1] = make_float4(k.z, q1.w, __uint_as_float(pos + 1u), 0.f);
+      srow[slot * 3 + 2] = make_float4(q2.x, q2.y, q2.z, q0.z);
+      sid[slot] = id;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // the derivative rows, gathered next to the splat rows: 12 float4 per entry, consecutive lanes take consecutive pieces
+    for (int i = lane; i < nrel * JROW_F4; i += 64) {
+      const int e = i / JROW_F4, part = i - e * JROW_F4;
+      drow[i] = rows[(size_t)sid[e] * JROW_F4 + part];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int s = 0; s < nrel; s++) {
+      const float4 a0 = srow[s * 3 + 0], a1 = srow[s * 3 + 1], c = srow[s * 3 + 2];
+      const float dx = a0.x - pxf, dy = a0.y - pyf;
+      // the forward's own expression (gsaj_common.h): power <= 0 / alpha >= 1/255 are decided on identical bits
+      const float p2 = gsaj_power2(dx, dy, a0.z, a0.w, a1.x);
+      const float oG = a1.y * __builtin_amdgcn_exp2f(p2);
+      const bool valid = __float_as_uint(a1.z) <= last && p2 <= 0.0f && oG >= (1.0f / 255.0f);
+      if (__builtin_amdgcn_ballot_w64(valid) == 0ull) continue;
+      // a pixel that skips the entry runs the same arithmetic with o G = 0: alpha = 0, dalpha = 0, nothing changes
+      const float oGm = valid ? oG : 0.f;
+      const float alpha = fminf(0.99f, oGm);
+      // d power = sum_j f_j d(sum j)/dtau with the reverse compositor's coefficients of w (render_bwd.hip, v[0..4]); dalpha = o G d power
+      const float ca = a0.z * (-2.0f / GSAJ_LOG2E), cb = a0.w * (-1.0f / GSAJ_LOG2E), cc = a1.x * (-2.0f / GSAJ_LOG2E);
+      const float f0 = oGm * (-(ca * dx + cb * dy) * half_w);
+      const float f1 = oGm * (-(cc * dy + cb * dx) * half_h);
+      const float f2 = oGm * (-0.5f * dx * dx);
+      const float f3 = oGm * (-0.5f * dx * dy);
+      const float f4 = oGm * (-0.5f * dy * dy);
+      const float *D = reinterpret_cast<const float *>(drow + s * JROW_F4);
+      const float w = alpha * T;  // the forward's weight, from the forward's operations
+      const float inv1ma = __builtin_amdgcn_rcpf(1.f - alpha);
+      float e[6];
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        const float da = f0 * D[k] + f1 * D[6 + k] + f2 * D[12 + k] + f3 * D[18 + k] + f4 * D[24 + k];
+        e[k] = T * (da - alpha * S[k]);
+        S[k] += da * inv1ma;
+      }
+      const float cv[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+      for (int ch = 0; ch < 4; ch++) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) J[ch][k] += cv[ch] * e[k];
+      }
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) J[ch][k] += w * D[36 + 3 * ch + k];
+      }
+#pragma unroll
+      for (int k = 0; k < 6; k++) J[3][k] += w * D[30 + k];
+#pragma unroll
+      for (int ch = 0; ch < 4; ch++) C[ch] = __builtin_fmaf(cv[ch], w, C[ch]);
+      T = __builtin_fmaf(-alpha, T, T);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+
+  // background: C += T_final bg, so J_ch -= bg[ch] T_final S_final (colour rows)
+  const float bgv[3] = {bg[0], bg[1], bg[2]};
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) {
+    const float tb = T * bgv[ch];
+#pragma unroll
+    for (int k = 0; k < 6; k++) J[ch][k] -= tb * S[k];
+  }
+  if (inside) {
+    if (jo.jac) {
+      float2 *o = reinterpret_cast<float2 *>(jo.jac + pid * 24);
+#pragma unroll
+      for (int ch = 0; ch < 4; ch++) {
+#pragma unroll
+        for (int k = 0; k < 6; k += 2) o[ch * 3 + k / 2] = make_float2(J[ch][k], J[ch][k + 1]);
+      }
+    }
+    if (jo.color) {
+      jo.color[pid] = __builtin_fmaf(T, bgv[0], C[0]);
+      jo.color[HW + pid] = __builtin_fmaf(T, bgv[1], C[1]);
+      jo.color[2 * HW + pid] = __builtin_fmaf(T, bgv[2], C[2]);
+    }
+    if (jo.depth) jo.depth[pid] = C[3];
+  }
+  if (!jo.partials) return;
+
+  // ---- this pixel's seeds and curvatures, its share of g = sum s J and H = sum h J^T J, and the loss terms ----
+  float sv[4] = {0.f, 0.f, 0.f, 0.f}, hv[4] = {0.f, 0.f, 0.f, 0.f};
+  float ls[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  bool want_h = true;
+  if (LOSS) {
+    if (inside) {
+      const LossConsts L = loss_consts(fl.flags, fl.alpha, fl.rgb_thr, fl.exp_a, fl.exp_b, HW, 1.f);
+      const bool mask = fl.grad_mask ? fl.grad_mask[pid] != 0 : true;
+      const float gd = L.mono ? 0.f : fl.gt_depth[pid], d = L.mono ? 0.f : fl.depth[pid];
+      const float g0 = fl.gt_color[pid], g1 = fl.gt_color[HW + pid], g2 = fl.gt_color[2 * HW + pid];
+      const float c0 = fl.color[pid], c1 = fl.color[HW + pid], c2 = fl.color[2 * HW + pid], op = fl.opacity[pid];
+      const LossPixel o = loss_pixel(L, g0, g1, g2, c0, c1, c2, op, mask, gd, d);
+      const LossGN q = loss_pixel_gn(L, o, g0, g1, g2, c0, c1, c2, op, mask, gd, d, jo.delta);
+#pragma unroll
+      for (int ch = 0; ch < 4; ch++) sv[ch] = q.s[ch], hv[ch] = q.h[ch];
+      // the pixel's share of loss = k_rgb sum w|r| + k_d sum |r_d| (loss_consts: k_rgb = (alpha | 1) / 3HW, k_d = (1 - alpha) / HW),
+      // of L_rgb and L_depth, and the two exposure sums of loss_pixel
+      ls[0] = L.k_rgb * o.s_rgb + L.k_d * o.s_d;
+      ls[1] = o.s_rgb / (3.f * (float)HW);
+      ls[2] = o.s_d / (float)HW;
+      ls[3] = o.s_a;
+      ls[4] = o.s_b;
+    }
+  } else {
+    want_h = jo.curv_c != nullptr;
+    if (inside) {
+      if (jo.seed_c) {
+        sv[0] = jo.seed_c[pid]; sv[1] = jo.seed_c[HW + pid]; sv[2] = jo.seed_c[2 * HW + pid]; sv[3] = jo.seed_d[pid];
+      }
+      if (want_h) {
+        hv[0] = jo.curv_c[pid]; hv[1] = jo.curv_c[HW + pid]; hv[2] = jo.curv_c[2 * HW + pid]; hv[3] = jo.curv_d[pid];
+      }
+    }
+  }
+  float *out = jo.partials + (size_t)blockIdx.x * GN_ROW;
+  int n = 0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+#pragma unroll
+    for (int l = k; l < 6; l++, n++) {
+      float v = 0.f;
+      if (want_h) {
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) v += (hv[ch] * J[ch][k]) * J[ch][l];
+        v = wave_sum(v);
+      }
+      if (lane == 0) out[n] = v;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    float v = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 4; ch++) v += sv[ch] * J[ch][k];
+    v = wave_sum(v);
+    if (lane == 0) out[21 + k] = v;
+  }
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    const float v = wave_sum(ls[k]);
+    if (lane == 0) out[27 + k] = v;
+  }
+}
+
+// ---- the partial rows summed in slot order, in fp64 ------------------------------------------------------------------------
+// GN_SUM_THREADS threads = GN_GROUPS row groups x 32 columns: thread (r, c) adds rows r, r + GN_GROUPS, ... of column c, four loads in
+// flight at a time and added in row order, then the groups are added in order.  (A frame of 640x480 has 4800 rows: eight groups
+// with one dependent load after the other took 158 us, as long as the compositor.)  sums: [GN_ROW] doubles in LDS, complete after
+// the call's barrier.
+#define GN_SUM_THREADS 1024
+#define GN_GROUPS (GN_SUM_THREADS / 32)
+__device__ __forceinline__ void gn_sum_rows(const float *__restrict__ partials, int n, double (*red)[GN_ROW], double *sums) {
+  const int c = threadIdx.x & 31, r = threadIdx.x >> 5;
+  double acc = 0.0;
+  for (int i0 = r; i0 < n; i0 += 4 * GN_GROUPS) {
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = i0 + u * GN_GROUPS;
+      v[u] = i < n ? partials[(size_t)i * GN_ROW + c] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) acc += (double)v[u];
+  }
+  red[r][c] = acc;
+  __syncthreads();
+  if (r == 0) {
+    double t = red[0][c];
+    for (int q = 1; q < GN_GROUPS; q++) t += red[q][c];
+    sums[c] = t;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_reduce(const float *__restrict__ partials, int n, const uint32_t *__restrict__ counters,
+                                                   float *__restrict__ H_out, float *__restrict__ g_out) {
+  __shared__ double red[GN_GROUPS][GN_ROW], sums[GN_ROW];
+  if (counters[4]) return;  // aborted async frame
+  gn_sum_rows(partials, n, red, sums);
+  const int t = threadIdx.x;
+  if (H_out && t < 21) H_out[t] = (float)sums[t];
+  if (g_out && t >= 21 && t < 27) g_out[t - 21] = (float)sums[t];
+}
+
+struct GnStepParams {
+  const float *partials;
+  int n;
+  float lambda_init, nu, lambda_min, lambda_max, threshold;
+  const float *projection;
+  float *st;
+  const uint32_t *skip;
+};
+
+// (H + lambda diag(H) + eps I) tau = -g by Cholesky in fp64; eps = 1e-9 x the mean diagonal of H + 1e-30 keeps a direction the
+// frame says nothing about (H row == 0) solvable.  Returns false on a non-positive (or non-finite) pivot.
+__device__ bool gn_solve(const float *Hs, const float *gs, double lambda, double *tau) {
+  double A[6][6], Lc[6][6], y[6];
+  int n = 0;
+  double tr = 0.0;
+  for (int k = 0; k < 6; k++)
+    for (int l = k; l < 6; l++, n++) A[k][l] = A[l][k] = (double)Hs[n];
+  for (int k = 0; k < 6; k++) tr += A[k][k];
+  const double eps = 1e-9 * (tr / 6.0) + 1e-30;
+  for (int k = 0; k < 6; k++) A[k][k] = A[k][k] + lambda * A[k][k] + eps;
+  for (int j = 0; j < 6; j++) {
+    double d = A[j][j];
+    for (int k = 0; k < j; k++) d -= Lc[j][k] * Lc[j][k];
+    if (!(d > 0.0) || !(d < 1e300)) return false;
+    const double ljj = sqrt(d);
+    Lc[j][j] = ljj;
+    for (int i = j + 1; i < 6; i++) {
+      double v = A[i][j];
+      for (int k = 0; k < j; k++) v -= Lc[i][k] * Lc[j][k];
+      Lc[i][j] = v / ljj;
+    }
+  }
+  for (int i = 0; i < 6; i++) {
+    double v = -(double)gs[i];
+    for (int k = 0; k < i; k++) v -= Lc[i][k] * y[k];
+    y[i] = v / Lc[i][i];
+  }
+  for (int i = 5; i >= 0; i--) {
+    double v = y[i];
+    for (int k = i + 1; k < 6; k++) v -= Lc[k][i] * tau[k];
+    tau[i] = v / Lc[i][i];
+  }
+  for (int i = 0; i < 6; i++)
+    if (!(fabs(tau[i]) < 1e300)) return false;
+  return true;
+}
+
+__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_step(GnStepParams p) {
+  __shared__ double red[GN_GROUPS][GN_ROW], sums[GN_ROW];
+  // the frame these rows belong to was aborted on the device (its kernels returned at once: the rows are the PREVIOUS iteration's)
+  if (p.skip && *p.skip != 0u) return;
+  gn_sum_rows(p.partials, p.n, red, sums);
+  if (threadIdx.x != 0) return;
+  float *st = p.st;
+  const float loss = (float)sums[27];
+  st[GN_LAST + 0] = loss;
+  st[GN_LAST + 1] = (float)sums[28];
+  st[GN_LAST + 2] = (float)sums[29];
+  const bool has = st[GN_HAS] != 0.f;
+  float lambda = has ? st[GN_LAMBDA] : p.lambda_init;
+  if (!has || loss <= st[GN_ACC_LOSS]) {  // accept the pose these rows were rendered at
+    st[GN_ACC_LOSS] = loss;
+    for (int i = 0; i < 16; i++) st[GN_ACC_W2C + i] = st[PS_W2C + i];
+    for (int i = 0; i < 21; i++) st[GN_H + i] = (float)sums[i];
+    for (int i = 0; i < 6; i++) st[GN_G + i] = (float)sums[21 + i];
+    lambda = fmaxf(lambda / p.nu, p.lambda_min);
+    st[GN_HAS] = 1.f;
+    st[GN_ACCEPTED] += 1.f;
+  } else {  // reject: back to the accepted pose and its normal equations, more damping
+    for (int i = 0; i < 16; i++) st[PS_W2C + i] = st[GN_ACC_W2C + i];
+    lambda = fminf(lambda * p.nu, p.lambda_max);
+    st[GN_REJECTED] += 1.f;
+  }
+  double tau64[6];
+  float delta[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const bool ok = gn_solve(st + GN_H, st + GN_G, (double)lambda, tau64);
+  if (ok) {
+    for (int i = 0; i < 6; i++) delta[i] = (float)tau64[i];
+  } else {
+    lambda = fminf(lambda * p.nu, p.lambda_max);  // no step from this factorisation: more damping next time
+  }
+  st[GN_LAMBDA] = lambda;
+  // Exp(tau) W2C, the camera matrices, tau, |tau|, converged (tau = 0 on a failed factorisation: the pose comes out unchanged)
+  pose_apply_delta(st, delta, p.projection, p.threshold);
+  if (!ok) st[PS_CONV] = 0.f;
+}
+
+// ---- launchers (api.hip) ------------------------------------------------------------------------------------------------------
+size_t gsaj_jac_rows_bytes(int P) { return gsaj_align(sizeof(float) * JROW_F * (size_t)(P > 0 ? P : 1)); }
+int gsaj_jac_slots(int W, int H) { return gsaj_fwd_loss_slots(W, H); }
+
+int launch_splat_jac(const BwdParams &p, const GeomWS &g, const ImageWS &im, float *rows, hipStream_t s) {
+  const int nblk = (p.P + 63) / 64;
+  hipLaunchKernelGGL(k_splat_jac, dim3(nblk), dim3(64), 0, s, p, g.clamped, im.counters, rows);
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}
+
+int launch_render_jac(int P, int W, int H, int grid_x, int grid_y, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im,
+                      const float *rows, float *jac_out, float *out_color, float *out_depth, const float *seed_c, const float *seed_d,
+                      const float *curv_c, const float *curv_d, float *partials, const FusedLoss *fl, float irls_delta, hipStream_t s) {
+  const int tiles = grid_x * grid_y;
+  const unsigned nblk = (unsigned)gsaj_jac_slots(W, H);
+  JacOut jo;
+  jo.jac = jac_out; jo.color = out_color; jo.depth = out_depth; jo.seed_c = seed_c; jo.seed_d = seed_d; jo.curv_c = curv_c;
+  jo.curv_d = curv_d; jo.partials = partials; jo.delta = irls_delta;
+  if (fl)
+    hipLaunchKernelGGL(k_render_jac<true>, dim3(nblk), dim3(64), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg, b.point_list, b.taken,
+                       reinterpret_cast<const float4 *>(rows), jo, *fl);
+  else
+    hipLaunchKernelGGL(k_render_jac<false>, dim3(nblk), dim3(64), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg, b.point_list, b.taken,
+                       reinterpret_cast<const float4 *>(rows), jo, FusedLoss{});
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}
+
+int launch_gn_reduce(const float *partials, int n, const ImageWS &im, float *H_out, float *g_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_gn_reduce, dim3(1), dim3(GN_SUM_THREADS), 0, s, partials, n, im.counters, H_out, g_out);
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}
+
+extern "C" int gsaj_gn_state_floats(void) { return GSAJ_GN_STATE_FLOATS; }
+
+extern "C" int gsaj_pose_gn_step(const float *gn_partials, int n_partials, float lambda_init, float nu, float lambda_min, float lambda_max,
+                                 float converged_threshold, const float *projection_matrix, float *gn_state, const uint32_t *skip,
+                                 void *stream) {
+  if (!gn_partials || n_partials <= 0 || !gn_state || !(nu > 1.f) || !(lambda_min > 0.f) || !(lambda_max >= lambda_min) ||
+      !(lambda_init >= lambda_min) || !(lambda_init <= lambda_max)) {
+    gsaj_set_error("gsaj_pose_gn_step: gn_partials, n_partials > 0 and gn_state are required; nu > 1, 0 < lambda_min <= lambda_init <= lambda_max");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  GnStepParams p;
+  p.partials = gn_partials; p.n = n_partials; p.lambda_init = lambda_init; p.nu = nu; p.lambda_min = lambda_min; p.lambda_max = lambda_max;
+  p.threshold = converged_threshold; p.projection = projection_matrix; p.st = gn_state; p.skip = skip;
+  hipLaunchKernelGGL(k_gn_step, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, p);
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}

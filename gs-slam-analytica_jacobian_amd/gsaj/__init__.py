@@ -1,0 +1,10 @@
+"""gsaj -- torch-tensor front end of libgsaj_hip.so.  Submodules are imported by name (gsaj.rasterizer, gsaj.tracking, ...);
+the package itself imports nothing, so that `from gsaj import synthetic` needs neither torch nor the library."""
+__all__ = ["GaussNewtonTracker"]
+
+
+def __getattr__(name):
+    if name == "GaussNewtonTracker":  # gsaj.GaussNewtonTracker: second-order tracking (gsaj.gauss_newton), loaded on first use
+        from .gauss_newton import GaussNewtonTracker
+        return GaussNewtonTracker
+    raise AttributeError("module 'gsaj' has no attribute %r" % name)

@@ -114,6 +114,15 @@ SIGNATURES = {
     "gsaj_map_step": (c_int, [c_int, c_int, c_int, c_int, P, P]),
     "gsaj_eval_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gsaj_eval_frame": (c_int, [c_int, c_int, c_int, c_int] + [P] * 7),
+    "gsaj_pose_jac_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gsaj_pose_jac_partial_rows": (c_int, [c_int, c_int]),
+    "gsaj_rasterize_pose_jacobian": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P, P,
+                                             c_float, c_float, P, P, P, P, P] + [P] * 5 + [P] * 4 + [P]),
+    "gsaj_rasterize_pose_jacobian_loss": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P, P,
+                                                  c_float, c_float, P, P, P, P, P, c_int, c_float, c_float, P, P, P, P, P, P, P, P,
+                                                  c_float, P, P, P]),
+    "gsaj_gn_state_floats": (c_int, []),
+    "gsaj_pose_gn_step": (c_int, [P, c_int] + [c_float] * 5 + [P, P, P, P]),
 }
 
 _lib = None

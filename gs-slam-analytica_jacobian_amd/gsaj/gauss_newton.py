@@ -1,0 +1,155 @@
+"""Second-order tracking of one frame on the device: Gauss-Newton / Levenberg-Marquardt on the pose, next to
+gsaj.tracking.DeviceTracker's first-order loop (DESIGN.md "Gauss-Newton tracking").
+
+One iteration is three C-ABI calls that touch no host state: asynchronous forward -> gsaj_rasterize_pose_jacobian_loss (the
+per-pixel pose Jacobian in forward mode and, fused, the 6x6 normal equations H = sum h J^T J, g = sum s J of the tracking loss
+with the L1 terms as iteratively reweighted least squares) -> gsaj_pose_gn_step (accept / reject against the last accepted loss,
+damping, a 6x6 Cholesky solve, W2C <- Exp(tau) W2C and the camera matrices of the next render).  An iteration renders at the pose
+the previous one proposed; whether that pose is kept is decided by the NEXT step, from the loss rendered there.  Exposure enters as
+the fixed affine e^a C + b; only tau is solved for.  No graph capture and no process group.
+
+An asynchronous frame that does not fit its arena is aborted on the device: its kernels return at once and the step, handed the
+frame's abort word, changes nothing; iterate() raises when it is done, exactly as DeviceTracker.iterate does."""
+import torch
+
+from . import _lib
+from .grad_mask import GradMask
+from .losses import MONOCULAR, TRACKING
+from .rasterizer import FrameContext, unpack_sym6
+
+# gn_state (include/gsaj.h): [0:80) the pose-state layout, then the Levenberg-Marquardt fields
+_O = dict(w2c=(0, 16), exposure=(33, 35), view=(35, 51), proj=(51, 67), campos=(67, 70), tau=(70, 76), norm=(76, 77), conv=(77, 78),
+          lam=(80, 81), acc_loss=(81, 82), has=(82, 83), accepted=(83, 84), rejected=(84, 85), last=(85, 88), acc_w2c=(88, 104),
+          H=(104, 125), g=(125, 131))
+
+
+class GaussNewtonTracker:
+    def __init__(self, P, W, H, M, device, w2c, projection_matrix, tanfovx, tanfovy, bg, means3D, opacities, sh_degree=0, shs=None,
+                 colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, monocular=False, alpha=0.95,
+                 rgb_boundary_threshold=0.01, record_bits=32, irls_delta=0.01, lambda_init=1e-3, nu=4.0, lambda_min=1e-7,
+                 lambda_max=1e7, converged_threshold=1e-4):
+        """The Gaussians (device tensors) are those of the current map: the loop reads them, it never writes them.  irls_delta: the
+        residual below which an L1 term is treated as a quadratic (0: pure IRLS weights 1 / |r|).  lambda_init / nu / lambda_min /
+        lambda_max: the damping and its factor; converged_threshold: |tau| below which the device reports convergence."""
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise _lib.GsajError("GaussNewtonTracker needs a HIP device (there is no CPU path)")
+        self.lib = _lib.load()
+        self.ctx = FrameContext(P, W, H, M, self.dev, has_scales=scales is not None, record_bits=record_bits)
+        self.state = torch.zeros(self.lib.gsaj_gn_state_floats(), dtype=torch.float32, device=self.dev)
+        self.projection = torch.as_tensor(projection_matrix, dtype=torch.float32).reshape(4, 4).contiguous().to(self.dev)
+        self.praw = self.projection
+        self.tanfov = (float(tanfovx), float(tanfovy))
+        self.flags = TRACKING | (MONOCULAR if monocular else 0)
+        self.alpha, self.thr = float(alpha), float(rgb_boundary_threshold)
+        self.delta = float(irls_delta)
+        self.lm_args = (float(lambda_init), float(nu), float(lambda_min), float(lambda_max), float(converged_threshold))
+        self.bg, self.means, self.opac = bg, means3D, opacities
+        self.kw = dict(sh_degree=sh_degree, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
+                       cov3D_precomp=cov3D_precomp)
+        self._abort_ptr = self.ctx.abort_flag_ptr()
+        self.gt_color = self.gt_depth = self.grad_mask = None
+        self._grad_op = None
+        self.iterations = 0
+        self.reset(w2c)
+
+    def reset(self, w2c, exposure=(0.0, 0.0)):
+        """A new frame: pose, no accepted step, lambda back to lambda_init -- in place."""
+        s = self.state
+        s.zero_()
+        s[0:16] = torch.as_tensor(w2c, dtype=torch.float32).reshape(16).to(self.dev)
+        s[33] = float(exposure[0])
+        s[34] = float(exposure[1])
+        w = s[0:16].view(4, 4)
+        s[35:51] = w.t().reshape(16)
+        s[51:67] = (w.t() @ self.projection).reshape(16)
+        s[67:70] = -(torch.linalg.inv(w[:3, :3].double().cpu()) @ w[:3, 3].double().cpu()).float().to(self.dev)
+        s[80] = self.lm_args[0]
+        s[88:104] = s[0:16]
+
+    def _v(self, name, shape=None):
+        a, b = _O[name]
+        t = self.state[a:b]
+        return t.view(*shape) if shape else t
+
+    w2c = property(lambda s: s._v("w2c", (4, 4)))
+    viewmatrix = property(lambda s: s._v("view", (4, 4)))
+    projmatrix = property(lambda s: s._v("proj", (4, 4)))
+    campos = property(lambda s: s._v("campos"))
+    exposure_a = property(lambda s: s.state[33:34])
+    exposure_b = property(lambda s: s.state[34:35])
+    tau = property(lambda s: s._v("tau"))
+    converged = property(lambda s: s.state[77])
+    accepted_w2c = property(lambda s: s._v("acc_w2c", (4, 4)))
+
+    @property
+    def loss_terms(self):
+        """[loss, L_rgb, L_depth] of the last iteration's render (device)."""
+        return self._v("last")
+
+    @property
+    def lm(self):
+        """dict(lam, accepted, rejected, accepted_loss: device scalars; H [6,6], g [6]: the accepted normal equations)."""
+        return dict(lam=self.state[80], accepted=self.state[83], rejected=self.state[84], accepted_loss=self.state[81],
+                    H=unpack_sym6(self._v("H")), g=self._v("g"))
+
+    def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2c=None, edge_threshold=None, grad_blocks=False):
+        """New frame: ground truth (device, [3,H,W] / [H,W]; grad_mask [1,H,W] or None) and optionally a new initial pose; copied into
+        buffers the tracker owns.  edge_threshold (with grad_mask None): the tracker computes the frame's gradient mask itself
+        (gsaj.grad_mask) from its own copy of gt_color.  A mask, given or computed, is there for every frame of a tracker or for none."""
+        masked = grad_mask is not None or edge_threshold is not None
+        if self.gt_color is None:
+            self.gt_color = gt_color.to(self.dev, torch.float32).contiguous().clone()
+            self.gt_depth = None if gt_depth is None else gt_depth.to(self.dev, torch.float32).contiguous().clone()
+            if grad_mask is not None:
+                self.grad_mask = grad_mask.to(self.dev, torch.uint8).contiguous().view(-1).clone()
+            elif masked:
+                self.grad_mask = torch.empty(self.gt_color[0].numel(), dtype=torch.uint8, device=self.dev)
+        else:
+            if (gt_depth is None) != (self.gt_depth is None) or masked != (self.grad_mask is not None):
+                raise _lib.GsajError("set_frame: depth / mask must be given for every frame of a tracker or for none")
+            self.gt_color.copy_(gt_color)
+            if gt_depth is not None:
+                self.gt_depth.copy_(gt_depth)
+            if grad_mask is not None:
+                self.grad_mask.copy_(grad_mask.to(self.dev, torch.uint8).view(-1))
+        if grad_mask is None and masked:
+            if self._grad_op is None:
+                _, H, W = self.gt_color.shape
+                self._grad_op = GradMask(W, H, self.dev)
+            self._grad_op(self.gt_color, edge_threshold, blocks=grad_blocks, out=self.grad_mask)
+        if w2c is not None:
+            self.reset(w2c)
+
+    def _iteration(self, sync):
+        c = self.ctx
+        c.forward(self.bg, self.means, self.opac, self.viewmatrix, self.projmatrix, self.campos, self.tanfov[0], self.tanfov[1], sync=sync,
+                  **self.kw)
+        L = dict(flags=self.flags, alpha=self.alpha, rgb_boundary_threshold=self.thr, gt_color=self.gt_color, gt_depth=self.gt_depth,
+                 grad_mask=self.grad_mask, exposure_a=self.exposure_a, exposure_b=self.exposure_b)
+        o = c.pose_jacobian_loss(L, self.bg, self.means, self.viewmatrix, self.projmatrix, self.praw, self.campos, self.tanfov[0],
+                                 self.tanfov[1], irls_delta=self.delta, **self.kw)
+        _lib.check(self.lib.gsaj_pose_gn_step(o["partials"].data_ptr(), o["partials"].shape[0], *self.lm_args, self.projection.data_ptr(),
+                                              self.state.data_ptr(), self._abort_ptr, torch.cuda.current_stream(self.dev).cuda_stream),
+                   "gsaj_pose_gn_step")
+
+    def iterate(self, n, check_every=0):
+        """Up to n iterations; check_every > 0: stop once the device reports |tau| < converged_threshold, looked at every check_every
+        iterations.  Returns the number run.  Raises GsajError after the loop if an asynchronous frame was aborted on the device
+        (those iterations changed nothing); the next call re-sizes the arena with one synchronous iteration."""
+        if self.gt_color is None:
+            raise _lib.GsajError("set_frame() first")
+        done = 0
+        with torch.cuda.device(self.dev):
+            while done < n:
+                self._iteration(self.ctx.capacity == 0)  # the very first iteration sizes the binning arena: synchronous forward
+                done += 1
+                if check_every and done % check_every == 0 and bool(self.converged.item() != 0.0):
+                    break
+        self.iterations += done
+        try:
+            self.ctx.status()
+        except _lib.GsajError:
+            self.ctx.capacity = 0
+            raise
+        return done

@@ -46,6 +46,18 @@ def _require_cuda(t, what):
         raise RuntimeError("%s must live on the GPU (HIP device): libgsaj_hip has no CPU path" % what)
 
 
+_SYM6 = [(k, l) for k in range(6) for l in range(k, 6)]  # the 21 stored elements of a symmetric 6x6: upper triangle by rows
+
+
+def unpack_sym6(h21):
+    """[..., 21] (upper triangle by rows, as the normal-equation kernels store H) -> symmetric [..., 6, 6]."""
+    out = h21.new_zeros(tuple(h21.shape[:-1]) + (6, 6))
+    for n, (k, l) in enumerate(_SYM6):
+        out[..., k, l] = h21[..., n]
+        out[..., l, k] = h21[..., n]
+    return out
+
+
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, projmatrix_raw, tan_fovx, tan_fovy, image_height, image_width, sh,
                         degree, campos, prefiltered, debug, record_bits=32):
@@ -529,6 +541,75 @@ class FrameContext:
                 _ptr(g["rot"])]), _ptr(g["tau"]), g["tau_sum"].data_ptr(), _stream(self.dev)),
             "gsaj_rasterize_backward")
         return g
+
+    # ---- per-pixel pose Jacobians and normal equations (gsaj_rasterize_pose_jacobian / _loss; DESIGN "Gauss-Newton tracking") ----
+    def _jac_ready(self, what):
+        if self.dev.type != "cuda":
+            raise _lib.GsajError("%s needs a HIP device (there is no CPU path)" % what)
+        if self.binning.numel() == 0:
+            raise _lib.GsajError("%s: run a forward of this context first (it walks the finished forward's state)" % what)
+        band = getattr(self, "band", None)
+        if band is not None and band != (0, (self.H + 15) // 16):
+            raise _lib.GsajError("%s: a tile band is set on this context (band sharding of the Jacobian is not supported)" % what)
+        if not hasattr(self, "jac_ws"):
+            byte = dict(device=self.dev, dtype=torch.uint8)
+            self.jac_ws = torch.empty(self.lib.gsaj_pose_jac_workspace_bytes(self.P, self.W, self.H), **byte)
+            self.gn_rows = self.lib.gsaj_pose_jac_partial_rows(self.W, self.H)
+
+    def pose_jacobian(self, bg, means3D, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, seeds=None, curvature=None,
+                      want_jacobian=False, want_images=False, sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None,
+                      cov3D_precomp=None, scale_modifier=1.0):
+        """The per-pixel pose Jacobian d(colour, depth)/dtau of the last forward of this context and, from it, the normal equations
+        of a weighted least-squares problem.  seeds = (s_color [3,H,W], s_depth [1,H,W] or [H,W]): g = sum s J; curvature = (h_color,
+        h_depth), same shapes: H = sum h J^T J.  -> dict(H [6,6] or None, g [6] or None, jacobian [H,W,4,6] or None; with
+        want_images also color [3,H,W], depth [1,H,W] as the walk re-derives them: the forward's bits).  Tensors are new each call."""
+        self._jac_ready("pose_jacobian")
+        f = dict(device=self.dev, dtype=_F32)
+        jac = torch.empty((self.H, self.W, 4, 6), **f) if want_jacobian else None
+        col = torch.empty((3, self.H, self.W), **f) if want_images else None
+        dep = torch.empty((1, self.H, self.W), **f) if want_images else None
+        H21 = torch.zeros(21, **f) if curvature is not None else None
+        g6 = torch.zeros(6, **f) if seeds is not None else None
+        sc, sd = (None, None) if seeds is None else [_prep(t, self.dev, "seeds") for t in seeds]
+        cc, cd = (None, None) if curvature is None else [_prep(t, self.dev, "curvature") for t in curvature]
+        with torch.cuda.device(self.dev):
+            _lib.check(self.lib.gsaj_rasterize_pose_jacobian(
+                self.P, int(sh_degree), self.M, self.R, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
+                _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix),
+                _ptr(projmatrix_raw), _ptr(campos), float(tanfovx), float(tanfovy), self.radii.data_ptr(), self.geom.data_ptr(),
+                self.binning.data_ptr(), self.img.data_ptr(), self.jac_ws.data_ptr(), _ptr(jac), _ptr(col), _ptr(dep), _ptr(H21), _ptr(g6),
+                _ptr(sc), _ptr(sd), _ptr(cc), _ptr(cd), _stream(self.dev)), "gsaj_rasterize_pose_jacobian")
+        out = dict(H=None if H21 is None else unpack_sym6(H21), g=g6, jacobian=jac)
+        if want_images:
+            out.update(color=col, depth=dep)
+        return out
+
+    def pose_jacobian_loss(self, loss, bg, means3D, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, irls_delta=0.0,
+                           partials=None, want_jacobian=False, sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None,
+                           cov3D_precomp=None, scale_modifier=1.0):
+        """The fused form: seeds and curvatures of the tracking loss (`loss`: the dict of forward_loss / backward_loss) derived per
+        pixel from this context's color / depth / opacity, with IRLS delta.  Fills `partials` (float32 [gn_rows, 32], made on the
+        first call if None: one fixed-slot row per workgroup -- H (21), g (6), loss, L_rgb, L_depth, two exposure sums) for
+        gsaj_pose_gn_step.  -> dict(partials, jacobian or None)."""
+        self._jac_ready("pose_jacobian_loss")
+        if partials is None:
+            if not hasattr(self, "gn_partials"):
+                self.gn_partials = torch.zeros((self.gn_rows, 32), device=self.dev, dtype=_F32)
+            partials = self.gn_partials
+        if tuple(partials.shape) != (self.gn_rows, 32) or partials.dtype != _F32 or not partials.is_contiguous() or partials.device != self.dev:
+            raise _lib.GsajError("pose_jacobian_loss: partials must be a contiguous float32 [%d, 32] tensor on %s" % (self.gn_rows, self.dev))
+        jac = torch.empty((self.H, self.W, 4, 6), device=self.dev, dtype=_F32) if want_jacobian else None
+        with torch.cuda.device(self.dev):
+            _lib.check(self.lib.gsaj_rasterize_pose_jacobian_loss(
+                self.P, int(sh_degree), self.M, self.R, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
+                _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix),
+                _ptr(projmatrix_raw), _ptr(campos), float(tanfovx), float(tanfovy), self.radii.data_ptr(), self.geom.data_ptr(),
+                self.binning.data_ptr(), self.img.data_ptr(), self.jac_ws.data_ptr(), int(loss["flags"]), float(loss["alpha"]),
+                float(loss["rgb_boundary_threshold"]), self.color.data_ptr(), self.depth.data_ptr(), self.opacity.data_ptr(),
+                _ptr(loss["gt_color"]), _ptr(loss.get("gt_depth")), _ptr(loss.get("grad_mask")), _ptr(loss.get("exposure_a")),
+                _ptr(loss.get("exposure_b")), float(irls_delta), partials.data_ptr(), _ptr(jac), _stream(self.dev)),
+                "gsaj_rasterize_pose_jacobian_loss")
+        return dict(partials=partials, jacobian=jac)
 
     def interactions(self):
         """sum over pixels of n_contrib = Gaussian-pixel interactions of the last forward."""

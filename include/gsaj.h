@@ -462,6 +462,71 @@ int gsaj_pose_adam_step_batch(int K, const float *dL_dtau, const float *dL_dexpo
                               float converged_threshold, const float *projection_matrix, float *pose_states, const uint32_t *skip,
                               size_t skip_stride_bytes, void *stream);
 
+/* ---- Gauss-Newton tracking: per-pixel pose Jacobians, normal equations, Levenberg-Marquardt step -----------------
+ * tau = [rho(3), theta(3)] is the left increment W2C <- Exp(tau) W2C.  The pose Jacobian of a pixel, J_p [4,6] (rows r, g, b,
+ * depth of what gsaj_rasterize_forward writes), is the exact transpose of the map the backward implements: for any seed images
+ * s, sum_p sum_ch s[ch,p] J_p[ch,:] == dL_dtau_sum of gsaj_rasterize_backward(seeds = s) in real arithmetic -- the 0.99 alpha cap
+ * is no gradient gate, power > 0 / alpha < 1/255 entries and entries behind a pixel's last contributor add nothing, the
+ * background term -T_final S bg is included, radii and tile rectangles are constants.
+ *
+ * Both entry points take the geometry arguments of gsaj_rasterize_backward and the geom / binning / image workspaces of a
+ * FINISHED forward of the same frame (synchronous, asynchronous or loss-fused; R = what the backward would be given; a tile band
+ * is not supported), and a scratch workspace jac_ws of gsaj_pose_jac_workspace_bytes(P, W, H) bytes (no initialisation needed).
+ * No float atomics: results are the same bits run to run.  An aborted asynchronous frame leaves every output as it was.
+ *
+ * gsaj_rasterize_pose_jacobian -- the explicit form.  Outputs, each may be NULL: jac_out [H,W,4,6]; out_color [3,H,W] and
+ *   out_depth [H,W], the images re-derived by the walk (the forward's bits); g_out [6] = sum s J from the seed images seed_color
+ *   [3,H,W], seed_depth [H,W]; H_out [21] = the upper triangle, by rows, of sum h J^T J from the curvature images curv_color
+ *   [3,H,W], curv_depth [H,W].  g_out needs both seed images, H_out both curvature images (GSAJ_ERR_INVALID_ARGUMENT otherwise,
+ *   and for the argument errors of gsaj_rasterize_backward).
+ * gsaj_rasterize_pose_jacobian_loss -- the fused form, for the tracking loss of gsaj_rasterize_backward_loss (same loss arguments;
+ *   exposure enters as the fixed affine e^a C + b, it is not solved for).  With the residuals r of csrc/loss_terms.h, kappa_rgb =
+ *   k_rgb w_rgb, kappa_d = k_d and irls_delta >= 0 (iteratively reweighted least squares for the L1 terms):
+ *     seed s = kappa (dr/dC) clamp(r / delta, -1, 1)   (delta == 0: the backward's own seed, bit for bit)
+ *     curvature h = kappa (dr/dC)^2 / max(|r|, delta)  (0 where the gate is closed, or r == 0 with delta == 0)
+ *   gn_partials [gsaj_pose_jac_partial_rows(W, H)][GSAJ_GN_PARTIAL_FLOATS]: one row per workgroup, fixed slots --
+ *   [0:21) H, [21:27) g, [27] loss, [28] L_rgb, [29] L_depth, [30:32) the exposure sums of the fused forward -- which
+ *   gsaj_pose_gn_step (or any reader) adds up in slot order.  jac_out may be NULL.
+ *
+ * gsaj_pose_gn_step -- one Levenberg-Marquardt step on the device, one launch, no host read.  gn_state: GSAJ_GN_STATE_FLOATS
+ *   floats owned by the caller; [0:80) have the layout of the pose state above (W2C, exposure at 33 / 34, the camera matrices,
+ *   tau, |tau|, converged; the Adam slots are unused), then
+ *     [80] lambda   [81] accepted loss   [82] 1.0 once a pose has been accepted   [83] accepted steps   [84] rejected steps
+ *     [85:88) loss, L_rgb, L_depth of the last call   [88:104) accepted W2C   [104:125) accepted H   [125:131) accepted g
+ *   Initialise [0:16) with the pose (and [33:35) with the exposure) and zero the rest.  The call sums the rows; on the first
+ *   call, or if loss <= accepted loss, it accepts -- saves (loss, W2C, H, g), lambda <- max(lambda / nu, lambda_min), lambda
+ *   starting from lambda_init -- otherwise it rejects: restores the accepted W2C, H, g, lambda <- min(lambda nu, lambda_max).
+ *   Then (H + lambda diag(H) + eps I) tau = -g is solved by Cholesky in fp64 (eps = 1e-9 x the mean of diag(H) + 1e-30) and
+ *   W2C <- Exp(tau) W2C is applied with the operations of gsaj_pose_adam_step, the camera matrices are refreshed, tau, |tau| and
+ *   converged = |tau| < converged_threshold written.  A non-positive pivot raises lambda and leaves the pose unchanged for the
+ *   call (tau = 0, converged = 0).  skip: as in gsaj_pose_adam_step -- a non-zero word (aborted frame) changes nothing.
+ *   GSAJ_ERR_INVALID_ARGUMENT unless nu > 1 and 0 < lambda_min <= lambda_init <= lambda_max. */
+#define GSAJ_GN_PARTIAL_FLOATS 32
+#define GSAJ_GN_STATE_FLOATS 136
+size_t gsaj_pose_jac_workspace_bytes(int P, int W, int H);
+int gsaj_pose_jac_partial_rows(int W, int H);
+int gsaj_rasterize_pose_jacobian(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D, const float *shs,
+                                 const float *colors_precomp, const float *scales, float scale_modifier, const float *rotations,
+                                 const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix,
+                                 const float *projmatrix_raw, const float *campos, float tanfovx, float tanfovy, const int *radii,
+                                 void *geom_ws, void *binning_ws, void *image_ws, void *jac_ws, float *jac_out /*NULL ok*/,
+                                 float *out_color /*NULL ok*/, float *out_depth /*NULL ok*/, float *H_out /*[21] NULL ok*/,
+                                 float *g_out /*[6] NULL ok*/, const float *seed_color, const float *seed_depth,
+                                 const float *curv_color, const float *curv_depth, void *stream);
+int gsaj_rasterize_pose_jacobian_loss(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
+                                      const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                      const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
+                                      const float *projmatrix, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                      float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
+                                      void *jac_ws, int loss_flags, float alpha, float rgb_boundary_threshold, const float *color,
+                                      const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
+                                      const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, float irls_delta,
+                                      float *gn_partials, float *jac_out /*NULL ok*/, void *stream);
+int gsaj_gn_state_floats(void);
+int gsaj_pose_gn_step(const float *gn_partials, int n_partials, float lambda_init, float nu, float lambda_min, float lambda_max,
+                      float converged_threshold, const float *projection_matrix, float *gn_state, const uint32_t *skip,
+                      void *stream);
+
 /* ---- distCUDA2 -------------------------------------------------------------------
  * simple_knn._C.distCUDA2 (reference submodules/simple-knn/simple_knn.cu:45-220, spatial.cu): for P points
  * [P,3] the mean of the squared distances to the 3 nearest other points -> mean_dists [P].  Exact search;

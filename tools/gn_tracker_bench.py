@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Second-order against first-order tracking (gsaj.gauss_newton.GaussNewtonTracker against gsaj.tracking.DeviceTracker, whose code
+this change leaves as it is): ms per iteration (device events, median of `repeats` windows after a warm-up) and the iteration --
+and the time -- at which each first meets tests/test_gpu_track_and_map.py's criterion (translation error below 0.35 x its starting
+value and rotation error below 0.02), on that test's 160x120 scene (three consecutive frames, each started from the previous
+frame's true pose) and on the cfg2 frame (640x480, 50 000 Gaussians, started 1.2 cm / 0.3 degrees off).
+
+Finding the first iteration that meets the criterion reads the pose back after every iteration; the timings are taken in separate,
+unobserved windows.  usage: gn_tracker_bench.py [out.json] [window=50] [repeats=7]"""
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gs-slam-analytica_jacobian_amd"))
+import torch  # noqa: E402
+from gsaj import synthetic as syn  # noqa: E402
+from gsaj.gauss_newton import GaussNewtonTracker  # noqa: E402
+from gsaj.rasterizer import FrameContext  # noqa: E402
+from gsaj.tracking import DeviceTracker  # noqa: E402
+
+DEV = torch.device("cuda:0")
+T = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device=DEV)  # noqa: E731
+ADAM = dict(lr_rot=0.003, lr_trans=0.002)   # the learning rates of tests/test_gpu_track_and_map.py
+
+
+def errors(w2c, true):
+    w2c = np.asarray(w2c, np.float64)
+    return float(np.abs(w2c[:3, 3] - true[:3, 3]).max()), float(np.abs(w2c[:3, :3] @ true[:3, :3].T - np.eye(3)).max())
+
+
+def first_hit(tr, pose, true, before, budget):
+    """The iteration at which the criterion first holds for `pose()` (None: not within the budget), the trace of the translation
+    error over its starting value through the whole budget, and the rotation error at its end."""
+    trace, hit, rot = [], None, 0.0
+    for it in range(1, budget + 1):
+        tr.iterate(1)
+        after, rot = errors(pose().cpu().numpy(), true)
+        trace.append(round(after / before, 4))
+        if hit is None and after < 0.35 * before and rot < 0.02:
+            hit = it
+    return hit, trace, rot
+
+
+def ms_per_iteration(tr, reset, window, repeats):
+    reset()
+    tr.iterate(10)  # warm-up: code objects, the arena
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    out = []
+    for _ in range(repeats):
+        reset()
+        tr.iterate(1)
+        ev[0].record()
+        tr.iterate(window)
+        ev[1].record()
+        torch.cuda.synchronize()
+        out.append(ev[0].elapsed_time(ev[1]) / window)
+    return float(np.median(out)), float(min(out)), float(max(out))
+
+
+def case(name, cam_true, w2c_start, sc, gt, window, repeats, budgets=(100, 30), gn_kw=None):
+    P, W, H, M = sc["means3D"].shape[0], cam_true["W"], cam_true["H"], sc["shs"].shape[1]
+    g = dict(means3D=T(sc["means3D"]), opacities=T(sc["opacities"]), shs=T(sc["shs"]), scales=T(sc["scales"]), rotations=T(sc["rotations"]),
+             sh_degree=3)
+    bg = torch.zeros(3, device=DEV)
+    true = np.ascontiguousarray(cam_true["viewmatrix"].T).astype(np.float64)
+    before = errors(w2c_start, true)[0]
+    args = (P, W, H, M, DEV, w2c_start, T(cam_true["projmatrix_raw"]), cam_true["tanfovx"], cam_true["tanfovy"], bg)
+    adam = DeviceTracker(*args, alpha=0.9, **ADAM, **g)
+    gnt = GaussNewtonTracker(*args, alpha=0.9, **(gn_kw or {}), **g)
+    out = dict(workload=name, P=P, W=W, H=H, start_translation_error=before)
+    for key, tr, pose, budget in (("adam", adam, lambda: adam.w2c, budgets[0]), ("gauss_newton", gnt, lambda: gnt.accepted_w2c, budgets[1])):
+        reset = lambda tr=tr: tr.set_frame(gt[0], gt[1], w2c=w2c_start)  # noqa: E731
+        reset()
+        hit, trace, rot = first_hit(tr, pose, true, before, budget)
+        lm = {k: float(v) for k, v in tr.lm.items() if k in ("lam", "accepted", "rejected")} if key == "gauss_newton" else {}
+        med, lo, hi = ms_per_iteration(tr, reset, window, repeats)
+        out[key] = dict(iterations_to_criterion=hit, ms_per_iteration=round(med, 4), ms_min=round(lo, 4), ms_max=round(hi, 4),
+                        ms_to_criterion=None if hit is None else round(hit * med, 3), budget=budget, error_ratio_at_budget=trace[-1],
+                        lowest_error_ratio=min(trace), rotation_error_at_budget=round(rot, 6), error_ratio_trace=trace)
+        out[key].update(lm)   # (the damping and the counters at the end of the budget)
+    return out
+
+
+def main():
+    path = sys.argv[1] if len(sys.argv) > 1 else None
+    window = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+    repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    res = []
+    # the scene of tests/test_gpu_track_and_map.py: frame k started from frame k - 1's true pose
+    W, H, F = 160, 120, 140.0
+    cams = syn.keyframe_cameras(4, radius=0.25, W=W, H=H, fx=F, fy=F, cx=W / 2 - 0.5, cy=H / 2 - 0.5)
+    sc = syn.make_scene(3000, 21, cams[2], z_range=(1.0, 4.0), log_scale_range=(math.log(0.02), math.log(0.1)))
+    fc = FrameContext(3000, W, H, 16, DEV)
+    g = [T(sc[k]) for k in ("means3D", "opacities", "shs", "scales", "rotations")]
+    bg = torch.zeros(3, device=DEV)
+
+    def render(fc, c, g):
+        fc.forward(bg, g[0], g[1], T(c["viewmatrix"]), T(c["projmatrix"]), T(c["campos"]), c["tanfovx"], c["tanfovy"], sh_degree=3, shs=g[2],
+                   scales=g[3], rotations=g[4])
+        return fc.color.clone(), fc.depth[0].clone()
+
+    for k in range(1, 4):
+        res.append(case("160x120, 3000 Gaussians, frame %d from frame %d's pose" % (k, k - 1), cams[k],
+                        np.ascontiguousarray(cams[k - 1]["viewmatrix"].T), sc, render(fc, cams[k], g), window, repeats))
+    cam2, sc2 = syn.config_scene("cfg2")
+    fc2 = FrameContext(sc2["means3D"].shape[0], cam2["W"], cam2["H"], 16, DEV)
+    g2 = [T(sc2[k]) for k in ("means3D", "opacities", "shs", "scales", "rotations")]
+    start = np.ascontiguousarray(cam2["viewmatrix"].T).astype(np.float64)
+    a = math.radians(0.3)
+    d = np.eye(4)
+    d[:3, :3] = np.array([[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
+    d[:3, 3] = [0.012, -0.008, 0.01]
+    res.append(case("cfg2 (640x480, 50 000 Gaussians)", cam2, (d @ start).astype(np.float32), sc2, render(fc2, cam2, g2), window, repeats))
+    text = json.dumps(dict(device=torch.cuda.get_device_name(0), window=window, repeats=repeats, cases=res), indent=1)
+    print(text)
+    if path:
+        with open(path, "w") as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
