@@ -95,7 +95,7 @@ int gsaj_profile_end(float *stage_ms, int *stage_launches) {
 }
 
 const char *gsaj_last_error(void) { return g_err; }
-int gsaj_version(void) { return 107; }
+int gsaj_version(void) { return 108; }
 
 size_t gsaj_geom_workspace_bytes(int P) { return geom_carve(nullptr, (size_t)(P > 0 ? P : 0), nullptr) + 256; }
 size_t gsaj_image_workspace_bytes(int W, int H) { return image_carve(nullptr, W, H, nullptr) + 256; }
@@ -705,7 +705,7 @@ static int pose_jac_impl(const char *who, int P, int D, int M, int R, const floa
                          float tanfovx, float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws, void *jac_ws,
                          float *jac_out, float *out_color, float *out_depth, float *H_out, float *g_out, const float *seed_color,
                          const float *seed_depth, const float *curv_color, const float *curv_depth, float *gn_partials,
-                         const FusedLoss *fl, float irls_delta, void *stream) {
+                         const FusedLoss *fl, float irls_delta, void *stream, bool joint = false) {
   if (P <= 0 || R < 0 || W <= 0 || H <= 0 || !bg || !means3D || !viewmatrix || !projmatrix || !projmatrix_raw || !geom_ws ||
       !binning_ws || !image_ws || !jac_ws || (shs && !campos) || (scales && !rotations) || (!scales && !cov3D_precomp)) {
     gsaj_set_error("%s: invalid argument", who);
@@ -740,7 +740,7 @@ static int pose_jac_impl(const char *who, int P, int D, int M, int R, const floa
   const bool sums = fl || H_out || g_out;
   float *partials = fl ? gn_partials : (sums ? ws_partials : nullptr);
   rc = launch_render_jac(P, W, H, gx, gy, bg, g, b, im, rows, jac_out, out_color, out_depth, g_out ? seed_color : nullptr,
-                         g_out ? seed_depth : nullptr, H_out ? curv_color : nullptr, H_out ? curv_depth : nullptr, partials, fl, irls_delta, s);
+                         g_out ? seed_depth : nullptr, H_out ? curv_color : nullptr, H_out ? curv_depth : nullptr, partials, fl, irls_delta, joint ? 1 : 0, s);
   if (rc != GSAJ_OK || fl || !sums) return rc;
   return launch_gn_reduce(partials, gsaj_jac_slots(W, H), im, H_out, g_out, s);
 }
@@ -758,6 +758,33 @@ int gsaj_rasterize_pose_jacobian(int P, int D, int M, int R, const float *bg, in
                        out_color, out_depth, H_out, g_out, seed_color, seed_depth, curv_color, curv_depth, nullptr, nullptr, 0.f, stream);
 }
 
+static int pose_jac_loss_impl(const char *who, bool joint, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
+                              const float *shs, const float *scales, float scale_modifier, const float *rotations,
+                              const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, const float *projmatrix_raw,
+                              const float *campos, float tanfovx, float tanfovy, const int *radii, void *geom_ws, void *binning_ws,
+                              void *image_ws, void *jac_ws, int loss_flags, float alpha, float rgb_boundary_threshold, const float *color,
+                              const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
+                              const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, float irls_delta,
+                              float *gn_partials, float *jac_out, void *stream) {
+  int rc = fused_loss_args(who, loss_flags, gt_color, gt_depth, exposure_a, exposure_b);
+  if (rc != GSAJ_OK) return rc;
+  if (joint && ((loss_flags & GSAJ_LOSS_NO_EXPOSURE) || !exposure_a || !exposure_b)) {
+    gsaj_set_error("%s: the joint form solves for the exposure: exposure_a / exposure_b are required, GSAJ_LOSS_NO_EXPOSURE is not allowed", who);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if (!color || !opacity || (!(loss_flags & GSAJ_LOSS_MONOCULAR) && !depth) || !gn_partials || !(irls_delta >= 0.f)) {
+    gsaj_set_error("%s: the forward's color / depth / opacity images, gn_partials and irls_delta >= 0 are required", who);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  FusedLoss fl{};
+  fl.flags = loss_flags; fl.alpha = alpha; fl.rgb_thr = rgb_boundary_threshold;
+  fl.gt_color = gt_color; fl.gt_depth = gt_depth; fl.grad_mask = grad_mask; fl.exp_a = exposure_a; fl.exp_b = exposure_b;
+  fl.color = color; fl.depth = depth; fl.opacity = opacity;
+  return pose_jac_impl(who, P, D, M, R, bg, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                       projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws, image_ws, jac_ws, jac_out, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gn_partials, &fl, irls_delta, stream, joint);
+}
+
 int gsaj_rasterize_pose_jacobian_loss(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
                                       const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
                                       const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
@@ -768,20 +795,26 @@ int gsaj_rasterize_pose_jacobian_loss(int P, int D, int M, int R, const float *b
                                       const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, float irls_delta,
                                       float *gn_partials, float *jac_out, void *stream) {
   (void)colors_precomp;
-  int rc = fused_loss_args("gsaj_rasterize_pose_jacobian_loss", loss_flags, gt_color, gt_depth, exposure_a, exposure_b);
-  if (rc != GSAJ_OK) return rc;
-  if (!color || !opacity || (!(loss_flags & GSAJ_LOSS_MONOCULAR) && !depth) || !gn_partials || !(irls_delta >= 0.f)) {
-    gsaj_set_error("gsaj_rasterize_pose_jacobian_loss: the forward's color / depth / opacity images, gn_partials and irls_delta >= 0 are required");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  FusedLoss fl{};
-  fl.flags = loss_flags; fl.alpha = alpha; fl.rgb_thr = rgb_boundary_threshold;
-  fl.gt_color = gt_color; fl.gt_depth = gt_depth; fl.grad_mask = grad_mask; fl.exp_a = exposure_a; fl.exp_b = exposure_b;
-  fl.color = color; fl.depth = depth; fl.opacity = opacity;
-  return pose_jac_impl("gsaj_rasterize_pose_jacobian_loss", P, D, M, R, bg, W, H, means3D, shs, scales, scale_modifier, rotations,
-                       cov3D_precomp, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws, image_ws,
-                       jac_ws, jac_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gn_partials, &fl, irls_delta,
-                       stream);
+  return pose_jac_loss_impl("gsaj_rasterize_pose_jacobian_loss", false, P, D, M, R, bg, W, H, means3D, shs, scales, scale_modifier, rotations,
+                            cov3D_precomp, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws,
+                            image_ws, jac_ws, loss_flags, alpha, rgb_boundary_threshold, color, depth, opacity, gt_color, gt_depth, grad_mask,
+                            exposure_a, exposure_b, irls_delta, gn_partials, jac_out, stream);
+}
+
+int gsaj_rasterize_pose_jacobian_loss8(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
+                                       const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                       const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
+                                       const float *projmatrix, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                       float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
+                                       void *jac_ws, int loss_flags, float alpha, float rgb_boundary_threshold, const float *color,
+                                       const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
+                                       const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, float irls_delta,
+                                       float *gn8_partials, float *jac_out, void *stream) {
+  (void)colors_precomp;
+  return pose_jac_loss_impl("gsaj_rasterize_pose_jacobian_loss8", true, P, D, M, R, bg, W, H, means3D, shs, scales, scale_modifier, rotations,
+                            cov3D_precomp, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws,
+                            image_ws, jac_ws, loss_flags, alpha, rgb_boundary_threshold, color, depth, opacity, gt_color, gt_depth, grad_mask,
+                            exposure_a, exposure_b, irls_delta, gn8_partials, jac_out, stream);
 }
 
 int gsaj_mark_visible(int P, const float *means3D, const float *viewmatrix, const float *projmatrix, uint8_t *present,

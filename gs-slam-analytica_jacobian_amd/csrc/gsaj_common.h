@@ -260,13 +260,15 @@ int launch_gaussian_backward_batch(const BwdParams &p, int K, const GeomWS &g, c
                                    int accumulate, int gather, hipStream_t s);
 // pose_jac.hip: per-Gaussian derivative rows (`rows`: gsaj_jac_rows_bytes(P) bytes), the forward-mode compositor over a finished
 // forward's state (every output may be NULL; fl != NULL: seeds and curvatures from the tracking loss with IRLS delta, else from the
-// seed / curvature images; partials [gsaj_jac_slots(W, H)][GSAJ_GN_PARTIAL_FLOATS]) and the explicit form's fixed-order sum
+// seed / curvature images; partials [gsaj_jac_slots(W, H)][GSAJ_GN_PARTIAL_FLOATS]; joint (with fl): the exposure columns too, partials
+// [gsaj_jac_slots(W, H)][GSAJ_GN8_PARTIAL_FLOATS]) and the explicit form's fixed-order sum
 size_t gsaj_jac_rows_bytes(int P);
 int gsaj_jac_slots(int W, int H);
 int launch_splat_jac(const BwdParams &p, const GeomWS &g, const ImageWS &im, float *rows, hipStream_t s);
 int launch_render_jac(int P, int W, int H, int grid_x, int grid_y, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im,
                       const float *rows, float *jac_out, float *out_color, float *out_depth, const float *seed_c, const float *seed_d,
-                      const float *curv_c, const float *curv_d, float *partials, const FusedLoss *fl, float irls_delta, hipStream_t s);
+                      const float *curv_c, const float *curv_d, float *partials, const FusedLoss *fl, float irls_delta, int joint,
+                      hipStream_t s);
 int launch_gn_reduce(const float *partials, int n, const ImageWS &im, float *H_out, float *g_out, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 // in-place exclusive scan of n counters by ONE workgroup (knn.hip; the radix sort's digit offsets, seed.hip's compaction offsets)

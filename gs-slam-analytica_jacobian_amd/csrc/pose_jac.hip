@@ -20,6 +20,11 @@
 //  k_gn_reduce     the explicit form's tail: the rows summed in slot order (fp64) -> H [21], g [6].
 //  k_gn_step       the fused form's tail: the same sum, then accept / reject, damping, a 6x6 Cholesky solve in fp64 and
 //                  Exp(tau) W2C with the Adam pose step's own device functions (pose_se3.h).  One launch, no host read.
+//  k_render_jac8 / k_gn8_step   the joint form: the unknowns are x = [rho, theta, a, b] with the exposure e^a C + b of the tracking
+//                  loss.  r_ch = m (e^a C_ch + b - gt_ch), so relative to the rendered colour the exposure parameters are two more
+//                  Jacobian columns, J8[ch] = [J[ch][0..5], C_ch, 1 / e^a] (0, 0 in the depth row), under the same seeds and
+//                  curvatures: H8 (36, upper triangle by rows) and g8 (8) in ONE 64-float row per workgroup, 8x8 solve, a and b
+//                  stepped, saved and restored with the pose.  The same body and the same step, instantiated for 8 unknowns.
 #include "gsaj_common.h"
 #include "gaussian_chain.h"
 #include "loss_terms.h"
@@ -31,6 +36,7 @@
 #define JAC_CHUNK 32   // list positions examined (and at most that many entries staged) per wave and trip: 1.5 KB of splat rows + 6 KB
                        // of derivative rows + the ids = 7.8 KB of LDS per wave
 #define GN_ROW GSAJ_GN_PARTIAL_FLOATS  // H (21, upper triangle by rows), g (6), loss, L_rgb, L_depth, d/da, d/db partials
+#define GN8_ROW GSAJ_GN8_PARTIAL_FLOATS  // joint form: H8 (36), g8 (8), loss, L_rgb, L_depth, d/da, d/db partials, 15 zeros
 
 // gn_state fields behind the pose state (include/gsaj.h)
 #define GN_LAMBDA 80
@@ -43,6 +49,12 @@
 #define GN_H 104
 #define GN_G 125
 static_assert(GN_G + 6 <= GSAJ_GN_STATE_FLOATS, "gn_state layout");
+// joint form: [0:104) as above, then H8, g8 and the accepted exposure; the exposure step x[6], x[7] of the last call goes into the
+// two floats the pose state leaves unused behind `converged`
+#define GN8_G (GN_H + 36)
+#define GN8_ACC_EXP (GN8_G + 8)
+#define GN8_DEXP 78
+static_assert(GN8_ACC_EXP + 2 <= GSAJ_GN8_STATE_FLOATS && GN8_ROW == 64, "gn8_state layout");
 
 // ---- per-Gaussian derivative rows ----------------------------------------------------------------------------------------
 // The chain is linear in the ten sums the reverse compositor hands it, so its transpose is the chain applied to unit sums:
@@ -105,11 +117,14 @@ struct JacOut {
   float delta;                      // fused form: the IRLS delta
 };
 
-template <bool LOSS>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_render_jac(
+// JOINT (with LOSS): the exposure columns and the 64-float row of the joint form; the walk is the same code.
+template <bool LOSS, bool JOINT>
+__device__ __forceinline__ void render_jac_body(
     int W, int H, int gx, int tiles, int P, ImageWS im, const float4 *__restrict__ splat, const float4 *__restrict__ splat16,
     const float *__restrict__ bg, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ taken,
     const float4 *__restrict__ rows, JacOut jo, FusedLoss fl) {
+  static_assert(LOSS || !JOINT, "the joint form is a form of the loss-fused compositor");
+  constexpr int ROW = JOINT ? GN8_ROW : GN_ROW;
   __shared__ float4 srow[JAC_CHUNK * 3];         // (x, y, kx, ky) (kz, o, 1-based list position, -) (r, g, b, depth)
   __shared__ float4 drow[JAC_CHUNK * JROW_F4];   // the entries' derivative rows
   __shared__ uint32_t sid[JAC_CHUNK];
@@ -120,7 +135,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   const int wave = ((int)blockIdx.x >> 3) & 3;
   const int rank = ((int)blockIdx.x >> 5) * 8 + ((int)blockIdx.x & 7);
   if (rank >= tiles) {
-    if (jo.partials && lane < GN_ROW) jo.partials[(size_t)blockIdx.x * GN_ROW + lane] = 0.f;
+    if (jo.partials && lane < ROW) jo.partials[(size_t)blockIdx.x * ROW + lane] = 0.f;
     return;
   }
   const int tile = (int)min(im.tile_order[rank], (uint32_t)(tiles - 1));
@@ -259,6 +274,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   // ---- this pixel's seeds and curvatures, its share of g = sum s J and H = sum h J^T J, and the loss terms ----
   float sv[4] = {0.f, 0.f, 0.f, 0.f}, hv[4] = {0.f, 0.f, 0.f, 0.f};
   float ls[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  float cx[3] = {0.f, 0.f, 0.f}, iea = 0.f;  // joint form: the exposure columns of the colour rows (a: the forward's colour, b: 1 / e^a)
   bool want_h = true;
   if (LOSS) {
     if (inside) {
@@ -278,6 +294,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       ls[2] = o.s_d / (float)HW;
       ls[3] = o.s_a;
       ls[4] = o.s_b;
+      if (JOINT) {
+        cx[0] = c0; cx[1] = c1; cx[2] = c2;
+        iea = __fdiv_rn(1.f, L.ea);
+      }
     }
   } else {
     want_h = jo.curv_c != nullptr;
@@ -290,7 +310,44 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       }
     }
   }
-  float *out = jo.partials + (size_t)blockIdx.x * GN_ROW;
+  float *out = jo.partials + (size_t)blockIdx.x * ROW;
+  if (JOINT) {
+    // 49 sums.  Four at a time go through ONE tree (wave_reduce.h: two half-wave swaps fold lane bits 5 and 4 of four values into one
+    // register, four row rotations finish it): 7 cross-lane steps per four values where four butterflies take 24, and row r's first
+    // lane stores its own value, so the row's stores are 13 x 4 lanes wide instead of 49 by lane 0.  The tree is fixed -- the same bits
+    // run to run -- and adds the pairs wave_sum's butterfly adds (bit 5, bit 4, then 8, 4, 2, 1 within a row): the pose block comes
+    // out as the 6-form's bits (measured, not promised).
+    float v[52];
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+#pragma unroll
+      for (int l = k; l < 8; l++, n++) {
+        float t = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) {
+          const float jk = k < 6 ? J[ch][k] : (ch == 3 ? 0.f : (k == 6 ? cx[ch] : iea));
+          const float jl = l < 6 ? J[ch][l] : (ch == 3 ? 0.f : (l == 6 ? cx[ch] : iea));
+          t += (hv[ch] * jk) * jl;
+        }
+        v[n] = t;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++, n++) {
+      float t = 0.f;
+#pragma unroll
+      for (int ch = 0; ch < 4; ch++) t += sv[ch] * (k < 6 ? J[ch][k] : (ch == 3 ? 0.f : (k == 6 ? cx[ch] : iea)));
+      v[n] = t;
+    }
+#pragma unroll
+    for (int k = 0; k < 5; k++, n++) v[n] = ls[k];
+    v[49] = v[50] = v[51] = 0.f;
+#pragma unroll
+    for (int q = 0; q < 13; q++) store4(out + 4 * q, lane, reduce4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]));
+    if (lane >= 52) out[lane] = 0.f;
+    return;
+  }
   int n = 0;
 #pragma unroll
   for (int k = 0; k < 6; k++) {
@@ -320,22 +377,39 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   }
 }
 
+template <bool LOSS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_render_jac(
+    int W, int H, int gx, int tiles, int P, ImageWS im, const float4 *__restrict__ splat, const float4 *__restrict__ splat16,
+    const float *__restrict__ bg, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ taken,
+    const float4 *__restrict__ rows, JacOut jo, FusedLoss fl) {
+  render_jac_body<LOSS, false>(W, H, gx, tiles, P, im, splat, splat16, bg, point_list, taken, rows, jo, fl);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_render_jac8(
+    int W, int H, int gx, int tiles, int P, ImageWS im, const float4 *__restrict__ splat, const float4 *__restrict__ splat16,
+    const float *__restrict__ bg, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ taken,
+    const float4 *__restrict__ rows, JacOut jo, FusedLoss fl) {
+  render_jac_body<true, true>(W, H, gx, tiles, P, im, splat, splat16, bg, point_list, taken, rows, jo, fl);
+}
+
 // ---- the partial rows summed in slot order, in fp64 ------------------------------------------------------------------------
-// GN_SUM_THREADS threads = GN_GROUPS row groups x 32 columns: thread (r, c) adds rows r, r + GN_GROUPS, ... of column c, four loads in
-// flight at a time and added in row order, then the groups are added in order.  (A frame of 640x480 has 4800 rows: eight groups
-// with one dependent load after the other took 158 us, as long as the compositor.)  sums: [GN_ROW] doubles in LDS, complete after
-// the call's barrier.
+// GN_SUM_THREADS threads = GROUPS row groups x ROW columns (32 groups of the 32-float row, 16 of the joint form's 64-float row): thread
+// (r, c) adds rows r, r + GROUPS, ... of column c, four loads in flight at a time and added in row order, then the groups are added in
+// order.  (A frame of 640x480 has 4800 rows: eight groups with one dependent load after the other took 158 us, as long as the
+// compositor.)  sums: [ROW] doubles in LDS, complete after the call's barrier.
 #define GN_SUM_THREADS 1024
 #define GN_GROUPS (GN_SUM_THREADS / 32)
-__device__ __forceinline__ void gn_sum_rows(const float *__restrict__ partials, int n, double (*red)[GN_ROW], double *sums) {
-  const int c = threadIdx.x & 31, r = threadIdx.x >> 5;
+template <int ROW>
+__device__ __forceinline__ void gn_sum_rows(const float *__restrict__ partials, int n, double (*red)[ROW], double *sums) {
+  constexpr int GROUPS = GN_SUM_THREADS / ROW;
+  const int c = threadIdx.x & (ROW - 1), r = threadIdx.x / ROW;
   double acc = 0.0;
-  for (int i0 = r; i0 < n; i0 += 4 * GN_GROUPS) {
+  for (int i0 = r; i0 < n; i0 += 4 * GROUPS) {
     float v[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) {
-      const int i = i0 + u * GN_GROUPS;
-      v[u] = i < n ? partials[(size_t)i * GN_ROW + c] : 0.f;
+      const int i = i0 + u * GROUPS;
+      v[u] = i < n ? partials[(size_t)i * ROW + c] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < 4; u++) acc += (double)v[u];
@@ -344,7 +418,7 @@ __device__ __forceinline__ void gn_sum_rows(const float *__restrict__ partials, 
   __syncthreads();
   if (r == 0) {
     double t = red[0][c];
-    for (int q = 1; q < GN_GROUPS; q++) t += red[q][c];
+    for (int q = 1; q < GROUPS; q++) t += red[q][c];
     sums[c] = t;
   }
   __syncthreads();
@@ -354,7 +428,7 @@ __global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_reduce(const float *__res
                                                    float *__restrict__ H_out, float *__restrict__ g_out) {
   __shared__ double red[GN_GROUPS][GN_ROW], sums[GN_ROW];
   if (counters[4]) return;  // aborted async frame
-  gn_sum_rows(partials, n, red, sums);
+  gn_sum_rows<GN_ROW>(partials, n, red, sums);
   const int t = threadIdx.x;
   if (H_out && t < 21) H_out[t] = (float)sums[t];
   if (g_out && t >= 21 && t < 27) g_out[t - 21] = (float)sums[t];
@@ -369,83 +443,106 @@ struct GnStepParams {
   const uint32_t *skip;
 };
 
-// (H + lambda diag(H) + eps I) tau = -g by Cholesky in fp64; eps = 1e-9 x the mean diagonal of H + 1e-30 keeps a direction the
-// frame says nothing about (H row == 0) solvable.  Returns false on a non-positive (or non-finite) pivot.
+// (H + lambda diag(H) + eps I) x = -g by Cholesky in fp64, NX unknowns; eps = 1e-9 x the mean diagonal of H + 1e-30 keeps a direction
+// the frame says nothing about (H row == 0) solvable.  Returns false on a non-positive (or non-finite) pivot.
+template <int NX>
 __device__ bool gn_solve(const float *Hs, const float *gs, double lambda, double *tau) {
-  double A[6][6], Lc[6][6], y[6];
+  double A[NX][NX], Lc[NX][NX], y[NX];
   int n = 0;
   double tr = 0.0;
-  for (int k = 0; k < 6; k++)
-    for (int l = k; l < 6; l++, n++) A[k][l] = A[l][k] = (double)Hs[n];
-  for (int k = 0; k < 6; k++) tr += A[k][k];
-  const double eps = 1e-9 * (tr / 6.0) + 1e-30;
-  for (int k = 0; k < 6; k++) A[k][k] = A[k][k] + lambda * A[k][k] + eps;
-  for (int j = 0; j < 6; j++) {
+  for (int k = 0; k < NX; k++)
+    for (int l = k; l < NX; l++, n++) A[k][l] = A[l][k] = (double)Hs[n];
+  for (int k = 0; k < NX; k++) tr += A[k][k];
+  const double eps = 1e-9 * (tr / (double)NX) + 1e-30;
+  for (int k = 0; k < NX; k++) A[k][k] = A[k][k] + lambda * A[k][k] + eps;
+  for (int j = 0; j < NX; j++) {
     double d = A[j][j];
     for (int k = 0; k < j; k++) d -= Lc[j][k] * Lc[j][k];
     if (!(d > 0.0) || !(d < 1e300)) return false;
     const double ljj = sqrt(d);
     Lc[j][j] = ljj;
-    for (int i = j + 1; i < 6; i++) {
+    for (int i = j + 1; i < NX; i++) {
       double v = A[i][j];
       for (int k = 0; k < j; k++) v -= Lc[i][k] * Lc[j][k];
       Lc[i][j] = v / ljj;
     }
   }
-  for (int i = 0; i < 6; i++) {
+  for (int i = 0; i < NX; i++) {
     double v = -(double)gs[i];
     for (int k = 0; k < i; k++) v -= Lc[i][k] * y[k];
     y[i] = v / Lc[i][i];
   }
-  for (int i = 5; i >= 0; i--) {
+  for (int i = NX - 1; i >= 0; i--) {
     double v = y[i];
-    for (int k = i + 1; k < 6; k++) v -= Lc[k][i] * tau[k];
+    for (int k = i + 1; k < NX; k++) v -= Lc[k][i] * tau[k];
     tau[i] = v / Lc[i][i];
   }
-  for (int i = 0; i < 6; i++)
+  for (int i = 0; i < NX; i++)
     if (!(fabs(tau[i]) < 1e300)) return false;
   return true;
 }
 
-__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_step(GnStepParams p) {
-  __shared__ double red[GN_GROUPS][GN_ROW], sums[GN_ROW];
+// NX = 6: the pose alone (rows of GN_ROW floats, H [21], g [6]).  NX = 8: the pose and the exposure (rows of GN8_ROW floats, H8 [36],
+// g8 [8]); a and b live in the pose state (PS_EXP), are stepped by x[6], x[7], saved on accept and restored on reject with W2C.
+template <int NX>
+__device__ __forceinline__ void gn_step_body(const GnStepParams &p) {
+  constexpr int ROW = NX == 8 ? GN8_ROW : GN_ROW, NH = NX * (NX + 1) / 2, G_AT = NX == 8 ? GN8_G : GN_G;
+  __shared__ double red[GN_SUM_THREADS / ROW][ROW], sums[ROW];
   // the frame these rows belong to was aborted on the device (its kernels returned at once: the rows are the PREVIOUS iteration's)
   if (p.skip && *p.skip != 0u) return;
-  gn_sum_rows(p.partials, p.n, red, sums);
+  gn_sum_rows<ROW>(p.partials, p.n, red, sums);
   if (threadIdx.x != 0) return;
   float *st = p.st;
-  const float loss = (float)sums[27];
+  const float loss = (float)sums[NH + NX];
   st[GN_LAST + 0] = loss;
-  st[GN_LAST + 1] = (float)sums[28];
-  st[GN_LAST + 2] = (float)sums[29];
+  st[GN_LAST + 1] = (float)sums[NH + NX + 1];
+  st[GN_LAST + 2] = (float)sums[NH + NX + 2];
   const bool has = st[GN_HAS] != 0.f;
   float lambda = has ? st[GN_LAMBDA] : p.lambda_init;
   if (!has || loss <= st[GN_ACC_LOSS]) {  // accept the pose these rows were rendered at
     st[GN_ACC_LOSS] = loss;
     for (int i = 0; i < 16; i++) st[GN_ACC_W2C + i] = st[PS_W2C + i];
-    for (int i = 0; i < 21; i++) st[GN_H + i] = (float)sums[i];
-    for (int i = 0; i < 6; i++) st[GN_G + i] = (float)sums[21 + i];
+    for (int i = 0; i < NH; i++) st[GN_H + i] = (float)sums[i];
+    for (int i = 0; i < NX; i++) st[G_AT + i] = (float)sums[NH + i];
+    if (NX == 8) {
+      st[GN8_ACC_EXP] = st[PS_EXP];
+      st[GN8_ACC_EXP + 1] = st[PS_EXP + 1];
+    }
     lambda = fmaxf(lambda / p.nu, p.lambda_min);
     st[GN_HAS] = 1.f;
     st[GN_ACCEPTED] += 1.f;
   } else {  // reject: back to the accepted pose and its normal equations, more damping
     for (int i = 0; i < 16; i++) st[PS_W2C + i] = st[GN_ACC_W2C + i];
+    if (NX == 8) {
+      st[PS_EXP] = st[GN8_ACC_EXP];
+      st[PS_EXP + 1] = st[GN8_ACC_EXP + 1];
+    }
     lambda = fminf(lambda * p.nu, p.lambda_max);
     st[GN_REJECTED] += 1.f;
   }
-  double tau64[6];
-  float delta[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const bool ok = gn_solve(st + GN_H, st + GN_G, (double)lambda, tau64);
+  double tau64[NX];
+  float delta[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const bool ok = gn_solve<NX>(st + GN_H, st + G_AT, (double)lambda, tau64);
   if (ok) {
-    for (int i = 0; i < 6; i++) delta[i] = (float)tau64[i];
+    for (int i = 0; i < NX; i++) delta[i] = (float)tau64[i];
   } else {
     lambda = fminf(lambda * p.nu, p.lambda_max);  // no step from this factorisation: more damping next time
   }
   st[GN_LAMBDA] = lambda;
   // Exp(tau) W2C, the camera matrices, tau, |tau|, converged (tau = 0 on a failed factorisation: the pose comes out unchanged)
   pose_apply_delta(st, delta, p.projection, p.threshold);
+  if (NX == 8) {  // (x[6], x[7] = 0 on a failed factorisation: the exposure comes out unchanged)
+    st[PS_EXP] += delta[6];
+    st[PS_EXP + 1] += delta[7];
+    st[GN8_DEXP] = delta[6];
+    st[GN8_DEXP + 1] = delta[7];
+    if (!(fmaxf(fabsf(delta[6]), fabsf(delta[7])) < p.threshold)) st[PS_CONV] = 0.f;
+  }
   if (!ok) st[PS_CONV] = 0.f;
 }
+
+__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_step(GnStepParams p) { gn_step_body<6>(p); }
+__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn8_step(GnStepParams p) { gn_step_body<8>(p); }
 
 // ---- launchers (api.hip) ------------------------------------------------------------------------------------------------------
 size_t gsaj_jac_rows_bytes(int P) { return gsaj_align(sizeof(float) * JROW_F * (size_t)(P > 0 ? P : 1)); }
@@ -460,13 +557,17 @@ int launch_splat_jac(const BwdParams &p, const GeomWS &g, const ImageWS &im, flo
 
 int launch_render_jac(int P, int W, int H, int grid_x, int grid_y, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im,
                       const float *rows, float *jac_out, float *out_color, float *out_depth, const float *seed_c, const float *seed_d,
-                      const float *curv_c, const float *curv_d, float *partials, const FusedLoss *fl, float irls_delta, hipStream_t s) {
+                      const float *curv_c, const float *curv_d, float *partials, const FusedLoss *fl, float irls_delta, int joint,
+                      hipStream_t s) {
   const int tiles = grid_x * grid_y;
   const unsigned nblk = (unsigned)gsaj_jac_slots(W, H);
   JacOut jo;
   jo.jac = jac_out; jo.color = out_color; jo.depth = out_depth; jo.seed_c = seed_c; jo.seed_d = seed_d; jo.curv_c = curv_c;
   jo.curv_d = curv_d; jo.partials = partials; jo.delta = irls_delta;
-  if (fl)
+  if (fl && joint)
+    hipLaunchKernelGGL(k_render_jac8, dim3(nblk), dim3(64), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg, b.point_list, b.taken,
+                       reinterpret_cast<const float4 *>(rows), jo, *fl);
+  else if (fl)
     hipLaunchKernelGGL(k_render_jac<true>, dim3(nblk), dim3(64), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg, b.point_list, b.taken,
                        reinterpret_cast<const float4 *>(rows), jo, *fl);
   else
@@ -484,18 +585,37 @@ int launch_gn_reduce(const float *partials, int n, const ImageWS &im, float *H_o
 
 extern "C" int gsaj_gn_state_floats(void) { return GSAJ_GN_STATE_FLOATS; }
 
-extern "C" int gsaj_pose_gn_step(const float *gn_partials, int n_partials, float lambda_init, float nu, float lambda_min, float lambda_max,
-                                 float converged_threshold, const float *projection_matrix, float *gn_state, const uint32_t *skip,
-                                 void *stream) {
+extern "C" int gsaj_gn8_state_floats(void) { return GSAJ_GN8_STATE_FLOATS; }
+
+static int gn_step_launch(const char *who, bool joint, const float *gn_partials, int n_partials, float lambda_init, float nu, float lambda_min,
+                          float lambda_max, float converged_threshold, const float *projection_matrix, float *gn_state,
+                          const uint32_t *skip, void *stream) {
   if (!gn_partials || n_partials <= 0 || !gn_state || !(nu > 1.f) || !(lambda_min > 0.f) || !(lambda_max >= lambda_min) ||
       !(lambda_init >= lambda_min) || !(lambda_init <= lambda_max)) {
-    gsaj_set_error("gsaj_pose_gn_step: gn_partials, n_partials > 0 and gn_state are required; nu > 1, 0 < lambda_min <= lambda_init <= lambda_max");
+    gsaj_set_error("%s: gn_partials, n_partials > 0 and gn_state are required; nu > 1, 0 < lambda_min <= lambda_init <= lambda_max", who);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   GnStepParams p;
   p.partials = gn_partials; p.n = n_partials; p.lambda_init = lambda_init; p.nu = nu; p.lambda_min = lambda_min; p.lambda_max = lambda_max;
   p.threshold = converged_threshold; p.projection = projection_matrix; p.st = gn_state; p.skip = skip;
-  hipLaunchKernelGGL(k_gn_step, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, p);
+  if (joint)
+    hipLaunchKernelGGL(k_gn8_step, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(k_gn_step, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, p);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
+}
+
+extern "C" int gsaj_pose_gn_step(const float *gn_partials, int n_partials, float lambda_init, float nu, float lambda_min, float lambda_max,
+                                 float converged_threshold, const float *projection_matrix, float *gn_state, const uint32_t *skip,
+                                 void *stream) {
+  return gn_step_launch("gsaj_pose_gn_step", false, gn_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold,
+                        projection_matrix, gn_state, skip, stream);
+}
+
+extern "C" int gsaj_pose_gn8_step(const float *gn8_partials, int n_partials, float lambda_init, float nu, float lambda_min, float lambda_max,
+                                  float converged_threshold, const float *projection_matrix, float *gn8_state, const uint32_t *skip,
+                                  void *stream) {
+  return gn_step_launch("gsaj_pose_gn8_step", true, gn8_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold,
+                        projection_matrix, gn8_state, skip, stream);
 }

@@ -10,6 +10,7 @@
 //   block_excl_scan_add              workgroup exclusive scan: wave scans + one LDS hop for the wave totals, ONE barrier;
 //   block_scan_total                 the workgroup's total from the same LDS words
 //   block_excl_scan_runs             the same over n items, a contiguous run per lane, with the largest item
+//   reduce4 / store4                 four per-lane partials through one tree (7 cross-lane steps where four butterflies take 24)
 //   reduce10 / store10               ten per-lane partials at once, register-only:
 //
 // v_permlane32_swap / v_permlane16_swap exchange half-waves / odd-even rows between two
@@ -157,6 +158,17 @@ __device__ __forceinline__ float row_allreduce(float v) {  // sum over the 16 la
   v = dpp_add<0x122>(v);  // row_ror:2
   v = dpp_add<0x121>(v);  // row_ror:1
   return v;
+}
+// Four values at once: after reduce4() every lane of row r = lane>>4 holds the wave's sum of v{0,2,1,3}[r]; store4: the first lane of
+// each row stores it, a[0..3] = the sums of v0..v3.  A fixed tree of depth 6, like wave_sum's, in another order.
+__device__ __forceinline__ float reduce4(float v0, float v1, float v2, float v3) {
+  return row_allreduce(merge16(merge32(v0, v1), merge32(v2, v3)));
+}
+__device__ __forceinline__ void store4(float *a, int lane, float x) {
+  if ((lane & 15) == 0) {
+    const int r = lane >> 4;
+    a[((r & 1) << 1) | (r >> 1)] = x;
+  }
 }
 __device__ __forceinline__ void reduce10(const float (&v)[10], float &x0, float &x1, float &x2) {
   const float w0 = merge32(v[0], v[1]), w1 = merge32(v[2], v[3]), w2 = merge32(v[4], v[5]), w3 = merge32(v[6], v[7]),

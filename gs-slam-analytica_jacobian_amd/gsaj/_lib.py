@@ -123,6 +123,11 @@ SIGNATURES = {
                                                   c_float, P, P, P]),
     "gsaj_gn_state_floats": (c_int, []),
     "gsaj_pose_gn_step": (c_int, [P, c_int] + [c_float] * 5 + [P, P, P, P]),
+    "gsaj_rasterize_pose_jacobian_loss8": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P, P,
+                                                   c_float, c_float, P, P, P, P, P, c_int, c_float, c_float, P, P, P, P, P, P, P, P,
+                                                   c_float, P, P, P]),
+    "gsaj_gn8_state_floats": (c_int, []),
+    "gsaj_pose_gn8_step": (c_int, [P, c_int] + [c_float] * 5 + [P, P, P, P]),
 }
 
 _lib = None

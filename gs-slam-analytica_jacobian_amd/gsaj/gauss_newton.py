@@ -8,6 +8,11 @@ damping, a 6x6 Cholesky solve, W2C <- Exp(tau) W2C and the camera matrices of th
 the previous one proposed; whether that pose is kept is decided by the NEXT step, from the loss rendered there.  Exposure enters as
 the fixed affine e^a C + b; only tau is solved for.  No graph capture and no process group.
 
+solve_exposure=True is the joint form: the unknowns are [rho, theta, a, b], as the frontend's tracking loop optimises them.  The same
+three calls with gsaj_rasterize_pose_jacobian_loss8 (two more Jacobian columns per colour row, the forward's colour for a and 1 / e^a
+for b: 8x8 normal equations in 64-float rows) and gsaj_pose_gn8_step (8x8 solve; a and b are stepped, saved on an accepted step and
+restored on a rejected one together with the pose).
+
 An asynchronous frame that does not fit its arena is aborted on the device: its kernels return at once and the step, handed the
 frame's abort word, changes nothing; iterate() raises when it is done, exactly as DeviceTracker.iterate does."""
 import torch
@@ -15,28 +20,36 @@ import torch
 from . import _lib
 from .grad_mask import GradMask
 from .losses import MONOCULAR, TRACKING
-from .rasterizer import FrameContext, unpack_sym6
+from .rasterizer import FrameContext, unpack_sym6, unpack_sym8
 
 # gn_state (include/gsaj.h): [0:80) the pose-state layout, then the Levenberg-Marquardt fields
 _O = dict(w2c=(0, 16), exposure=(33, 35), view=(35, 51), proj=(51, 67), campos=(67, 70), tau=(70, 76), norm=(76, 77), conv=(77, 78),
           lam=(80, 81), acc_loss=(81, 82), has=(82, 83), accepted=(83, 84), rejected=(84, 85), last=(85, 88), acc_w2c=(88, 104),
           H=(104, 125), g=(125, 131))
+# the joint form's state: [0:104) as above, then the accepted H8, g8 and exposure; the last exposure step behind `converged`
+_O8 = dict(_O, H=(104, 140), g=(140, 148), acc_exposure=(148, 150), dexposure=(78, 80))
 
 
 class GaussNewtonTracker:
     def __init__(self, P, W, H, M, device, w2c, projection_matrix, tanfovx, tanfovy, bg, means3D, opacities, sh_degree=0, shs=None,
                  colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, monocular=False, alpha=0.95,
                  rgb_boundary_threshold=0.01, record_bits=32, irls_delta=0.01, lambda_init=1e-3, nu=4.0, lambda_min=1e-7,
-                 lambda_max=1e7, converged_threshold=1e-4):
+                 lambda_max=1e7, converged_threshold=1e-4, solve_exposure=False):
         """The Gaussians (device tensors) are those of the current map: the loop reads them, it never writes them.  irls_delta: the
         residual below which an L1 term is treated as a quadratic (0: pure IRLS weights 1 / |r|).  lambda_init / nu / lambda_min /
-        lambda_max: the damping and its factor; converged_threshold: |tau| below which the device reports convergence."""
+        lambda_max: the damping and its factor; converged_threshold: |tau| below which the device reports convergence.
+        solve_exposure: solve for the exposure (a, b) together with the pose (then convergence also needs |da|, |db| below the threshold)."""
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
             raise _lib.GsajError("GaussNewtonTracker needs a HIP device (there is no CPU path)")
         self.lib = _lib.load()
         self.ctx = FrameContext(P, W, H, M, self.dev, has_scales=scales is not None, record_bits=record_bits)
-        self.state = torch.zeros(self.lib.gsaj_gn_state_floats(), dtype=torch.float32, device=self.dev)
+        self.solve_exposure = bool(solve_exposure)
+        self._o = _O8 if self.solve_exposure else _O
+        self._step, self._step_name = ((self.lib.gsaj_pose_gn8_step, "gsaj_pose_gn8_step") if self.solve_exposure else
+                                       (self.lib.gsaj_pose_gn_step, "gsaj_pose_gn_step"))
+        n_state = self.lib.gsaj_gn8_state_floats() if self.solve_exposure else self.lib.gsaj_gn_state_floats()
+        self.state = torch.zeros(n_state, dtype=torch.float32, device=self.dev)
         self.projection = torch.as_tensor(projection_matrix, dtype=torch.float32).reshape(4, 4).contiguous().to(self.dev)
         self.praw = self.projection
         self.tanfov = (float(tanfovx), float(tanfovy))
@@ -66,9 +79,11 @@ class GaussNewtonTracker:
         s[67:70] = -(torch.linalg.inv(w[:3, :3].double().cpu()) @ w[:3, 3].double().cpu()).float().to(self.dev)
         s[80] = self.lm_args[0]
         s[88:104] = s[0:16]
+        if self.solve_exposure:
+            s[148:150] = s[33:35]
 
     def _v(self, name, shape=None):
-        a, b = _O[name]
+        a, b = self._o[name]
         t = self.state[a:b]
         return t.view(*shape) if shape else t
 
@@ -83,15 +98,21 @@ class GaussNewtonTracker:
     accepted_w2c = property(lambda s: s._v("acc_w2c", (4, 4)))
 
     @property
+    def accepted_exposure(self):
+        """[a, b] of the last accepted step (device).  Without solve_exposure the exposure never moves: the state's own [a, b]."""
+        return self._v("acc_exposure") if self.solve_exposure else self.state[33:35]
+
+    @property
     def loss_terms(self):
         """[loss, L_rgb, L_depth] of the last iteration's render (device)."""
         return self._v("last")
 
     @property
     def lm(self):
-        """dict(lam, accepted, rejected, accepted_loss: device scalars; H [6,6], g [6]: the accepted normal equations)."""
+        """dict(lam, accepted, rejected, accepted_loss: device scalars; H [6,6], g [6]: the accepted normal equations -- [8,8], [8] over
+        [rho, theta, a, b] with solve_exposure)."""
         return dict(lam=self.state[80], accepted=self.state[83], rejected=self.state[84], accepted_loss=self.state[81],
-                    H=unpack_sym6(self._v("H")), g=self._v("g"))
+                    H=(unpack_sym8 if self.solve_exposure else unpack_sym6)(self._v("H")), g=self._v("g"))
 
     def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2c=None, edge_threshold=None, grad_blocks=False):
         """New frame: ground truth (device, [3,H,W] / [H,W]; grad_mask [1,H,W] or None) and optionally a new initial pose; copied into
@@ -128,13 +149,12 @@ class GaussNewtonTracker:
         L = dict(flags=self.flags, alpha=self.alpha, rgb_boundary_threshold=self.thr, gt_color=self.gt_color, gt_depth=self.gt_depth,
                  grad_mask=self.grad_mask, exposure_a=self.exposure_a, exposure_b=self.exposure_b)
         o = c.pose_jacobian_loss(L, self.bg, self.means, self.viewmatrix, self.projmatrix, self.praw, self.campos, self.tanfov[0],
-                                 self.tanfov[1], irls_delta=self.delta, **self.kw)
-        _lib.check(self.lib.gsaj_pose_gn_step(o["partials"].data_ptr(), o["partials"].shape[0], *self.lm_args, self.projection.data_ptr(),
-                                              self.state.data_ptr(), self._abort_ptr, torch.cuda.current_stream(self.dev).cuda_stream),
-                   "gsaj_pose_gn_step")
+                                 self.tanfov[1], irls_delta=self.delta, solve_exposure=self.solve_exposure, **self.kw)
+        _lib.check(self._step(o["partials"].data_ptr(), o["partials"].shape[0], *self.lm_args, self.projection.data_ptr(),
+                              self.state.data_ptr(), self._abort_ptr, torch.cuda.current_stream(self.dev).cuda_stream), self._step_name)
 
     def iterate(self, n, check_every=0):
-        """Up to n iterations; check_every > 0: stop once the device reports |tau| < converged_threshold, looked at every check_every
+        """Up to n iterations; check_every > 0: stop once the device reports |tau| (and, with solve_exposure, |da|, |db|) < converged_threshold, looked at every check_every
         iterations.  Returns the number run.  Raises GsajError after the loop if an asynchronous frame was aborted on the device
         (those iterations changed nothing); the next call re-sizes the arena with one synchronous iteration."""
         if self.gt_color is None:

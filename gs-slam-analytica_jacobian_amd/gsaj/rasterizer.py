@@ -58,6 +58,18 @@ def unpack_sym6(h21):
     return out
 
 
+def unpack_sym8(h36):
+    """[..., 36] (upper triangle by rows, as the joint form stores H8) -> symmetric [..., 8, 8]."""
+    out = h36.new_zeros(tuple(h36.shape[:-1]) + (8, 8))
+    n = 0
+    for k in range(8):
+        for l in range(k, 8):
+            out[..., k, l] = h36[..., n]
+            out[..., l, k] = h36[..., n]
+            n += 1
+    return out
+
+
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, projmatrix_raw, tan_fovx, tan_fovy, image_height, image_width, sh,
                         degree, campos, prefiltered, debug, record_bits=32):
@@ -586,29 +598,32 @@ class FrameContext:
 
     def pose_jacobian_loss(self, loss, bg, means3D, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, irls_delta=0.0,
                            partials=None, want_jacobian=False, sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None,
-                           cov3D_precomp=None, scale_modifier=1.0):
+                           cov3D_precomp=None, scale_modifier=1.0, solve_exposure=False):
         """The fused form: seeds and curvatures of the tracking loss (`loss`: the dict of forward_loss / backward_loss) derived per
         pixel from this context's color / depth / opacity, with IRLS delta.  Fills `partials` (float32 [gn_rows, 32], made on the
         first call if None: one fixed-slot row per workgroup -- H (21), g (6), loss, L_rgb, L_depth, two exposure sums) for
-        gsaj_pose_gn_step.  -> dict(partials, jacobian or None)."""
+        gsaj_pose_gn_step.  solve_exposure: the joint form over [rho, theta, a, b] (gsaj_rasterize_pose_jacobian_loss8) -- rows of
+        64 floats: H8 (36), g8 (8), loss, L_rgb, L_depth, two exposure sums, zeros -- for gsaj_pose_gn8_step; the loss must carry
+        exposure_a / exposure_b.  -> dict(partials, jacobian or None)."""
         self._jac_ready("pose_jacobian_loss")
+        width, own, name = (64, "gn8_partials", "gsaj_rasterize_pose_jacobian_loss8") if solve_exposure else (
+            32, "gn_partials", "gsaj_rasterize_pose_jacobian_loss")
         if partials is None:
-            if not hasattr(self, "gn_partials"):
-                self.gn_partials = torch.zeros((self.gn_rows, 32), device=self.dev, dtype=_F32)
-            partials = self.gn_partials
-        if tuple(partials.shape) != (self.gn_rows, 32) or partials.dtype != _F32 or not partials.is_contiguous() or partials.device != self.dev:
-            raise _lib.GsajError("pose_jacobian_loss: partials must be a contiguous float32 [%d, 32] tensor on %s" % (self.gn_rows, self.dev))
+            if not hasattr(self, own):
+                setattr(self, own, torch.zeros((self.gn_rows, width), device=self.dev, dtype=_F32))
+            partials = getattr(self, own)
+        if tuple(partials.shape) != (self.gn_rows, width) or partials.dtype != _F32 or not partials.is_contiguous() or partials.device != self.dev:
+            raise _lib.GsajError("pose_jacobian_loss: partials must be a contiguous float32 [%d, %d] tensor on %s" % (self.gn_rows, width, self.dev))
         jac = torch.empty((self.H, self.W, 4, 6), device=self.dev, dtype=_F32) if want_jacobian else None
         with torch.cuda.device(self.dev):
-            _lib.check(self.lib.gsaj_rasterize_pose_jacobian_loss(
+            _lib.check(getattr(self.lib, name)(
                 self.P, int(sh_degree), self.M, self.R, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
                 _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix),
                 _ptr(projmatrix_raw), _ptr(campos), float(tanfovx), float(tanfovy), self.radii.data_ptr(), self.geom.data_ptr(),
                 self.binning.data_ptr(), self.img.data_ptr(), self.jac_ws.data_ptr(), int(loss["flags"]), float(loss["alpha"]),
                 float(loss["rgb_boundary_threshold"]), self.color.data_ptr(), self.depth.data_ptr(), self.opacity.data_ptr(),
                 _ptr(loss["gt_color"]), _ptr(loss.get("gt_depth")), _ptr(loss.get("grad_mask")), _ptr(loss.get("exposure_a")),
-                _ptr(loss.get("exposure_b")), float(irls_delta), partials.data_ptr(), _ptr(jac), _stream(self.dev)),
-                "gsaj_rasterize_pose_jacobian_loss")
+                _ptr(loss.get("exposure_b")), float(irls_delta), partials.data_ptr(), _ptr(jac), _stream(self.dev)), name)
         return dict(partials=partials, jacobian=jac)
 
     def interactions(self):

@@ -480,7 +480,7 @@ int gsaj_pose_adam_step_batch(int K, const float *dL_dtau, const float *dL_dexpo
  *   [3,H,W], curv_depth [H,W].  g_out needs both seed images, H_out both curvature images (GSAJ_ERR_INVALID_ARGUMENT otherwise,
  *   and for the argument errors of gsaj_rasterize_backward).
  * gsaj_rasterize_pose_jacobian_loss -- the fused form, for the tracking loss of gsaj_rasterize_backward_loss (same loss arguments;
- *   exposure enters as the fixed affine e^a C + b, it is not solved for).  With the residuals r of csrc/loss_terms.h, kappa_rgb =
+ *   exposure enters as the fixed affine e^a C + b, it is not solved for: the joint form below does).  With the residuals r of csrc/loss_terms.h, kappa_rgb =
  *   k_rgb w_rgb, kappa_d = k_d and irls_delta >= 0 (iteratively reweighted least squares for the L1 terms):
  *     seed s = kappa (dr/dC) clamp(r / delta, -1, 1)   (delta == 0: the backward's own seed, bit for bit)
  *     curvature h = kappa (dr/dC)^2 / max(|r|, delta)  (0 where the gate is closed, or r == 0 with delta == 0)
@@ -500,9 +500,27 @@ int gsaj_pose_adam_step_batch(int K, const float *dL_dtau, const float *dL_dexpo
  *   W2C <- Exp(tau) W2C is applied with the operations of gsaj_pose_adam_step, the camera matrices are refreshed, tau, |tau| and
  *   converged = |tau| < converged_threshold written.  A non-positive pivot raises lambda and leaves the pose unchanged for the
  *   call (tau = 0, converged = 0).  skip: as in gsaj_pose_adam_step -- a non-zero word (aborted frame) changes nothing.
- *   GSAJ_ERR_INVALID_ARGUMENT unless nu > 1 and 0 < lambda_min <= lambda_init <= lambda_max. */
+ *   GSAJ_ERR_INVALID_ARGUMENT unless nu > 1 and 0 < lambda_min <= lambda_init <= lambda_max.
+ *
+ * The joint form -- the exposure solved together with the pose.  The unknowns are x = [rho(3), theta(3), a, b]; with the residual
+ * r_ch = m (e^a C_ch + b - gt_ch), dr_ch = m e^a (dC_ch + C_ch da + db / e^a): relative to the rendered colour the exposure
+ * parameters are two more Jacobian columns, J8[ch] = [J[ch][0..5], C_ch, 1 / e^a] (C: the forward's image; both 0 in the depth
+ * row), under the SAME seeds s and curvatures h as above (the derivative of the opacity weight is neglected, as there).
+ * gsaj_rasterize_pose_jacobian_loss8 -- the arguments of gsaj_rasterize_pose_jacobian_loss;
+ *   gn8_partials [gsaj_pose_jac_partial_rows(W, H)][GSAJ_GN8_PARTIAL_FLOATS]: [0:36) H8 = sum h J8^T J8, the upper triangle by
+ *   rows, [36:44) g8 = sum s J8, [44] loss, [45] L_rgb, [46] L_depth, [47:49) the exposure sums of the fused forward, [49:64) zero.
+ *   GSAJ_LOSS_NO_EXPOSURE or a NULL exposure pointer is GSAJ_ERR_INVALID_ARGUMENT, as are the argument errors of the 6-form.
+ * gsaj_pose_gn8_step -- gsaj_pose_gn_step on 8 unknowns.  gn8_state: GSAJ_GN8_STATE_FLOATS floats; [0:104) as gn_state, then
+ *     [104:140) accepted H8   [140:148) accepted g8   [148:150) accepted exposure a, b   (and [78:80) the exposure step x[6], x[7])
+ *   Initialise as gn_state.  Accept saves the exposure [33:35) with the pose, reject restores it with the pose.  The 8x8 system
+ *   (H8 + lambda diag(H8) + eps I) x = -g8 (eps from the mean of the 8 diagonal elements) is solved by Cholesky in fp64; W2C <-
+ *   Exp(x[0:6]) W2C, a <- a + x[6], b <- b + x[7]; converged = |tau| < converged_threshold and max(|x[6]|, |x[7]|) <
+ *   converged_threshold.  A non-positive pivot raises lambda and changes neither pose nor exposure; a non-zero skip word changes
+ *   nothing. */
 #define GSAJ_GN_PARTIAL_FLOATS 32
 #define GSAJ_GN_STATE_FLOATS 136
+#define GSAJ_GN8_PARTIAL_FLOATS 64
+#define GSAJ_GN8_STATE_FLOATS 152
 size_t gsaj_pose_jac_workspace_bytes(int P, int W, int H);
 int gsaj_pose_jac_partial_rows(int W, int H);
 int gsaj_rasterize_pose_jacobian(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D, const float *shs,
@@ -526,6 +544,19 @@ int gsaj_gn_state_floats(void);
 int gsaj_pose_gn_step(const float *gn_partials, int n_partials, float lambda_init, float nu, float lambda_min, float lambda_max,
                       float converged_threshold, const float *projection_matrix, float *gn_state, const uint32_t *skip,
                       void *stream);
+int gsaj_rasterize_pose_jacobian_loss8(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
+                                       const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                       const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
+                                       const float *projmatrix, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                       float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
+                                       void *jac_ws, int loss_flags, float alpha, float rgb_boundary_threshold, const float *color,
+                                       const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
+                                       const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, float irls_delta,
+                                       float *gn8_partials, float *jac_out /*NULL ok*/, void *stream);
+int gsaj_gn8_state_floats(void);
+int gsaj_pose_gn8_step(const float *gn8_partials, int n_partials, float lambda_init, float nu, float lambda_min, float lambda_max,
+                       float converged_threshold, const float *projection_matrix, float *gn8_state, const uint32_t *skip,
+                       void *stream);
 
 /* ---- distCUDA2 -------------------------------------------------------------------
  * simple_knn._C.distCUDA2 (reference submodules/simple-knn/simple_knn.cu:45-220, spatial.cu): for P points

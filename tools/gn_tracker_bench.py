@@ -6,7 +6,11 @@ value and rotation error below 0.02), on that test's 160x120 scene (three consec
 frame's true pose) and on the cfg2 frame (640x480, 50 000 Gaussians, started 1.2 cm / 0.3 degrees off).
 
 Finding the first iteration that meets the criterion reads the pose back after every iteration; the timings are taken in separate,
-unobserved windows.  usage: gn_tracker_bench.py [out.json] [window=50] [repeats=7]"""
+unobserved windows.  usage: gn_tracker_bench.py [--solve-exposure] [out.json] [window=50] [repeats=7]
+
+--solve-exposure: every ground-truth frame is turned into e^a* C + b* with (a*, b*) = EXPOSURE and every tracker starts from exposure
+(0, 0).  A third tracker joins the two, GaussNewtonTracker(solve_exposure=True); its criterion is the pose criterion AND max(|a - a*|,
+|b - b*|) below 0.35 x its starting value.  The other two keep the pose criterion; the exposure error each ends with is reported."""
 import json
 import math
 import os
@@ -25,6 +29,7 @@ from gsaj.tracking import DeviceTracker  # noqa: E402
 DEV = torch.device("cuda:0")
 T = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device=DEV)  # noqa: E731
 ADAM = dict(lr_rot=0.003, lr_trans=0.002)   # the learning rates of tests/test_gpu_track_and_map.py
+EXPOSURE = (0.2, -0.05)                      # --solve-exposure: (a*, b*) of the ground-truth frames
 
 
 def errors(w2c, true):
@@ -32,15 +37,21 @@ def errors(w2c, true):
     return float(np.abs(w2c[:3, 3] - true[:3, 3]).max()), float(np.abs(w2c[:3, :3] @ true[:3, :3].T - np.eye(3)).max())
 
 
-def first_hit(tr, pose, true, before, budget):
+def exposure_error(e, exposure):
+    return float(np.abs(np.asarray(e, np.float64).reshape(2) - np.asarray(exposure)).max())
+
+
+def first_hit(tr, pose, true, before, budget, exposure=None, exposure_of=None):
     """The iteration at which the criterion first holds for `pose()` (None: not within the budget), the trace of the translation
-    error over its starting value through the whole budget, and the rotation error at its end."""
+    error over its starting value through the whole budget, and the rotation error at its end.  exposure_of (with exposure = (a*, b*)):
+    the criterion also asks for the exposure error of `exposure_of()` below 0.35 x its starting value, max(|a*|, |b*|)."""
     trace, hit, rot = [], None, 0.0
     for it in range(1, budget + 1):
         tr.iterate(1)
         after, rot = errors(pose().cpu().numpy(), true)
         trace.append(round(after / before, 4))
-        if hit is None and after < 0.35 * before and rot < 0.02:
+        ok = exposure_of is None or exposure_error(exposure_of().cpu().numpy(), exposure) < 0.35 * max(abs(exposure[0]), abs(exposure[1]))
+        if hit is None and after < 0.35 * before and rot < 0.02 and ok:
             hit = it
     return hit, trace, rot
 
@@ -61,7 +72,7 @@ def ms_per_iteration(tr, reset, window, repeats):
     return float(np.median(out)), float(min(out)), float(max(out))
 
 
-def case(name, cam_true, w2c_start, sc, gt, window, repeats, budgets=(100, 30), gn_kw=None):
+def case(name, cam_true, w2c_start, sc, gt, window, repeats, budgets=(100, 30), gn_kw=None, exposure=None):
     P, W, H, M = sc["means3D"].shape[0], cam_true["W"], cam_true["H"], sc["shs"].shape[1]
     g = dict(means3D=T(sc["means3D"]), opacities=T(sc["opacities"]), shs=T(sc["shs"]), scales=T(sc["scales"]), rotations=T(sc["rotations"]),
              sh_degree=3)
@@ -72,11 +83,21 @@ def case(name, cam_true, w2c_start, sc, gt, window, repeats, budgets=(100, 30), 
     adam = DeviceTracker(*args, alpha=0.9, **ADAM, **g)
     gnt = GaussNewtonTracker(*args, alpha=0.9, **(gn_kw or {}), **g)
     out = dict(workload=name, P=P, W=W, H=H, start_translation_error=before)
-    for key, tr, pose, budget in (("adam", adam, lambda: adam.w2c, budgets[0]), ("gauss_newton", gnt, lambda: gnt.accepted_w2c, budgets[1])):
+    trackers = [("adam", adam, lambda: adam.w2c, budgets[0], None), ("gauss_newton", gnt, lambda: gnt.accepted_w2c, budgets[1], None)]
+    if exposure is not None:
+        gt = (math.exp(exposure[0]) * gt[0] + exposure[1], gt[1])
+        gn8 = GaussNewtonTracker(*args, alpha=0.9, solve_exposure=True, **(gn_kw or {}), **g)
+        trackers.append(("gauss_newton_joint", gn8, lambda: gn8.accepted_w2c, budgets[1], lambda: gn8.accepted_exposure))
+        out["exposure"] = list(exposure)
+    for key, tr, pose, budget, exposure_of in trackers:
         reset = lambda tr=tr: tr.set_frame(gt[0], gt[1], w2c=w2c_start)  # noqa: E731
         reset()
-        hit, trace, rot = first_hit(tr, pose, true, before, budget)
-        lm = {k: float(v) for k, v in tr.lm.items() if k in ("lam", "accepted", "rejected")} if key == "gauss_newton" else {}
+        hit, trace, rot = first_hit(tr, pose, true, before, budget, exposure, exposure_of)
+        lm = {k: float(v) for k, v in tr.lm.items() if k in ("lam", "accepted", "rejected")} if key != "adam" else {}
+        if exposure is not None:   # what each tracker's exposure ends at (the 6-form's never moves)
+            src = getattr(tr, "pose", tr)   # (DeviceTracker keeps its exposure in its PoseTracker)
+            e = exposure_of() if exposure_of else torch.cat([src.exposure_a.reshape(1), src.exposure_b.reshape(1)])
+            lm["exposure_error_at_budget"] = round(exposure_error(e.cpu().numpy(), exposure), 6)
         med, lo, hi = ms_per_iteration(tr, reset, window, repeats)
         out[key] = dict(iterations_to_criterion=hit, ms_per_iteration=round(med, 4), ms_min=round(lo, 4), ms_max=round(hi, 4),
                         ms_to_criterion=None if hit is None else round(hit * med, 3), budget=budget, error_ratio_at_budget=trace[-1],
@@ -86,9 +107,11 @@ def case(name, cam_true, w2c_start, sc, gt, window, repeats, budgets=(100, 30), 
 
 
 def main():
-    path = sys.argv[1] if len(sys.argv) > 1 else None
-    window = int(sys.argv[2]) if len(sys.argv) > 2 else 50
-    repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 7
+    argv = [a for a in sys.argv[1:] if a != "--solve-exposure"]
+    exposure = EXPOSURE if len(argv) < len(sys.argv) - 1 else None
+    path = argv[0] if len(argv) > 0 else None
+    window = int(argv[1]) if len(argv) > 1 else 50
+    repeats = int(argv[2]) if len(argv) > 2 else 7
     res = []
     # the scene of tests/test_gpu_track_and_map.py: frame k started from frame k - 1's true pose
     W, H, F = 160, 120, 140.0
@@ -105,7 +128,7 @@ def main():
 
     for k in range(1, 4):
         res.append(case("160x120, 3000 Gaussians, frame %d from frame %d's pose" % (k, k - 1), cams[k],
-                        np.ascontiguousarray(cams[k - 1]["viewmatrix"].T), sc, render(fc, cams[k], g), window, repeats))
+                        np.ascontiguousarray(cams[k - 1]["viewmatrix"].T), sc, render(fc, cams[k], g), window, repeats, exposure=exposure))
     cam2, sc2 = syn.config_scene("cfg2")
     fc2 = FrameContext(sc2["means3D"].shape[0], cam2["W"], cam2["H"], 16, DEV)
     g2 = [T(sc2[k]) for k in ("means3D", "opacities", "shs", "scales", "rotations")]
@@ -114,8 +137,10 @@ def main():
     d = np.eye(4)
     d[:3, :3] = np.array([[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
     d[:3, 3] = [0.012, -0.008, 0.01]
-    res.append(case("cfg2 (640x480, 50 000 Gaussians)", cam2, (d @ start).astype(np.float32), sc2, render(fc2, cam2, g2), window, repeats))
-    text = json.dumps(dict(device=torch.cuda.get_device_name(0), window=window, repeats=repeats, cases=res), indent=1)
+    res.append(case("cfg2 (640x480, 50 000 Gaussians)", cam2, (d @ start).astype(np.float32), sc2, render(fc2, cam2, g2), window, repeats,
+                    exposure=exposure))
+    text = json.dumps(dict(device=torch.cuda.get_device_name(0), window=window, repeats=repeats, solve_exposure=exposure is not None, cases=res),
+                      indent=1)
     print(text)
     if path:
         with open(path, "w") as fh:
