@@ -434,7 +434,7 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_scatter_instances(int P, int gx, 
       }                                                                                              \
     }                                                                                                \
   }
-  if (!use_lds) {  // (more than 8 x 8192 tiles: beyond 16 384 x 2048 pixels)
+  if (!use_lds) {  // (more than SCAT_LDS_TILES class-local tiles, ceil(gy / 8) * gx > 4096: e.g. beyond 4096 x 2048 pixels)
     SCAT_FOR_EACH_TILE({ inst_id[im.tile_offset[t] + atomicAdd(&im.tile_cursor[t], 1u)] = id; })
     return;
   }
