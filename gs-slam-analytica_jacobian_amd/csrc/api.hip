@@ -105,15 +105,209 @@ size_t gsaj_binning_workspace_bytes(int R) {
 
 static char *align_base(void *p) { return reinterpret_cast<char *>(gsaj_align(reinterpret_cast<size_t>(p))); }
 
+// ---- argument groups of the rasteriser entry points (host only; DESIGN.md "Argument groups") --------------------------------
+// Every extern "C" rasteriser function fills these once from its own parameters -- members in the order of the ABI, so that an
+// initialiser reads like the signature -- and the functions behind them take the groups.  Where a launcher's struct already is the
+// group it is filled directly: BwdParams holds the twelve gradient outputs and radii, FusedLoss the loss arguments, JacOut the
+// Jacobian walk's outputs.
+struct Scene {  // the Gaussian map (colors_precomp is in the splat rows once the forward has run: later calls do not read it)
+  int P, D, M;
+  const float *means3D, *shs, *colors_precomp, *opacities, *scales;
+  float scale_modifier;
+  const float *rotations, *cov3D_precomp;
+};
+struct Views {  // K views of it: viewmatrix / projmatrix [K,16], campos [K,3]; the single-frame entry points have K = 1
+  int K;
+  const float *bg;
+  int W, H;
+  const float *viewmatrix, *projmatrix, *projmatrix_raw, *campos;
+  float tanfovx, tanfovy;
+};
+struct Arenas {  // the workspaces as the caller handed them over (per view of a batched call: K consecutive blocks each)
+  void *geom, *binning;
+  size_t binning_bytes;     // what the caller says the binning arena holds (a backward takes no size: the forward checked it)
+  int instances;            // what the binning arena is carved for: R (synchronous forms), the capacity (asynchronous and batched)
+  int tile_list_capacity;   // asynchronous forms: the tile list the LDS sort is sized for (0: SORT_CAP)
+  void *image;
+};
+struct FwdOut {  // what a forward writes: images [K,3,H,W] / [K,1,H,W], radii / n_touched [K,P]; fused forms: scalars [K,5], dexposure [K,2]
+  float *color, *depth, *opacity;
+  int *radii, *n_touched;
+  float *scalars, *dexposure;
+};
+struct PixelSeeds {  // where the reverse compositor's dL/dpixel comes from: two images, or (fl != NULL) the loss, derived per pixel
+  const float *dL_dpix, *dL_dpix_depth;
+  const FusedLoss *fl;
+};
+struct GnSums {  // what becomes of the Jacobian walk's partial rows: the explicit form sums them into H_out / g_out; the fused form
+  float *H_out, *g_out;  // (fl != NULL) leaves them in JacOut.partials for gsaj_pose_gn_step / gsaj_pose_gn8_step (joint)
+  FusedLoss *fl;
+  bool joint;
+};
+struct Carved { GeomWS g; BinWS b; ImageWS im; ViewStrides vs; };
+static const size_t SIZE_NOT_GIVEN = SIZE_MAX;  // Arenas.binning_bytes of the calls that take no size: carve()'s size check always passes
+
+// The one place the three workspaces are carved.  batch_K == 0, the single-frame calls: from the aligned base of whatever the caller
+// gave, zero strides.  batch_K > 0, the batched calls: the caller's blocks must be aligned themselves (view v's block is v strides on)
+// and K binning blocks must fit.
+static int carve(const Arenas &a, int P, int W, int H, int batch_K, Carved *c) {
+  c->vs = ViewStrides{0, 0, 0};
+  if (batch_K > 0) {
+    c->vs.geom = gsaj_geom_workspace_bytes(P);
+    c->vs.image = gsaj_image_workspace_bytes(W, H);
+    c->vs.bin = gsaj_binning_workspace_bytes(a.instances);
+    if (((uintptr_t)a.geom | (uintptr_t)a.binning | (uintptr_t)a.image) & 255) {
+      gsaj_set_error("batched entry points need 256-byte aligned workspaces");
+      return GSAJ_ERR_INVALID_ARGUMENT;
+    }
+    if (a.binning_bytes < c->vs.bin * (size_t)batch_K) {
+      gsaj_set_error("binning workspace smaller than K x gsaj_binning_workspace_bytes(capacity=%d)", a.instances);
+      return GSAJ_ERR_WORKSPACE_TOO_SMALL;
+    }
+  }
+  geom_carve(align_base(a.geom), (size_t)P, &c->g);
+  image_carve(align_base(a.image), W, H, &c->im);
+  bin_carve(align_base(a.binning), (size_t)a.instances, &c->b);
+  return GSAJ_OK;
+}
+
+// what every forward asks of the map after its own required pointers
+static int check_scene(const char *who, const Scene &sc, const float *campos) {
+  if ((sc.shs == nullptr) == (sc.colors_precomp == nullptr)) {
+    gsaj_set_error("Please provide excatly one of either SHs or precomputed colors!");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if (((sc.scales == nullptr || sc.rotations == nullptr) && sc.cov3D_precomp == nullptr) ||
+      ((sc.scales != nullptr || sc.rotations != nullptr) && sc.cov3D_precomp != nullptr)) {
+    gsaj_set_error("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if (sc.shs && (!campos || sc.M <= 0 || sc.D < 0 || (sc.D + 1) * (sc.D + 1) > sc.M || sc.D > 3)) {
+    gsaj_set_error("%s: SH degree %d needs %d coefficients, got M=%d", who, sc.D, (sc.D + 1) * (sc.D + 1), sc.M);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  return GSAJ_OK;
+}
+
+static int sort_cap_of(int tile_list_capacity) {
+  return (tile_list_capacity > 0 && tile_list_capacity < SORT_CAP) ? tile_list_capacity : SORT_CAP;
+}
+
+static FwdParams fwd_params(const Scene &sc, const Views &v, int prefiltered, const Arenas &a) {
+  FwdParams p;
+  p.P = sc.P; p.D = sc.D; p.M = sc.M; p.W = v.W; p.H = v.H;
+  p.means3D = sc.means3D; p.shs = sc.shs; p.colors_precomp = sc.colors_precomp; p.opacities = sc.opacities;
+  p.scales = sc.scales; p.rotations = sc.rotations; p.cov3D_precomp = sc.cov3D_precomp;
+  p.viewmatrix = v.viewmatrix; p.projmatrix = v.projmatrix; p.campos = v.campos;
+  p.scale_modifier = sc.scale_modifier; p.tanfovx = v.tanfovx; p.tanfovy = v.tanfovy;
+  p.focal_y = v.H / (2.0f * v.tanfovy);
+  p.focal_x = v.W / (2.0f * v.tanfovx);
+  p.prefiltered = prefiltered;
+  p.grid_x = (v.W + TILE - 1) / TILE; p.grid_y = (v.H + TILE - 1) / TILE;
+  p.capacity = a.instances;
+  p.sort_cap = sort_cap_of(a.tile_list_capacity);
+  p.views = v.K;
+  return p;
+}
+
+// p arrives with what the caller gave it directly: the twelve gradient outputs (none for the Jacobian walk) and radii
+static void bwd_params(BwdParams *p, const Scene &sc, const Views &v, const GeomWS &g) {
+  p->P = sc.P; p->D = sc.D; p->M = sc.M; p->W = v.W; p->H = v.H;
+  p->means3D = sc.means3D; p->shs = sc.shs; p->scales = sc.scales; p->rotations = sc.rotations;
+  p->cov3Ds = sc.cov3D_precomp ? sc.cov3D_precomp : g.cov3D;
+  p->viewmatrix = v.viewmatrix; p->projmatrix = v.projmatrix; p->projmatrix_raw = v.projmatrix_raw; p->campos = v.campos;
+  p->scale_modifier = sc.scale_modifier; p->tanfovx = v.tanfovx; p->tanfovy = v.tanfovy;
+  p->focal_y = v.H / (2.0f * v.tanfovy);
+  p->focal_x = v.W / (2.0f * v.tanfovx);
+  p->grid_x = (v.W + TILE - 1) / TILE; p->grid_y = (v.H + TILE - 1) / TILE;
+  if (!p->radii) p->radii = g.internal_radii;
+}
+
+// the loss arguments as the entry points name them (the backward forms add the forward's images themselves)
+static FusedLoss loss_args(int loss_flags, float alpha, float rgb_boundary_threshold, const float *gt_color, const float *gt_depth,
+                           const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, int exposure_stride = 1) {
+  FusedLoss fl{};
+  fl.flags = loss_flags; fl.alpha = alpha; fl.rgb_thr = rgb_boundary_threshold;
+  fl.gt_color = gt_color; fl.gt_depth = gt_depth; fl.grad_mask = grad_mask; fl.exp_a = exposure_a; fl.exp_b = exposure_b;
+  fl.exp_stride = exposure_stride;
+  return fl;
+}
+
+// fl arrives with the caller's loss arguments as given (K: the views of a batched call).  They are checked, before anything is
+// launched; then the pointers the flags rule out are nulled, so that the kernels' per-view shifts (fused_loss_view) leave them alone.
+// No kernel reads them in those cases: gt_depth and depth are read behind `L.mono ? 0.f : ...` only, and exp_a / exp_b in
+// loss_consts behind GSAJ_LOSS_NO_EXPOSURE only (loss_terms.h).
+static int fused_loss(const char *who, FusedLoss *fl, int K = 1) {
+  if (K <= 0) {
+    gsaj_set_error("%s: invalid argument (K=%d)", who, K);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  const bool mono = fl->flags & GSAJ_LOSS_MONOCULAR, noexp = fl->flags & GSAJ_LOSS_NO_EXPOSURE;
+  if ((fl->flags & GSAJ_LOSS_COMPUTE_LOSS) || !fl->gt_color || (!mono && !fl->gt_depth) || (!noexp && (!fl->exp_a || !fl->exp_b)) ||
+      fl->exp_stride < 1) {
+    gsaj_set_error("%s: invalid loss arguments (flags=%d, exposure stride %d; GSAJ_LOSS_COMPUTE_LOSS has no fused form)", who, fl->flags,
+                   fl->exp_stride);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if (mono) fl->gt_depth = fl->depth = nullptr;
+  if (noexp) fl->exp_a = fl->exp_b = nullptr;
+  return GSAJ_OK;
+}
+
+// the backward forms of the fused loss read the images the forward wrote
+static int check_loss_images(const char *who, const FusedLoss &fl) {
+  if (!fl.color || !fl.opacity || (!(fl.flags & GSAJ_LOSS_MONOCULAR) && !fl.depth)) {
+    gsaj_set_error("%s: the forward's color / depth / opacity images are required", who);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  return GSAJ_OK;
+}
+
+// the forward forms of the fused loss write these
+static int check_loss_outputs(const char *who, const FwdOut &o, const void *loss_ws) {
+  if (!o.scalars || !loss_ws) {
+    gsaj_set_error("%s: out_scalars and loss_ws are required", who);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  return GSAJ_OK;
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------------------
+// checks, carve (all three workspaces, for whoever goes on) and the per-Gaussian kernels of one frame
+static int preprocess_frame(const Scene &sc, const Views &v, int prefiltered, const FwdOut &o, const Arenas &a, Carved *c,
+                            hipStream_t s) {
+  if (sc.P <= 0 || v.W <= 0 || v.H <= 0 || !sc.means3D || !sc.opacities || !v.viewmatrix || !v.projmatrix || !a.geom || !a.image ||
+      !o.n_touched) {
+    gsaj_set_error("gsaj_forward_preprocess: invalid argument (P=%d W=%d H=%d)", sc.P, v.W, v.H);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  int rc = check_scene("gsaj_forward_preprocess", sc, v.campos);
+  if (rc != GSAJ_OK) return rc;
+  carve(a, sc.P, v.W, v.H, 0, c);
+  return launch_preprocess(fwd_params(sc, v, prefiltered, a), o.radii ? o.radii : c->g.internal_radii, o.n_touched, c->g, c->im, c->vs, s);
+}
+
+// tile binning, the compositor and (fl != NULL) the loss sums of v.K carved frames
+static int composite(int P, const Views &v, int sort_cap, int flags, const FwdOut &o, const Carved &c, const FusedLoss *fl, hipStream_t s) {
+  const int gx = (v.W + TILE - 1) / TILE, gy = (v.H + TILE - 1) / TILE;
+  int rc = launch_tile_binning(P, sort_cap, (flags & GSAJ_FWD_RECORDS_FP16) ? 1 : 0, gx, gy, c.g, c.b, c.im, v.K, c.vs, s);
+  if (rc != GSAJ_OK) return rc;
+  rc = launch_render_forward(P, v.W, v.H, gx, gy, v.bg, c.g, c.b, c.im, o.color, o.depth, o.opacity, o.n_touched, v.K, c.vs, s, fl);
+  if (rc != GSAJ_OK || !fl) return rc;
+  return launch_loss_finalize(*fl, gsaj_fwd_loss_slots(v.W, v.H), v.W, v.H, c.im.counters + 4, o.scalars, s, v.K, c.vs.image, o.dexposure);
+}
+
 int gsaj_forward_preprocess(int P, int D, int M, int W, int H, const float *means3D, const float *shs,
                             const float *colors_precomp, const float *opacities, const float *scales,
                             float scale_modifier, const float *rotations, const float *cov3D_precomp,
                             const float *viewmatrix, const float *projmatrix, const float *campos, float tanfovx,
                             float tanfovy, int prefiltered, int *radii, int *n_touched, void *geom_ws, void *image_ws,
                             void *stream) {
-  return gsaj_forward_preprocess_cap(P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                                     cov3D_precomp, viewmatrix, projmatrix, campos, tanfovx, tanfovy, prefiltered, radii,
-                                     n_touched, geom_ws, image_ws, 0, 0, stream);
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, nullptr, W, H, viewmatrix, projmatrix, nullptr, campos, tanfovx, tanfovy};
+  const FwdOut o{nullptr, nullptr, nullptr, radii, n_touched, nullptr, nullptr};
+  Carved c;
+  return preprocess_frame(sc, v, prefiltered, o, Arenas{geom_ws, nullptr, 0, 0, 0, image_ws}, &c, (hipStream_t)stream);
 }
 
 int gsaj_forward_preprocess_cap(int P, int D, int M, int W, int H, const float *means3D, const float *shs,
@@ -122,42 +316,12 @@ int gsaj_forward_preprocess_cap(int P, int D, int M, int W, int H, const float *
                                 const float *viewmatrix, const float *projmatrix, const float *campos, float tanfovx,
                                 float tanfovy, int prefiltered, int *radii, int *n_touched, void *geom_ws, void *image_ws,
                                 int capacity, int tile_list_capacity, void *stream) {
-  if (P <= 0 || W <= 0 || H <= 0 || !means3D || !opacities || !viewmatrix || !projmatrix || !geom_ws || !image_ws ||
-      !n_touched) {
-    gsaj_set_error("gsaj_forward_preprocess: invalid argument (P=%d W=%d H=%d)", P, W, H);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if ((shs == nullptr) == (colors_precomp == nullptr)) {
-    gsaj_set_error("Please provide excatly one of either SHs or precomputed colors!");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (((scales == nullptr || rotations == nullptr) && cov3D_precomp == nullptr) ||
-      ((scales != nullptr || rotations != nullptr) && cov3D_precomp != nullptr)) {
-    gsaj_set_error("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (shs && (!campos || M <= 0 || D < 0 || (D + 1) * (D + 1) > M || D > 3)) {
-    gsaj_set_error("gsaj_forward_preprocess: SH degree %d needs %d coefficients, got M=%d", D, (D + 1) * (D + 1), M);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  GeomWS g;
-  geom_carve(align_base(geom_ws), (size_t)P, &g);
-  FwdParams p;
-  p.P = P; p.D = D; p.M = M; p.W = W; p.H = H;
-  p.means3D = means3D; p.shs = shs; p.colors_precomp = colors_precomp; p.opacities = opacities;
-  p.scales = scales; p.rotations = rotations; p.cov3D_precomp = cov3D_precomp;
-  p.viewmatrix = viewmatrix; p.projmatrix = projmatrix; p.campos = campos;
-  p.scale_modifier = scale_modifier; p.tanfovx = tanfovx; p.tanfovy = tanfovy;
-  p.focal_y = H / (2.0f * tanfovy);
-  p.focal_x = W / (2.0f * tanfovx);
-  p.prefiltered = prefiltered;
-  p.grid_x = (W + TILE - 1) / TILE; p.grid_y = (H + TILE - 1) / TILE;
-  p.capacity = capacity;
-  p.sort_cap = (tile_list_capacity > 0 && tile_list_capacity < SORT_CAP) ? tile_list_capacity : SORT_CAP;
-  p.views = 1;
-  ImageWS im;
-  image_carve(align_base(image_ws), W, H, &im);
-  return launch_preprocess(p, radii ? radii : g.internal_radii, n_touched, g, im, ViewStrides{0, 0, 0}, (hipStream_t)stream);
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, nullptr, W, H, viewmatrix, projmatrix, nullptr, campos, tanfovx, tanfovy};
+  const FwdOut o{nullptr, nullptr, nullptr, radii, n_touched, nullptr, nullptr};
+  Carved c;
+  return preprocess_frame(sc, v, prefiltered, o, Arenas{geom_ws, nullptr, 0, capacity, tile_list_capacity, image_ws}, &c,
+                          (hipStream_t)stream);
 }
 
 int gsaj_forward_num_rendered(int W, int H, const void *image_ws, void *stream, int *num_rendered, int *max_tile_list) {
@@ -235,36 +399,36 @@ int gsaj_set_tile_band(int W, int H, void *image_ws, int tile_row_begin, int til
   return GSAJ_OK;
 }
 
-int gsaj_forward_render(int P, int R, int max_tile_list, int W, int H, const float *bg, const float *colors_precomp,
-                        const int *radii,
-                        void *geom_ws, void *binning_ws, size_t binning_ws_bytes, void *image_ws, float *out_color,
-                        float *out_depth, float *out_opacity, int *n_touched, int flags, void *stream) {
-  if (P <= 0 || R < 0 || W <= 0 || H <= 0 || !bg || !geom_ws || !binning_ws || !image_ws || !out_color || !out_depth ||
-      !out_opacity || !n_touched) {
+// the synchronous second half: the arena is carved for the R the caller read back
+static int render_frame(int P, const Views &v, int max_tile_list, int flags, const FwdOut &o, const Arenas &a, hipStream_t s) {
+  const int R = a.instances;
+  if (P <= 0 || R < 0 || v.W <= 0 || v.H <= 0 || !v.bg || !a.geom || !a.binning || !a.image || !o.color || !o.depth ||
+      !o.opacity || !o.n_touched) {
     gsaj_set_error("gsaj_forward_render: invalid argument");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   const size_t need = gsaj_binning_workspace_bytes(R);
-  if (binning_ws_bytes < need) {
-    gsaj_set_error("binning workspace too small: have %zu bytes, need %zu for R=%d", binning_ws_bytes, need, R);
+  if (a.binning_bytes < need) {
+    gsaj_set_error("binning workspace too small: have %zu bytes, need %zu for R=%d", a.binning_bytes, need, R);
     return GSAJ_ERR_WORKSPACE_TOO_SMALL;
   }
-  hipStream_t s = (hipStream_t)stream;
-  GeomWS g;
-  geom_carve(align_base(geom_ws), (size_t)P, &g);
-  ImageWS im;
-  image_carve(align_base(image_ws), W, H, &im);
-  BinWS b;
-  bin_carve(align_base(binning_ws), (size_t)R, &b);
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  (void)colors_precomp;  // (already in the splat rows: gsaj_forward_preprocess)
-  (void)radii;
+  Carved c;
+  carve(a, P, v.W, v.H, 0, &c);
   // per-tile lists sorted by the tile's workgroup: in one LDS pass when the list fits the capacity sized from max_tile_list,
   // in LDS-sized chunks + merge passes when it does not (max_tile_list < 0 forces that path with the smallest capacity)
   const int sort_cap = max_tile_list < 0 ? 128 : (max_tile_list > SORT_CAP ? SORT_CAP : max_tile_list);
-  int rc;
-  if ((rc = launch_tile_binning(P, sort_cap, (flags & GSAJ_FWD_RECORDS_FP16) ? 1 : 0, gx, gy, g, b, im, 1, ViewStrides{0, 0, 0}, s)) != GSAJ_OK) return rc;
-  return launch_render_forward(P, W, H, gx, gy, bg, g, b, im, out_color, out_depth, out_opacity, n_touched, 1, ViewStrides{0, 0, 0}, s);
+  return composite(P, v, sort_cap, flags, o, c, nullptr, s);
+}
+
+int gsaj_forward_render(int P, int R, int max_tile_list, int W, int H, const float *bg, const float *colors_precomp,
+                        const int *radii,
+                        void *geom_ws, void *binning_ws, size_t binning_ws_bytes, void *image_ws, float *out_color,
+                        float *out_depth, float *out_opacity, int *n_touched, int flags, void *stream) {
+  (void)colors_precomp;  // (already in the splat rows: gsaj_forward_preprocess)
+  (void)radii;
+  const Views v{1, bg, W, H, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f};
+  const FwdOut o{out_color, out_depth, out_opacity, nullptr, n_touched, nullptr, nullptr};
+  return render_frame(P, v, max_tile_list, flags, o, Arenas{geom_ws, binning_ws, binning_ws_bytes, R, 0, image_ws}, (hipStream_t)stream);
 }
 
 int gsaj_rasterize_forward(int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
@@ -274,55 +438,39 @@ int gsaj_rasterize_forward(int P, int D, int M, const float *bg, int W, int H, c
                            float tanfovy, int prefiltered, float *out_color, float *out_depth, float *out_opacity,
                            int *radii, int *n_touched, void *geom_ws, void *binning_ws, size_t binning_ws_bytes,
                            void *image_ws, int *num_rendered_out, int flags, void *stream) {
-  int rc = gsaj_forward_preprocess(P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
-                                   rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
-                                   prefiltered, radii, n_touched, geom_ws, image_ws, stream);
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, bg, W, H, viewmatrix, projmatrix, nullptr, campos, tanfovx, tanfovy};
+  const FwdOut o{out_color, out_depth, out_opacity, radii, n_touched, nullptr, nullptr};
+  Arenas a{geom_ws, binning_ws, binning_ws_bytes, 0, 0, image_ws};
+  Carved c;
+  int rc = preprocess_frame(sc, v, prefiltered, o, a, &c, (hipStream_t)stream);
   if (rc != GSAJ_OK) return rc;
-  int R = 0, max_tile = 0;
-  rc = gsaj_forward_num_rendered(W, H, image_ws, stream, &R, &max_tile);
-  if (num_rendered_out) *num_rendered_out = R;
+  int max_tile = 0;
+  rc = gsaj_forward_num_rendered(W, H, image_ws, stream, &a.instances, &max_tile);
+  if (num_rendered_out) *num_rendered_out = a.instances;
   if (rc != GSAJ_OK) return rc;
-  rc = gsaj_forward_render(P, R, max_tile, W, H, bg, colors_precomp, radii, geom_ws, binning_ws, binning_ws_bytes, image_ws,
-                           out_color, out_depth, out_opacity, n_touched, flags, stream);
-  return rc == GSAJ_OK ? R : rc;
+  rc = render_frame(P, v, max_tile, flags, o, a, (hipStream_t)stream);
+  return rc == GSAJ_OK ? a.instances : rc;
 }
 
-static int forward_async_impl(int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
-                              const float *colors_precomp, const float *opacities, const float *scales,
-                              float scale_modifier, const float *rotations, const float *cov3D_precomp,
-                              const float *viewmatrix, const float *projmatrix, const float *campos, float tanfovx,
-                              float tanfovy, int prefiltered, float *out_color, float *out_depth, float *out_opacity,
-                              int *radii, int *n_touched, void *geom_ws, void *binning_ws, size_t binning_ws_bytes,
-                              int capacity, int tile_list_capacity, void *image_ws, int flags, void *stream, const FusedLoss *fl,
-                              float *out_scalars) {
-  if (capacity <= 0 || !binning_ws || !bg || !out_color || !out_depth || !out_opacity || !n_touched) {
+// fl != NULL: the loss-fused form (partials = the aligned loss workspace)
+static int forward_async(const Scene &sc, const Views &v, int prefiltered, int flags, const FwdOut &o, const Arenas &a,
+                         const FusedLoss *fl, hipStream_t s) {
+  if (a.instances <= 0 || !a.binning || !v.bg || !o.color || !o.depth || !o.opacity || !o.n_touched) {
     gsaj_set_error("gsaj_rasterize_forward_async: invalid argument");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  if (binning_ws_bytes < gsaj_binning_workspace_bytes(capacity)) {
-    gsaj_set_error("binning workspace smaller than gsaj_binning_workspace_bytes(capacity=%d)", capacity);
+  if (a.binning_bytes < gsaj_binning_workspace_bytes(a.instances)) {
+    gsaj_set_error("binning workspace smaller than gsaj_binning_workspace_bytes(capacity=%d)", a.instances);
     return GSAJ_ERR_WORKSPACE_TOO_SMALL;
   }
-  int rc = gsaj_forward_preprocess_cap(P, D, M, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
-                                       rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tanfovx, tanfovy,
-                                       prefiltered, radii, n_touched, geom_ws, image_ws, capacity, tile_list_capacity, stream);
+  Carved c;
+  int rc = preprocess_frame(sc, v, prefiltered, o, a, &c, s);
   if (rc != GSAJ_OK) return rc;
   // No host round trip: grids do not depend on R, the arena is carved for `capacity` instances, and
   // k_scan aborts the frame on the device if R or a tile list does not fit (gsaj_forward_num_rendered
   // reports it whenever the caller chooses to look).
-  hipStream_t s = (hipStream_t)stream;
-  GeomWS g;
-  geom_carve(align_base(geom_ws), (size_t)P, &g);
-  ImageWS im;
-  image_carve(align_base(image_ws), W, H, &im);
-  BinWS b;
-  bin_carve(align_base(binning_ws), (size_t)capacity, &b);
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  const int sort_cap = (tile_list_capacity > 0 && tile_list_capacity < SORT_CAP) ? tile_list_capacity : SORT_CAP;
-  if ((rc = launch_tile_binning(P, sort_cap, (flags & GSAJ_FWD_RECORDS_FP16) ? 1 : 0, gx, gy, g, b, im, 1, ViewStrides{0, 0, 0}, s)) != GSAJ_OK) return rc;
-  if ((rc = launch_render_forward(P, W, H, gx, gy, bg, g, b, im, out_color, out_depth, out_opacity, n_touched, 1, ViewStrides{0, 0, 0}, s, fl)) != GSAJ_OK) return rc;
-  if (fl) return launch_loss_finalize(*fl, gsaj_fwd_loss_slots(W, H), W, H, im.counters + 4, out_scalars, s);
-  return GSAJ_OK;
+  return composite(sc.P, v, sort_cap_of(a.tile_list_capacity), flags, o, c, fl, s);
 }
 
 int gsaj_rasterize_forward_async(int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
@@ -332,22 +480,11 @@ int gsaj_rasterize_forward_async(int P, int D, int M, const float *bg, int W, in
                                  float tanfovy, int prefiltered, float *out_color, float *out_depth, float *out_opacity,
                                  int *radii, int *n_touched, void *geom_ws, void *binning_ws, size_t binning_ws_bytes,
                                  int capacity, int tile_list_capacity, void *image_ws, int flags, void *stream) {
-  return forward_async_impl(P, D, M, bg, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                            viewmatrix, projmatrix, campos, tanfovx, tanfovy, prefiltered, out_color, out_depth, out_opacity, radii,
-                            n_touched, geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws, flags, stream,
-                            nullptr, nullptr);
-}
-
-static int fused_loss_args(const char *who, int loss_flags, const float *gt_color, const float *gt_depth, const float *exposure_a,
-                           const float *exposure_b, int exposure_stride = 1) {
-  const bool mono = loss_flags & GSAJ_LOSS_MONOCULAR, noexp = loss_flags & GSAJ_LOSS_NO_EXPOSURE;
-  if ((loss_flags & GSAJ_LOSS_COMPUTE_LOSS) || !gt_color || (!mono && !gt_depth) || (!noexp && (!exposure_a || !exposure_b)) ||
-      exposure_stride < 1) {
-    gsaj_set_error("%s: invalid loss arguments (flags=%d, exposure stride %d; GSAJ_LOSS_COMPUTE_LOSS has no fused form)", who, loss_flags,
-                   exposure_stride);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  return GSAJ_OK;
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, bg, W, H, viewmatrix, projmatrix, nullptr, campos, tanfovx, tanfovy};
+  const FwdOut o{out_color, out_depth, out_opacity, radii, n_touched, nullptr, nullptr};
+  const Arenas a{geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws};
+  return forward_async(sc, v, prefiltered, flags, o, a, nullptr, (hipStream_t)stream);
 }
 
 size_t gsaj_fused_loss_workspace_bytes(int W, int H) { return (size_t)gsaj_fwd_loss_slots(W, H) * 4 * sizeof(float) + 256; }
@@ -361,92 +498,33 @@ int gsaj_rasterize_forward_loss(int P, int D, int M, const float *bg, int W, int
                                 int flags, int loss_flags, float alpha, float rgb_boundary_threshold, const float *gt_color,
                                 const float *gt_depth, const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b,
                                 float *out_scalars, void *loss_ws, void *stream) {
-  int rc = fused_loss_args("gsaj_rasterize_forward_loss", loss_flags, gt_color, gt_depth, exposure_a, exposure_b);
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, bg, W, H, viewmatrix, projmatrix, nullptr, campos, tanfovx, tanfovy};
+  const FwdOut o{out_color, out_depth, out_opacity, radii, n_touched, out_scalars, nullptr};
+  const Arenas a{geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws};
+  FusedLoss fl = loss_args(loss_flags, alpha, rgb_boundary_threshold, gt_color, gt_depth, grad_mask, exposure_a, exposure_b);
+  int rc = fused_loss("gsaj_rasterize_forward_loss", &fl);
   if (rc != GSAJ_OK) return rc;
-  if (!out_scalars || !loss_ws) {
-    gsaj_set_error("gsaj_rasterize_forward_loss: out_scalars and loss_ws are required");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  FusedLoss fl{};
-  fl.flags = loss_flags; fl.alpha = alpha; fl.rgb_thr = rgb_boundary_threshold;
-  fl.gt_color = gt_color; fl.gt_depth = gt_depth; fl.grad_mask = grad_mask; fl.exp_a = exposure_a; fl.exp_b = exposure_b;
+  if ((rc = check_loss_outputs("gsaj_rasterize_forward_loss", o, loss_ws)) != GSAJ_OK) return rc;
   fl.partials = reinterpret_cast<float *>(align_base(loss_ws));
-  return forward_async_impl(P, D, M, bg, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                            viewmatrix, projmatrix, campos, tanfovx, tanfovy, prefiltered, out_color, out_depth, out_opacity, radii,
-                            n_touched, geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws, flags, stream, &fl,
-                            out_scalars);
+  return forward_async(sc, v, prefiltered, flags, o, a, &fl, (hipStream_t)stream);
 }
 
 // ---- batched multi-view entry points: K views of ONE Gaussian map (a mapping window) --------------------------------
-static int batch_workspaces(int K, int P, int capacity, int W, int H, void *geom_ws, void *binning_ws, size_t binning_ws_bytes,
-                            void *image_ws, GeomWS *g, BinWS *b, ImageWS *im, ViewStrides *vs) {
-  vs->geom = gsaj_geom_workspace_bytes(P);
-  vs->image = gsaj_image_workspace_bytes(W, H);
-  vs->bin = gsaj_binning_workspace_bytes(capacity);
-  if (((uintptr_t)geom_ws | (uintptr_t)binning_ws | (uintptr_t)image_ws) & 255) {
-    gsaj_set_error("batched entry points need 256-byte aligned workspaces");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (binning_ws_bytes < vs->bin * (size_t)K) {
-    gsaj_set_error("binning workspace smaller than K x gsaj_binning_workspace_bytes(capacity=%d)", capacity);
-    return GSAJ_ERR_WORKSPACE_TOO_SMALL;
-  }
-  geom_carve(reinterpret_cast<char *>(geom_ws), (size_t)P, g);
-  image_carve(reinterpret_cast<char *>(image_ws), W, H, im);
-  bin_carve(reinterpret_cast<char *>(binning_ws), (size_t)capacity, b);
-  return GSAJ_OK;
-}
-
 // fl != NULL: the loss-fused form (view 0's pointers; partials = the aligned loss workspace)
-static int forward_batch_impl(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
-                              const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
-                              const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
-                              const float *projmatrices, const float *campos, float tanfovx, float tanfovy, int prefiltered,
-                              float *out_color, float *out_depth, float *out_opacity, int *radii, int *n_touched, void *geom_ws,
-                              void *binning_ws, size_t binning_ws_bytes, int capacity, int tile_list_capacity, void *image_ws,
-                              int flags, void *stream, const FusedLoss *fl, float *out_scalars, float *out_dexposure) {
-  if (K <= 0 || P <= 0 || W <= 0 || H <= 0 || capacity <= 0 || !means3D || !opacities || !viewmatrices || !projmatrices || !bg ||
-      !out_color || !out_depth || !out_opacity || !radii || !n_touched || !geom_ws || !binning_ws || !image_ws) {
-    gsaj_set_error("gsaj_rasterize_forward_batch: invalid argument (K=%d P=%d W=%d H=%d capacity=%d)", K, P, W, H, capacity);
+static int forward_batch(const Scene &sc, const Views &v, int prefiltered, int flags, const FwdOut &o, const Arenas &a,
+                         const FusedLoss *fl, hipStream_t s) {
+  if (v.K <= 0 || sc.P <= 0 || v.W <= 0 || v.H <= 0 || a.instances <= 0 || !sc.means3D || !sc.opacities || !v.viewmatrix ||
+      !v.projmatrix || !v.bg || !o.color || !o.depth || !o.opacity || !o.radii || !o.n_touched || !a.geom || !a.binning || !a.image) {
+    gsaj_set_error("gsaj_rasterize_forward_batch: invalid argument (K=%d P=%d W=%d H=%d capacity=%d)", v.K, sc.P, v.W, v.H, a.instances);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  if ((shs == nullptr) == (colors_precomp == nullptr)) {
-    gsaj_set_error("Please provide excatly one of either SHs or precomputed colors!");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (((scales == nullptr || rotations == nullptr) && cov3D_precomp == nullptr) ||
-      ((scales != nullptr || rotations != nullptr) && cov3D_precomp != nullptr)) {
-    gsaj_set_error("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (shs && (!campos || M <= 0 || D < 0 || (D + 1) * (D + 1) > M || D > 3)) {
-    gsaj_set_error("gsaj_rasterize_forward_batch: SH degree %d needs %d coefficients, got M=%d", D, (D + 1) * (D + 1), M);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  GeomWS g; BinWS b; ImageWS im; ViewStrides vs;
-  int rc = batch_workspaces(K, P, capacity, W, H, geom_ws, binning_ws, binning_ws_bytes, image_ws, &g, &b, &im, &vs);
+  int rc = check_scene("gsaj_rasterize_forward_batch", sc, v.campos);
   if (rc != GSAJ_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  FwdParams p;
-  p.P = P; p.D = D; p.M = M; p.W = W; p.H = H;
-  p.means3D = means3D; p.shs = shs; p.colors_precomp = colors_precomp; p.opacities = opacities;
-  p.scales = scales; p.rotations = rotations; p.cov3D_precomp = cov3D_precomp;
-  p.viewmatrix = viewmatrices; p.projmatrix = projmatrices; p.campos = campos;
-  p.scale_modifier = scale_modifier; p.tanfovx = tanfovx; p.tanfovy = tanfovy;
-  p.focal_y = H / (2.0f * tanfovy);
-  p.focal_x = W / (2.0f * tanfovx);
-  p.prefiltered = prefiltered;
-  p.grid_x = (W + TILE - 1) / TILE; p.grid_y = (H + TILE - 1) / TILE;
-  p.capacity = capacity;
-  p.sort_cap = (tile_list_capacity > 0 && tile_list_capacity < SORT_CAP) ? tile_list_capacity : SORT_CAP;
-  p.views = K;
-  if ((rc = launch_preprocess(p, radii, n_touched, g, im, vs, s)) != GSAJ_OK) return rc;
-  if ((rc = launch_tile_binning(P, p.sort_cap, (flags & GSAJ_FWD_RECORDS_FP16) ? 1 : 0, p.grid_x, p.grid_y, g, b, im, K, vs, s)) != GSAJ_OK)
-    return rc;
-  if ((rc = launch_render_forward(P, W, H, p.grid_x, p.grid_y, bg, g, b, im, out_color, out_depth, out_opacity, n_touched, K, vs, s, fl)) != GSAJ_OK)
-    return rc;
-  if (fl) return launch_loss_finalize(*fl, gsaj_fwd_loss_slots(W, H), W, H, im.counters + 4, out_scalars, s, K, vs.image, out_dexposure);
-  return GSAJ_OK;
+  Carved c;
+  if ((rc = carve(a, sc.P, v.W, v.H, v.K, &c)) != GSAJ_OK) return rc;
+  if ((rc = launch_preprocess(fwd_params(sc, v, prefiltered, a), o.radii, o.n_touched, c.g, c.im, c.vs, s)) != GSAJ_OK) return rc;
+  return composite(sc.P, v, sort_cap_of(a.tile_list_capacity), flags, o, c, fl, s);
 }
 
 int gsaj_rasterize_forward_batch(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
@@ -456,32 +534,16 @@ int gsaj_rasterize_forward_batch(int K, int P, int D, int M, const float *bg, in
                                  float *out_color, float *out_depth, float *out_opacity, int *radii, int *n_touched, void *geom_ws,
                                  void *binning_ws, size_t binning_ws_bytes, int capacity, int tile_list_capacity, void *image_ws,
                                  int flags, void *stream) {
-  return forward_batch_impl(K, P, D, M, bg, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                            viewmatrices, projmatrices, campos, tanfovx, tanfovy, prefiltered, out_color, out_depth, out_opacity, radii,
-                            n_touched, geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws, flags, stream,
-                            nullptr, nullptr, nullptr);
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{K, bg, W, H, viewmatrices, projmatrices, nullptr, campos, tanfovx, tanfovy};
+  const FwdOut o{out_color, out_depth, out_opacity, radii, n_touched, nullptr, nullptr};
+  const Arenas a{geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws};
+  return forward_batch(sc, v, prefiltered, flags, o, a, nullptr, (hipStream_t)stream);
 }
 
 static size_t fused_loss_view_bytes(int W, int H) { return (gsaj_fused_loss_workspace_bytes(W, H) + 255) & ~(size_t)255; }
 
 size_t gsaj_fused_loss_batch_workspace_bytes(int K, int W, int H) { return (size_t)(K > 0 ? K : 0) * fused_loss_view_bytes(W, H); }
-
-// the loss arguments of the two batched fused entry points, checked before anything is launched
-static int fused_loss_batch_args(const char *who, int K, int loss_flags, const float *gt_color, const float *gt_depth,
-                                 const float *exposure_a, const float *exposure_b, int exposure_stride, FusedLoss *fl, float alpha,
-                                 float rgb_boundary_threshold, const uint8_t *grad_mask) {
-  if (K <= 0) {
-    gsaj_set_error("%s: invalid argument (K=%d)", who, K);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  int rc = fused_loss_args(who, loss_flags, gt_color, gt_depth, exposure_a, exposure_b, exposure_stride);
-  if (rc != GSAJ_OK) return rc;
-  const bool noexp = loss_flags & GSAJ_LOSS_NO_EXPOSURE;
-  fl->flags = loss_flags; fl->alpha = alpha; fl->rgb_thr = rgb_boundary_threshold;
-  fl->gt_color = gt_color; fl->gt_depth = (loss_flags & GSAJ_LOSS_MONOCULAR) ? nullptr : gt_depth; fl->grad_mask = grad_mask;
-  fl->exp_a = noexp ? nullptr : exposure_a; fl->exp_b = noexp ? nullptr : exposure_b; fl->exp_stride = exposure_stride;
-  return GSAJ_OK;
-}
 
 int gsaj_rasterize_forward_loss_batch(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
                                       const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
@@ -492,70 +554,47 @@ int gsaj_rasterize_forward_loss_batch(int K, int P, int D, int M, const float *b
                                       int flags, int loss_flags, float alpha, float rgb_boundary_threshold, const float *gt_color,
                                       const float *gt_depth, const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b,
                                       int exposure_stride, float *out_scalars, float *out_dexposure, void *loss_ws, void *stream) {
-  FusedLoss fl{};
-  int rc = fused_loss_batch_args("gsaj_rasterize_forward_loss_batch", K, loss_flags, gt_color, gt_depth, exposure_a, exposure_b,
-                                 exposure_stride, &fl, alpha, rgb_boundary_threshold, grad_mask);
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{K, bg, W, H, viewmatrices, projmatrices, nullptr, campos, tanfovx, tanfovy};
+  const FwdOut o{out_color, out_depth, out_opacity, radii, n_touched, out_scalars, out_dexposure};
+  const Arenas a{geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws};
+  FusedLoss fl = loss_args(loss_flags, alpha, rgb_boundary_threshold, gt_color, gt_depth, grad_mask, exposure_a, exposure_b, exposure_stride);
+  int rc = fused_loss("gsaj_rasterize_forward_loss_batch", &fl, K);
   if (rc != GSAJ_OK) return rc;
-  if (!out_scalars || !loss_ws) {
-    gsaj_set_error("gsaj_rasterize_forward_loss_batch: out_scalars and loss_ws are required");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
+  if ((rc = check_loss_outputs("gsaj_rasterize_forward_loss_batch", o, loss_ws)) != GSAJ_OK) return rc;
   fl.partials = reinterpret_cast<float *>(align_base(loss_ws));  // [K][slots][4], dense: K x 255 bytes of the workspace are slack
-  return forward_batch_impl(K, P, D, M, bg, W, H, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                            viewmatrices, projmatrices, campos, tanfovx, tanfovy, prefiltered, out_color, out_depth, out_opacity, radii,
-                            n_touched, geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws, flags, stream, &fl,
-                            out_scalars, out_dexposure);
+  return forward_batch(sc, v, prefiltered, flags, o, a, &fl, (hipStream_t)stream);
 }
 
-// fl != NULL: the loss-fused form (view 0's pointers); dL_dpix / dL_dpix_depth are not read then
-static int backward_batch_impl(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
-                               const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
-                               const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
-                               const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
-                               float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
-                               const float *dL_dpix, const float *dL_dpix_depth, float *dL_dmean2D, float *dL_dconic,
-                               float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D, float *dL_dcov3D,
-                               float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau, float *dL_dtau_sum, int flags,
-                               void *stream, const FusedLoss *fl) {
-  if (K <= 0 || P <= 0 || capacity <= 0 || W <= 0 || H <= 0 || !bg || !means3D || !viewmatrices || !projmatrices || !projmatrix_raw ||
-      !radii || !geom_ws || !binning_ws || !image_ws || (!fl && (!dL_dpix || !dL_dpix_depth)) || !dL_dopacity || !dL_dmean3D || !dL_dcov3D ||
-      !dL_dtau_sum) {
+// ---- backward --------------------------------------------------------------------------------------------------------------------
+static int backward_batch(BwdParams *p, const Scene &sc, const Views &v, const Arenas &a, const PixelSeeds &seeds, int flags,
+                          hipStream_t s) {
+  if (v.K <= 0 || sc.P <= 0 || a.instances <= 0 || v.W <= 0 || v.H <= 0 || !v.bg || !sc.means3D || !v.viewmatrix || !v.projmatrix ||
+      !v.projmatrix_raw || !p->radii || !a.geom || !a.binning || !a.image || (!seeds.fl && (!seeds.dL_dpix || !seeds.dL_dpix_depth)) ||
+      !p->dL_dopacity || !p->dL_dmean3D || !p->dL_dcov3D || !p->dL_dtau_sum) {
     gsaj_set_error("gsaj_rasterize_backward_batch: invalid argument");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  if ((shs && (!dL_dsh || !campos)) || (scales && (!rotations || !dL_dscale || !dL_drot)) || (!scales && !cov3D_precomp)) {
+  if ((sc.shs && (!p->dL_dsh || !v.campos)) || (sc.scales && (!sc.rotations || !p->dL_dscale || !p->dL_drot)) ||
+      (!sc.scales && !sc.cov3D_precomp)) {
     gsaj_set_error("gsaj_rasterize_backward_batch: missing gradient buffer for a provided input");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  GeomWS g; BinWS b; ImageWS im; ViewStrides vs;
-  int rc = batch_workspaces(K, P, capacity, W, H, geom_ws, binning_ws, gsaj_binning_workspace_bytes(capacity) * (size_t)K, image_ws,
-                            &g, &b, &im, &vs);
+  Carved c;
+  int rc = carve(a, sc.P, v.W, v.H, v.K, &c);
   if (rc != GSAJ_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+  bwd_params(p, sc, v, c.g);
   // the whole window in one call: the chain kernel sums the reverse compositor's instance rows itself (no gather launch, no gsum
   // round trip); the two halves called separately go through gsum as before
   const int fused = (flags & (GSAJ_BWD_ONLY_COMPOSITE | GSAJ_BWD_ONLY_CHAIN)) ? 0 : 1;
   if (!(flags & GSAJ_BWD_ONLY_CHAIN)) {
-    if ((rc = launch_render_backward(capacity, W, H, gx, gy, bg, g, b, im, dL_dpix, dL_dpix_depth, K, vs, s, fl)) != GSAJ_OK) return rc;
-    if (!fused && (rc = launch_gather_sums(P, K, radii, g, b, im, vs, s)) != GSAJ_OK) return rc;
+    rc = launch_render_backward(a.instances, v.W, v.H, p->grid_x, p->grid_y, v.bg, c.g, c.b, c.im, seeds.dL_dpix, seeds.dL_dpix_depth,
+                                v.K, c.vs, s, seeds.fl);
+    if (rc != GSAJ_OK) return rc;
+    if (!fused && (rc = launch_gather_sums(sc.P, v.K, p->radii, c.g, c.b, c.im, c.vs, s)) != GSAJ_OK) return rc;
   }
   if (flags & GSAJ_BWD_ONLY_COMPOSITE) return GSAJ_OK;
-  BwdParams p;
-  p.P = P; p.D = D; p.M = M; p.W = W; p.H = H;
-  p.means3D = means3D; p.shs = shs; p.scales = scales; p.rotations = rotations;
-  p.cov3Ds = cov3D_precomp ? cov3D_precomp : g.cov3D;
-  p.viewmatrix = viewmatrices; p.projmatrix = projmatrices; p.projmatrix_raw = projmatrix_raw; p.campos = campos;
-  p.scale_modifier = scale_modifier; p.tanfovx = tanfovx; p.tanfovy = tanfovy;
-  p.focal_y = H / (2.0f * tanfovy);
-  p.focal_x = W / (2.0f * tanfovx);
-  p.grid_x = gx; p.grid_y = gy;
-  p.radii = radii;
-  p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
-  p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
-  p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
-  (void)colors_precomp;
-  return launch_gaussian_backward_batch(p, K, g, b, im, vs, (flags & GSAJ_BWD_ACCUMULATE) ? 1 : 0, fused, s);
+  return launch_gaussian_backward_batch(*p, v.K, c.g, c.b, c.im, c.vs, (flags & GSAJ_BWD_ACCUMULATE) ? 1 : 0, fused, s);
 }
 
 int gsaj_rasterize_backward_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
@@ -567,10 +606,15 @@ int gsaj_rasterize_backward_batch(int K, int P, int D, int M, int capacity, cons
                                   float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D, float *dL_dcov3D,
                                   float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau, float *dL_dtau_sum, int flags,
                                   void *stream) {
-  return backward_batch_impl(K, P, D, M, capacity, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
-                             cov3D_precomp, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws,
-                             binning_ws, image_ws, dL_dpix, dL_dpix_depth, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth,
-                             dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dtau, dL_dtau_sum, flags, stream, nullptr);
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{K, bg, W, H, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy};
+  const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, capacity, 0, image_ws};
+  BwdParams p{};
+  p.radii = radii;
+  p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
+  p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
+  p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
+  return backward_batch(&p, sc, v, a, PixelSeeds{dL_dpix, dL_dpix_depth, nullptr}, flags, (hipStream_t)stream);
 }
 
 int gsaj_rasterize_backward_loss_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
@@ -584,72 +628,49 @@ int gsaj_rasterize_backward_loss_batch(int K, int P, int D, int M, int capacity,
                                        float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D,
                                        float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau,
                                        float *dL_dtau_sum, int flags, void *stream) {
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{K, bg, W, H, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy};
+  const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, capacity, 0, image_ws};
   FusedLoss fl{};
   if (!(flags & GSAJ_BWD_ONLY_CHAIN)) {  // (the chain half reads no image: its loss arguments are ignored)
-    int rc = fused_loss_batch_args("gsaj_rasterize_backward_loss_batch", K, loss_flags, gt_color, gt_depth, exposure_a, exposure_b,
-                                   exposure_stride, &fl, alpha, rgb_boundary_threshold, grad_mask);
+    fl = loss_args(loss_flags, alpha, rgb_boundary_threshold, gt_color, gt_depth, grad_mask, exposure_a, exposure_b, exposure_stride);
+    fl.color = color; fl.depth = depth; fl.opacity = opacity;
+    int rc = fused_loss("gsaj_rasterize_backward_loss_batch", &fl, K);
     if (rc != GSAJ_OK) return rc;
-    if (!color || !opacity || (!(loss_flags & GSAJ_LOSS_MONOCULAR) && !depth)) {
-      gsaj_set_error("gsaj_rasterize_backward_loss_batch: the forward's color / depth / opacity images are required");
-      return GSAJ_ERR_INVALID_ARGUMENT;
-    }
-    fl.color = color; fl.depth = (loss_flags & GSAJ_LOSS_MONOCULAR) ? nullptr : depth; fl.opacity = opacity;
+    if ((rc = check_loss_images("gsaj_rasterize_backward_loss_batch", fl)) != GSAJ_OK) return rc;
   }
-  return backward_batch_impl(K, P, D, M, capacity, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations,
-                             cov3D_precomp, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws,
-                             binning_ws, image_ws, nullptr, nullptr, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth,
-                             dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dtau, dL_dtau_sum, flags, stream, &fl);
-}
-
-static int backward_impl(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
-                         const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
-                         const float *rotations, const float *cov3D_precomp, const float *viewmatrix,
-                         const float *projmatrix, const float *projmatrix_raw, const float *campos, float tanfovx,
-                         float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
-                         const float *dL_dpix, const float *dL_dpix_depth, float *dL_dmean2D, float *dL_dconic,
-                         float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D,
-                         float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau,
-                         float *dL_dtau_sum, void *stream, const FusedLoss *fl) {
-  // pose-only mode (tracking: only the camera is optimised): every per-Gaussian output pointer NULL, dL_dtau_sum given
-  const bool pose_only = !dL_dmean2D && !dL_dconic && !dL_dopacity && !dL_dcolor && !dL_ddepth && !dL_dmean3D && !dL_dcov3D &&
-                         !dL_dsh && !dL_dscale && !dL_drot && dL_dtau_sum;
-  if (P <= 0 || R < 0 || W <= 0 || H <= 0 || !bg || !means3D || !viewmatrix || !projmatrix || !projmatrix_raw ||
-      !geom_ws || !binning_ws || !image_ws || (!fl && (!dL_dpix || !dL_dpix_depth)) ||
-      (!pose_only && (!dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor || !dL_ddepth || !dL_dmean3D || !dL_dcov3D))) {
-    gsaj_set_error("gsaj_rasterize_backward: invalid argument");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if ((shs && ((!pose_only && !dL_dsh) || !campos)) || (scales && (!rotations || (!pose_only && (!dL_dscale || !dL_drot)))) ||
-      (!scales && !cov3D_precomp)) {
-    gsaj_set_error("gsaj_rasterize_backward: missing gradient buffer for a provided input");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  GeomWS g;
-  geom_carve(align_base(geom_ws), (size_t)P, &g);
-  ImageWS im;
-  image_carve(align_base(image_ws), W, H, &im);
-  BinWS b;
-  bin_carve(align_base(binning_ws), (size_t)R, &b);
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  // every output row is written by the kernels (zeros for culled Gaussians): no memsets
-  int rc = launch_render_backward(R, W, H, gx, gy, bg, g, b, im, dL_dpix, dL_dpix_depth, 1, ViewStrides{0, 0, 0}, s, fl);
-  if (rc != GSAJ_OK) return rc;
-  BwdParams p;
-  p.P = P; p.D = D; p.M = M; p.W = W; p.H = H;
-  p.means3D = means3D; p.shs = shs; p.scales = scales; p.rotations = rotations;
-  p.cov3Ds = cov3D_precomp ? cov3D_precomp : g.cov3D;
-  p.viewmatrix = viewmatrix; p.projmatrix = projmatrix; p.projmatrix_raw = projmatrix_raw; p.campos = campos;
-  p.scale_modifier = scale_modifier; p.tanfovx = tanfovx; p.tanfovy = tanfovy;
-  p.focal_y = H / (2.0f * tanfovy);
-  p.focal_x = W / (2.0f * tanfovx);
-  p.grid_x = gx; p.grid_y = gy;
-  p.radii = radii ? radii : g.internal_radii;
+  BwdParams p{};
+  p.radii = radii;
   p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
   p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
   p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
-  (void)colors_precomp;
-  return launch_gaussian_backward(p, g, b, im, s);
+  return backward_batch(&p, sc, v, a, PixelSeeds{nullptr, nullptr, &fl}, flags, (hipStream_t)stream);
+}
+
+static int backward_frame(BwdParams *p, const Scene &sc, const Views &v, const Arenas &a, const PixelSeeds &seeds, hipStream_t s) {
+  // pose-only mode (tracking: only the camera is optimised): every per-Gaussian output pointer NULL, dL_dtau_sum given
+  const bool pose_only = !p->dL_dmean2D && !p->dL_dconic && !p->dL_dopacity && !p->dL_dcolor && !p->dL_ddepth && !p->dL_dmean3D &&
+                         !p->dL_dcov3D && !p->dL_dsh && !p->dL_dscale && !p->dL_drot && p->dL_dtau_sum;
+  if (sc.P <= 0 || a.instances < 0 || v.W <= 0 || v.H <= 0 || !v.bg || !sc.means3D || !v.viewmatrix || !v.projmatrix ||
+      !v.projmatrix_raw || !a.geom || !a.binning || !a.image || (!seeds.fl && (!seeds.dL_dpix || !seeds.dL_dpix_depth)) ||
+      (!pose_only && (!p->dL_dmean2D || !p->dL_dconic || !p->dL_dopacity || !p->dL_dcolor || !p->dL_ddepth || !p->dL_dmean3D ||
+                      !p->dL_dcov3D))) {
+    gsaj_set_error("gsaj_rasterize_backward: invalid argument");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if ((sc.shs && ((!pose_only && !p->dL_dsh) || !v.campos)) ||
+      (sc.scales && (!sc.rotations || (!pose_only && (!p->dL_dscale || !p->dL_drot)))) || (!sc.scales && !sc.cov3D_precomp)) {
+    gsaj_set_error("gsaj_rasterize_backward: missing gradient buffer for a provided input");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  Carved c;
+  carve(a, sc.P, v.W, v.H, 0, &c);
+  bwd_params(p, sc, v, c.g);
+  // every output row is written by the kernels (zeros for culled Gaussians): no memsets
+  int rc = launch_render_backward(a.instances, v.W, v.H, p->grid_x, p->grid_y, v.bg, c.g, c.b, c.im, seeds.dL_dpix, seeds.dL_dpix_depth,
+                                  1, c.vs, s, seeds.fl);
+  if (rc != GSAJ_OK) return rc;
+  return launch_gaussian_backward(*p, c.g, c.b, c.im, s);
 }
 
 int gsaj_rasterize_backward(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
@@ -661,10 +682,15 @@ int gsaj_rasterize_backward(int P, int D, int M, int R, const float *bg, int W, 
                             float *dL_dopacity, float *dL_dcolor, float *dL_ddepth, float *dL_dmean3D,
                             float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau,
                             float *dL_dtau_sum, void *stream) {
-  return backward_impl(P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                       projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws, image_ws, dL_dpix, dL_dpix_depth,
-                       dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dtau,
-                       dL_dtau_sum, stream, nullptr);
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, bg, W, H, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy};
+  const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, R, 0, image_ws};
+  BwdParams p{};
+  p.radii = radii;
+  p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
+  p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
+  p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
+  return backward_frame(&p, sc, v, a, PixelSeeds{dL_dpix, dL_dpix_depth, nullptr}, (hipStream_t)stream);
 }
 
 int gsaj_rasterize_backward_loss(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D, const float *shs,
@@ -677,20 +703,20 @@ int gsaj_rasterize_backward_loss(int P, int D, int M, int R, const float *bg, in
                                  const float *exposure_b, float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor,
                                  float *dL_ddepth, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscale,
                                  float *dL_drot, float *dL_dtau, float *dL_dtau_sum, void *stream) {
-  int rc = fused_loss_args("gsaj_rasterize_backward_loss", loss_flags, gt_color, gt_depth, exposure_a, exposure_b);
-  if (rc != GSAJ_OK) return rc;
-  if (!color || !opacity || (!(loss_flags & GSAJ_LOSS_MONOCULAR) && !depth)) {
-    gsaj_set_error("gsaj_rasterize_backward_loss: the forward's color / depth / opacity images are required");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  FusedLoss fl{};
-  fl.flags = loss_flags; fl.alpha = alpha; fl.rgb_thr = rgb_boundary_threshold;
-  fl.gt_color = gt_color; fl.gt_depth = gt_depth; fl.grad_mask = grad_mask; fl.exp_a = exposure_a; fl.exp_b = exposure_b;
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, bg, W, H, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy};
+  const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, R, 0, image_ws};
+  FusedLoss fl = loss_args(loss_flags, alpha, rgb_boundary_threshold, gt_color, gt_depth, grad_mask, exposure_a, exposure_b);
   fl.color = color; fl.depth = depth; fl.opacity = opacity;
-  return backward_impl(P, D, M, R, bg, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                       projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws, image_ws, nullptr, nullptr,
-                       dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dtau,
-                       dL_dtau_sum, stream, &fl);
+  int rc = fused_loss("gsaj_rasterize_backward_loss", &fl);
+  if (rc != GSAJ_OK) return rc;
+  if ((rc = check_loss_images("gsaj_rasterize_backward_loss", fl)) != GSAJ_OK) return rc;
+  BwdParams p{};
+  p.radii = radii;
+  p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
+  p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
+  p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
+  return backward_frame(&p, sc, v, a, PixelSeeds{nullptr, nullptr, &fl}, (hipStream_t)stream);
 }
 
 // ---- Gauss-Newton tracking: per-pixel pose Jacobians and normal equations (pose_jac.hip) ------------------------------------
@@ -699,50 +725,50 @@ size_t gsaj_pose_jac_workspace_bytes(int P, int W, int H) {
 }
 int gsaj_pose_jac_partial_rows(int W, int H) { return gsaj_jac_slots(W, H); }
 
-static int pose_jac_impl(const char *who, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D, const float *shs,
-                         const float *scales, float scale_modifier, const float *rotations, const float *cov3D_precomp,
-                         const float *viewmatrix, const float *projmatrix, const float *projmatrix_raw, const float *campos,
-                         float tanfovx, float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws, void *jac_ws,
-                         float *jac_out, float *out_color, float *out_depth, float *H_out, float *g_out, const float *seed_color,
-                         const float *seed_depth, const float *curv_color, const float *curv_depth, float *gn_partials,
-                         const FusedLoss *fl, float irls_delta, void *stream, bool joint = false) {
-  if (P <= 0 || R < 0 || W <= 0 || H <= 0 || !bg || !means3D || !viewmatrix || !projmatrix || !projmatrix_raw || !geom_ws ||
-      !binning_ws || !image_ws || !jac_ws || (shs && !campos) || (scales && !rotations) || (!scales && !cov3D_precomp)) {
+// the fused form's loss arguments (fl arrives as the caller gave them), in the order a caller is told about them
+static int pose_jac_loss_args(const char *who, bool joint, FusedLoss *fl, const float *gn_partials, float irls_delta) {
+  int rc = fused_loss(who, fl);
+  if (rc != GSAJ_OK) return rc;
+  if (joint && ((fl->flags & GSAJ_LOSS_NO_EXPOSURE) || !fl->exp_a || !fl->exp_b)) {
+    gsaj_set_error("%s: the joint form solves for the exposure: exposure_a / exposure_b are required, GSAJ_LOSS_NO_EXPOSURE is not allowed", who);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if (!fl->color || !fl->opacity || (!(fl->flags & GSAJ_LOSS_MONOCULAR) && !fl->depth) || !gn_partials || !(irls_delta >= 0.f)) {
+    gsaj_set_error("%s: the forward's color / depth / opacity images, gn_partials and irls_delta >= 0 are required", who);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  return GSAJ_OK;
+}
+
+// p: radii only (no gradient output).  jo: the walk's outputs as the caller named them; the explicit form's seed / curvature images
+// are dropped where their sum was not asked for, and its partial rows live in the Jacobian workspace behind the derivative rows.
+static int pose_jac(const char *who, BwdParams *p, const Scene &sc, const Views &v, const Arenas &a, void *jac_ws, JacOut jo,
+                    const GnSums &gn, hipStream_t s) {
+  int rc = gn.fl ? pose_jac_loss_args(who, gn.joint, gn.fl, jo.partials, jo.delta) : GSAJ_OK;
+  if (rc != GSAJ_OK) return rc;
+  if (sc.P <= 0 || a.instances < 0 || v.W <= 0 || v.H <= 0 || !v.bg || !sc.means3D || !v.viewmatrix || !v.projmatrix ||
+      !v.projmatrix_raw || !a.geom || !a.binning || !a.image || !jac_ws || (sc.shs && !v.campos) || (sc.scales && !sc.rotations) ||
+      (!sc.scales && !sc.cov3D_precomp)) {
     gsaj_set_error("%s: invalid argument", who);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  if (!fl && ((g_out && (!seed_color || !seed_depth)) || (H_out && (!curv_color || !curv_depth)))) {
+  if (!gn.fl && ((gn.g_out && (!jo.seed_c || !jo.seed_d)) || (gn.H_out && (!jo.curv_c || !jo.curv_d)))) {
     gsaj_set_error("%s: g_out needs both seed images, H_out both curvature images", who);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  hipStream_t s = (hipStream_t)stream;
-  GeomWS g;
-  geom_carve(align_base(geom_ws), (size_t)P, &g);
-  ImageWS im;
-  image_carve(align_base(image_ws), W, H, &im);
-  BinWS b;
-  bin_carve(align_base(binning_ws), (size_t)R, &b);
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+  Carved c;
+  carve(a, sc.P, v.W, v.H, 0, &c);
+  bwd_params(p, sc, v, c.g);
   float *rows = reinterpret_cast<float *>(align_base(jac_ws));
-  float *ws_partials = reinterpret_cast<float *>(reinterpret_cast<char *>(rows) + gsaj_jac_rows_bytes(P));
-  BwdParams p{};
-  p.P = P; p.D = D; p.M = M; p.W = W; p.H = H;
-  p.means3D = means3D; p.shs = shs; p.scales = scales; p.rotations = rotations;
-  p.cov3Ds = cov3D_precomp ? cov3D_precomp : g.cov3D;
-  p.viewmatrix = viewmatrix; p.projmatrix = projmatrix; p.projmatrix_raw = projmatrix_raw; p.campos = campos;
-  p.scale_modifier = scale_modifier; p.tanfovx = tanfovx; p.tanfovy = tanfovy;
-  p.focal_y = H / (2.0f * tanfovy);
-  p.focal_x = W / (2.0f * tanfovx);
-  p.grid_x = gx; p.grid_y = gy;
-  p.radii = radii ? radii : g.internal_radii;
-  int rc = launch_splat_jac(p, g, im, rows, s);
+  rc = launch_splat_jac(*p, c.g, c.im, rows, s);
   if (rc != GSAJ_OK) return rc;
-  const bool sums = fl || H_out || g_out;
-  float *partials = fl ? gn_partials : (sums ? ws_partials : nullptr);
-  rc = launch_render_jac(P, W, H, gx, gy, bg, g, b, im, rows, jac_out, out_color, out_depth, g_out ? seed_color : nullptr,
-                         g_out ? seed_depth : nullptr, H_out ? curv_color : nullptr, H_out ? curv_depth : nullptr, partials, fl, irls_delta, joint ? 1 : 0, s);
-  if (rc != GSAJ_OK || fl || !sums) return rc;
-  return launch_gn_reduce(partials, gsaj_jac_slots(W, H), im, H_out, g_out, s);
+  const bool sums = gn.fl || gn.H_out || gn.g_out;
+  if (!gn.g_out) jo.seed_c = jo.seed_d = nullptr;
+  if (!gn.H_out) jo.curv_c = jo.curv_d = nullptr;
+  if (!gn.fl) jo.partials = sums ? reinterpret_cast<float *>(reinterpret_cast<char *>(rows) + gsaj_jac_rows_bytes(sc.P)) : nullptr;
+  rc = launch_render_jac(*p, v.bg, c.g, c.b, c.im, rows, jo, gn.fl, gn.joint ? 1 : 0, s);
+  if (rc != GSAJ_OK || gn.fl || !sums) return rc;
+  return launch_gn_reduce(jo.partials, gsaj_jac_slots(v.W, v.H), c.im, gn.H_out, gn.g_out, s);
 }
 
 int gsaj_rasterize_pose_jacobian(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D, const float *shs,
@@ -752,37 +778,13 @@ int gsaj_rasterize_pose_jacobian(int P, int D, int M, int R, const float *bg, in
                                  void *geom_ws, void *binning_ws, void *image_ws, void *jac_ws, float *jac_out, float *out_color,
                                  float *out_depth, float *H_out, float *g_out, const float *seed_color, const float *seed_depth,
                                  const float *curv_color, const float *curv_depth, void *stream) {
-  (void)colors_precomp;  // (already in the splat rows)
-  return pose_jac_impl("gsaj_rasterize_pose_jacobian", P, D, M, R, bg, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
-                       viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws, image_ws, jac_ws, jac_out,
-                       out_color, out_depth, H_out, g_out, seed_color, seed_depth, curv_color, curv_depth, nullptr, nullptr, 0.f, stream);
-}
-
-static int pose_jac_loss_impl(const char *who, bool joint, int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
-                              const float *shs, const float *scales, float scale_modifier, const float *rotations,
-                              const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, const float *projmatrix_raw,
-                              const float *campos, float tanfovx, float tanfovy, const int *radii, void *geom_ws, void *binning_ws,
-                              void *image_ws, void *jac_ws, int loss_flags, float alpha, float rgb_boundary_threshold, const float *color,
-                              const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
-                              const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, float irls_delta,
-                              float *gn_partials, float *jac_out, void *stream) {
-  int rc = fused_loss_args(who, loss_flags, gt_color, gt_depth, exposure_a, exposure_b);
-  if (rc != GSAJ_OK) return rc;
-  if (joint && ((loss_flags & GSAJ_LOSS_NO_EXPOSURE) || !exposure_a || !exposure_b)) {
-    gsaj_set_error("%s: the joint form solves for the exposure: exposure_a / exposure_b are required, GSAJ_LOSS_NO_EXPOSURE is not allowed", who);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (!color || !opacity || (!(loss_flags & GSAJ_LOSS_MONOCULAR) && !depth) || !gn_partials || !(irls_delta >= 0.f)) {
-    gsaj_set_error("%s: the forward's color / depth / opacity images, gn_partials and irls_delta >= 0 are required", who);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  FusedLoss fl{};
-  fl.flags = loss_flags; fl.alpha = alpha; fl.rgb_thr = rgb_boundary_threshold;
-  fl.gt_color = gt_color; fl.gt_depth = gt_depth; fl.grad_mask = grad_mask; fl.exp_a = exposure_a; fl.exp_b = exposure_b;
-  fl.color = color; fl.depth = depth; fl.opacity = opacity;
-  return pose_jac_impl(who, P, D, M, R, bg, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                       projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws, image_ws, jac_ws, jac_out, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gn_partials, &fl, irls_delta, stream, joint);
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, bg, W, H, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy};
+  const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, R, 0, image_ws};
+  const JacOut jo{jac_out, out_color, out_depth, seed_color, seed_depth, curv_color, curv_depth, nullptr, 0.f};
+  BwdParams p{};
+  p.radii = radii;
+  return pose_jac("gsaj_rasterize_pose_jacobian", &p, sc, v, a, jac_ws, jo, GnSums{H_out, g_out, nullptr, false}, (hipStream_t)stream);
 }
 
 int gsaj_rasterize_pose_jacobian_loss(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
@@ -794,11 +796,16 @@ int gsaj_rasterize_pose_jacobian_loss(int P, int D, int M, int R, const float *b
                                       const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
                                       const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, float irls_delta,
                                       float *gn_partials, float *jac_out, void *stream) {
-  (void)colors_precomp;
-  return pose_jac_loss_impl("gsaj_rasterize_pose_jacobian_loss", false, P, D, M, R, bg, W, H, means3D, shs, scales, scale_modifier, rotations,
-                            cov3D_precomp, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws,
-                            image_ws, jac_ws, loss_flags, alpha, rgb_boundary_threshold, color, depth, opacity, gt_color, gt_depth, grad_mask,
-                            exposure_a, exposure_b, irls_delta, gn_partials, jac_out, stream);
+  const char *who = "gsaj_rasterize_pose_jacobian_loss";
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, bg, W, H, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy};
+  const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, R, 0, image_ws};
+  const JacOut jo{jac_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gn_partials, irls_delta};
+  FusedLoss fl = loss_args(loss_flags, alpha, rgb_boundary_threshold, gt_color, gt_depth, grad_mask, exposure_a, exposure_b);
+  fl.color = color; fl.depth = depth; fl.opacity = opacity;
+  BwdParams p{};
+  p.radii = radii;
+  return pose_jac(who, &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, false}, (hipStream_t)stream);
 }
 
 int gsaj_rasterize_pose_jacobian_loss8(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
@@ -810,11 +817,16 @@ int gsaj_rasterize_pose_jacobian_loss8(int P, int D, int M, int R, const float *
                                        const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
                                        const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, float irls_delta,
                                        float *gn8_partials, float *jac_out, void *stream) {
-  (void)colors_precomp;
-  return pose_jac_loss_impl("gsaj_rasterize_pose_jacobian_loss8", true, P, D, M, R, bg, W, H, means3D, shs, scales, scale_modifier, rotations,
-                            cov3D_precomp, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, radii, geom_ws, binning_ws,
-                            image_ws, jac_ws, loss_flags, alpha, rgb_boundary_threshold, color, depth, opacity, gt_color, gt_depth, grad_mask,
-                            exposure_a, exposure_b, irls_delta, gn8_partials, jac_out, stream);
+  const char *who = "gsaj_rasterize_pose_jacobian_loss8";
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{1, bg, W, H, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy};
+  const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, R, 0, image_ws};
+  const JacOut jo{jac_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gn8_partials, irls_delta};
+  FusedLoss fl = loss_args(loss_flags, alpha, rgb_boundary_threshold, gt_color, gt_depth, grad_mask, exposure_a, exposure_b);
+  fl.color = color; fl.depth = depth; fl.opacity = opacity;
+  BwdParams p{};
+  p.radii = radii;
+  return pose_jac(who, &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, true}, (hipStream_t)stream);
 }
 
 int gsaj_mark_visible(int P, const float *means3D, const float *viewmatrix, const float *projmatrix, uint8_t *present,
@@ -901,11 +913,11 @@ int gsaj_debug_export_view_sums_gather(int P, int capacity, int W, int H, void *
     gsaj_set_error("gsaj_debug_export_view_sums_gather: invalid argument");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  GeomWS g; BinWS b; ImageWS im; ViewStrides vs;
-  int rc = batch_workspaces(1, P, capacity, W, H, geom_ws, binning_ws, gsaj_binning_workspace_bytes(capacity), image_ws, &g, &b, &im, &vs);
+  Carved c;
+  int rc = carve(Arenas{geom_ws, binning_ws, SIZE_NOT_GIVEN, capacity, 0, image_ws}, P, W, H, 1, &c);
   if (rc != GSAJ_OK) return rc;
-  if ((rc = launch_gather_sums(P, 1, nullptr, g, b, im, vs, (hipStream_t)stream)) != GSAJ_OK) return rc;
-  GSAJ_HIP_CHECK(hipMemcpyAsync(sums, g.gsum, sizeof(float4) * 3 * (size_t)P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if ((rc = launch_gather_sums(P, 1, nullptr, c.g, c.b, c.im, c.vs, (hipStream_t)stream)) != GSAJ_OK) return rc;
+  GSAJ_HIP_CHECK(hipMemcpyAsync(sums, c.g.gsum, sizeof(float4) * 3 * (size_t)P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return GSAJ_OK;
 }
 

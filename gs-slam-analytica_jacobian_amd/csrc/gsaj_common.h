@@ -265,10 +265,16 @@ int launch_gaussian_backward_batch(const BwdParams &p, int K, const GeomWS &g, c
 size_t gsaj_jac_rows_bytes(int P);
 int gsaj_jac_slots(int W, int H);
 int launch_splat_jac(const BwdParams &p, const GeomWS &g, const ImageWS &im, float *rows, hipStream_t s);
-int launch_render_jac(int P, int W, int H, int grid_x, int grid_y, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im,
-                      const float *rows, float *jac_out, float *out_color, float *out_depth, const float *seed_c, const float *seed_d,
-                      const float *curv_c, const float *curv_d, float *partials, const FusedLoss *fl, float irls_delta, int joint,
-                      hipStream_t s);
+struct JacOut {
+  float *jac;                       // [H,W,4,6] or NULL
+  float *color, *depth;             // re-derived images [3,H,W], [H,W] or NULL
+  const float *seed_c, *seed_d;     // explicit form: seed images [3,H,W], [H,W] (NULL: no g)
+  const float *curv_c, *curv_d;     // explicit form: curvature images (NULL: no H)
+  float *partials;                  // [workgroups][GN_ROW] or NULL
+  float delta;                      // fused form: the IRLS delta
+};
+int launch_render_jac(const BwdParams &p, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im, const float *rows,
+                      const JacOut &jo, const FusedLoss *fl, int joint, hipStream_t s);
 int launch_gn_reduce(const float *partials, int n, const ImageWS &im, float *H_out, float *g_out, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 // in-place exclusive scan of n counters by ONE workgroup (knn.hip; the radix sort's digit offsets, seed.hip's compaction offsets)

@@ -108,14 +108,6 @@ __global__ __launch_bounds__(64) void k_splat_jac(BwdParams p, const uint8_t *__
 }
 
 // ---- forward-mode compositor ----------------------------------------------------------------------------------------------
-struct JacOut {
-  float *jac;                       // [H,W,4,6] or NULL
-  float *color, *depth;             // re-derived images [3,H,W], [H,W] or NULL
-  const float *seed_c, *seed_d;     // explicit form: seed images [3,H,W], [H,W] (NULL: no g)
-  const float *curv_c, *curv_d;     // explicit form: curvature images (NULL: no H)
-  float *partials;                  // [workgroups][GN_ROW] or NULL
-  float delta;                      // fused form: the IRLS delta
-};
 
 // JOINT (with LOSS): the exposure columns and the 64-float row of the joint form; the walk is the same code.
 template <bool LOSS, bool JOINT>
@@ -555,15 +547,10 @@ int launch_splat_jac(const BwdParams &p, const GeomWS &g, const ImageWS &im, flo
   return GSAJ_OK;
 }
 
-int launch_render_jac(int P, int W, int H, int grid_x, int grid_y, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im,
-                      const float *rows, float *jac_out, float *out_color, float *out_depth, const float *seed_c, const float *seed_d,
-                      const float *curv_c, const float *curv_d, float *partials, const FusedLoss *fl, float irls_delta, int joint,
-                      hipStream_t s) {
-  const int tiles = grid_x * grid_y;
+int launch_render_jac(const BwdParams &p, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im, const float *rows,
+                      const JacOut &jo, const FusedLoss *fl, int joint, hipStream_t s) {
+  const int W = p.W, H = p.H, P = p.P, grid_x = p.grid_x, tiles = p.grid_x * p.grid_y;
   const unsigned nblk = (unsigned)gsaj_jac_slots(W, H);
-  JacOut jo;
-  jo.jac = jac_out; jo.color = out_color; jo.depth = out_depth; jo.seed_c = seed_c; jo.seed_d = seed_d; jo.curv_c = curv_c;
-  jo.curv_d = curv_d; jo.partials = partials; jo.delta = irls_delta;
   if (fl && joint)
     hipLaunchKernelGGL(k_render_jac8, dim3(nblk), dim3(64), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg, b.point_list, b.taken,
                        reinterpret_cast<const float4 *>(rows), jo, *fl);

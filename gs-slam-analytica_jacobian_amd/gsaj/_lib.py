@@ -17,6 +17,27 @@ HEADER = os.path.join(os.path.dirname(PKG_ROOT), "include", "gsaj.h")
 c_int, c_float, c_double, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 P = c_void_p  # every device / host pointer travels as void*
 
+# ---- the argument groups of the rasteriser entry points, each spelled once (the groups csrc/api.hip and gsaj/rasterizer.py build;
+# DESIGN.md "Argument groups"); tests/test_cpu_signatures.py holds every entry against the header type by type
+_PDM = [c_int, c_int, c_int]                        # P, D, M
+_BG_WH = [P, c_int, c_int]                          # bg, W, H
+_SCENE_BWD = [P, P, P, P, c_float, P, P]            # means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp
+_SCENE_FWD = _SCENE_BWD[:3] + [P] + _SCENE_BWD[3:]  # the forward family has opacities after colors_precomp
+_VIEW_FWD = [P, P, P, c_float, c_float]             # viewmatrix, projmatrix, campos, tanfovx, tanfovy
+_VIEW_BWD = _VIEW_FWD[:2] + [P] + _VIEW_FWD[2:]     # the backward family has projmatrix_raw after projmatrix
+_FWD_OUT = [P] * 5                                  # out_color, out_depth, out_opacity, radii, n_touched
+_FWD_STATE = _FWD_OUT + [P, P, c_size_t, c_int, c_int, P, c_int]  # + geom_ws, binning_ws, binning_ws_bytes, capacity, tile_list_capacity, image_ws, flags
+_BWD_STATE = [P] * 4                                # radii, geom_ws, binning_ws, image_ws
+_LOSS = [c_int, c_float, c_float]                   # loss_flags, alpha, rgb_boundary_threshold
+_IMAGES = [P] * 3                                   # color, depth, opacity: the forward's images (the backward forms of the loss)
+_LOSS_GT = [P] * 5                                  # gt_color, gt_depth, grad_mask, exposure_a, exposure_b
+_GRADS = [P] * 12                                   # dL_dmean2D .. dL_drot, dL_dtau, dL_dtau_sum
+_FWD = _PDM + _BG_WH + _SCENE_FWD + _VIEW_FWD + [c_int]                        # P .. prefiltered of the one-call forwards
+_BWD = _PDM + [c_int] + _BG_WH + _SCENE_BWD + _VIEW_BWD + _BWD_STATE          # P, D, M, R .. image_ws of everything run on a finished forward
+_BWD_BATCH = [c_int] + _PDM + [c_int] + _BWD[4:]                              # K, P, D, M, capacity ..
+_PREPROCESS = _PDM + [c_int, c_int] + _SCENE_FWD + _VIEW_FWD + [c_int, P, P, P, P]  # P, D, M, W, H .. prefiltered, radii, n_touched, geom_ws, image_ws
+_JAC_LOSS = _BWD + [P] + _LOSS + _IMAGES + _LOSS_GT + [c_float, P, P, P]      # .. jac_ws, the loss, irls_delta, gn_partials, jac_out, stream
+
 # name -> (restype, argtypes); must list every function include/gsaj.h declares
 SIGNATURES = {
     "gsaj_last_error": (ctypes.c_char_p, []),
@@ -24,37 +45,23 @@ SIGNATURES = {
     "gsaj_geom_workspace_bytes": (c_size_t, [c_int]),
     "gsaj_image_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gsaj_binning_workspace_bytes": (c_size_t, [c_int]),
-    "gsaj_forward_preprocess": (c_int, [c_int] * 5 + [P, P, P, P, P, c_float, P, P, P, P, P, c_float, c_float, c_int, P, P, P, P, P]),
+    "gsaj_forward_preprocess": (c_int, _PREPROCESS + [P]),
     "gsaj_forward_num_rendered": (c_int, [c_int, c_int, P, P, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "gsaj_forward_render": (c_int, [c_int] * 5 + [P, P, P, P, P, c_size_t, P, P, P, P, P, c_int, P]),
-    "gsaj_rasterize_forward": (c_int, [c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_float, P, P, P, P, P,
-                                       c_float, c_float, c_int, P, P, P, P, P, P, P, c_size_t, P,
-                                       ctypes.POINTER(c_int), c_int, P]),
-    "gsaj_rasterize_forward_async": (c_int, [c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_float, P, P, P, P, P,
-                                             c_float, c_float, c_int, P, P, P, P, P, P, P, c_size_t, c_int, c_int, P, c_int, P]),
-    "gsaj_rasterize_forward_batch": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_float, P, P, P, P, P,
-                                             c_float, c_float, c_int, P, P, P, P, P, P, P, c_size_t, c_int, c_int, P, c_int, P]),
-    "gsaj_rasterize_backward_batch": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P,
-                                              P, P, c_float, c_float, P, P, P, P, P, P] + [P] * 12 + [c_int, P]),
+    "gsaj_rasterize_forward": (c_int, _FWD + _FWD_OUT + [P, P, c_size_t, P, ctypes.POINTER(c_int), c_int, P]),
+    "gsaj_rasterize_forward_async": (c_int, _FWD + _FWD_STATE + [P]),
+    "gsaj_rasterize_forward_batch": (c_int, [c_int] + _FWD + _FWD_STATE + [P]),
+    "gsaj_rasterize_backward_batch": (c_int, _BWD_BATCH + [P, P] + _GRADS + [c_int, P]),
     "gsaj_fused_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "gsaj_rasterize_forward_loss": (c_int, [c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_float, P, P, P, P, P,
-                                            c_float, c_float, c_int, P, P, P, P, P, P, P, c_size_t, c_int, c_int, P, c_int,
-                                            c_int, c_float, c_float, P, P, P, P, P, P, P, P]),
-    "gsaj_rasterize_backward_loss": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P, P,
-                                             c_float, c_float, P, P, P, P, c_int, c_float, c_float, P, P, P, P, P, P, P, P] + [P] * 12 + [P]),
+    "gsaj_rasterize_forward_loss": (c_int, _FWD + _FWD_STATE + _LOSS + _LOSS_GT + [P, P, P]),
+    "gsaj_rasterize_backward_loss": (c_int, _BWD + _LOSS + _IMAGES + _LOSS_GT + _GRADS + [P]),
     "gsaj_fused_loss_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "gsaj_rasterize_forward_loss_batch": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_float, P, P, P, P, P,
-                                                  c_float, c_float, c_int, P, P, P, P, P, P, P, c_size_t, c_int, c_int, P, c_int,
-                                                  c_int, c_float, c_float, P, P, P, P, P, c_int, P, P, P, P]),
-    "gsaj_rasterize_backward_loss_batch": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P,
-                                                   P, P, c_float, c_float, P, P, P, P, c_int, c_float, c_float, P, P, P, P, P, P, P, P,
-                                                   c_int] + [P] * 12 + [c_int, P]),
+    "gsaj_rasterize_forward_loss_batch": (c_int, [c_int] + _FWD + _FWD_STATE + _LOSS + _LOSS_GT + [c_int, P, P, P, P]),
+    "gsaj_rasterize_backward_loss_batch": (c_int, _BWD_BATCH + _LOSS + _IMAGES + _LOSS_GT + [c_int] + _GRADS + [c_int, P]),
     "gsaj_forward_aborted_count": (c_int, [c_int, c_int, P, P, ctypes.POINTER(c_int)]),
     "gsaj_set_tile_band": (c_int, [c_int, c_int, P, c_int, c_int, P]),
-    "gsaj_forward_preprocess_cap": (c_int, [c_int] * 5 + [P, P, P, P, P, c_float, P, P, P, P, P, c_float, c_float, c_int, P, P,
-                                            P, P, c_int, c_int, P]),
-    "gsaj_rasterize_backward": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P, P,
-                                        c_float, c_float, P, P, P, P, P, P] + [P] * 12 + [P]),
+    "gsaj_forward_preprocess_cap": (c_int, _PREPROCESS + [c_int, c_int, P]),
+    "gsaj_rasterize_backward": (c_int, _BWD + [P, P] + _GRADS + [P]),
     "gsaj_mark_visible": (c_int, [c_int, P, P, P, P, P]),
     "gsaj_debug_export": (c_int, [c_int] * 4 + [P] * 3 + [P] * 11 + [P]),
     "gsaj_debug_export_taken": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
@@ -116,16 +123,11 @@ SIGNATURES = {
     "gsaj_eval_frame": (c_int, [c_int, c_int, c_int, c_int] + [P] * 7),
     "gsaj_pose_jac_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gsaj_pose_jac_partial_rows": (c_int, [c_int, c_int]),
-    "gsaj_rasterize_pose_jacobian": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P, P,
-                                             c_float, c_float, P, P, P, P, P] + [P] * 5 + [P] * 4 + [P]),
-    "gsaj_rasterize_pose_jacobian_loss": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P, P,
-                                                  c_float, c_float, P, P, P, P, P, c_int, c_float, c_float, P, P, P, P, P, P, P, P,
-                                                  c_float, P, P, P]),
+    "gsaj_rasterize_pose_jacobian": (c_int, _BWD + [P] + [P] * 5 + [P] * 4 + [P]),
+    "gsaj_rasterize_pose_jacobian_loss": (c_int, _JAC_LOSS),
     "gsaj_gn_state_floats": (c_int, []),
     "gsaj_pose_gn_step": (c_int, [P, c_int] + [c_float] * 5 + [P, P, P, P]),
-    "gsaj_rasterize_pose_jacobian_loss8": (c_int, [c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_float, P, P, P, P, P, P,
-                                                   c_float, c_float, P, P, P, P, P, c_int, c_float, c_float, P, P, P, P, P, P, P, P,
-                                                   c_float, P, P, P]),
+    "gsaj_rasterize_pose_jacobian_loss8": (c_int, _JAC_LOSS),
     "gsaj_gn8_state_floats": (c_int, []),
     "gsaj_pose_gn8_step": (c_int, [P, c_int] + [c_float] * 5 + [P, P, P, P]),
 }

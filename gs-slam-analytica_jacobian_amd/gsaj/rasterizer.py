@@ -46,6 +46,105 @@ def _require_cuda(t, what):
         raise RuntimeError("%s must live on the GPU (HIP device): libgsaj_hip has no CPU path" % what)
 
 
+# ---- the argument groups of the rasteriser entry points (include/gsaj.h), each built in ONE place as a tuple in ABI order; a call is
+# a concatenation of groups (DESIGN.md "Argument groups").  The groups that depend on a context's buffers are methods of _Context.
+_ABSENT = object()  # an argument the entry point at hand does not have (the backward family takes no opacities, the forward no raw projection)
+
+
+def _off(t, nbytes):
+    """_ptr(t) moved on by nbytes (a view group's first view); NULL stays NULL."""
+    return None if t is None or t.numel() == 0 else t.data_ptr() + nbytes
+
+
+def _scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, opacities=_ABSENT):
+    """means3D .. cov3D_precomp; the forward family has opacities after colors_precomp."""
+    if opacities is _ABSENT:
+        return _ptr(means3D), _ptr(shs), _ptr(colors_precomp), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp)
+    return (_ptr(means3D), _ptr(shs), _ptr(colors_precomp), _ptr(opacities), _ptr(scales), float(scale_modifier), _ptr(rotations),
+            _ptr(cov3D_precomp))
+
+
+def _view(viewmatrix, projmatrix, campos, tanfovx, tanfovy, projmatrix_raw=_ABSENT, v0=None):
+    """viewmatrix .. tanfovy; the backward family has projmatrix_raw (one for all views) after projmatrix.  v0 given: the views from v0
+    on of a batched call, whose [K,4,4] stacks must be tensors (only campos [K,3] may be absent)."""
+    if v0 is None:
+        vm, pm, cp = _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos)
+    else:
+        vm, pm, cp = viewmatrix.data_ptr() + 64 * v0, projmatrix.data_ptr() + 64 * v0, _off(campos, 12 * v0)
+    if projmatrix_raw is _ABSENT:
+        return vm, pm, cp, float(tanfovx), float(tanfovy)
+    return vm, pm, _ptr(projmatrix_raw), cp, float(tanfovx), float(tanfovy)
+
+
+def _grad_out(g, pose_only=False, v0=0, P=0):
+    """The twelve gradient outputs from a slot dict: ten per-Gaussian ones (all NULL: the pose-only form; a BatchContext's slot has no
+    conic / color / depth), then dL_dtau and dL_dtau_sum.  v0: the per-view ones ([K,P,.], [K,6]) from that view on."""
+    per = (None,) * 10 if pose_only else (
+        g["mean2D"].data_ptr() + 12 * P * v0, _ptr(g.get("conic")), g["opacity"].data_ptr(), _ptr(g.get("color")), _ptr(g.get("depth")),
+        g["mean3D"].data_ptr(), g["cov3D"].data_ptr(), _ptr(g["sh"]), _ptr(g["scale"]), _ptr(g["rot"]))
+    tau_sum = g["tau_sum"] if "tau_sum" in g else g["tau_all"]
+    return per + (_off(g["tau"], 24 * P * v0), tau_sum.data_ptr() + 24 * v0)
+
+
+class _Context:
+    """What FrameContext (one view: K = 1, v0 = 0) and BatchContext (views [v0, v0 + kv) of K) hand the entry points from their own
+    buffers.  Both have P, W, H, M, flags, the output images, radii / n_touched, the three workspaces, capacity, tile_list_capacity and
+    the byte strides between two views' workspace blocks."""
+
+    def _head(self, sh_degree, bg, count=None, K=None):
+        """[K,] P, D, M, [count = R or capacity,] bg, W, H"""
+        head = (self.P, int(sh_degree), self.M) if count is None else (self.P, int(sh_degree), self.M, count)
+        return (head if K is None else (K,) + head) + (_ptr(bg), self.W, self.H)
+
+    def _bind(self):
+        """Once the buffers exist.  A context owns its images, radii / n_touched and the geometry and image workspaces for its whole
+        life, so their addresses are read once and not per call (the host time of a short tracking iteration is mostly such reads);
+        the binning arena is re-allocated as the map grows and is read per call.  (These attributes are not to be re-assigned: the
+        asynchronous forwards, the backwards and the Jacobian walk would go on using the buffers bound here.)"""
+        self._own = tuple(t.data_ptr() for t in (self.color, self.depth, self.opacity, self.radii, self.n_touched, self.geom, self.img))
+
+    def _images(self, v0=0):
+        """color, depth, opacity of view v0"""
+        HW = 4 * self.H * self.W * v0
+        return self._own[0] + 3 * HW, self._own[1] + HW, self._own[2] + HW
+
+    def _fwd_state(self, v0=0, kv=None):
+        """What the asynchronous forwards write and work in: color .. n_touched, geom_ws .. image_ws, flags (kv None: the one view of a
+        FrameContext, whose arena is as large as its tensor says)."""
+        nbytes, HW = self.binning.numel() if kv is None else self.bin_stride * kv, 4 * self.H * self.W * v0
+        color, depth, opacity, radii, n_touched, geom, img = self._own
+        return (color + 3 * HW, depth + HW, opacity + HW, radii + 4 * self.P * v0, n_touched + 4 * self.P * v0, geom + self.geom_stride * v0,
+                self.binning.data_ptr() + self.bin_stride * v0, nbytes, self.capacity, self.tile_list_capacity, img + self.img_stride * v0,
+                self.flags)
+
+    def _bwd_state(self, v0=0):
+        """What every pass over a finished forward reads: radii, geom_ws, binning_ws, image_ws"""
+        return (self._own[3] + 4 * self.P * v0, self._own[5] + self.geom_stride * v0, self.binning.data_ptr() + self.bin_stride * v0,
+                self._own[6] + self.img_stride * v0)
+
+    def _loss(self, L, v0=0, images=False, batched=False):
+        """The loss arguments of the fused entry points from the dict forward_loss describes: flags, alpha, threshold, [the forward's
+        images: the backward forms,] the ground truth and the exposure pair moved on to view v0 [, exposure_stride: the batched forms]."""
+        HW, es = self.H * self.W * v0, int(L.get("exposure_stride", 1)) if batched else 1
+        if batched:
+            K, HW1 = self.K, self.H * self.W
+            for name, n in (("gt_color", 3 * K * HW1), ("gt_depth", K * HW1), ("grad_mask", K * HW1)):
+                t = L.get(name)
+                if t is not None and (t.device.type != "cuda" or not t.is_contiguous() or t.numel() != n or
+                                      t.dtype != (torch.uint8 if name == "grad_mask" else _F32)):
+                    raise _lib.GsajError("forward_loss / backward_loss: %s must be a contiguous device tensor of %d elements" % (name, n))
+            for name in ("exposure_a", "exposure_b"):
+                t = L.get(name)
+                if t is not None and (t.device.type != "cuda" or t.dtype != _F32 or t.dim() != 1 or t.shape[0] != K or
+                                      (K > 1 and t.stride(0) != es)):
+                    raise _lib.GsajError("forward_loss / backward_loss: %s must be a float32 device tensor [K] whose stride is "
+                                         "exposure_stride = %d floats" % (name, es))
+        head = (int(L["flags"]), float(L["alpha"]), float(L["rgb_boundary_threshold"]))
+        gt = (_off(L["gt_color"], 12 * HW), _off(L.get("gt_depth"), 4 * HW), _off(L.get("grad_mask"), HW),
+              _off(L.get("exposure_a"), 4 * es * v0), _off(L.get("exposure_b"), 4 * es * v0))
+        return (head + self._images(v0) if images else head) + (gt + (es,) if batched else gt)
+
+
 _SYM6 = [(k, l) for k in range(6) for l in range(k, 6)]  # the 21 stored elements of a symmetric 6x6: upper triangle by rows
 
 
@@ -113,9 +212,8 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     st = _stream(dev)
     with torch.cuda.device(dev):
         _lib.check(lib.gsaj_forward_preprocess(
-            P, int(degree), M, W, H, _ptr(means3D), _ptr(sh), _ptr(colors), _ptr(opacity), _ptr(scales),
-            float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix),
-            _ptr(campos), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), radii.data_ptr(),
+            P, int(degree), M, W, H, *_scene(means3D, sh, colors, scales, scale_modifier, rotations, cov3D_precomp, opacities=opacity),
+            *_view(viewmatrix, projmatrix, campos, tan_fovx, tan_fovy), int(bool(prefiltered)), radii.data_ptr(),
             n_touched.data_ptr(), geom.data_ptr(), img.data_ptr(), st), "gsaj_forward_preprocess")
         R, mt = ctypes.c_int(0), ctypes.c_int(0)
         _lib.check(lib.gsaj_forward_num_rendered(W, H, img.data_ptr(), st, ctypes.byref(R), ctypes.byref(mt)),
@@ -175,18 +273,15 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     campos = _prep(campos, dev, "campos")
     dL_dout_color = _prep(dL_dout_color, dev, "dL_dout_color")
     dL_dout_depths = _prep(dL_dout_depths, dev, "dL_dout_depths")
-    st = _stream(dev)
+    g = dict(mean2D=dL_dmeans2D, conic=dL_dconic, opacity=dL_dopacity, color=dL_dcolors, depth=dL_ddepths, mean3D=dL_dmeans3D,
+             cov3D=dL_dcov3D, sh=dL_dsh, scale=dL_dscales if scales is not None else None,
+             rot=dL_drotations if rotations is not None else None, tau=dL_dtau, tau_sum=dL_dtau_sum)
     with torch.cuda.device(dev):
         _lib.check(lib.gsaj_rasterize_backward(
-            P, int(degree), M, int(R), _ptr(background), W, H, _ptr(means3D), _ptr(sh), _ptr(colors), _ptr(scales),
-            float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix),
-            _ptr(projmatrix_raw), _ptr(campos), float(tan_fovx), float(tan_fovy), radii.data_ptr(),
-            geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), _ptr(dL_dout_color),
-            _ptr(dL_dout_depths), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(),
-            dL_dcolors.data_ptr(), dL_ddepths.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(),
-            _ptr(dL_dsh), _ptr(dL_dscales) if scales is not None else None,
-            _ptr(dL_drotations) if rotations is not None else None,
-            dL_dtau.data_ptr() if dL_dtau is not None else None, dL_dtau_sum.data_ptr(), st), "gsaj_rasterize_backward")
+            P, int(degree), M, int(R), _ptr(background), W, H, *_scene(means3D, sh, colors, scales, scale_modifier, rotations, cov3D_precomp),
+            *_view(viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, projmatrix_raw=projmatrix_raw), radii.data_ptr(),
+            geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr(), _ptr(dL_dout_color), _ptr(dL_dout_depths),
+            *_grad_out(g), _stream(dev)), "gsaj_rasterize_backward")
         if debug:
             torch.cuda.synchronize(dev)
     if scales is None:
@@ -333,10 +428,11 @@ class ArenaWatch:
         return int(self.host[:, 0].max()), int(self.host[:, 2].max())
 
 
-class FrameContext:
+class FrameContext(_Context):
     """Pre-allocated outputs and workspaces for repeated forward+backward passes over one scene
     size (the tracking / mapping inner loop): no allocation and two C-ABI calls per step.
     The binning workspace grows geometrically when a frame produces more instances."""
+    geom_stride = img_stride = bin_stride = 0  # one view: nothing is ever moved on to a later view's block
 
     def __init__(self, P, W, H, M, device, has_scales=True, per_gaussian_tau=False, grad_slots=1, n_keyframes=0,
                  keyframe=0, record_bits=32):
@@ -378,6 +474,7 @@ class FrameContext:
                 tau_sum=v["tau_all"][keyframe] if n_keyframes else torch.zeros((6,), **f),
                 tau_all=v.get("tau_all")))
         self.bucket, self.g = self.buckets[0], self.slots[0]
+        self._bind()
 
     def set_tile_band(self, tile_row_begin, tile_row_end):
         """Render only tile rows [begin, end) from now on (gsaj_set_tile_band; gsaj.tile_band_shard): the frame's other
@@ -437,45 +534,35 @@ class FrameContext:
         """sync=True: read R back (16-byte D2H, the reference's only sync) and size the arena exactly.
         sync=False: no host round trip at all -- the arena sized by an earlier synchronous frame (x1.5)
         is reused and an overflowing frame aborts on the device; call status() when convenient."""
-        with torch.cuda.device(self.dev):
-            return self._forward(bg, means3D, opacities, viewmatrix, projmatrix, campos, tanfovx, tanfovy, sh_degree, shs, colors_precomp,
-                                 scales, rotations, cov3D_precomp, scale_modifier, sync)
-
-    def _forward(self, bg, means3D, opacities, viewmatrix, projmatrix, campos, tanfovx, tanfovy, sh_degree, shs, colors_precomp, scales,
-                 rotations, cov3D_precomp, scale_modifier, sync):
         lib, st = self.lib, _stream(self.dev)
-        if not sync and self.capacity > 0:
-            self._grow_ahead()
-            _lib.check(lib.gsaj_rasterize_forward_async(
-                self.P, int(sh_degree), self.M, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
-                _ptr(opacities), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tanfovx), float(tanfovy), 0,
-                self.color.data_ptr(), self.depth.data_ptr(), self.opacity.data_ptr(), self.radii.data_ptr(),
-                self.n_touched.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(), self.binning.numel(),
-                self.capacity, self.tile_list_capacity, self.img.data_ptr(), self.flags, st), "gsaj_rasterize_forward_async")
-            self.R = self.capacity  # what the backward must be given (arena carving)
-            if self.auto_grow:
-                self.watch.post()
-            return self.R
-        _lib.check(lib.gsaj_forward_preprocess(
-            self.P, int(sh_degree), self.M, self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
-            _ptr(opacities), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix),
-            _ptr(projmatrix), _ptr(campos), float(tanfovx), float(tanfovy), 0, self.radii.data_ptr(),
-            self.n_touched.data_ptr(), self.geom.data_ptr(), self.img.data_ptr(), st), "gsaj_forward_preprocess")
-        R, mt = ctypes.c_int(0), ctypes.c_int(0)
-        _lib.check(lib.gsaj_forward_num_rendered(self.W, self.H, self.img.data_ptr(), st, ctypes.byref(R), ctypes.byref(mt)),
-                   "gsaj_forward_num_rendered")
-        self.R, self.max_tile_list = R.value, mt.value
-        # asynchronous frames get an LDS sort sized for the longest tile list seen so far + 10 % (the launcher rounds up to a power
-        # of two, which is what the bitonic network pads to anyway; more LDS than that only costs resident workgroups: 2x the
-        # longest list made cfg5's sort 2.2x slower).  A longer list is still sorted -- in LDS-sized chunks and merge passes
-        self.tile_list_capacity = min(SORT_CAP, max(self.tile_list_capacity, int(1.1 * self.max_tile_list) + 1, 256))
-        self._ensure_binning(self.R)
-        self.true_R = self.R
-        _lib.check(lib.gsaj_forward_render(
-            self.P, self.R, -1 if FORCE_CHUNKED_SORT else self.max_tile_list, self.W, self.H, _ptr(bg), _ptr(colors_precomp), self.radii.data_ptr(), self.geom.data_ptr(),
-            self.binning.data_ptr(), self.binning.numel(), self.img.data_ptr(), self.color.data_ptr(),
-            self.depth.data_ptr(), self.opacity.data_ptr(), self.n_touched.data_ptr(), self.flags, st), "gsaj_forward_render")
+        scene = _scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, opacities=opacities)
+        view = _view(viewmatrix, projmatrix, campos, tanfovx, tanfovy)
+        with torch.cuda.device(self.dev):
+            if not sync and self.capacity > 0:
+                self._grow_ahead()
+                _lib.check(lib.gsaj_rasterize_forward_async(*self._head(sh_degree, bg), *scene, *view, 0, *self._fwd_state(), st),
+                           "gsaj_rasterize_forward_async")
+                self.R = self.capacity  # what the backward must be given (arena carving)
+                if self.auto_grow:
+                    self.watch.post()
+                return self.R
+            _lib.check(lib.gsaj_forward_preprocess(
+                self.P, int(sh_degree), self.M, self.W, self.H, *scene, *view, 0, self.radii.data_ptr(),
+                self.n_touched.data_ptr(), self.geom.data_ptr(), self.img.data_ptr(), st), "gsaj_forward_preprocess")
+            R, mt = ctypes.c_int(0), ctypes.c_int(0)
+            _lib.check(lib.gsaj_forward_num_rendered(self.W, self.H, self.img.data_ptr(), st, ctypes.byref(R), ctypes.byref(mt)),
+                       "gsaj_forward_num_rendered")
+            self.R, self.max_tile_list = R.value, mt.value
+            # asynchronous frames get an LDS sort sized for the longest tile list seen so far + 10 % (the launcher rounds up to a power
+            # of two, which is what the bitonic network pads to anyway; more LDS than that only costs resident workgroups: 2x the
+            # longest list made cfg5's sort 2.2x slower).  A longer list is still sorted -- in LDS-sized chunks and merge passes
+            self.tile_list_capacity = min(SORT_CAP, max(self.tile_list_capacity, int(1.1 * self.max_tile_list) + 1, 256))
+            self._ensure_binning(self.R)
+            self.true_R = self.R
+            _lib.check(lib.gsaj_forward_render(
+                self.P, self.R, -1 if FORCE_CHUNKED_SORT else self.max_tile_list, self.W, self.H, _ptr(bg), _ptr(colors_precomp),
+                self.radii.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(), self.binning.numel(), self.img.data_ptr(),
+                *self._images(), self.n_touched.data_ptr(), self.flags, st), "gsaj_forward_render")
         return self.R
 
     # ---- the loss fused into the compositors (gsaj_rasterize_forward_loss / _backward_loss; SURVEY 8(f)-1) -----------------
@@ -491,15 +578,10 @@ class FrameContext:
         with torch.cuda.device(self.dev):
             self._grow_ahead()
             _lib.check(self.lib.gsaj_rasterize_forward_loss(
-                self.P, int(sh_degree), self.M, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
-                _ptr(opacities), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tanfovx), float(tanfovy), 0,
-                self.color.data_ptr(), self.depth.data_ptr(), self.opacity.data_ptr(), self.radii.data_ptr(),
-                self.n_touched.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(), self.binning.numel(),
-                self.capacity, self.tile_list_capacity, self.img.data_ptr(), self.flags, int(loss["flags"]), float(loss["alpha"]),
-                float(loss["rgb_boundary_threshold"]), _ptr(loss["gt_color"]), _ptr(loss.get("gt_depth")), _ptr(loss.get("grad_mask")),
-                _ptr(loss.get("exposure_a")), _ptr(loss.get("exposure_b")), loss["scalars"].data_ptr(), self.loss_ws.data_ptr(),
-                _stream(self.dev)), "gsaj_rasterize_forward_loss")
+                *self._head(sh_degree, bg),
+                *_scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, opacities=opacities),
+                *_view(viewmatrix, projmatrix, campos, tanfovx, tanfovy), 0, *self._fwd_state(), *self._loss(loss),
+                loss["scalars"].data_ptr(), self.loss_ws.data_ptr(), _stream(self.dev)), "gsaj_rasterize_forward_loss")
             if self.auto_grow:
                 self.watch.post()
         self.R = self.capacity
@@ -510,21 +592,12 @@ class FrameContext:
                       pose_only=False):
         """backward() with the pixel seeds derived inside the reverse compositor from this context's color / depth / opacity and the
         ground truth of `loss` (same dict as forward_loss): no dL/dcolor, dL/ddepth images exist."""
-        g = self.slots[slot]
-        if g["tau_all"] is not None:
-            g["tau_all"].zero_()
+        g = self._slot(slot)
         with torch.cuda.device(self.dev):
             _lib.check(self.lib.gsaj_rasterize_backward_loss(
-                self.P, int(sh_degree), self.M, self.R, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs),
-                _ptr(colors_precomp), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                _ptr(viewmatrix), _ptr(projmatrix), _ptr(projmatrix_raw), _ptr(campos), float(tanfovx), float(tanfovy),
-                self.radii.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(), self.img.data_ptr(), int(loss["flags"]),
-                float(loss["alpha"]), float(loss["rgb_boundary_threshold"]), self.color.data_ptr(), self.depth.data_ptr(),
-                self.opacity.data_ptr(), _ptr(loss["gt_color"]), _ptr(loss.get("gt_depth")), _ptr(loss.get("grad_mask")),
-                _ptr(loss.get("exposure_a")), _ptr(loss.get("exposure_b")), *([None] * 10 if pose_only else [
-                    g["mean2D"].data_ptr(), g["conic"].data_ptr(), g["opacity"].data_ptr(), g["color"].data_ptr(),
-                    g["depth"].data_ptr(), g["mean3D"].data_ptr(), g["cov3D"].data_ptr(), _ptr(g["sh"]), _ptr(g["scale"]),
-                    _ptr(g["rot"])]), _ptr(g["tau"]), g["tau_sum"].data_ptr(), _stream(self.dev)), "gsaj_rasterize_backward_loss")
+                *self._head(sh_degree, bg, self.R), *_scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp),
+                *_view(viewmatrix, projmatrix, campos, tanfovx, tanfovy, projmatrix_raw=projmatrix_raw), *self._bwd_state(),
+                *self._loss(loss, images=True), *_grad_out(g, pose_only), _stream(self.dev)), "gsaj_rasterize_backward_loss")
         return g
 
     def backward(self, bg, means3D, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, dL_dcolor, dL_ddepth,
@@ -532,26 +605,18 @@ class FrameContext:
                  scale_modifier=1.0, slot=0, pose_only=False):
         """pose_only=True (tracking: only the camera is optimised): the per-Gaussian parameter gradients are neither
         computed to the end nor stored; only g["tau_sum"] (and g["tau"] if allocated) are valid afterwards."""
+        g = self._slot(slot)
+        with torch.cuda.device(self.dev):
+            _lib.check(self.lib.gsaj_rasterize_backward(
+                *self._head(sh_degree, bg, self.R), *_scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp),
+                *_view(viewmatrix, projmatrix, campos, tanfovx, tanfovy, projmatrix_raw=projmatrix_raw), *self._bwd_state(),
+                _ptr(dL_dcolor), _ptr(dL_ddepth), *_grad_out(g, pose_only), _stream(self.dev)), "gsaj_rasterize_backward")
+        return g
+
+    def _slot(self, slot):
         g = self.slots[slot]
         if g["tau_all"] is not None:
             g["tau_all"].zero_()  # rows of the other ranks' keyframes must be zero before the sum all-reduce
-        with torch.cuda.device(self.dev):
-            self._backward(g, bg, means3D, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, dL_dcolor, dL_ddepth, sh_degree,
-                           shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier, pose_only)
-        return g
-
-    def _backward(self, g, bg, means3D, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy, dL_dcolor, dL_ddepth, sh_degree,
-                  shs, colors_precomp, scales, rotations, cov3D_precomp, scale_modifier, pose_only):
-        _lib.check(self.lib.gsaj_rasterize_backward(
-            self.P, int(sh_degree), self.M, self.R, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs),
-            _ptr(colors_precomp), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-            _ptr(viewmatrix), _ptr(projmatrix), _ptr(projmatrix_raw), _ptr(campos), float(tanfovx), float(tanfovy),
-            self.radii.data_ptr(), self.geom.data_ptr(), self.binning.data_ptr(), self.img.data_ptr(), _ptr(dL_dcolor),
-            _ptr(dL_ddepth), *([None] * 10 if pose_only else [
-                g["mean2D"].data_ptr(), g["conic"].data_ptr(), g["opacity"].data_ptr(), g["color"].data_ptr(),
-                g["depth"].data_ptr(), g["mean3D"].data_ptr(), g["cov3D"].data_ptr(), _ptr(g["sh"]), _ptr(g["scale"]),
-                _ptr(g["rot"])]), _ptr(g["tau"]), g["tau_sum"].data_ptr(), _stream(self.dev)),
-            "gsaj_rasterize_backward")
         return g
 
     # ---- per-pixel pose Jacobians and normal equations (gsaj_rasterize_pose_jacobian / _loss; DESIGN "Gauss-Newton tracking") ----
@@ -586,11 +651,10 @@ class FrameContext:
         cc, cd = (None, None) if curvature is None else [_prep(t, self.dev, "curvature") for t in curvature]
         with torch.cuda.device(self.dev):
             _lib.check(self.lib.gsaj_rasterize_pose_jacobian(
-                self.P, int(sh_degree), self.M, self.R, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
-                _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix),
-                _ptr(projmatrix_raw), _ptr(campos), float(tanfovx), float(tanfovy), self.radii.data_ptr(), self.geom.data_ptr(),
-                self.binning.data_ptr(), self.img.data_ptr(), self.jac_ws.data_ptr(), _ptr(jac), _ptr(col), _ptr(dep), _ptr(H21), _ptr(g6),
-                _ptr(sc), _ptr(sd), _ptr(cc), _ptr(cd), _stream(self.dev)), "gsaj_rasterize_pose_jacobian")
+                *self._head(sh_degree, bg, self.R), *_scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp),
+                *_view(viewmatrix, projmatrix, campos, tanfovx, tanfovy, projmatrix_raw=projmatrix_raw), *self._bwd_state(),
+                self.jac_ws.data_ptr(), _ptr(jac), _ptr(col), _ptr(dep), _ptr(H21), _ptr(g6), _ptr(sc), _ptr(sd), _ptr(cc), _ptr(cd),
+                _stream(self.dev)), "gsaj_rasterize_pose_jacobian")
         out = dict(H=None if H21 is None else unpack_sym6(H21), g=g6, jacobian=jac)
         if want_images:
             out.update(color=col, depth=dep)
@@ -608,22 +672,19 @@ class FrameContext:
         self._jac_ready("pose_jacobian_loss")
         width, own, name = (64, "gn8_partials", "gsaj_rasterize_pose_jacobian_loss8") if solve_exposure else (
             32, "gn_partials", "gsaj_rasterize_pose_jacobian_loss")
-        if partials is None:
+        if partials is None:  # (the context's own rows: made right here, nothing to check)
             if not hasattr(self, own):
                 setattr(self, own, torch.zeros((self.gn_rows, width), device=self.dev, dtype=_F32))
             partials = getattr(self, own)
-        if tuple(partials.shape) != (self.gn_rows, width) or partials.dtype != _F32 or not partials.is_contiguous() or partials.device != self.dev:
+        elif tuple(partials.shape) != (self.gn_rows, width) or partials.dtype != _F32 or not partials.is_contiguous() or partials.device != self.dev:
             raise _lib.GsajError("pose_jacobian_loss: partials must be a contiguous float32 [%d, %d] tensor on %s" % (self.gn_rows, width, self.dev))
         jac = torch.empty((self.H, self.W, 4, 6), device=self.dev, dtype=_F32) if want_jacobian else None
         with torch.cuda.device(self.dev):
             _lib.check(getattr(self.lib, name)(
-                self.P, int(sh_degree), self.M, self.R, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
-                _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix),
-                _ptr(projmatrix_raw), _ptr(campos), float(tanfovx), float(tanfovy), self.radii.data_ptr(), self.geom.data_ptr(),
-                self.binning.data_ptr(), self.img.data_ptr(), self.jac_ws.data_ptr(), int(loss["flags"]), float(loss["alpha"]),
-                float(loss["rgb_boundary_threshold"]), self.color.data_ptr(), self.depth.data_ptr(), self.opacity.data_ptr(),
-                _ptr(loss["gt_color"]), _ptr(loss.get("gt_depth")), _ptr(loss.get("grad_mask")), _ptr(loss.get("exposure_a")),
-                _ptr(loss.get("exposure_b")), float(irls_delta), partials.data_ptr(), _ptr(jac), _stream(self.dev)), name)
+                *self._head(sh_degree, bg, self.R), *_scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp),
+                *_view(viewmatrix, projmatrix, campos, tanfovx, tanfovy, projmatrix_raw=projmatrix_raw), *self._bwd_state(),
+                self.jac_ws.data_ptr(), *self._loss(loss, images=True), float(irls_delta), partials.data_ptr(), _ptr(jac),
+                _stream(self.dev)), name)
         return dict(partials=partials, jacobian=jac)
 
     def interactions(self):
@@ -632,7 +693,7 @@ class FrameContext:
         return int(dbg["n_contrib"].to(torch.int64).sum().item())
 
 
-class BatchContext:
+class BatchContext(_Context):
     """K views of ONE Gaussian map through the batched C-ABI entry points (gsaj_rasterize_forward_batch / _backward_batch): the
     mapping window of the reference (utils/slam_backend.py:168-232) in one set of launches.  Per-view outputs: color / depth /
     opacity [K,.,H,W], radii / n_touched [K,P], g["mean2D"] [K,P,3] (densification reads it per view), g["tau_all"] [K,6];
@@ -683,6 +744,7 @@ class BatchContext:
             self.groups = [(0, k0, None), (k0, K - k0, torch.cuda.Stream(self.dev))]
         else:
             self.groups = [(0, K, None)]
+        self._bind()
 
     def _size(self, capacity):
         self.capacity = int(capacity)
@@ -734,21 +796,26 @@ class BatchContext:
             if st is not None:
                 cur.wait_stream(st)
 
-    def _launch(self, bg, means3D, opacities, viewmatrices, projmatrices, campos, tanfovx, tanfovy, sh_degree, shs, colors_precomp, scales,
-                rotations, cov3D_precomp, scale_modifier):
-        HW, P = self.H * self.W, self.P
+    def _grow_ahead(self):
+        """(asynchronous windows) re-allocate the arena if a recent window came close to filling it; no host synchronisation."""
+        seen = self.watch.poll() if self.auto_grow else None
+        if seen is None:
+            return
+        if seen[0] > self.watch.grow_at * self.capacity:
+            self._size(int(1.5 * seen[0]) + 1024)
+            self.watch.grown += 1
+        if seen[1] > self.tile_list_capacity > 0:
+            self.tile_list_capacity = min(SORT_CAP, int(1.1 * seen[1]) + 1)
+
+    def _launch(self, name, map_args, view_args, tail=lambda v0: ()):
+        """One forward call per view group, each on its stream: map_args = (sh_degree, bg, scene), view_args what _view takes,
+        tail(v0) what the entry point `name` takes between flags and stream."""
+        sh_degree, bg, scene = map_args
         cur = self._fork()
         for v0, kv, st in self.groups:
-            stream = cur if st is None else st
-            _lib.check(self.lib.gsaj_rasterize_forward_batch(
-                kv, P, int(sh_degree), self.M, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
-                _ptr(opacities), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                viewmatrices.data_ptr() + 64 * v0, projmatrices.data_ptr() + 64 * v0, None if campos is None else campos.data_ptr() + 12 * v0,
-                float(tanfovx), float(tanfovy), 0, self.color.data_ptr() + 12 * HW * v0, self.depth.data_ptr() + 4 * HW * v0,
-                self.opacity.data_ptr() + 4 * HW * v0, self.radii.data_ptr() + 4 * P * v0, self.n_touched.data_ptr() + 4 * P * v0,
-                self.geom.data_ptr() + self.geom_stride * v0, self.binning.data_ptr() + self.bin_stride * v0, self.bin_stride * kv,
-                self.capacity, self.tile_list_capacity, self.img.data_ptr() + self.img_stride * v0, self.flags, stream.cuda_stream),
-                "gsaj_rasterize_forward_batch")
+            _lib.check(getattr(self.lib, name)(
+                *self._head(sh_degree, bg, K=kv), *scene, *_view(*view_args, v0=v0), 0, *self._fwd_state(v0, kv), *tail(v0),
+                (cur if st is None else st).cuda_stream), name)
         self._join(cur)
 
     def forward(self, bg, means3D, opacities, viewmatrices, projmatrices, campos, tanfovx, tanfovy, sh_degree=0, shs=None,
@@ -757,18 +824,13 @@ class BatchContext:
         sync=False: no host round trip (arena from an earlier synchronous call; overflowing views abort on the device).
         sync=True: the K instance counts are read back; if a view did not fit, the arena grows and the batch is re-run (tile bands
     set with set_tile_band stay in force: only the abort counters are cleared)."""
-        a = (bg, means3D, opacities, viewmatrices, projmatrices, campos, tanfovx, tanfovy, sh_degree, shs, colors_precomp, scales,
-             rotations, cov3D_precomp, scale_modifier)
+        a = ("gsaj_rasterize_forward_batch",
+             (sh_degree, bg, _scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, opacities=opacities)),
+             (viewmatrices, projmatrices, campos, tanfovx, tanfovy))
         if self.capacity == 0:
             self._size(max(4096, 12 * self.P))
-        elif not sync and self.auto_grow:
-            seen = self.watch.poll()
-            if seen is not None:
-                if seen[0] > self.watch.grow_at * self.capacity:
-                    self._size(int(1.5 * seen[0]) + 1024)
-                    self.watch.grown += 1
-                if seen[1] > self.tile_list_capacity > 0:
-                    self.tile_list_capacity = min(SORT_CAP, int(1.1 * seen[1]) + 1)
+        elif not sync:
+            self._grow_ahead()
         self._launch(*a)
         if not sync:
             if self.auto_grow:
@@ -792,29 +854,19 @@ class BatchContext:
         self.tile_list_capacity = min(SORT_CAP, max(self.tile_list_capacity, int(1.1 * max(m for _, m, _ in st)) + 1, 256))
         return st
 
-    def backward(self, bg, means3D, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy, dL_dcolor, dL_ddepth,
-                 sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, scale_modifier=1.0, slot=0,
-                 split=False):
-        """split=True (one stream): the window's two halves as two calls, GSAJ_BWD_ONLY_COMPOSITE then GSAJ_BWD_ONLY_CHAIN -- the
-        per-view sums go through the geometry workspace (k_gather_sums) instead of being formed inside the chain kernel; the
-        results are the same bits."""
+    def _backward(self, name, slot, split, map_args, view_args, seeds):
+        """The one schedule of both backward forms.  A single group: the whole window in one call, or (split) its two halves,
+        GSAJ_BWD_ONLY_COMPOSITE then GSAJ_BWD_ONLY_CHAIN.  View groups: the composite halves on their streams, join, then the
+        accumulating chains in group order on the caller's stream.  seeds(v0): where dL/dpixel of the views from v0 on comes from."""
         g = self.slots[slot]
         if g["tau_every_window"] is not None:
             g["tau_every_window"].zero_()  # rows of the other ranks' windows must be zero before the sum all-reduce
-        HW, P = self.H * self.W, self.P
+        sh_degree, bg, scene = map_args
 
         def call(v0, kv, stream, flags):
-            _lib.check(self.lib.gsaj_rasterize_backward_batch(
-                kv, P, int(sh_degree), self.M, self.capacity, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs),
-                _ptr(colors_precomp), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                viewmatrices.data_ptr() + 64 * v0, projmatrices.data_ptr() + 64 * v0, _ptr(projmatrix_raw),
-                None if campos is None else campos.data_ptr() + 12 * v0, float(tanfovx), float(tanfovy), self.radii.data_ptr() + 4 * P * v0,
-                self.geom.data_ptr() + self.geom_stride * v0, self.binning.data_ptr() + self.bin_stride * v0,
-                self.img.data_ptr() + self.img_stride * v0, dL_dcolor.data_ptr() + 12 * HW * v0, dL_ddepth.data_ptr() + 4 * HW * v0,
-                g["mean2D"].data_ptr() + 12 * P * v0, None, g["opacity"].data_ptr(), None, None, g["mean3D"].data_ptr(),
-                g["cov3D"].data_ptr(), _ptr(g["sh"]), _ptr(g["scale"]), _ptr(g["rot"]),
-                None if g["tau"] is None else g["tau"].data_ptr() + 24 * P * v0, g["tau_all"].data_ptr() + 24 * v0, flags,
-                stream.cuda_stream), "gsaj_rasterize_backward_batch")
+            _lib.check(getattr(self.lib, name)(
+                *self._head(sh_degree, bg, self.capacity, K=kv), *scene, *_view(*view_args, v0=v0), *self._bwd_state(v0), *seeds(v0),
+                *_grad_out(g, v0=v0, P=self.P), flags, stream.cuda_stream), name)
 
         cur = self._fork()
         if len(self.groups) == 1:
@@ -831,28 +883,20 @@ class BatchContext:
             call(v0, kv, cur, 4 | (1 if i > 0 else 0))
         return g
 
-    # ---- the loss fused into the batched compositors (gsaj_rasterize_forward_loss_batch / _backward_loss_batch) ---------------
-    def _loss_args(self, L, v0):
-        """The loss arguments both fused calls share, for the view group that starts at view v0: (flags, alpha, threshold), then the
-        ground-truth pointers and the exposure pair moved on to view v0."""
-        HW, es = self.H * self.W, int(L.get("exposure_stride", 1))
-        K = self.K
-        for name, n in (("gt_color", 3 * K * HW), ("gt_depth", K * HW), ("grad_mask", K * HW)):
-            t = L.get(name)
-            if t is not None and (t.device.type != "cuda" or not t.is_contiguous() or t.numel() != n or
-                                  t.dtype != (torch.uint8 if name == "grad_mask" else _F32)):
-                raise _lib.GsajError("forward_loss / backward_loss: %s must be a contiguous device tensor of %d elements" % (name, n))
-        for name in ("exposure_a", "exposure_b"):
-            t = L.get(name)
-            if t is not None and (t.device.type != "cuda" or t.dtype != _F32 or t.dim() != 1 or t.shape[0] != K or
-                                  (K > 1 and t.stride(0) != es)):
-                raise _lib.GsajError("forward_loss / backward_loss: %s must be a float32 device tensor [K] whose stride is "
-                                     "exposure_stride = %d floats" % (name, es))
-        off = lambda t, b: None if t is None else t.data_ptr() + b * v0  # noqa: E731
-        return ((int(L["flags"]), float(L["alpha"]), float(L["rgb_boundary_threshold"])),
-                (off(L["gt_color"], 12 * HW), off(L.get("gt_depth"), 4 * HW), off(L.get("grad_mask"), HW),
-                 off(L.get("exposure_a"), 4 * es), off(L.get("exposure_b"), 4 * es), es))
+    def backward(self, bg, means3D, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy, dL_dcolor, dL_ddepth,
+                 sh_degree=0, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, scale_modifier=1.0, slot=0,
+                 split=False):
+        """split=True (one stream): the window's two halves as two calls, GSAJ_BWD_ONLY_COMPOSITE then GSAJ_BWD_ONLY_CHAIN -- the
+        per-view sums go through the geometry workspace (k_gather_sums) instead of being formed inside the chain kernel; the
+        results are the same bits."""
+        HW = self.H * self.W
+        return self._backward(
+            "gsaj_rasterize_backward_batch", slot, split,
+            (sh_degree, bg, _scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp)),
+            (viewmatrices, projmatrices, campos, tanfovx, tanfovy, projmatrix_raw),
+            lambda v0: (dL_dcolor.data_ptr() + 12 * HW * v0, dL_ddepth.data_ptr() + 4 * HW * v0))
 
+    # ---- the loss fused into the batched compositors (gsaj_rasterize_forward_loss_batch / _backward_loss_batch) ---------------
     def forward_loss(self, L, bg, means3D, opacities, viewmatrices, projmatrices, campos, tanfovx, tanfovy, sh_degree=0, shs=None,
                      colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, scale_modifier=1.0):
         """forward(sync=False) whose compositor also sums every view's loss: L is the dict FrameContext.forward_loss takes with
@@ -864,7 +908,7 @@ class BatchContext:
         rows of scalars / dexposure as they were."""
         if self.capacity <= 0:
             raise _lib.GsajError("forward_loss: size the arena with one synchronous forward() first")
-        K, HW, P = self.K, self.H * self.W, self.P
+        K = self.K
         sc, dx = L["scalars"], L.get("dexposure")
         for t, shape in ((sc, (K, 5)), (dx, (K, 2))):
             if t is not None and (t.device.type != "cuda" or t.dtype != _F32 or not t.is_contiguous() or tuple(t.shape) != shape):
@@ -872,29 +916,13 @@ class BatchContext:
         if not hasattr(self, "loss_ws"):
             self.loss_ws_stride = self.lib.gsaj_fused_loss_batch_workspace_bytes(1, self.W, self.H)
             self.loss_ws = torch.empty(self.lib.gsaj_fused_loss_batch_workspace_bytes(K, self.W, self.H), device=self.dev, dtype=torch.uint8)
-        if self.auto_grow:
-            seen = self.watch.poll()
-            if seen is not None:
-                if seen[0] > self.watch.grow_at * self.capacity:
-                    self._size(int(1.5 * seen[0]) + 1024)
-                    self.watch.grown += 1
-                if seen[1] > self.tile_list_capacity > 0:
-                    self.tile_list_capacity = min(SORT_CAP, int(1.1 * seen[1]) + 1)
-        cur = self._fork()
-        for v0, kv, st in self.groups:
-            stream = cur if st is None else st
-            head, loss = self._loss_args(L, v0)
-            _lib.check(self.lib.gsaj_rasterize_forward_loss_batch(
-                kv, P, int(sh_degree), self.M, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs), _ptr(colors_precomp),
-                _ptr(opacities), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                viewmatrices.data_ptr() + 64 * v0, projmatrices.data_ptr() + 64 * v0, None if campos is None else campos.data_ptr() + 12 * v0,
-                float(tanfovx), float(tanfovy), 0, self.color.data_ptr() + 12 * HW * v0, self.depth.data_ptr() + 4 * HW * v0,
-                self.opacity.data_ptr() + 4 * HW * v0, self.radii.data_ptr() + 4 * P * v0, self.n_touched.data_ptr() + 4 * P * v0,
-                self.geom.data_ptr() + self.geom_stride * v0, self.binning.data_ptr() + self.bin_stride * v0, self.bin_stride * kv,
-                self.capacity, self.tile_list_capacity, self.img.data_ptr() + self.img_stride * v0, self.flags, *head, *loss,
-                sc.data_ptr() + 20 * v0, None if dx is None else dx.data_ptr() + 8 * v0, self.loss_ws.data_ptr() + self.loss_ws_stride * v0,
-                stream.cuda_stream), "gsaj_rasterize_forward_loss_batch")
-        self._join(cur)
+        self._grow_ahead()
+        self._launch(
+            "gsaj_rasterize_forward_loss_batch",
+            (sh_degree, bg, _scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, opacities=opacities)),
+            (viewmatrices, projmatrices, campos, tanfovx, tanfovy),
+            lambda v0: self._loss(L, v0, batched=True) + (sc.data_ptr() + 20 * v0, _off(dx, 8 * v0),
+                                                          self.loss_ws.data_ptr() + self.loss_ws_stride * v0))
         if self.auto_grow:
             self.watch.post()
 
@@ -903,39 +931,11 @@ class BatchContext:
         """backward() with every view's pixel seeds derived inside the reverse compositor from this context's color / depth / opacity
         and the ground truth of L (same dict as forward_loss): no [K,3,H,W] / [K,1,H,W] seed images exist.  The gradients are those
         of forward -> LossSeedsBatch -> backward bit for bit; split and the view groups work as in backward()."""
-        g = self.slots[slot]
-        if g["tau_every_window"] is not None:
-            g["tau_every_window"].zero_()
-        HW, P = self.H * self.W, self.P
-
-        def call(v0, kv, stream, flags):
-            head, loss = self._loss_args(L, v0)
-            _lib.check(self.lib.gsaj_rasterize_backward_loss_batch(
-                kv, P, int(sh_degree), self.M, self.capacity, _ptr(bg), self.W, self.H, _ptr(means3D), _ptr(shs),
-                _ptr(colors_precomp), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                viewmatrices.data_ptr() + 64 * v0, projmatrices.data_ptr() + 64 * v0, _ptr(projmatrix_raw),
-                None if campos is None else campos.data_ptr() + 12 * v0, float(tanfovx), float(tanfovy), self.radii.data_ptr() + 4 * P * v0,
-                self.geom.data_ptr() + self.geom_stride * v0, self.binning.data_ptr() + self.bin_stride * v0,
-                self.img.data_ptr() + self.img_stride * v0, *head, self.color.data_ptr() + 12 * HW * v0, self.depth.data_ptr() + 4 * HW * v0,
-                self.opacity.data_ptr() + 4 * HW * v0, *loss, g["mean2D"].data_ptr() + 12 * P * v0, None, g["opacity"].data_ptr(), None,
-                None, g["mean3D"].data_ptr(), g["cov3D"].data_ptr(), _ptr(g["sh"]), _ptr(g["scale"]), _ptr(g["rot"]),
-                None if g["tau"] is None else g["tau"].data_ptr() + 24 * P * v0, g["tau_all"].data_ptr() + 24 * v0, flags,
-                stream.cuda_stream), "gsaj_rasterize_backward_loss_batch")
-
-        cur = self._fork()
-        if len(self.groups) == 1:
-            if split:
-                call(0, self.K, cur, 2)
-                call(0, self.K, cur, 4)
-            else:
-                call(0, self.K, cur, 0)
-            return g
-        for v0, kv, st in self.groups:      # per-view halves: independent, one stream each
-            call(v0, kv, cur if st is None else st, 2)
-        self._join(cur)                      # the accumulating per-Gaussian chains: in group order on the caller's stream
-        for i, (v0, kv, st) in enumerate(self.groups):
-            call(v0, kv, cur, 4 | (1 if i > 0 else 0))
-        return g
+        return self._backward(
+            "gsaj_rasterize_backward_loss_batch", slot, split,
+            (sh_degree, bg, _scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp)),
+            (viewmatrices, projmatrices, campos, tanfovx, tanfovy, projmatrix_raw),
+            lambda v0: self._loss(L, v0, images=True, batched=True))
 
     def view_sums(self, v, stored=False):
         """[P,12]: the reverse compositor's 10 sums per Gaussian of view v of the last backward (gsaj_debug_export_view_sums_gather:

@@ -8,10 +8,10 @@ import re
 import pytest
 import torch
 
+from abi import COMPUTE_LOSS, MONOCULAR, NO_EXPOSURE, call
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("gsaj_fused_loss_batch_workspace_bytes", "gsaj_rasterize_forward_loss_batch", "gsaj_rasterize_backward_loss_batch")
-COMPUTE_LOSS, MONOCULAR, NO_EXPOSURE = 8, 2, 4
-X = 0x1000  # a non-NULL pointer nothing reads: the calls below return before any launch
 
 
 def _lib():
@@ -50,21 +50,17 @@ def test_batch_workspace_is_k_rounded_single_view_blocks(W, H):
         assert lib.gsaj_fused_loss_batch_workspace_bytes(K, W, H) == K * one
 
 
-def _forward(lib, K=3, flags=0, gt_color=X, gt_depth=X, exp_a=X, exp_b=X, stride=1, scalars=X, ws=X):
-    return lib.gsaj_rasterize_forward_loss_batch(
-        K, 300, 3, 16, X, 37, 29, X, X, None, X, X, 1.0, X, None, X, X, X, 0.5, 0.5, 0, X, X, X, X, X, X, X, 1 << 20, 4096, 0, X, 0,
-        flags, 0.9, 0.01, gt_color, gt_depth, None, exp_a, exp_b, stride, scalars, None, ws, None)
+def _forward(lib, **kw):  # (the calls are built by parameter name from the argument groups of tests/abi.py)
+    return call(lib, "gsaj_rasterize_forward_loss_batch", **kw)
 
 
-def _backward(lib, K=3, flags=0, gt_color=X, gt_depth=X, exp_a=X, exp_b=X, stride=1, color=X, bwd_flags=0):
-    return lib.gsaj_rasterize_backward_loss_batch(
-        K, 300, 3, 16, 4096, X, 37, 29, X, X, None, X, 1.0, X, None, X, X, X, X, 0.5, 0.5, X, X, X, X, flags, 0.9, 0.01, color, X, X,
-        gt_color, gt_depth, None, exp_a, exp_b, stride, *([X] * 12), bwd_flags, None)
+def _backward(lib, **kw):
+    return call(lib, "gsaj_rasterize_backward_loss_batch", **kw)
 
 
-CASES = [("K <= 0", dict(K=0)), ("K < 0", dict(K=-2)), ("COMPUTE_LOSS", dict(flags=COMPUTE_LOSS)), ("NULL gt_color", dict(gt_color=None)),
-         ("NULL exposure_a without NO_EXPOSURE", dict(exp_a=None)), ("NULL exposure_b without NO_EXPOSURE", dict(exp_b=None)),
-         ("exposure_stride 0", dict(stride=0)), ("exposure_stride < 0", dict(stride=-80)),
+CASES = [("K <= 0", dict(K=0)), ("K < 0", dict(K=-2)), ("COMPUTE_LOSS", dict(loss_flags=COMPUTE_LOSS)), ("NULL gt_color", dict(gt_color=None)),
+         ("NULL exposure_a without NO_EXPOSURE", dict(exposure_a=None)), ("NULL exposure_b without NO_EXPOSURE", dict(exposure_b=None)),
+         ("exposure_stride 0", dict(exposure_stride=0)), ("exposure_stride < 0", dict(exposure_stride=-80)),
          ("NULL gt_depth without MONOCULAR", dict(gt_depth=None))]
 
 
@@ -77,7 +73,7 @@ def test_loss_argument_errors_are_returned_without_a_launch(what, kw):
         assert b"loss_batch" in msg and b"invalid" in msg, (what, msg)
 
 
-@pytest.mark.parametrize("kw", [dict(scalars=None), dict(ws=None)], ids=["NULL out_scalars", "NULL loss_ws"])
+@pytest.mark.parametrize("kw", [dict(out_scalars=None), dict(loss_ws=None)], ids=["NULL out_scalars", "NULL loss_ws"])
 def test_forward_needs_its_outputs(kw):
     _, lib = _lib()
     assert _forward(lib, **kw) == -1

@@ -81,8 +81,9 @@ def main():
             violations.append("%s %s: %r -> %r" % (key + (p, b)))
     doc = {"method": "hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC (+ -ffp-contract=off on %s) -Rpass-analysis=kernel-resource-usage "
                      "--cuda-device-only, every .hip of csrc/, the parent against this change" % ", ".join(sorted(NOCONTRACT)),
-           "requirement": "every kernel except %s identical in VGPRs, SGPRs, AGPRs, LDS, scratch and occupancy; %s: no scratch, LDS "
-                          "unchanged, occupancy not below the parent's" % (", ".join(a.changed + a.loss_forms), ", ".join(a.loss_forms)),
+           "requirement": "every kernel%s identical in VGPRs, SGPRs, AGPRs, LDS, scratch and occupancy%s" % (
+               " except " + ", ".join(a.changed + a.loss_forms) if a.changed or a.loss_forms else "",
+               "; %s: no scratch, LDS unchanged, occupancy not below the parent's" % ", ".join(a.loss_forms) if a.loss_forms else ""),
            "violations": violations, "kernels": kernels}
     with open(a.out, "w") as fh:
         json.dump(doc, fh, indent=1)
