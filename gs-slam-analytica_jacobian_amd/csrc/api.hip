@@ -95,7 +95,7 @@ int gsaj_profile_end(float *stage_ms, int *stage_launches) {
 }
 
 const char *gsaj_last_error(void) { return g_err; }
-int gsaj_version(void) { return 108; }
+int gsaj_version(void) { return 109; }
 
 size_t gsaj_geom_workspace_bytes(int P) { return geom_carve(nullptr, (size_t)(P > 0 ? P : 0), nullptr) + 256; }
 size_t gsaj_image_workspace_bytes(int W, int H) { return image_carve(nullptr, W, H, nullptr) + 256; }
@@ -144,7 +144,6 @@ struct GnSums {  // what becomes of the Jacobian walk's partial rows: the explic
   FusedLoss *fl;
   bool joint;
 };
-struct Carved { GeomWS g; BinWS b; ImageWS im; ViewStrides vs; };
 static const size_t SIZE_NOT_GIVEN = SIZE_MAX;  // Arenas.binning_bytes of the calls that take no size: carve()'s size check always passes
 
 // The one place the three workspaces are carved.  batch_K == 0, the single-frame calls: from the aligned base of whatever the caller
@@ -726,8 +725,8 @@ size_t gsaj_pose_jac_workspace_bytes(int P, int W, int H) {
 int gsaj_pose_jac_partial_rows(int W, int H) { return gsaj_jac_slots(W, H); }
 
 // the fused form's loss arguments (fl arrives as the caller gave them), in the order a caller is told about them
-static int pose_jac_loss_args(const char *who, bool joint, FusedLoss *fl, const float *gn_partials, float irls_delta) {
-  int rc = fused_loss(who, fl);
+static int pose_jac_loss_args(const char *who, bool joint, FusedLoss *fl, const float *gn_partials, float irls_delta, int K = 1) {
+  int rc = fused_loss(who, fl, K);
   if (rc != GSAJ_OK) return rc;
   if (joint && ((fl->flags & GSAJ_LOSS_NO_EXPOSURE) || !fl->exp_a || !fl->exp_b)) {
     gsaj_set_error("%s: the joint form solves for the exposure: exposure_a / exposure_b are required, GSAJ_LOSS_NO_EXPOSURE is not allowed", who);
@@ -827,6 +826,80 @@ int gsaj_rasterize_pose_jacobian_loss8(int P, int D, int M, int R, const float *
   BwdParams p{};
   p.radii = radii;
   return pose_jac(who, &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, true}, (hipStream_t)stream);
+}
+
+// ---- the same for K views of one map: gridDim.y = K, K consecutive blocks of every workspace (the loss-fused forms only) ----------
+static size_t jac_rows_view_bytes(int P) { return gsaj_jac_rows_bytes(P); }  // (a multiple of 256: view v's rows are v of these on)
+
+size_t gsaj_pose_jac_batch_workspace_bytes(int K, int P, int W, int H) {
+  (void)W; (void)H;  // (the batched forms keep no partial rows of their own: the caller owns gn_partials)
+  return (size_t)(K > 0 ? K : 0) * jac_rows_view_bytes(P);
+}
+
+static int pose_jac_batch(const char *who, BwdParams *p, const Scene &sc, const Views &v, const Arenas &a, void *jac_ws, JacOut jo,
+                          const GnSums &gn, hipStream_t s) {
+  int rc = pose_jac_loss_args(who, gn.joint, gn.fl, jo.partials, jo.delta, v.K);
+  if (rc != GSAJ_OK) return rc;
+  if (sc.P <= 0 || a.instances <= 0 || v.W <= 0 || v.H <= 0 || !v.bg || !sc.means3D || !v.viewmatrix || !v.projmatrix ||
+      !v.projmatrix_raw || !p->radii || !a.geom || !a.binning || !a.image || !jac_ws || (sc.shs && !v.campos) ||
+      (sc.scales && !sc.rotations) || (!sc.scales && !sc.cov3D_precomp)) {
+    gsaj_set_error("%s: invalid argument", who);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  Carved c;
+  if ((rc = carve(a, sc.P, v.W, v.H, v.K, &c)) != GSAJ_OK) return rc;
+  if ((uintptr_t)jac_ws & 255) {
+    gsaj_set_error("batched entry points need 256-byte aligned workspaces");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  bwd_params(p, sc, v, c.g);  // (cov3Ds: the caller's, or view 0's geometry block -- the only one a batched forward writes)
+  float *rows = reinterpret_cast<float *>(jac_ws);
+  if ((rc = launch_splat_jac_batch(*p, v.K, c.g, c.im, rows, c.vs, s)) != GSAJ_OK) return rc;
+  return launch_render_jac_batch(*p, v.K, v.bg, c, rows, jo, *gn.fl, gn.joint ? 1 : 0, s);
+}
+
+int gsaj_rasterize_pose_jacobian_loss_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
+                                            const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                            const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                            const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                            float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
+                                            int loss_flags, float alpha, float rgb_boundary_threshold, const float *color,
+                                            const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
+                                            const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b,
+                                            int exposure_stride, void *jac_ws, float irls_delta, float *gn_partials, float *jac_out,
+                                            void *stream) {
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{K, bg, W, H, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy};
+  const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, capacity, 0, image_ws};
+  const JacOut jo{jac_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gn_partials, irls_delta};
+  FusedLoss fl = loss_args(loss_flags, alpha, rgb_boundary_threshold, gt_color, gt_depth, grad_mask, exposure_a, exposure_b, exposure_stride);
+  fl.color = color; fl.depth = depth; fl.opacity = opacity;
+  BwdParams p{};
+  p.radii = radii;
+  return pose_jac_batch("gsaj_rasterize_pose_jacobian_loss_batch", &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, false},
+                        (hipStream_t)stream);
+}
+
+int gsaj_rasterize_pose_jacobian_loss8_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
+                                             const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                             const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                             const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                             float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
+                                             int loss_flags, float alpha, float rgb_boundary_threshold, const float *color,
+                                             const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
+                                             const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b,
+                                             int exposure_stride, void *jac_ws, float irls_delta, float *gn8_partials, float *jac_out,
+                                             void *stream) {
+  const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
+  const Views v{K, bg, W, H, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy};
+  const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, capacity, 0, image_ws};
+  const JacOut jo{jac_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gn8_partials, irls_delta};
+  FusedLoss fl = loss_args(loss_flags, alpha, rgb_boundary_threshold, gt_color, gt_depth, grad_mask, exposure_a, exposure_b, exposure_stride);
+  fl.color = color; fl.depth = depth; fl.opacity = opacity;
+  BwdParams p{};
+  p.radii = radii;
+  return pose_jac_batch("gsaj_rasterize_pose_jacobian_loss8_batch", &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, true},
+                        (hipStream_t)stream);
 }
 
 int gsaj_mark_visible(int P, const float *means3D, const float *viewmatrix, const float *projmatrix, uint8_t *present,

@@ -174,6 +174,9 @@ static inline size_t bin_carve(char *base, size_t R, BinWS *g) {
 }
 #undef CARVE
 
+// the three workspaces of a call as carved (api.hip: carve()); batched calls: view 0's blocks and the strides to the next view's
+struct Carved { GeomWS g; BinWS b; ImageWS im; ViewStrides vs; };
+
 // ---- error plumbing (api.hip) -------------------------------------------------------------
 void gsaj_set_error(const char *fmt, ...);
 #define GSAJ_HIP_CHECK(expr)                                                          \
@@ -276,6 +279,11 @@ struct JacOut {
 int launch_render_jac(const BwdParams &p, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im, const float *rows,
                       const JacOut &jo, const FusedLoss *fl, int joint, hipStream_t s);
 int launch_gn_reduce(const float *partials, int n, const ImageWS &im, float *H_out, float *g_out, hipStream_t s);
+// K views of one map, the loss-fused forms: p.viewmatrix / projmatrix / campos [K,.], p.radii [K,P]; rows: K blocks of
+// gsaj_jac_rows_bytes(P); jo.partials [K][gsaj_jac_slots(W, H)][row], jo.jac [K,H,W,4,6] or NULL; fl: view 0's pointers
+int launch_splat_jac_batch(const BwdParams &p, int K, const GeomWS &g, const ImageWS &im, float *rows, ViewStrides vs, hipStream_t s);
+int launch_render_jac_batch(const BwdParams &p, int K, const float *bg, const Carved &c, const float *rows, const JacOut &jo,
+                            const FusedLoss &fl, int joint, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 // in-place exclusive scan of n counters by ONE workgroup (knn.hip; the radix sort's digit offsets, seed.hip's compaction offsets)
 void launch_exclusive_scan_u32(int n, uint32_t *v, hipStream_t s);

@@ -25,6 +25,11 @@
 //                  Jacobian columns, J8[ch] = [J[ch][0..5], C_ch, 1 / e^a] (0, 0 in the depth row), under the same seeds and
 //                  curvatures: H8 (36, upper triangle by rows) and g8 (8) in ONE 64-float row per workgroup, 8x8 solve, a and b
 //                  stepped, saved and restored with the pose.  The same body and the same step, instantiated for 8 unknowns.
+//  k_splat_jac_batch / k_render_jac_batch / k_gn_step_batch / k_gn8_step_batch   K views of ONE map (gridDim.y = K, or one workgroup per
+//                  view): the same bodies on view v's blocks -- every per-view pointer moved on by blockIdx.y x its stride -- for K
+//                  independent solves in one set of launches (a keyframe window's poses against a fixed map; K start poses of one
+//                  frame).  Only cov3D is not per view: a batched forward writes it into view 0's geometry block only.
+//  k_gn_select     one wave: the view of smallest accepted loss among the active views that have accepted a pose.
 #include "gsaj_common.h"
 #include "gaussian_chain.h"
 #include "loss_terms.h"
@@ -60,51 +65,71 @@ static_assert(GN8_ACC_EXP + 2 <= GSAJ_GN8_STATE_FLOATS && GN8_ROW == 64, "gn8_st
 // The chain is linear in the ten sums the reverse compositor hands it, so its transpose is the chain applied to unit sums:
 // row j of d(.)/dtau = the tau the chain returns for sum j = 1, all others 0.  Opacity does not depend on tau.  The colour
 // rows are the view-direction term of the SH colour (rho columns only, masked by the clamp flags: sh_backward).
+// (The rows' code is a macro, not a function: written into k_splat_jac it compiles to the instructions that kernel always had --
+// inlined from a function it did not -- and the batched kernel gets the same text.)
+#define SPLAT_JAC_ROWS(p, clamped, counters, rows) \
+  if (counters[4]) return; \
+  const int idx = blockIdx.x * 64 + threadIdx.x; \
+  if (idx >= p.P) return; \
+  const size_t ii = (size_t)idx; \
+  const int radius = p.radii[ii]; \
+  const float3 mean = make_float3(p.means3D[3 * ii], p.means3D[3 * ii + 1], p.means3D[3 * ii + 2]); \
+  float c6[6]; \
+  _Pragma("unroll") \
+  for (int k = 0; k < 6; k++) c6[k] = p.cov3Ds[6 * ii + k]; \
+  uint8_t cl[3] = {0, 0, 0}; \
+  if (p.shs) { \
+    cl[0] = clamped[3 * ii]; cl[1] = clamped[3 * ii + 1]; cl[2] = clamped[3 * ii + 2]; \
+  } \
+  if (radius <= 0) return; \
+  float *row = rows + ii * JROW_F; \
+  _Pragma("unroll 1") \
+  for (int u = 0; u < 6; u++) { \
+    const float4 s0 = make_float4(u == 0 ? 1.f : 0.f, u == 1 ? 1.f : 0.f, u == 2 ? 1.f : 0.f, u == 3 ? 1.f : 0.f); \
+    const float4 s1 = make_float4(u == 4 ? 1.f : 0.f, 0.f, 0.f, 0.f); \
+    const float4 s2 = make_float4(0.f, u == 5 ? 1.f : 0.f, 0.f, 0.f); \
+    GaussianGrads o; \
+    float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; \
+    gaussian_chain_geom(p, mean, c6, s0, s1, s2, o, tau); \
+  _Pragma("unroll") \
+    for (int k = 0; k < 6; k++) row[6 * u + k] = tau[k]; \
+  } \
+  float col[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; \
+  if (p.shs) { \
+    const float3 cam = make_float3(p.campos[0], p.campos[1], p.campos[2]); \
+    const float *sh_row = p.shs + ii * 3 * (size_t)p.M; \
+    float w_unused[16]; \
+  _Pragma("unroll") \
+    for (int ch = 0; ch < 3; ch++) { \
+      const float3 unit = make_float3(ch == 0 ? 1.f : 0.f, ch == 1 ? 1.f : 0.f, ch == 2 ? 1.f : 0.f); \
+      const float3 dmean = sh_backward<1>(p.D, p.M, mean, cam, sh_row, w_unused, cl, unit); \
+      col[3 * ch] = -dmean.x; col[3 * ch + 1] = -dmean.y; col[3 * ch + 2] = -dmean.z; \
+    } \
+  } \
+  float4 *row4 = reinterpret_cast<float4 *>(row + 36); \
+  row4[0] = make_float4(col[0], col[1], col[2], col[3]); \
+  row4[1] = make_float4(col[4], col[5], col[6], col[7]); \
+  row4[2] = make_float4(col[8], 0.f, 0.f, 0.f);
+
 __global__ __launch_bounds__(64) void k_splat_jac(BwdParams p, const uint8_t *__restrict__ clamped, const uint32_t *__restrict__ counters,
                                                   float *__restrict__ rows) {
-  if (counters[4]) return;  // aborted async frame
-  const int idx = blockIdx.x * 64 + threadIdx.x;
-  if (idx >= p.P) return;
-  // every input of this Gaussian is requested up front (streaming kernel)
-  const size_t ii = (size_t)idx;
-  const int radius = p.radii[ii];
-  const float3 mean = make_float3(p.means3D[3 * ii], p.means3D[3 * ii + 1], p.means3D[3 * ii + 2]);
-  float c6[6];
-#pragma unroll
-  for (int k = 0; k < 6; k++) c6[k] = p.cov3Ds[6 * ii + k];
-  uint8_t cl[3] = {0, 0, 0};
-  if (p.shs) {
-    cl[0] = clamped[3 * ii]; cl[1] = clamped[3 * ii + 1]; cl[2] = clamped[3 * ii + 2];
-  }
-  if (radius <= 0) return;  // rows of culled Gaussians are never read: no tile list names them
-  float *row = rows + ii * JROW_F;
-#pragma unroll 1
-  for (int u = 0; u < 6; u++) {  // mean2D x, y, conic a, b, c, depth
-    const float4 s0 = make_float4(u == 0 ? 1.f : 0.f, u == 1 ? 1.f : 0.f, u == 2 ? 1.f : 0.f, u == 3 ? 1.f : 0.f);
-    const float4 s1 = make_float4(u == 4 ? 1.f : 0.f, 0.f, 0.f, 0.f);
-    const float4 s2 = make_float4(0.f, u == 5 ? 1.f : 0.f, 0.f, 0.f);
-    GaussianGrads o;
-    float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    gaussian_chain_geom(p, mean, c6, s0, s1, s2, o, tau);
-#pragma unroll
-    for (int k = 0; k < 6; k++) row[6 * u + k] = tau[k];
-  }
-  float col[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (p.shs) {
-    const float3 cam = make_float3(p.campos[0], p.campos[1], p.campos[2]);
-    const float *sh_row = p.shs + ii * 3 * (size_t)p.M;
-    float w_unused[16];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-      const float3 unit = make_float3(ch == 0 ? 1.f : 0.f, ch == 1 ? 1.f : 0.f, ch == 2 ? 1.f : 0.f);
-      const float3 dmean = sh_backward<1>(p.D, p.M, mean, cam, sh_row, w_unused, cl, unit);
-      col[3 * ch] = -dmean.x; col[3 * ch + 1] = -dmean.y; col[3 * ch + 2] = -dmean.z;  // (gaussian_chain: tau[0..2] -= dmean)
-    }
-  }
-  float4 *row4 = reinterpret_cast<float4 *>(row + 36);
-  row4[0] = make_float4(col[0], col[1], col[2], col[3]);
-  row4[1] = make_float4(col[4], col[5], col[6], col[7]);
-  row4[2] = make_float4(col[8], 0.f, 0.f, 0.f);
+  SPLAT_JAC_ROWS(p, clamped, counters, rows)
+}
+
+// K views of one map (gridDim.y = K): view v's camera, radii, clamp flags, abort word and rows come from view v's blocks.  p.cov3Ds
+// is NOT moved on: Sigma does not depend on the view, and a batched forward writes it into view 0's geometry block only (or the
+// caller gave it) -- as k_chain_window reads it.  projmatrix_raw is shared.
+__global__ __launch_bounds__(64) void k_splat_jac_batch(BwdParams p, const uint8_t *__restrict__ clamped, const uint32_t *__restrict__ counters,
+                                                        float *__restrict__ rows, ViewStrides vs, size_t rows_stride) {
+  const size_t view = blockIdx.y;
+  p.viewmatrix += 16 * view;
+  p.projmatrix += 16 * view;
+  if (p.shs) p.campos += 3 * view;
+  p.radii += view * (size_t)p.P;
+  clamped = gsaj_shift(clamped, view * vs.geom);
+  counters = gsaj_shift(counters, view * vs.image);
+  rows = gsaj_shift(rows, view * rows_stride);
+  SPLAT_JAC_ROWS(p, clamped, counters, rows)
 }
 
 // ---- forward-mode compositor ----------------------------------------------------------------------------------------------
@@ -384,6 +409,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   render_jac_body<true, true>(W, H, gx, tiles, P, im, splat, splat16, bg, point_list, taken, rows, jo, fl);
 }
 
+// K views of one map (gridDim.y = K), the loss-fused forms only: the same body on view v's blocks.  Every per-view pointer is moved on
+// by blockIdx.y x its stride (workgroup-uniform: scalar adds), as k_render_fwd / k_render_bwd do; view v owns gridDim.x partial rows.
+template <bool JOINT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_render_jac_batch(
+    int W, int H, int gx, int tiles, int P, ImageWS im, const float4 *__restrict__ splat, const float4 *__restrict__ splat16,
+    const float *__restrict__ bg, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ taken,
+    const float4 *__restrict__ rows, JacOut jo, FusedLoss fl, ViewStrides vs, size_t rows_stride) {
+  {
+    const size_t view = blockIdx.y, HWv = (size_t)H * W;
+    im = image_view(im, view * vs.image);
+    splat = gsaj_shift(splat, view * vs.geom);
+    splat16 = gsaj_shift(splat16, view * vs.geom);
+    point_list = gsaj_shift(point_list, view * vs.bin);
+    taken = gsaj_shift(taken, view * vs.bin);
+    rows = gsaj_shift(rows, view * rows_stride);
+    if (jo.jac) jo.jac += view * HWv * 24;
+    jo.partials += view * (size_t)gridDim.x * (JOINT ? GN8_ROW : GN_ROW);
+    fused_loss_view(fl, view, HWv, 0);  // (no loss partials here: the sums are slots of jo.partials)
+  }
+  render_jac_body<true, JOINT>(W, H, gx, tiles, P, im, splat, splat16, bg, point_list, taken, rows, jo, fl);
+}
+
 // ---- the partial rows summed in slot order, in fp64 ------------------------------------------------------------------------
 // GN_SUM_THREADS threads = GROUPS row groups x ROW columns (32 groups of the 32-float row, 16 of the joint form's 64-float row): thread
 // (r, c) adds rows r, r + GROUPS, ... of column c, four loads in flight at a time and added in row order, then the groups are added in
@@ -536,6 +583,50 @@ __device__ __forceinline__ void gn_step_body(const GnStepParams &p) {
 __global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_step(GnStepParams p) { gn_step_body<6>(p); }
 __global__ __launch_bounds__(GN_SUM_THREADS) void k_gn8_step(GnStepParams p) { gn_step_body<8>(p); }
 
+// K states in one launch: workgroup v is k_gn_step / k_gn8_step on view v's rows (p.n of them), state and skip word.  active [K]
+// bytes or NULL: an inactive view's state is not touched.  The projection matrix and the LM scalars are shared.
+template <int NX>
+__device__ __forceinline__ void gn_step_view(GnStepParams p, const uint8_t *__restrict__ active, size_t skip_stride) {
+  constexpr int ROW = NX == 8 ? GN8_ROW : GN_ROW, STATE = NX == 8 ? GSAJ_GN8_STATE_FLOATS : GSAJ_GN_STATE_FLOATS;
+  const size_t v = blockIdx.x;
+  if (active && !active[v]) return;
+  p.partials += v * (size_t)p.n * ROW;
+  p.st += v * STATE;
+  if (p.skip) p.skip = gsaj_shift(p.skip, v * skip_stride);
+  gn_step_body<NX>(p);
+}
+__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_step_batch(GnStepParams p, const uint8_t *__restrict__ active, size_t skip_stride) {
+  gn_step_view<6>(p, active, skip_stride);
+}
+__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn8_step_batch(GnStepParams p, const uint8_t *__restrict__ active, size_t skip_stride) {
+  gn_step_view<8>(p, active, skip_stride);
+}
+
+// One wave: the view of smallest accepted loss among the views that are active, have accepted a pose and whose loss is finite; ties
+// go to the lowest index; none: -1 (and +inf).
+__global__ __launch_bounds__(64) void k_gn_select(int K, const float *__restrict__ states, int state_floats, const uint8_t *__restrict__ active,
+                                                  int *__restrict__ best, float *__restrict__ best_loss) {
+  const int lane = threadIdx.x;
+  float bl = __builtin_inff();
+  int bi = 0x7fffffff;
+  for (int v = lane; v < K; v += 64) {  // (ascending v per lane: a strict < keeps the lowest index of a tie)
+    const float *st = states + (size_t)v * state_floats;
+    const float loss = st[GN_ACC_LOSS];
+    const bool ok = (!active || active[v]) && st[GN_HAS] != 0.f && fabsf(loss) < __builtin_inff();
+    if (ok && loss < bl) { bl = loss; bi = v; }  // (a finite loss is below the initial +inf)
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const float ol = __shfl_xor(bl, m);
+    const int oi = __shfl_xor(bi, m);
+    if (oi != 0x7fffffff && (bi == 0x7fffffff || ol < bl || (ol == bl && oi < bi))) { bl = ol; bi = oi; }
+  }
+  if (lane == 0) {
+    *best = bi == 0x7fffffff ? -1 : bi;
+    *best_loss = bi == 0x7fffffff ? __builtin_inff() : bl;
+  }
+}
+
 // ---- launchers (api.hip) ------------------------------------------------------------------------------------------------------
 size_t gsaj_jac_rows_bytes(int P) { return gsaj_align(sizeof(float) * JROW_F * (size_t)(P > 0 ? P : 1)); }
 int gsaj_jac_slots(int W, int H) { return gsaj_fwd_loss_slots(W, H); }
@@ -560,6 +651,28 @@ int launch_render_jac(const BwdParams &p, const float *bg, const GeomWS &g, cons
   else
     hipLaunchKernelGGL(k_render_jac<false>, dim3(nblk), dim3(64), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg, b.point_list, b.taken,
                        reinterpret_cast<const float4 *>(rows), jo, FusedLoss{});
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}
+
+int launch_splat_jac_batch(const BwdParams &p, int K, const GeomWS &g, const ImageWS &im, float *rows, ViewStrides vs, hipStream_t s) {
+  const int nblk = (p.P + 63) / 64;
+  hipLaunchKernelGGL(k_splat_jac_batch, dim3(nblk, K), dim3(64), 0, s, p, g.clamped, im.counters, rows, vs, gsaj_jac_rows_bytes(p.P));
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}
+
+int launch_render_jac_batch(const BwdParams &p, int K, const float *bg, const Carved &c, const float *rows, const JacOut &jo,
+                            const FusedLoss &fl, int joint, hipStream_t s) {
+  const int W = p.W, H = p.H, P = p.P, grid_x = p.grid_x, tiles = p.grid_x * p.grid_y;
+  const dim3 grid((unsigned)gsaj_jac_slots(W, H), (unsigned)K);
+  const size_t rows_stride = gsaj_jac_rows_bytes(P);
+  if (joint)
+    hipLaunchKernelGGL(k_render_jac_batch<true>, grid, dim3(64), 0, s, W, H, grid_x, tiles, P, c.im, c.g.splat, c.g.splat16, bg, c.b.point_list,
+                       c.b.taken, reinterpret_cast<const float4 *>(rows), jo, fl, c.vs, rows_stride);
+  else
+    hipLaunchKernelGGL(k_render_jac_batch<false>, grid, dim3(64), 0, s, W, H, grid_x, tiles, P, c.im, c.g.splat, c.g.splat16, bg, c.b.point_list,
+                       c.b.taken, reinterpret_cast<const float4 *>(rows), jo, fl, c.vs, rows_stride);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }
@@ -605,4 +718,50 @@ extern "C" int gsaj_pose_gn8_step(const float *gn8_partials, int n_partials, flo
                                   void *stream) {
   return gn_step_launch("gsaj_pose_gn8_step", true, gn8_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold,
                         projection_matrix, gn8_state, skip, stream);
+}
+
+// ---- K states in one launch ----------------------------------------------------------------------------------------------------
+struct GnBatch {  // what the batched step adds to the single one's arguments
+  int K;
+  const uint8_t *active;
+  size_t skip_stride;
+};
+
+static int gn_step_batch_launch(const char *who, bool joint, const GnBatch &b, const GnStepParams &p, hipStream_t s) {
+  if (b.K <= 0 || !p.partials || p.n <= 0 || !p.st || !(p.nu > 1.f) || !(p.lambda_min > 0.f) || !(p.lambda_max >= p.lambda_min) ||
+      !(p.lambda_init >= p.lambda_min) || !(p.lambda_init <= p.lambda_max)) {
+    gsaj_set_error("%s: K > 0, gn_partials, n_partials > 0 and gn_states are required; nu > 1, 0 < lambda_min <= lambda_init <= lambda_max", who);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if (joint)
+    hipLaunchKernelGGL(k_gn8_step_batch, dim3((unsigned)b.K), dim3(GN_SUM_THREADS), 0, s, p, b.active, b.skip_stride);
+  else
+    hipLaunchKernelGGL(k_gn_step_batch, dim3((unsigned)b.K), dim3(GN_SUM_THREADS), 0, s, p, b.active, b.skip_stride);
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}
+
+extern "C" int gsaj_pose_gn_step_batch(int K, const float *gn_partials, int n_partials, const uint8_t *active, float lambda_init, float nu,
+                                       float lambda_min, float lambda_max, float converged_threshold, const float *projection_matrix,
+                                       float *gn_states, const uint32_t *skip, size_t skip_stride_bytes, void *stream) {
+  const GnStepParams p{gn_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold, projection_matrix, gn_states, skip};
+  return gn_step_batch_launch("gsaj_pose_gn_step_batch", false, GnBatch{K, active, skip_stride_bytes}, p, (hipStream_t)stream);
+}
+
+extern "C" int gsaj_pose_gn8_step_batch(int K, const float *gn8_partials, int n_partials, const uint8_t *active, float lambda_init, float nu,
+                                        float lambda_min, float lambda_max, float converged_threshold, const float *projection_matrix,
+                                        float *gn8_states, const uint32_t *skip, size_t skip_stride_bytes, void *stream) {
+  const GnStepParams p{gn8_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold, projection_matrix, gn8_states, skip};
+  return gn_step_batch_launch("gsaj_pose_gn8_step_batch", true, GnBatch{K, active, skip_stride_bytes}, p, (hipStream_t)stream);
+}
+
+extern "C" int gsaj_pose_gn_select(int K, const float *gn_states, int state_floats, const uint8_t *active, int *best, float *best_loss,
+                                   void *stream) {
+  if (K <= 0 || !gn_states || (state_floats != GSAJ_GN_STATE_FLOATS && state_floats != GSAJ_GN8_STATE_FLOATS) || !best || !best_loss) {
+    gsaj_set_error("gsaj_pose_gn_select: K > 0, gn_states, state_floats = GSAJ_GN_STATE_FLOATS or GSAJ_GN8_STATE_FLOATS, best and best_loss are required");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  hipLaunchKernelGGL(k_gn_select, dim3(1), dim3(64), 0, (hipStream_t)stream, K, gn_states, state_floats, active, best, best_loss);
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
 }

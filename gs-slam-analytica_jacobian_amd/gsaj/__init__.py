@@ -1,10 +1,13 @@
 """gsaj -- torch-tensor front end of libgsaj_hip.so.  Submodules are imported by name (gsaj.rasterizer, gsaj.tracking, ...);
 the package itself imports nothing, so that `from gsaj import synthetic` needs neither torch nor the library."""
-__all__ = ["GaussNewtonTracker"]
+__all__ = ["GaussNewtonTracker", "GaussNewtonWindow"]
 
 
 def __getattr__(name):
     if name == "GaussNewtonTracker":  # gsaj.GaussNewtonTracker: second-order tracking (gsaj.gauss_newton), loaded on first use
         from .gauss_newton import GaussNewtonTracker
         return GaussNewtonTracker
+    if name == "GaussNewtonWindow":   # K such solves against one fixed map in one set of launches
+        from .gauss_newton import GaussNewtonWindow
+        return GaussNewtonWindow
     raise AttributeError("module 'gsaj' has no attribute %r" % name)

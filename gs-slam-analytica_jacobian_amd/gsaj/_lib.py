@@ -37,6 +37,8 @@ _BWD = _PDM + [c_int] + _BG_WH + _SCENE_BWD + _VIEW_BWD + _BWD_STATE          # 
 _BWD_BATCH = [c_int] + _PDM + [c_int] + _BWD[4:]                              # K, P, D, M, capacity ..
 _PREPROCESS = _PDM + [c_int, c_int] + _SCENE_FWD + _VIEW_FWD + [c_int, P, P, P, P]  # P, D, M, W, H .. prefiltered, radii, n_touched, geom_ws, image_ws
 _JAC_LOSS = _BWD + [P] + _LOSS + _IMAGES + _LOSS_GT + [c_float, P, P, P]      # .. jac_ws, the loss, irls_delta, gn_partials, jac_out, stream
+_JAC_LOSS_BATCH = _BWD_BATCH + _LOSS + _IMAGES + _LOSS_GT + [c_int, P, c_float, P, P, P]  # .. exposure_stride, jac_ws, irls_delta, gn_partials, jac_out, stream
+_GN_STEP_BATCH = [c_int, P, c_int, P] + [c_float] * 5 + [P, P, P, c_size_t, P]  # K, partials, n_partials, active, the LM scalars, projection, states, skip, its stride, stream
 
 # name -> (restype, argtypes); must list every function include/gsaj.h declares
 SIGNATURES = {
@@ -130,6 +132,12 @@ SIGNATURES = {
     "gsaj_rasterize_pose_jacobian_loss8": (c_int, _JAC_LOSS),
     "gsaj_gn8_state_floats": (c_int, []),
     "gsaj_pose_gn8_step": (c_int, [P, c_int] + [c_float] * 5 + [P, P, P, P]),
+    "gsaj_pose_jac_batch_workspace_bytes": (c_size_t, [c_int] * 4),
+    "gsaj_rasterize_pose_jacobian_loss_batch": (c_int, _JAC_LOSS_BATCH),
+    "gsaj_rasterize_pose_jacobian_loss8_batch": (c_int, _JAC_LOSS_BATCH),
+    "gsaj_pose_gn_step_batch": (c_int, _GN_STEP_BATCH),
+    "gsaj_pose_gn8_step_batch": (c_int, _GN_STEP_BATCH),
+    "gsaj_pose_gn_select": (c_int, [c_int, P, c_int, P, P, P, P]),
 }
 
 _lib = None

@@ -173,3 +173,200 @@ class GaussNewtonTracker:
             self.ctx.capacity = 0
             raise
         return done
+
+
+# ---- K independent solves against ONE map, in one set of launches ------------------------------------------------------------------
+def _launch(win, sync):  # (the one iteration's device work: host-logic tests replace it)
+    """Batched forward at the K proposed poses -> BatchContext.pose_jacobian_loss -> gsaj_pose_gn[8]_step_batch."""
+    c, n = win.ctx, win.state.shape[1]
+    views, projs, cps = win.matrices()
+    c.forward(win.bg, win.means, win.opac, views, projs, cps, win.tanfov[0], win.tanfov[1], sync=sync, **win.kw)
+    L = dict(flags=win.flags, alpha=win.alpha, rgb_boundary_threshold=win.thr, gt_color=win.gt_color, gt_depth=win.gt_depth,
+             grad_mask=win.grad_mask, exposure_a=win.state[:, 33], exposure_b=win.state[:, 34], exposure_stride=n)
+    o = c.pose_jacobian_loss(L, win.bg, win.means, views, projs, win.praw, cps, win.tanfov[0], win.tanfov[1], irls_delta=win.delta,
+                             solve_exposure=win.solve_exposure, **win.kw)
+    skip, skip_stride = c.abort_flags()
+    name = "gsaj_pose_gn8_step_batch" if win.solve_exposure else "gsaj_pose_gn_step_batch"
+    _lib.check(getattr(win.lib, name)(win.K, o["partials"].data_ptr(), o["partials"].shape[1], win.active.data_ptr(), *win.lm_args,
+                                      win.projection.data_ptr(), win.state.data_ptr(), skip, skip_stride,
+                                      torch.cuda.current_stream(win.dev).cuda_stream), name)
+
+
+def _select(win):  # (device work too)
+    """gsaj_pose_gn_select into win._best: int32 [2] = the index, the bits of its loss."""
+    _lib.check(win.lib.gsaj_pose_gn_select(win.K, win.state.data_ptr(), win.state.shape[1], win.active.data_ptr(), win._best.data_ptr(),
+                                           win._best.data_ptr() + 4, torch.cuda.current_stream(win.dev).cuda_stream), "gsaj_pose_gn_select")
+
+
+class GaussNewtonWindow:
+    """GaussNewtonTracker for K views of ONE fixed map, solved together: every kernel of an iteration runs once with gridDim.y = K
+    (batched forward, Jacobian walk, K Levenberg-Marquardt steps in one launch).  With the map fixed the K poses decouple, so the K
+    solves are exact, and each view's arithmetic is the single tracker's.  Two uses:
+      the keyframe window -- set_view(slot, ...): each slot has its own frame, pose and exposure;
+      multi-start tracking of one frame -- set_frame(..., w2cs=K starts): one frame in all K slots; best() names the hypothesis of
+      smallest accepted loss, chosen on the device.
+    `active` ([K] uint8, device) is a mask: a view whose byte is 0 is rendered but its state is not touched."""
+
+    def __init__(self, K, P, W, H, M, device, w2cs, projection_matrix, tanfovx, tanfovy, bg, means3D, opacities, sh_degree=0, shs=None,
+                 colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, monocular=False, alpha=0.95,
+                 rgb_boundary_threshold=0.01, record_bits=32, irls_delta=0.01, lambda_init=1e-3, nu=4.0, lambda_min=1e-7,
+                 lambda_max=1e7, converged_threshold=1e-4, solve_exposure=False, streams=1):
+        """The arguments of GaussNewtonTracker with K and w2cs [K,4,4]; streams: BatchContext's view groups."""
+        if torch.device(device).type != "cuda":
+            raise _lib.GsajError("GaussNewtonWindow needs a HIP device (there is no CPU path)")
+        from .rasterizer import BatchContext
+        ctx = BatchContext(K, P, W, H, M, device, has_scales=scales is not None, record_bits=record_bits, streams=streams)
+        self._init_host(ctx, w2cs, projection_matrix, (tanfovx, tanfovy), bg, means3D, opacities,
+                        dict(sh_degree=sh_degree, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
+                             cov3D_precomp=cov3D_precomp),
+                        dict(monocular=monocular, alpha=alpha, rgb_boundary_threshold=rgb_boundary_threshold, irls_delta=irls_delta),
+                        (lambda_init, nu, lambda_min, lambda_max, converged_threshold), solve_exposure)
+
+    def _init_host(self, ctx, w2cs, projection_matrix, tanfov, bg, means3D, opacities, kw, loss, lm_args, solve_exposure):
+        """Everything but the context: buffers and state, no kernel."""
+        self.ctx, self.lib = ctx, _lib.load()
+        self.K, self.W, self.H, self.dev = ctx.K, ctx.W, ctx.H, ctx.dev
+        self.solve_exposure = bool(solve_exposure)
+        self._o = _O8 if self.solve_exposure else _O
+        n_state = self.lib.gsaj_gn8_state_floats() if self.solve_exposure else self.lib.gsaj_gn_state_floats()
+        self.state = torch.zeros((self.K, n_state), dtype=torch.float32, device=self.dev)
+        self.projection = torch.as_tensor(projection_matrix, dtype=torch.float32).reshape(4, 4).contiguous().to(self.dev)
+        self.praw = self.projection
+        self.tanfov = (float(tanfov[0]), float(tanfov[1]))
+        self.flags = TRACKING | (MONOCULAR if loss["monocular"] else 0)
+        self.alpha, self.thr, self.delta = float(loss["alpha"]), float(loss["rgb_boundary_threshold"]), float(loss["irls_delta"])
+        self.lm_args = tuple(float(x) for x in lm_args)
+        self.bg, self.means, self.opac, self.kw = bg, means3D, opacities, kw
+        f = dict(dtype=torch.float32, device=self.dev)
+        self.gt_color = torch.zeros((self.K, 3, self.H, self.W), **f)
+        self.gt_depth = None if loss["monocular"] else torch.zeros((self.K, self.H, self.W), **f)
+        self.grad_mask = None  # uint8 [K*H*W] once a slot was given a mask (the other slots: all ones, which is no mask)
+        self.active = torch.ones(self.K, dtype=torch.uint8, device=self.dev)
+        self._best = torch.zeros(2, dtype=torch.int32, device=self.dev)
+        self._filled = [False] * self.K
+        self._sized = False
+        self.iterations = 0
+        w2cs = torch.as_tensor(w2cs, dtype=torch.float32)
+        if tuple(w2cs.shape) != (self.K, 4, 4):
+            raise _lib.GsajError("GaussNewtonWindow: w2cs must be [%d,4,4], got %r" % (self.K, tuple(w2cs.shape)))
+        for k in range(self.K):
+            self.reset(k, w2cs[k])
+
+    def _slot(self, slot):
+        if not 0 <= int(slot) < self.K:
+            raise _lib.GsajError("GaussNewtonWindow: slot %r is not one of the window's %d" % (slot, self.K))
+        return int(slot)
+
+    def reset(self, slot, w2c, exposure=(0.0, 0.0)):
+        """Slot `slot` starts over: pose (and exposure), no accepted step, lambda back to lambda_init -- as GaussNewtonTracker.reset."""
+        s = self.state[self._slot(slot)]
+        s.zero_()
+        s[0:16] = torch.as_tensor(w2c, dtype=torch.float32).reshape(16).to(self.dev)
+        s[33] = float(exposure[0])
+        s[34] = float(exposure[1])
+        w = s[0:16].view(4, 4)
+        s[35:51] = w.t().reshape(16)
+        s[51:67] = (w.t() @ self.projection).reshape(16)
+        s[67:70] = -(torch.linalg.inv(w[:3, :3].double().cpu()) @ w[:3, 3].double().cpu()).float().to(self.dev)
+        s[80] = self.lm_args[0]
+        s[88:104] = s[0:16]
+        if self.solve_exposure:
+            s[148:150] = s[33:35]
+
+    def set_view(self, slot, gt_color, gt_depth=None, grad_mask=None, w2c=None, exposure=None):
+        """The window use: slot `slot` gets its own frame -- ground truth (device, [3,H,W] / [H,W]; grad_mask [1,H,W] or None), copied
+        into the window's [K,...] buffers -- and optionally a new start pose (with `exposure` (a, b), default (0, 0))."""
+        k, H, W = self._slot(slot), self.H, self.W
+        if tuple(gt_color.shape) != (3, H, W):
+            raise _lib.GsajError("set_view: gt_color must be [3,%d,%d], got %r" % (H, W, tuple(gt_color.shape)))
+        if (gt_depth is None) != (self.gt_depth is None):
+            raise _lib.GsajError("set_view: a monocular window takes no depth, every other window needs it")
+        if gt_depth is not None and gt_depth.numel() != H * W:
+            raise _lib.GsajError("set_view: gt_depth must have %d elements, got %d" % (H * W, gt_depth.numel()))
+        if grad_mask is not None and grad_mask.numel() != H * W:
+            raise _lib.GsajError("set_view: grad_mask must have %d elements, got %d" % (H * W, grad_mask.numel()))
+        self.gt_color[k].copy_(gt_color)
+        if gt_depth is not None:
+            self.gt_depth[k].copy_(gt_depth.reshape(H, W))
+        if grad_mask is not None and self.grad_mask is None:
+            self.grad_mask = torch.ones(self.K * H * W, dtype=torch.uint8, device=self.dev)
+        if self.grad_mask is not None:
+            m = self.grad_mask[k * H * W:(k + 1) * H * W]
+            if grad_mask is None:
+                m.fill_(1)
+            else:
+                m.copy_(grad_mask.to(self.dev, torch.uint8).reshape(-1))
+        self._filled[k] = True
+        if w2c is not None or exposure is not None:
+            self.reset(k, self.state[k, 0:16].clone() if w2c is None else w2c, (0.0, 0.0) if exposure is None else exposure)
+
+    def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2cs=None, exposure=None):
+        """The multi-start use: ONE frame copied into all K slots, with K start poses w2cs [K,4,4] (None: the slots keep theirs)."""
+        if w2cs is not None:
+            w2cs = torch.as_tensor(w2cs, dtype=torch.float32)
+            if tuple(w2cs.shape) != (self.K, 4, 4):
+                raise _lib.GsajError("set_frame: w2cs must be [%d,4,4], got %r" % (self.K, tuple(w2cs.shape)))
+        for k in range(self.K):
+            self.set_view(k, gt_color, gt_depth, grad_mask, None if w2cs is None else w2cs[k], exposure)
+
+    def matrices(self):
+        """(viewmatrices [K,4,4], projmatrices [K,4,4], campos [K,3]) of the poses the next render is at, gathered from the state."""
+        s = self.state
+        return s[:, 35:51].reshape(self.K, 4, 4).contiguous(), s[:, 51:67].reshape(self.K, 4, 4).contiguous(), s[:, 67:70].contiguous()
+
+    def _v(self, name, shape=()):
+        a, b = self._o[name]
+        return self.state[:, a:b].view(self.K, *shape) if shape else self.state[:, a:b]
+
+    w2c = property(lambda s: s.state[:, 0:16].view(s.K, 4, 4))
+    exposure = property(lambda s: s.state[:, 33:35])
+    tau = property(lambda s: s._v("tau"))
+    converged = property(lambda s: s.state[:, 77])
+    accepted_w2c = property(lambda s: s.state[:, 88:104].view(s.K, 4, 4))
+
+    @property
+    def accepted_exposure(self):
+        """[K,2]: a, b of each view's last accepted step (without solve_exposure the exposure never moves: the state's own)."""
+        return self._v("acc_exposure") if self.solve_exposure else self.state[:, 33:35]
+
+    @property
+    def loss_terms(self):
+        """[K,3]: loss, L_rgb, L_depth of each view's last render."""
+        return self._v("last")
+
+    @property
+    def lm(self):
+        """GaussNewtonTracker.lm with [K,...] entries: lam, accepted, rejected, accepted_loss [K]; H [K,6,6] / [K,8,8], g [K,6] / [K,8]."""
+        s = self.state
+        return dict(lam=s[:, 80], accepted=s[:, 83], rejected=s[:, 84], accepted_loss=s[:, 81],
+                    H=(unpack_sym8 if self.solve_exposure else unpack_sym6)(self._v("H")), g=self._v("g"))
+
+    def iterate(self, n, check_every=0):
+        """Up to n iterations of all K views.  The first is synchronous (it sizes the arena); after it an iteration contains no host
+        read.  check_every > 0: every check_every iterations the K converged flags are read once, and the loop stops when every
+        active view has converged.  Returns the number run.  Raises GsajError after the loop if a view was aborted on the device
+        (its state was skipped in those iterations); the next call re-sizes the arena with one synchronous iteration."""
+        if not all(self._filled):
+            raise _lib.GsajError("set_view() every slot (or set_frame()) first: slots %r have no frame" %
+                                 [k for k, ok in enumerate(self._filled) if not ok])
+        done = 0
+        while done < n:
+            _launch(self, not self._sized)
+            self._sized = True
+            done += 1
+            if check_every and done % check_every == 0 and bool(((self.state[:, 77] != 0) | (self.active == 0)).all().item()):
+                break
+        self.iterations += done
+        aborted = self.ctx.clear_aborts()
+        if aborted:
+            self._sized = False
+            raise _lib.GsajError("%d asynchronous forward(s) of the window were aborted on the device (binning arena too small for a "
+                                 "view's instances): those views' states were skipped" % aborted)
+        return done
+
+    def best(self):
+        """(index, accepted loss) of the active view of smallest finite accepted loss (ties: the lowest index), chosen on the device
+        by gsaj_pose_gn_select and read back in one copy; (-1, inf) if no active view has accepted a pose."""
+        _select(self)
+        h = self._best.cpu()
+        return int(h[0]), float(h[1:2].view(torch.float32)[0])

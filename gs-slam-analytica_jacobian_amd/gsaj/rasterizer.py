@@ -693,6 +693,15 @@ class FrameContext(_Context):
         return int(dbg["n_contrib"].to(torch.int64).sum().item())
 
 
+def _launch_groups(ctx, name, calls):  # (the one place pose_jacobian_loss needs the device: host-logic tests replace it)
+    """One call of entry point `name` per view group of a BatchContext, each on its stream: calls = [(stream or None, arguments up to
+    the stream)]."""
+    cur = ctx._fork()
+    for st, args in calls:
+        _lib.check(getattr(ctx.lib, name)(*args, (cur if st is None else st).cuda_stream), name)
+    ctx._join(cur)
+
+
 class BatchContext(_Context):
     """K views of ONE Gaussian map through the batched C-ABI entry points (gsaj_rasterize_forward_batch / _backward_batch): the
     mapping window of the reference (utils/slam_backend.py:168-232) in one set of launches.  Per-view outputs: color / depth /
@@ -726,6 +735,7 @@ class BatchContext(_Context):
         self.img = torch.zeros(K * self.img_stride, **byte)  # zeroed once: holds the sticky abort counters
         self.binning = torch.empty(0, **byte)
         self.capacity, self.tile_list_capacity, self.bin_stride = 0, 0, 0
+        self.bands = {}  # view -> the tile band set on it (set_tile_band); the Jacobian walk refuses a window with one
         self.watch = ArenaWatch(self.img, self.K, self.img_stride, lib.gsaj_forward_abort_flag(W, H, self.img.data_ptr()) - 16 - self.img.data_ptr())
         self.auto_grow = os.environ.get("GSAJ_ARENA_WATCH", "1") != "0"  # sync=False windows: grow the arena ahead of an overflow (ArenaWatch)
         self.buckets, self.slots = [], []
@@ -757,6 +767,7 @@ class BatchContext(_Context):
         for v in (range(self.K) if views is None else views):
             _lib.check(self.lib.gsaj_set_tile_band(self.W, self.H, self.img.data_ptr() + int(v) * self.img_stride, int(tile_row_begin),
                                                    int(tile_row_end), _stream(self.dev)), "gsaj_set_tile_band")
+            self.bands[int(v)] = (int(tile_row_begin), int(tile_row_end))
 
     def status(self):
         """Blocking: per view (num_rendered, longest tile list, aborted)."""
@@ -936,6 +947,46 @@ class BatchContext(_Context):
             (sh_degree, bg, _scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp)),
             (viewmatrices, projmatrices, campos, tanfovx, tanfovy, projmatrix_raw),
             lambda v0: self._loss(L, v0, images=True, batched=True))
+
+    # ---- the pose Jacobians and normal equations of the K views (gsaj_rasterize_pose_jacobian_loss_batch / _loss8_batch) ----------
+    def pose_jacobian_loss(self, L, bg, means3D, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy, irls_delta=0.0,
+                           partials=None, want_jacobian=False, solve_exposure=False, sh_degree=0, shs=None, colors_precomp=None,
+                           scales=None, rotations=None, cov3D_precomp=None, scale_modifier=1.0):
+        """FrameContext.pose_jacobian_loss for the K views of the last forward of this context, in one set of launches: L is the
+        dict forward_loss / backward_loss take ([K,...] tensors; the exposure pair may be read in place with exposure_stride).  Fills
+        `partials` (float32 [K, gn_rows, 32], or [K, gn_rows, 64] with solve_exposure; made on the first call if None): view v's rows
+        are what the single-view entry point writes for view v -- for gsaj_pose_gn_step_batch / gsaj_pose_gn8_step_batch.  A view
+        aborted on the device keeps its rows.  -> dict(partials, jacobian [K,H,W,4,6] or None)."""
+        what = "pose_jacobian_loss"
+        if self.binning.numel() == 0:
+            raise _lib.GsajError("%s: run a forward of this context first (it walks the finished forward's state)" % what)
+        if any(b != (0, (self.H + 15) // 16) for b in self.bands.values()):
+            raise _lib.GsajError("%s: a tile band is set on a view of this context (band sharding of the Jacobian is not supported)" % what)
+        if not hasattr(self, "jac_ws"):
+            self.jac_stride = self.lib.gsaj_pose_jac_batch_workspace_bytes(1, self.P, self.W, self.H)
+            self.jac_ws = torch.empty(self.K * self.jac_stride, device=self.dev, dtype=torch.uint8)
+            self.gn_rows = self.lib.gsaj_pose_jac_partial_rows(self.W, self.H)
+        width, own, name = (64, "gn8_partials", "gsaj_rasterize_pose_jacobian_loss8_batch") if solve_exposure else (
+            32, "gn_partials", "gsaj_rasterize_pose_jacobian_loss_batch")
+        shape = (self.K, self.gn_rows, width)
+        if partials is None:
+            if not hasattr(self, own):
+                setattr(self, own, torch.zeros(shape, device=self.dev, dtype=_F32))
+            partials = getattr(self, own)
+        elif tuple(partials.shape) != shape or partials.dtype != _F32 or not partials.is_contiguous() or partials.device != self.dev:
+            raise _lib.GsajError("%s: partials must be a contiguous float32 [%d, %d, %d] tensor on %s" % ((what,) + shape + (self.dev,)))
+        for t in (means3D, viewmatrices, projmatrices, projmatrix_raw):
+            if not torch.is_tensor(t) or t.device.type != "cuda":
+                raise _lib.GsajError("%s: means3D and the camera matrices must be device tensors (there is no CPU path)" % what)
+        jac = torch.empty((self.K, self.H, self.W, 4, 6), device=self.dev, dtype=_F32) if want_jacobian else None
+        scene = _scene(means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp)
+        view_args = (viewmatrices, projmatrices, campos, tanfovx, tanfovy, projmatrix_raw)
+        calls = [(st, self._head(sh_degree, bg, self.capacity, K=kv) + scene + _view(*view_args, v0=v0) + self._bwd_state(v0) +
+                  self._loss(L, v0, images=True, batched=True) +
+                  (self.jac_ws.data_ptr() + self.jac_stride * v0, float(irls_delta), partials.data_ptr() + 4 * self.gn_rows * width * v0,
+                   _off(jac, 96 * self.H * self.W * v0))) for v0, kv, st in self.groups]
+        _launch_groups(self, name, calls)
+        return dict(partials=partials, jacobian=jac)
 
     def view_sums(self, v, stored=False):
         """[P,12]: the reverse compositor's 10 sums per Gaussian of view v of the last backward (gsaj_debug_export_view_sums_gather:

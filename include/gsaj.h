@@ -558,6 +558,52 @@ int gsaj_pose_gn8_step(const float *gn8_partials, int n_partials, float lambda_i
                        float converged_threshold, const float *projection_matrix, float *gn8_state, const uint32_t *skip,
                        void *stream);
 
+/* The same for K views of ONE map in one set of launches (gridDim.y = K): K independent solves -- the keyframe poses of a window
+ * against a fixed map, or K start poses of one frame.  The loss-fused forms only; a tile band on any view is not supported.
+ * gsaj_rasterize_pose_jacobian_loss_batch / _loss8_batch -- the arguments of gsaj_rasterize_backward_loss_batch up to the loss
+ *   group (on a FINISHED gsaj_rasterize_forward[_loss]_batch of the same K views: 256-byte aligned blocks, `capacity` as there),
+ *   then jac_ws (gsaj_pose_jac_batch_workspace_bytes(K, P, W, H) bytes, 256-byte aligned), irls_delta, gn_partials
+ *   [K][gsaj_pose_jac_partial_rows(W, H)][GSAJ_GN_PARTIAL_FLOATS | GSAJ_GN8_PARTIAL_FLOATS] and jac_out [K,H,W,4,6] or NULL.
+ *   View v's rows are the bits of the single-view entry point on view v's blocks.  cov3D is read from the caller's cov3D_precomp
+ *   or from view 0's geometry block, the only one a batched forward writes.  A view aborted on the device keeps its rows.
+ *   K <= 0, misaligned blocks and, in the joint form, GSAJ_LOSS_NO_EXPOSURE or a NULL exposure: GSAJ_ERR_INVALID_ARGUMENT.
+ * gsaj_pose_gn_step_batch / gsaj_pose_gn8_step_batch -- K workgroups, each gsaj_pose_gn_step / gsaj_pose_gn8_step on view v's
+ *   n_partials rows, state v of gn_states [K, GSAJ_GN_STATE_FLOATS | GSAJ_GN8_STATE_FLOATS] and the skip word at skip + v *
+ *   skip_stride_bytes; active [K] bytes or NULL (0: that state is not touched), as gsaj_pose_adam_step_batch.  The projection
+ *   matrix and the LM scalars are shared.
+ * gsaj_pose_gn_select -- *best (device int32) = the view of smallest accepted loss [81] among the views that are active, have
+ *   accepted a pose ([82] != 0) and have a finite loss, ties to the lowest index, -1 if there is none; *best_loss (device) its
+ *   loss (+inf if none).  state_floats: GSAJ_GN_STATE_FLOATS or GSAJ_GN8_STATE_FLOATS. */
+size_t gsaj_pose_jac_batch_workspace_bytes(int K, int P, int W, int H);
+int gsaj_rasterize_pose_jacobian_loss_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
+                                            const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                            const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                            const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                            float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
+                                            int loss_flags, float alpha, float rgb_boundary_threshold, const float *color,
+                                            const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
+                                            const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b,
+                                            int exposure_stride, void *jac_ws, float irls_delta, float *gn_partials,
+                                            float *jac_out /*NULL ok*/, void *stream);
+int gsaj_rasterize_pose_jacobian_loss8_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
+                                             const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
+                                             const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
+                                             const float *projmatrices, const float *projmatrix_raw, const float *campos, float tanfovx,
+                                             float tanfovy, const int *radii, void *geom_ws, void *binning_ws, void *image_ws,
+                                             int loss_flags, float alpha, float rgb_boundary_threshold, const float *color,
+                                             const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
+                                             const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b,
+                                             int exposure_stride, void *jac_ws, float irls_delta, float *gn8_partials,
+                                             float *jac_out /*NULL ok*/, void *stream);
+int gsaj_pose_gn_step_batch(int K, const float *gn_partials, int n_partials, const uint8_t *active, float lambda_init, float nu,
+                            float lambda_min, float lambda_max, float converged_threshold, const float *projection_matrix,
+                            float *gn_states, const uint32_t *skip, size_t skip_stride_bytes, void *stream);
+int gsaj_pose_gn8_step_batch(int K, const float *gn8_partials, int n_partials, const uint8_t *active, float lambda_init, float nu,
+                             float lambda_min, float lambda_max, float converged_threshold, const float *projection_matrix,
+                             float *gn8_states, const uint32_t *skip, size_t skip_stride_bytes, void *stream);
+int gsaj_pose_gn_select(int K, const float *gn_states, int state_floats, const uint8_t *active, int *best, float *best_loss,
+                        void *stream);
+
 /* ---- distCUDA2 -------------------------------------------------------------------
  * simple_knn._C.distCUDA2 (reference submodules/simple-knn/simple_knn.cu:45-220, spatial.cu): for P points
  * [P,3] the mean of the squared distances to the 3 nearest other points -> mean_dists [P].  Exact search;

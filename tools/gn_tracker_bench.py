@@ -10,7 +10,13 @@ unobserved windows.  usage: gn_tracker_bench.py [--solve-exposure] [out.json] [w
 
 --solve-exposure: every ground-truth frame is turned into e^a* C + b* with (a*, b*) = EXPOSURE and every tracker starts from exposure
 (0, 0).  A third tracker joins the two, GaussNewtonTracker(solve_exposure=True); its criterion is the pose criterion AND max(|a - a*|,
-|b - b*|) below 0.35 x its starting value.  The other two keep the pose criterion; the exposure error each ends with is reported."""
+|b - b*|) below 0.35 x its starting value.  The other two keep the pose criterion; the exposure error each ends with is reported.
+
+--window K: another measurement altogether -- one GaussNewtonWindow iteration of K views (every kernel once, gridDim.y = K) against K
+sequential GaussNewtonTracker iterations (K trackers, each with its own context, one after the other on the same stream), 6-form and
+joint form, on both scenes: ms per window iteration and per view, the ratio, and whether the window is slower than the sequential
+loop beyond the latter's own min-max spread.  Every slot holds the same frame from the same start, so that both sides do the same
+work.  usage: gn_tracker_bench.py --window K [out.json] [window=50] [repeats=7]"""
 import json
 import math
 import os
@@ -22,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gs-slam-analytica_jacobian_amd"))
 import torch  # noqa: E402
 from gsaj import synthetic as syn  # noqa: E402
-from gsaj.gauss_newton import GaussNewtonTracker  # noqa: E402
+from gsaj.gauss_newton import GaussNewtonTracker, GaussNewtonWindow  # noqa: E402
 from gsaj.rasterizer import FrameContext  # noqa: E402
 from gsaj.tracking import DeviceTracker  # noqa: E402
 
@@ -106,7 +112,50 @@ def case(name, cam_true, w2c_start, sc, gt, window, repeats, budgets=(100, 30), 
     return out
 
 
+class Sequential:
+    """K single trackers run one after the other, each for n iterations: what a caller without the window does (one blocking status
+    read per tracker and call, as one per call of the window)."""
+
+    def __init__(self, trackers):
+        self.trackers = trackers
+
+    def iterate(self, n):
+        for tr in self.trackers:
+            tr.iterate(n)
+
+
+def window_case(name, K, cam_true, w2c_start, sc, gt, window, repeats):
+    P, W, H, M = sc["means3D"].shape[0], cam_true["W"], cam_true["H"], sc["shs"].shape[1]
+    g = dict(means3D=T(sc["means3D"]), opacities=T(sc["opacities"]), shs=T(sc["shs"]), scales=T(sc["scales"]), rotations=T(sc["rotations"]),
+             sh_degree=3)
+    bg = torch.zeros(3, device=DEV)
+    tail = (T(cam_true["projmatrix_raw"]), cam_true["tanfovx"], cam_true["tanfovy"], bg)
+    out = dict(workload=name, K=K, P=P, W=W, H=H)
+    for key, joint in (("6-form", False), ("joint", True)):
+        frame = (math.exp(EXPOSURE[0]) * gt[0] + EXPOSURE[1], gt[1]) if joint else gt
+        win = GaussNewtonWindow(K, P, W, H, M, DEV, np.stack([w2c_start] * K), *tail, alpha=0.9, solve_exposure=joint, **g)
+        seq = Sequential([GaussNewtonTracker(P, W, H, M, DEV, w2c_start, *tail, alpha=0.9, solve_exposure=joint, **g) for _ in range(K)])
+
+        def reset_seq():
+            for tr in seq.trackers:
+                tr.set_frame(frame[0], frame[1], w2c=w2c_start)
+
+        w = ms_per_iteration(win, lambda: win.set_frame(frame[0], frame[1], w2cs=np.stack([w2c_start] * K)), window, repeats)
+        q = ms_per_iteration(seq, reset_seq, window, repeats)
+        # the same work must come out: every slot's accepted loss against the single trackers' after the same number of iterations
+        acc_w, acc_s = win.lm["accepted_loss"].cpu().numpy(), np.array([float(tr.lm["accepted_loss"]) for tr in seq.trackers])
+        out[key] = dict(window_ms_per_iteration=round(w[0], 4), window_ms_min=round(w[1], 4), window_ms_max=round(w[2], 4),
+                        sequential_ms_per_iteration=round(q[0], 4), sequential_ms_min=round(q[1], 4), sequential_ms_max=round(q[2], 4),
+                        window_ms_per_view=round(w[0] / K, 4), sequential_ms_per_view=round(q[0] / K, 4), speedup=round(q[0] / w[0], 3),
+                        slower_beyond_spread=bool(w[0] > q[0] + (q[2] - q[1])),
+                        accepted_loss_window=[float(x) for x in acc_w], accepted_loss_sequential=[float(x) for x in acc_s])
+    return out
+
+
 def main():
+    if "--window" in sys.argv:
+        i = sys.argv.index("--window")
+        return window_main(int(sys.argv[i + 1]), sys.argv[1:i] + sys.argv[i + 2:])
     argv = [a for a in sys.argv[1:] if a != "--solve-exposure"]
     exposure = EXPOSURE if len(argv) < len(sys.argv) - 1 else None
     path = argv[0] if len(argv) > 0 else None
@@ -141,6 +190,37 @@ def main():
                     exposure=exposure))
     text = json.dumps(dict(device=torch.cuda.get_device_name(0), window=window, repeats=repeats, solve_exposure=exposure is not None, cases=res),
                       indent=1)
+    print(text)
+    if path:
+        with open(path, "w") as fh:
+            fh.write(text + "\n")
+
+
+def window_main(K, argv):
+    path = argv[0] if len(argv) > 0 else None
+    window = int(argv[1]) if len(argv) > 1 else 50
+    repeats = int(argv[2]) if len(argv) > 2 else 7
+    bg = torch.zeros(3, device=DEV)
+
+    def render(c, sc):
+        fc = FrameContext(sc["means3D"].shape[0], c["W"], c["H"], 16, DEV)
+        fc.forward(bg, T(sc["means3D"]), T(sc["opacities"]), T(c["viewmatrix"]), T(c["projmatrix"]), T(c["campos"]), c["tanfovx"], c["tanfovy"],
+                   sh_degree=3, shs=T(sc["shs"]), scales=T(sc["scales"]), rotations=T(sc["rotations"]))
+        return fc.color.clone(), fc.depth[0].clone()
+
+    W, H, F = 160, 120, 140.0
+    cams = syn.keyframe_cameras(4, radius=0.25, W=W, H=H, fx=F, fy=F, cx=W / 2 - 0.5, cy=H / 2 - 0.5)
+    sc = syn.make_scene(3000, 21, cams[2], z_range=(1.0, 4.0), log_scale_range=(math.log(0.02), math.log(0.1)))
+    res = [window_case("160x120, 3000 Gaussians, frame 1 from frame 0's pose", K, cams[1], np.ascontiguousarray(cams[0]["viewmatrix"].T).astype(np.float32),
+                       sc, render(cams[1], sc), window, repeats)]
+    cam2, sc2 = syn.config_scene("cfg2")
+    start = np.ascontiguousarray(cam2["viewmatrix"].T).astype(np.float64)
+    a = math.radians(0.3)
+    d = np.eye(4)
+    d[:3, :3] = np.array([[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
+    d[:3, 3] = [0.012, -0.008, 0.01]
+    res.append(window_case("cfg2 (640x480, 50 000 Gaussians)", K, cam2, (d @ start).astype(np.float32), sc2, render(cam2, sc2), window, repeats))
+    text = json.dumps(dict(device=torch.cuda.get_device_name(0), window=window, repeats=repeats, K=K, cases=res), indent=1)
     print(text)
     if path:
         with open(path, "w") as fh:
