@@ -1,6 +1,6 @@
 """gsaj -- torch-tensor front end of libgsaj_hip.so.  Submodules are imported by name (gsaj.rasterizer, gsaj.tracking, ...);
 the package itself imports nothing, so that `from gsaj import synthetic` needs neither torch nor the library."""
-__all__ = ["GaussNewtonTracker", "GaussNewtonWindow"]
+__all__ = ["GaussNewtonTracker", "GaussNewtonWindow", "PyramidGaussNewtonTracker"]
 
 
 def __getattr__(name):
@@ -10,4 +10,7 @@ def __getattr__(name):
     if name == "GaussNewtonWindow":   # K such solves against one fixed map in one set of launches
         from .gauss_newton import GaussNewtonWindow
         return GaussNewtonWindow
+    if name == "PyramidGaussNewtonTracker":  # one such solve coarse to fine over a device image pyramid
+        from .gauss_newton import PyramidGaussNewtonTracker
+        return PyramidGaussNewtonTracker
     raise AttributeError("module 'gsaj' has no attribute %r" % name)

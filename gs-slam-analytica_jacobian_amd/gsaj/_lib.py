@@ -138,6 +138,10 @@ SIGNATURES = {
     "gsaj_pose_gn_step_batch": (c_int, _GN_STEP_BATCH),
     "gsaj_pose_gn8_step_batch": (c_int, _GN_STEP_BATCH),
     "gsaj_pose_gn_select": (c_int, [c_int, P, c_int, P, P, P, P]),
+    "gsaj_pyramid_bytes": (c_size_t, [c_int] * 5),
+    "gsaj_pyramid_level": (c_int, [c_int] * 6 + [ctypes.POINTER(c_int)] * 2 + [ctypes.POINTER(c_size_t)] * 3),
+    "gsaj_pyramid_build": (c_int, [c_int, c_int, c_int, P, P, P, c_float, P, P]),
+    "gsaj_pose_gn_relevel": (c_int, [P, c_int, P, c_float, P, P]),
 }
 
 _lib = None

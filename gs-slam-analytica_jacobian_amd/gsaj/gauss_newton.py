@@ -14,7 +14,10 @@ for b: 8x8 normal equations in 64-float rows) and gsaj_pose_gn8_step (8x8 solve;
 restored on a rejected one together with the pose).
 
 An asynchronous frame that does not fit its arena is aborted on the device: its kernels return at once and the step, handed the
-frame's abort word, changes nothing; iterate() raises when it is done, exactly as DeviceTracker.iterate does."""
+frame's abort word, changes nothing; iterate() raises when it is done, exactly as DeviceTracker.iterate does.
+
+PyramidGaussNewtonTracker runs the same iteration coarse to fine over the frame's image pyramid (gsaj.pyramid, csrc/pyramid.hip): one
+tracker per level on one shared state, re-levelled between levels on the device (gsaj_pose_gn_relevel)."""
 import torch
 
 from . import _lib
@@ -370,3 +373,163 @@ class GaussNewtonWindow:
         _select(self)
         h = self._best.cpu()
         return int(h[0]), float(h[1:2].view(torch.float32)[0])
+
+
+# ---- coarse to fine: one solve carried down an image pyramid -----------------------------------------------------------------------------
+def _level_tracker(pt, W, H, projection, tanfov, w2c):  # (device work: a context per level; host-logic tests replace it)
+    return GaussNewtonTracker(pt.P, W, H, pt.M, pt.dev, w2c, projection, tanfov[0], tanfov[1], pt.bg, pt.means, pt.opac, **pt.kw)
+
+
+def _relevel(pt, level, skip):  # (device work too)
+    """gsaj_pose_gn_relevel of the shared state to level `level`'s projection matrix; skip: a device address or None."""
+    with torch.cuda.device(pt.dev):
+        _lib.check(pt.lib.gsaj_pose_gn_relevel(pt.state.data_ptr(), pt.state.numel(), pt.trackers[level].projection.data_ptr(), pt.lambda_init,
+                                               skip, torch.cuda.current_stream(pt.dev).cuda_stream), "gsaj_pose_gn_relevel")
+
+
+def _level_iteration(t, sync):  # (device work too)
+    """One iteration of level tracker t: forward -> pose_jacobian_loss -> step, on the shared state."""
+    with torch.cuda.device(t.dev):
+        t._iteration(sync)
+
+
+class PyramidGaussNewtonTracker:
+    """GaussNewtonTracker coarse to fine: the frame's pyramid is built on the device (gsaj.pyramid.ImagePyramid), the solve starts at
+    level `levels` -- a wide basin and a cheap iteration -- and is handed from level to level down to the frame itself.  One
+    GaussNewtonTracker per level, level 0 included, each with its own context at its own resolution and camera, all on ONE
+    Levenberg-Marquardt state; between two levels gsaj_pose_gn_relevel takes the state to the next camera on the device.  The accepted
+    loss of one level says nothing about the next one's: it starts a new baseline there.  levels=0 is GaussNewtonTracker.
+    A batched form (GaussNewtonWindow) is not built."""
+
+    def __init__(self, P, W, H, M, device, w2c, projection_matrix, tanfovx, tanfovy, bg, means3D, opacities, levels=0, fx=None, fy=None,
+                 cx=None, cy=None, znear=0.01, zfar=100.0, depth_edge_ratio=0.1, **kw):
+        """The arguments of GaussNewtonTracker (projection_matrix, tanfovx, tanfovy: level 0's), then levels, the intrinsics of the
+        frame, from which every coarser level's camera follows (ImagePyramid.level_camera), and depth_edge_ratio: the relative depth
+        spread beyond which a coarse pixel counts as a depth discontinuity and carries no depth."""
+        if torch.device(device).type != "cuda":
+            raise _lib.GsajError("PyramidGaussNewtonTracker needs a HIP device (there is no CPU path)")
+        self._init_host(P, W, H, M, device, w2c, projection_matrix, (tanfovx, tanfovy), bg, means3D, opacities, levels,
+                        (fx, fy, cx, cy, znear, zfar), depth_edge_ratio, kw)
+
+    def _init_host(self, P, W, H, M, device, w2c, projection_matrix, tanfov, bg, means3D, opacities, levels, intrinsics, depth_edge_ratio, kw):
+        """Everything that is not a kernel: the level cameras, one tracker per level (through _level_tracker), the shared state."""
+        from .pyramid import MAX_LEVELS, level_camera
+        self.lib = _lib.load()
+        self.P, self.W, self.H, self.M, self.dev = int(P), int(W), int(H), int(M), torch.device(device)
+        self.levels = int(levels)
+        self.bg, self.means, self.opac, self.kw = bg, means3D, opacities, dict(kw)
+        self.lambda_init = float(kw.get("lambda_init", 1e-3))
+        self.depth_edge_ratio = float(depth_edge_ratio)
+        if not 0 <= self.levels <= MAX_LEVELS:
+            raise _lib.GsajError("PyramidGaussNewtonTracker: levels must be 0..%d, got %d" % (MAX_LEVELS, self.levels))
+        if self.levels and any(v is None for v in intrinsics[:4]):
+            raise _lib.GsajError("PyramidGaussNewtonTracker: levels > 0 needs the intrinsics fx, fy, cx, cy of the frame")
+        cams = [(self.W, self.H, projection_matrix, float(tanfov[0]), float(tanfov[1]))]
+        for l in range(1, self.levels + 1):
+            cams.append(level_camera(self.W, self.H, l, *intrinsics))
+            if cams[l][0] < 16 or cams[l][1] < 16:   # less than one tile carries no signal
+                raise _lib.GsajError("PyramidGaussNewtonTracker: level %d of a %dx%d frame is %dx%d, smaller than one 16x16 tile" % (
+                    l, self.W, self.H, cams[l][0], cams[l][1]))
+        self.trackers = [_level_tracker(self, c[0], c[1], c[2], (c[3], c[4]), w2c) for c in cams]
+        self.state = self.trackers[0].state
+        for t in self.trackers[1:]:   # ONE Levenberg-Marquardt state
+            t.state = self.state
+        self.pyramid = None           # made by the first set_frame(): whether it holds a mask is known then
+        self._level_mask = None       # edge_threshold: the per-level masks GradMask writes
+        self._snapshot = torch.empty_like(self.state)
+        self._at = 0                  # the level whose camera the state's matrices are for
+        self.iterations = 0
+        if self.levels:
+            self.trackers[-1].reset(w2c)
+            self._at = self.levels
+
+    solve_exposure = property(lambda s: s.trackers[0].solve_exposure)
+    w2c = property(lambda s: s.trackers[0].w2c)
+    converged = property(lambda s: s.trackers[0].converged)
+    accepted_w2c = property(lambda s: s.trackers[0].accepted_w2c)
+    accepted_exposure = property(lambda s: s.trackers[0].accepted_exposure)
+    loss_terms = property(lambda s: s.trackers[0].loss_terms)
+    lm = property(lambda s: s.trackers[0].lm)
+
+    def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2c=None, edge_threshold=None, grad_blocks=False):
+        """GaussNewtonTracker.set_frame, then the pyramid of the frame in one launch.  A given grad_mask is OR-reduced with the
+        images; with edge_threshold every level's mask is computed by gsaj.grad_mask on that level's colour: the gradient is taken
+        at that scale.  w2c: the start pose; the solve starts at the coarsest level."""
+        from .pyramid import ImagePyramid
+        t0 = self.trackers[0]
+        t0.set_frame(gt_color, gt_depth, grad_mask, None, edge_threshold, grad_blocks)
+        if self.levels:
+            given = grad_mask is not None
+            if self.pyramid is None:
+                self.pyramid = ImagePyramid(self.W, self.H, self.levels, self.dev, has_depth=t0.gt_depth is not None, has_mask=given)
+                for l in range(1, self.levels + 1):
+                    t = self.trackers[l]
+                    t.gt_color = self.pyramid.color(l)
+                    t.gt_depth = self.pyramid.depth(l) if t0.gt_depth is not None else None
+                    if given:
+                        t.grad_mask = self.pyramid.mask(l).view(-1)
+                    elif edge_threshold is not None:
+                        t.grad_mask = torch.empty(t.gt_color[0].numel(), dtype=torch.uint8, device=self.dev)
+                        t._grad_op = GradMask(t.gt_color.shape[2], t.gt_color.shape[1], self.dev)
+            self.pyramid.build(t0.gt_color, t0.gt_depth, t0.grad_mask if given else None, self.depth_edge_ratio)
+            if not given and edge_threshold is not None:
+                for t in self.trackers[1:]:
+                    t._grad_op(t.gt_color, edge_threshold, blocks=grad_blocks, out=t.grad_mask)
+        if w2c is not None:
+            self.trackers[-1].reset(w2c)
+            self._at = self.levels
+
+    def relevel(self, level, skip=None):
+        """The shared state to level `level`'s camera, on the device (gsaj_pose_gn_relevel)."""
+        if not 0 <= int(level) <= self.levels:
+            raise _lib.GsajError("PyramidGaussNewtonTracker: level %r is not one of 0..%d" % (level, self.levels))
+        _relevel(self, int(level), skip)
+        self._at = int(level)
+
+    def iterate(self, schedule, check_every=0):
+        """schedule: the iteration counts from the coarsest level to level 0 (levels + 1 of them; levels=0: a number will do).  Every
+        level runs GaussNewtonTracker's iteration with its own context; between levels the state is re-levelled on the device, with
+        the abort word of the level just finished as the skip word.  No host read but what check_every (per level: on to the next
+        level once the device reports convergence) and the first, arena-sizing iteration of each level imply.  Returns the numbers
+        run per level.  Raises GsajError after the loop if an asynchronous frame of any level was aborted on the device; the state is
+        then what it was before the call, and the next call re-sizes that level's arena with one synchronous iteration."""
+        if self.trackers[0].gt_color is None:
+            raise _lib.GsajError("set_frame() first")
+        if self.levels == 0:
+            n = schedule[0] if isinstance(schedule, (list, tuple)) and len(schedule) == 1 else schedule
+            done = self.trackers[0].iterate(n, check_every)
+            self.iterations += done
+            return [done]
+        schedule = [int(n) for n in schedule]
+        if len(schedule) != self.levels + 1 or min(schedule) < 0:
+            raise _lib.GsajError("iterate: schedule must hold %d non-negative counts, coarsest level first (got %r)" % (self.levels + 1, schedule))
+        self._snapshot.copy_(self.state)
+        done, prev, at = [], None, self._at
+        for l, n in zip(range(self.levels, -1, -1), schedule):
+            k = 0
+            if n:   # (a level with no iterations is passed over: the state goes straight to the next level that has some)
+                t = self.trackers[l]
+                if self._at != l:
+                    self.relevel(l, None if prev is None else prev._abort_ptr)
+                while k < n:
+                    _level_iteration(t, t.ctx.capacity == 0)
+                    k += 1
+                    if check_every and k % check_every == 0 and bool(self.converged.item() != 0.0):
+                        break
+                t.iterations += k
+                prev = t
+            done.append(k)
+        self.iterations += sum(done)
+        errors = []
+        for l, k in zip(range(self.levels, -1, -1), done):
+            if k:
+                try:
+                    self.trackers[l].ctx.status()
+                except _lib.GsajError as e:
+                    self.trackers[l].ctx.capacity = 0
+                    errors.append("level %d: %s" % (l, e))
+        if errors:
+            self.state.copy_(self._snapshot)
+            self._at = at
+            raise _lib.GsajError("; ".join(errors))
+        return done

@@ -604,6 +604,45 @@ int gsaj_pose_gn8_step_batch(int K, const float *gn8_partials, int n_partials, c
 int gsaj_pose_gn_select(int K, const float *gn_states, int state_floats, const uint8_t *active, int *best, float *best_loss,
                         void *stream);
 
+/* Coarse-to-fine: the image pyramid of a frame and the Levenberg-Marquardt state carried from one resolution to the next
+ * (csrc/pyramid.hip).  Level 0 is the frame: colour [3,H,W] fp32, depth [H,W] fp32 or NULL, mask [H,W] bytes or NULL.  Level l of
+ * 1..levels (levels <= GSAJ_PYRAMID_MAX_LEVELS) is W_l = W >> l by H_l = H >> l: a level-l pixel exists only where its whole
+ * 2^l x 2^l block of level-0 pixels lies inside the image -- an odd last column or row is dropped, never partially averaged.
+ * Level l from level l - 1, children p00 p01 / p10 p11 in row-major order, fp32, one rounding per operation:
+ *   colour  0.25f * ((p00 + p01) + (p10 + p11))
+ *   depth   a child is valid iff d > 0.0f (NaN and negatives are not).  No valid child: 0.  Otherwise dmin, dmax over the valid
+ *           children; dmax - dmin > depth_edge_ratio * dmin: 0 (the pixel straddles a depth discontinuity and must not pull the
+ *           pose); otherwise s * r[n], s = the valid children added in the order p00, p01, p10, p11, n their number,
+ *           r = {1, 0.5f, (float)(1.0 / 3.0), 0.25f}.  A 0 is an invalid child of the next level.
+ *   mask    the OR of the four children, non-zero written as 1
+ * The packed pyramid holds levels 1..levels one after the other, each colour [3,H_l,W_l], then depth [H_l,W_l], then mask
+ * [H_l,W_l] (the planes the frame has), every plane at a 256-byte aligned offset; the bytes between planes are never written.
+ * gsaj_pyramid_bytes -- its size (0 for arguments gsaj_pyramid_build would refuse).
+ * gsaj_pyramid_level -- host only: the size of level `level` (1..levels) and the byte offsets of its planes ((size_t)-1 for a plane
+ *   the pyramid does not have); every output pointer may be NULL.
+ * gsaj_pyramid_build -- all levels in ONE launch on `stream`, no host read, no atomics: every input element is read once, every
+ *   output element written once, the bits are the same run to run.  `pyramid`: gsaj_pyramid_bytes(W, H, levels, depth != NULL,
+ *   mask != NULL) bytes, 256-byte aligned.
+ * gsaj_pose_gn_relevel -- a gn_state / gn8_state (above) taken to the next resolution: one launch of one wave, no host read.  If a
+ *   pose has been accepted ([82] != 0), W2C [0:16) <- the accepted W2C [88:104) and, in the joint form, the exposure [33:35) <-
+ *   [148:150): the last proposed pose, which no step has judged, is discarded -- a loss at another resolution cannot judge it;
+ *   otherwise the pose stays.  The camera matrices [35:70) are refreshed from W2C and projection_matrix_next with the operations
+ *   of gsaj_pose_gn_step; [80] <- lambda_init; zeroed: [81], [82], tau, |tau| and converged [70:78) (and [78:80) in the joint
+ *   form), [85:88), the accepted H and g; [88:104) <- W2C and, in the joint form, [148:150) <- the exposure.  The step counters
+ *   [83], [84] are kept: they count over the frame.  With [82] = 0 the next gsaj_pose_gn_step accepts its loss as the new
+ *   baseline.  skip: as in gsaj_pose_gn_step -- a non-zero word (the level just finished was aborted) changes nothing.
+ * GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: levels outside 1..GSAJ_PYRAMID_MAX_LEVELS, W >> levels < 1 or
+ * H >> levels < 1, a NULL colour or pyramid, depth_edge_ratio < 0 or not finite; a NULL gn_state or projection_matrix_next, a
+ * state_floats that is neither GSAJ_GN_STATE_FLOATS nor GSAJ_GN8_STATE_FLOATS, lambda_init <= 0. */
+#define GSAJ_PYRAMID_MAX_LEVELS 4
+size_t gsaj_pyramid_bytes(int W, int H, int levels, int has_depth, int has_mask);
+int gsaj_pyramid_level(int W, int H, int levels, int has_depth, int has_mask, int level, int *W_l, int *H_l, size_t *color_off,
+                       size_t *depth_off, size_t *mask_off);
+int gsaj_pyramid_build(int W, int H, int levels, const float *color, const float *depth /*NULL ok*/, const uint8_t *mask /*NULL ok*/,
+                       float depth_edge_ratio, void *pyramid /*dev*/, void *stream);
+int gsaj_pose_gn_relevel(float *gn_state, int state_floats /*GSAJ_GN_STATE_FLOATS | GSAJ_GN8_STATE_FLOATS*/,
+                         const float *projection_matrix_next, float lambda_init, const uint32_t *skip, void *stream);
+
 /* ---- distCUDA2 -------------------------------------------------------------------
  * simple_knn._C.distCUDA2 (reference submodules/simple-knn/simple_knn.cu:45-220, spatial.cu): for P points
  * [P,3] the mean of the squared distances to the 3 nearest other points -> mean_dists [P].  Exact search;
