@@ -142,6 +142,8 @@ SIGNATURES = {
     "gsaj_pyramid_level": (c_int, [c_int] * 6 + [ctypes.POINTER(c_int)] * 2 + [ctypes.POINTER(c_size_t)] * 3),
     "gsaj_pyramid_build": (c_int, [c_int, c_int, c_int, P, P, P, c_float, P, P]),
     "gsaj_pose_gn_relevel": (c_int, [P, c_int, P, c_float, P, P]),
+    "gsaj_undistort_map": (c_int, [c_int, c_int, P, P, P, P, P, P]),
+    "gsaj_frame_ingest": (c_int, [c_int] * 5 + [c_size_t, P, P, P, P, c_size_t, c_double, c_int, P, P, P]),
 }
 
 _lib = None

@@ -643,6 +643,55 @@ int gsaj_pyramid_build(int W, int H, int levels, const float *color, const float
 int gsaj_pose_gn_relevel(float *gn_state, int state_floats /*GSAJ_GN_STATE_FLOATS | GSAJ_GN8_STATE_FLOATS*/,
                          const float *projection_matrix_next, float lambda_init, const uint32_t *skip, void *stream);
 
+/* ---- frame ingest: a camera frame from bytes to the tensors the trackers read (csrc/ingest.hip) ----------------------------------
+ * What the reference's datasets do per frame on the host (utils/dataset.py:257-278, :370-386, :499-513: cv2.remap of a distorted
+ * image, image / 255.0, clamp, permute, the float32 upload; depth / depth_scale), on the device: the bytes are uploaded as bytes.
+ *
+ * gsaj_undistort_map -- once per camera, fp64, what cv2.initUndistortRectifyMap(K, dist, R, newK, (W, H), CV_32FC1) is documented
+ *   to compute.  K_src = host {fx, fy, cx, cy} of the distorted camera, dist = host {k1, k2, p1, p2, k3}, iR = host, the 3 x 3
+ *   inverse of newK R, row-major (an input: the caller inverts).  For output pixel (u, v), every operation in fp64, one rounding
+ *   each, no fused multiply-add, every product and sum evaluated left to right as written:
+ *     X = iR[0] u + iR[1] v + iR[2];  Y = iR[3] u + iR[4] v + iR[5];  Wq = iR[6] u + iR[7] v + iR[8]
+ *     x = X / Wq;  y = Y / Wq;  r2 = x x + y y
+ *     rad = 1 + k1 r2 + k2 (r2 r2) + k3 ((r2 r2) r2)
+ *     xd = x rad + 2 p1 x y + p2 (r2 + 2 x x)            (2 p1 x y is ((2 p1) x) y, 2 x x is (2 x) x)
+ *     yd = y rad + p1 (r2 + 2 y y) + 2 p2 x y
+ *     map_x[v][u] = (float)(fx xd + cx);  map_y[v][u] = (float)(fy yd + cy)
+ * gsaj_frame_ingest -- once per frame, ONE launch for colour and depth.  src: bytes [Hs][Ws][channels], rows src_stride bytes
+ *   apart; channels 1 (the grey byte goes to all three planes, cvtColor GRAY2BGR), 3, or 4 (the fourth byte is ignored).  Plane c of
+ *   out_color [3,H,W] reads channel c, with GSAJ_INGEST_BGR channel 2 - c (a grey image has one channel: the flag changes nothing).
+ *   fp32, one rounding per operation, no fused multiply-add:
+ *   without a map (Ws = W, Hs = H):  out = min(max((float)byte / 255.0f, 0), 1) -- a true division: (float)k / 255.0f equals
+ *     (float)(k / 255.0) for all 256 bytes, which a multiplication by a reciprocal does not.
+ *   with map_x, map_y [H,W] (pixel coordinates in the source), an exact bilinear with a constant border of 0:
+ *     a coordinate pair that is not finite or lies outside [-1, Ws] x [-1, Hs] gives 0 (decided on the floats); otherwise
+ *     x0 = floorf(mx), ax = mx - x0, bx = 1.0f - ax, and y0, ay, by likewise; the taps p00 p01 / p10 p11 at (x0, y0), (x0 + 1, y0),
+ *     (x0, y0 + 1), (x0 + 1, y0 + 1) as floats, a tap outside 0 <= x < Ws, 0 <= y < Hs being 0.0f;
+ *     top = p00 bx + p01 ax;  bot = p10 bx + p11 ax;  val = top by + bot ay;  with GSAJ_INGEST_ROUND_U8 val = floorf(val + 0.5f),
+ *     the k / 255 lattice a uint8 remap output lives on;  out = min(max(val / 255.0f, 0), 1).
+ *   depth_raw (may be NULL, then out_depth is NULL too): uint16 [H][W], rows depth_stride bytes apart, never remapped (the reference
+ *     does not remap it either): out_depth [H,W] = (float)((double)d / depth_scale), with GSAJ_INGEST_DEPTH_MUL (float)((double)d *
+ *     depth_scale) (a RealSense's depth unit) -- NumPy's float64 result rounded to float32 once.
+ *   Where W % 4 == 0 and out_color, out_depth, map_x, map_y are 16-byte aligned a thread owns four consecutive pixels of a row (16-byte
+ *   stores and map loads; the source as one 4-byte aligned read where src and src_stride allow it, the depths as one 8-byte read
+ *   where depth_raw and depth_stride allow it); otherwise one thread per pixel.  Both give the same bits.  No atomics: every output
+ *   element is written once, the bits are the same run to run; nothing outside out_color and out_depth is written.
+ * Bit parity with cv2.remap is NOT claimed: its uint8 path quantises the map to 1/32 pixel and interpolates with 15-bit integer
+ * weights, so it differs from the exact bilinear by up to the local gradient x 1/64 pixel, plus rounding.
+ * GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: a non-positive size (or W H, Ws Hs above INT_MAX); channels not 1, 3 or 4;
+ * unknown flag bits; a NULL src, out_color, K_src, dist, iR, map_x or map_y of gsaj_undistort_map; src_stride < Ws channels; exactly
+ * one of the two maps; no map and (Ws, Hs) != (W, H); depth_raw without out_depth or the reverse; with depth: depth_stride < 2 W or
+ * odd, a depth_scale that is zero or not finite; an output or map pointer that is not 4-byte aligned. */
+#define GSAJ_INGEST_BGR 1
+#define GSAJ_INGEST_ROUND_U8 2
+#define GSAJ_INGEST_DEPTH_MUL 4
+int gsaj_undistort_map(int W, int H, const double *K_src /*host: fx fy cx cy*/, const double *dist /*host: k1 k2 p1 p2 k3*/,
+                       const double *iR /*host, 9*/, float *map_x /*dev [H,W]*/, float *map_y /*dev [H,W]*/, void *stream);
+int gsaj_frame_ingest(int W, int H, int Ws, int Hs, int channels, size_t src_stride, const uint8_t *src /*dev*/,
+                      const float *map_x /*dev or NULL*/, const float *map_y /*dev or NULL*/,
+                      const uint16_t *depth_raw /*dev or NULL*/, size_t depth_stride, double depth_scale, int flags,
+                      float *out_color /*dev [3,H,W]*/, float *out_depth /*dev [H,W] or NULL*/, void *stream);
+
 /* ---- distCUDA2 -------------------------------------------------------------------
  * simple_knn._C.distCUDA2 (reference submodules/simple-knn/simple_knn.cu:45-220, spatial.cu): for P points
  * [P,3] the mean of the squared distances to the 3 nearest other points -> mean_dists [P].  Exact search;
