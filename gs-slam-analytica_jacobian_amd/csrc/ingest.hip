@@ -2,6 +2,7 @@
 //   k_undistort_map  once per camera, fp64: the source coordinate of every output pixel under the Brown-Conrady model
 //   k_frame_ingest   once per frame, ONE launch for colour and depth: uint8 [Hs,Ws,C] -> fp32 [3,H,W] in [0, 1], direct or through the
 //                    map with an exact fp32 bilinear and a constant 0 border; uint16 depth -> fp32 metres
+//   k_rectify_u8     a grey image through the map to BYTES (what a stereo matcher reads), the same bilinear stopped before the division
 // Memory-bound with no reuse: no LDS, no barrier, no atomics; every output element is written once, the bits are the same run to run.
 // Compiled without FMA contraction: tests/ingest_restated.py restates both kernels one rounding at a time.
 #include "gsaj_common.h"
@@ -54,7 +55,9 @@ __device__ __forceinline__ float ingest_unit(float val, int flags) {
 __device__ __forceinline__ int ingest_channel(int c, int C, int flags) { return C == 1 ? 0 : (flags & GSAJ_INGEST_BGR) ? 2 - c : c; }
 
 // exact fp32 bilinear of the three planes at (mx, my); a tap outside the source is 0.0f, a coordinate that is not finite or lies
-// outside [-1, Ws] x [-1, Hs] gives 0 -- decided on the floats, before any conversion to an integer
+// outside [-1, Ws] x [-1, Hs] gives 0 -- decided on the floats, before any conversion to an integer.
+// BYTES (k_rectify_u8): the value rounded to a byte as GSAJ_INGEST_ROUND_U8 rounds it, left in grey levels
+template <bool BYTES = false>
 __device__ __forceinline__ void ingest_remap(const IngestParams &p, float mx, float my, float out[3]) {
   out[0] = out[1] = out[2] = 0.f;
   if (!(mx >= -1.f && mx <= (float)p.Ws && my >= -1.f && my <= (float)p.Hs)) return;
@@ -75,7 +78,8 @@ __device__ __forceinline__ void ingest_remap(const IngestParams &p, float mx, fl
     const float p00 = inx0 && iny0 ? (float)r0[c0 + ch] : 0.f, p01 = inx1 && iny0 ? (float)r0[c1 + ch] : 0.f;
     const float p10 = inx0 && iny1 ? (float)r1[c0 + ch] : 0.f, p11 = inx1 && iny1 ? (float)r1[c1 + ch] : 0.f;
     const float top = p00 * bx + p01 * ax, bot = p10 * bx + p11 * ax;
-    out[c] = ingest_unit(top * by + bot * ay, p.flags);
+    const float val = top * by + bot * ay;
+    out[c] = BYTES ? fminf(floorf(val + 0.5f), 255.f) : ingest_unit(val, p.flags);
   }
 }
 
@@ -171,6 +175,29 @@ __global__ __launch_bounds__(INGEST_BLOCK) void k_frame_ingest(IngestParams p) {
   }
 }
 
+// One thread per output pixel: the byte, and (out_color != NULL) the byte / 255.0f in all three planes -- bit for bit what
+// k_frame_ingest gives a one-channel image with GSAJ_INGEST_ROUND_U8 through the same map.  Without a map the byte is the source's.
+__global__ __launch_bounds__(INGEST_BLOCK) void k_rectify_u8(IngestParams p, uint8_t *out, size_t out_stride) {
+  const size_t i = (size_t)blockIdx.x * INGEST_BLOCK + threadIdx.x, n = (size_t)p.W * p.H;
+  if (i >= n) return;
+  const int u = (int)(i % (size_t)p.W), v = (int)(i / (size_t)p.W);
+  float b;
+  if (p.map_x) {
+    float o[3];
+    ingest_remap<true>(p, p.map_x[i], p.map_y[i], o);
+    b = o[0];
+  } else {
+    b = (float)p.src[(size_t)v * p.src_stride + u];
+  }
+  out[(size_t)v * out_stride + u] = (uint8_t)b;
+  if (p.out_color) {
+    const float c = fminf(fmaxf(b / 255.0f, 0.f), 1.f);
+    p.out_color[i] = c;
+    p.out_color[n + i] = c;
+    p.out_color[2 * n + i] = c;
+  }
+}
+
 // ---- C ABI ------------------------------------------------------------------------------------------------------------------------
 static bool ingest_aligned(const void *ptr, size_t a) { return reinterpret_cast<size_t>(ptr) % a == 0; }
 
@@ -263,6 +290,44 @@ extern "C" int gsaj_frame_ingest(int W, int H, int Ws, int Hs, int channels, siz
   const dim3 grid((unsigned)((threads + INGEST_BLOCK - 1) / INGEST_BLOCK));
   if (vec) hipLaunchKernelGGL(k_frame_ingest<true>, grid, dim3(INGEST_BLOCK), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(k_frame_ingest<false>, grid, dim3(INGEST_BLOCK), 0, (hipStream_t)stream, p);
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}
+
+extern "C" int gsaj_rectify_u8(int W, int H, int Ws, int Hs, size_t src_stride, const uint8_t *src, const float *map_x, const float *map_y,
+                               uint8_t *out, size_t out_stride, float *out_color, void *stream) {
+  if (W < 1 || H < 1 || Ws < 1 || Hs < 1 || (size_t)W * H > (size_t)INT32_MAX || (size_t)Ws * Hs > (size_t)INT32_MAX) {
+    gsaj_set_error("gsaj_rectify_u8: W, H, Ws and Hs must be positive with W * H and Ws * Hs <= INT_MAX (W=%d H=%d Ws=%d Hs=%d)", W, H, Ws, Hs);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if (!src || !out) {
+    gsaj_set_error("gsaj_rectify_u8: src and out are required");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if (src_stride < (size_t)Ws || out_stride < (size_t)W) {
+    gsaj_set_error("gsaj_rectify_u8: a row stride is less than its row (src_stride=%zu Ws=%d out_stride=%zu W=%d)", src_stride, Ws, out_stride, W);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if ((map_x == nullptr) != (map_y == nullptr)) {
+    gsaj_set_error("gsaj_rectify_u8: map_x and map_y must be given together or not at all");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if (!map_x && (Ws != W || Hs != H)) {
+    gsaj_set_error("gsaj_rectify_u8: without a map the source must have the output's size (W=%d H=%d Ws=%d Hs=%d)", W, H, Ws, Hs);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  if ((out_color && !ingest_aligned(out_color, 4)) || (map_x && (!ingest_aligned(map_x, 4) || !ingest_aligned(map_y, 4)))) {
+    gsaj_set_error("gsaj_rectify_u8: out_color, map_x and map_y must be 4-byte aligned");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  IngestParams p;
+  p.W = W; p.H = H; p.Ws = Ws; p.Hs = Hs; p.C = 1; p.flags = GSAJ_INGEST_ROUND_U8;
+  p.src_stride = src_stride; p.depth_stride = 0;
+  p.src = src; p.map_x = map_x; p.map_y = map_y; p.depth_raw = nullptr; p.depth_scale = 1.0;
+  p.out_color = out_color; p.out_depth = nullptr;
+  p.src_wide = 0; p.depth_wide = 0;
+  const size_t n = (size_t)W * H;
+  hipLaunchKernelGGL(k_rectify_u8, dim3((unsigned)((n + INGEST_BLOCK - 1) / INGEST_BLOCK)), dim3(INGEST_BLOCK), 0, (hipStream_t)stream, p, out, out_stride);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }

@@ -1,6 +1,6 @@
 """gsaj -- torch-tensor front end of libgsaj_hip.so.  Submodules are imported by name (gsaj.rasterizer, gsaj.tracking, ...);
 the package itself imports nothing, so that `from gsaj import synthetic` needs neither torch nor the library."""
-__all__ = ["GaussNewtonTracker", "GaussNewtonWindow", "PyramidGaussNewtonTracker"]
+__all__ = ["GaussNewtonTracker", "GaussNewtonWindow", "PyramidGaussNewtonTracker", "StereoMatcher", "StereoIngest"]
 
 
 def __getattr__(name):
@@ -13,4 +13,7 @@ def __getattr__(name):
     if name == "PyramidGaussNewtonTracker":  # one such solve coarse to fine over a device image pyramid
         from .gauss_newton import PyramidGaussNewtonTracker
         return PyramidGaussNewtonTracker
+    if name in ("StereoMatcher", "StereoIngest"):  # a stereo pair to disparity, depth and the left colour (gsaj.stereo)
+        from . import stereo
+        return getattr(stereo, name)
     raise AttributeError("module 'gsaj' has no attribute %r" % name)

@@ -144,6 +144,10 @@ SIGNATURES = {
     "gsaj_pose_gn_relevel": (c_int, [P, c_int, P, c_float, P, P]),
     "gsaj_undistort_map": (c_int, [c_int, c_int, P, P, P, P, P, P]),
     "gsaj_frame_ingest": (c_int, [c_int] * 5 + [c_size_t, P, P, P, P, c_size_t, c_double, c_int, P, P, P]),
+    "gsaj_stereo_workspace_bytes": (c_int, [c_int] * 4 + [ctypes.POINTER(c_size_t)]),
+    "gsaj_debug_stereo_offsets": (c_int, [c_int] * 4 + [ctypes.POINTER(c_size_t)] * 2),
+    "gsaj_rectify_u8": (c_int, [c_int] * 4 + [c_size_t, P, P, P, P, c_size_t, P, P]),
+    "gsaj_stereo_match": (c_int, [c_int, c_int, P, c_size_t, P, c_size_t] + [c_int] * 8 + [P, c_size_t, P, P, c_double, P]),
 }
 
 _lib = None

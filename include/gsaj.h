@@ -692,6 +692,67 @@ int gsaj_frame_ingest(int W, int H, int Ws, int Hs, int channels, size_t src_str
                       const uint16_t *depth_raw /*dev or NULL*/, size_t depth_stride, double depth_scale, int flags,
                       float *out_color /*dev [3,H,W]*/, float *out_depth /*dev [H,W] or NULL*/, void *stream);
 
+/* ---- stereo frames: rectify, semi-global matching, depth (csrc/stereo.hip; the byte remap in csrc/ingest.hip) -----------------------
+ * What the reference's StereoDataset does per frame on the host (utils/dataset.py:365-393): cv2.remap of both grey images,
+ * cv2.StereoSGBM (minDisparity 0, numDisparities 64, blockSize 20, uniquenessRatio 40), depth = bf / disparity.  The matcher below is
+ * this library's OWN statement of semi-global matching in integer arithmetic, parametrised the way StereoSGBM is; bit parity with
+ * OpenCV is NOT claimed (its pixel cost, its defaults and its path set are not restated here).  tests/stereo_restated.py restates it
+ * in NumPy; all of it but the depth line is integer, so the device equals the restatement bit for bit.
+ *
+ * gsaj_rectify_u8 -- grey bytes [Hs][Ws] (rows src_stride apart) through map_x, map_y [H,W] to bytes out [H][W] (rows out_stride
+ *   apart): exactly gsaj_frame_ingest's bilinear of a one-channel image with GSAJ_INGEST_ROUND_U8, stopped before the division:
+ *   out = (uint8)min(floorf(val + 0.5f), 255).  Without maps (Ws = W, Hs = H) the byte is copied.  out_color (may be NULL): fp32
+ *   [3,H,W], min(max((float)out / 255.0f, 0), 1) in all three planes -- the bits gsaj_frame_ingest gives the same image.
+ *
+ * gsaj_stereo_match -- left, right: rectified grey bytes [H][W].  D in {16, 32, 64, 128} disparities, D < W <= 4096; block radius r in
+ *   [0, 15] (a (2r+1)^2 window); penalties 0 <= P1 < P2 <= 1024; paths 4 or 8; uniqueness u in [0, 99]; lr_max_diff >= -1 (-1: no
+ *   left-right check).  (StereoSGBM's blockSize 20 is r = 10; 2 and 5 are what OpenCV is understood to substitute for unset
+ *   penalties -- unverified, hence parameters.)  All integers:
+ *   a. prefilter   P(x,y) = clamp(gx, -15, 15) + 15,  gx = (I(x+1,y-1) - I(x-1,y-1)) + 2 (I(x+1,y) - I(x-1,y)) + (I(x+1,y+1) -
+ *                  I(x-1,y+1)), coordinates clamped to the image
+ *   b. pixel cost  pc(x,y,d) = |P_L(x,y) - P_R(max(x-d, 0), y)|                                              (0..30)
+ *   c. block cost  C(x,y,d) = sum of pc(x',y',d) over |x'-x| <= r, |y'-y| <= r, x' and y' clamped to the image   (<= 28 830)
+ *   d. valid       only x in [D, W-1] carries a result; every x < D is invalid
+ *   e. paths       over the valid region, per direction rho -- paths = 4: (1,0) (-1,0) (0,1) (0,-1); paths = 8: also (1,1) (-1,1)
+ *                  (1,-1) (-1,-1).  With q = p - rho and m(q) = min_k L(q,k):
+ *                    L(p,d) = C(p,d) + min(L(q,d), L(q,d-1) + P1, L(q,d+1) + P1, m(q) + P2) - m(q)
+ *                  terms with d-1 or d+1 outside [0, D-1] are absent; L(p,.) = C(p,.) where q lies outside the valid region.
+ *                  S = the sum of L over the directions, in 32 bits (it exceeds 65 535)
+ *   f. winner      d* = argmin_d S(p,d), the lowest d among equals.  p is invalid if some d with |d - d*| > 1 has
+ *                  S(p,d) (100 - u) < S(p,d*) 100
+ *   g. sub-pixel   for 0 < d* < D-1: den = max(S(d*-1) + S(d*+1) - 2 S(d*), 1), d16 = 16 d* + ((S(d*-1) - S(d*+1)) 16 + den) / (2 den),
+ *                  C integer division (towards zero); otherwise d16 = 16 d*
+ *   h. left-right  (lr_max_diff >= 0) disp2(x2) of a row = the d* of the left pixel that passed f, has x - d* = x2 and the smallest
+ *                  S(x,d*), the largest x among equals; absent if there is none.  A candidate delta of a left pixel FAILS when
+ *                  x - delta >= 0, disp2(x - delta) is present and |disp2(x - delta) - delta| > lr_max_diff; the pixel is invalid if
+ *                  both delta = d16 >> 4 and delta = (d16 + 15) >> 4 fail.  No result depends on the order threads run in
+ *   i. output      disp16 int16 [H,W], -16 at every invalid pixel.  out_depth (may be NULL) fp32 [H,W], the reference's lines in its
+ *                  float64: delta = d16 / 16.0; delta == 0 -> 1e10; z = bf / delta; z < 0 -> 0; one rounding to fp32.  So an
+ *                  invalid pixel gives 0 and d16 = 0 gives (float)(bf 1e-10).  bf: baseline x focal length, positive and finite
+ *   No speckle filter (the reference leaves it at 0), minDisparity 0 only.
+ *   workspace: gsaj_stereo_workspace_bytes(W, H, D, paths, &bytes) bytes, 256-byte aligned; it holds the prefiltered images, C as
+ *   uint16 [H,W,D] and S as uint32 [H,W,D] (d innermost), and S is zeroed on the stream inside the call: no allocation, no host
+ *   synchronisation.  stages: 0 = everything; otherwise the GSAJ_STEREO_STAGE_* to run, each on what the workspace already holds
+ *   (measurement and tests: tools/stereo_bench.py times the stages one by one, a test may plant S and run the winner alone).
+ * gsaj_debug_stereo_offsets -- tests and tools only, host only: the byte offsets of C and S in the workspace; both stay there
+ *   after a call.
+ * GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: any parameter outside the ranges above, W * H * D above INT_MAX, unknown
+ * stage bits, a NULL image, workspace, disp16 or bytes, a row stride below its row, a misaligned workspace (256), disp16 (2) or float
+ * pointer (4), out_depth with a bf that is not positive and finite; for gsaj_rectify_u8 the errors of gsaj_frame_ingest's remap.
+ * GSAJ_ERR_WORKSPACE_TOO_SMALL: workspace_bytes below gsaj_stereo_workspace_bytes. */
+#define GSAJ_STEREO_STAGE_COST 1
+#define GSAJ_STEREO_STAGE_PATHS 2
+#define GSAJ_STEREO_STAGE_WINNER 4
+int gsaj_stereo_workspace_bytes(int W, int H, int D, int paths, size_t *bytes);
+int gsaj_debug_stereo_offsets(int W, int H, int D, int paths, size_t *cost_off, size_t *sum_off);
+int gsaj_rectify_u8(int W, int H, int Ws, int Hs, size_t src_stride, const uint8_t *src /*dev*/, const float *map_x /*dev or NULL*/,
+                    const float *map_y /*dev or NULL*/, uint8_t *out /*dev*/, size_t out_stride, float *out_color /*dev [3,H,W] or NULL*/,
+                    void *stream);
+int gsaj_stereo_match(int W, int H, const uint8_t *left /*dev*/, size_t left_stride, const uint8_t *right /*dev*/, size_t right_stride,
+                      int D, int r, int P1, int P2, int paths, int uniqueness, int lr_max_diff, int stages, void *workspace /*dev*/,
+                      size_t workspace_bytes, int16_t *disp16 /*dev [H,W]*/, float *out_depth /*dev [H,W] or NULL*/, double bf,
+                      void *stream);
+
 /* ---- distCUDA2 -------------------------------------------------------------------
  * simple_knn._C.distCUDA2 (reference submodules/simple-knn/simple_knn.cu:45-220, spatial.cu): for P points
  * [P,3] the mean of the squared distances to the 3 nearest other points -> mean_dists [P].  Exact search;
