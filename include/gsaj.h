@@ -57,12 +57,20 @@ const char *gsaj_last_error(void);
 int gsaj_version(void);
 
 /* ---- workspace sizes (bytes) -------------------------------------------------------- */
+/* The memory contract of every workspace (tests/test_gpu_memory_contracts.py runs each entry point on poisoned memory behind guard
+ * bands and holds it to these lines): a call writes nothing outside its outputs and the stated number of workspace bytes, and a
+ * workspace is either "no initialisation needed" -- it may hold any bytes, a smaller problem may follow a larger one in it -- or
+ * "zeroed once" by the caller when allocated and from then on only handed back to the same entry point at the same size: the words
+ * that need the zero (tickets, sticky counters) are put back by the call that used them.
+ * geom_ws: gsaj_geom_workspace_bytes(P) bytes, no initialisation needed. */
 size_t gsaj_geom_workspace_bytes(int P);
+/* image_ws: gsaj_image_workspace_bytes(W, H) bytes, zeroed once (the sticky abort counter, the frame counters and the tile band). */
 size_t gsaj_image_workspace_bytes(int W, int H);
 /* The binning workspace holds, per instance (one Gaussian in one tile's list): two 8-byte sort keys, the 4-byte list entry, a
  * 48-byte partial-gradient row with its one-byte `reached` flag, and a 4-byte `taken` word -- one byte per 8x8 pixel quadrant of
  * the tile, set by the forward compositor when some pixel of the quadrant composited the entry.  The reverse compositor stages only
- * entries taken by some quadrant, and keeps their compacted list in the (by then idle) first sort-key buffer. */
+ * entries taken by some quadrant, and keeps their compacted list in the (by then idle) first sort-key buffer.
+ * binning_ws: gsaj_binning_workspace_bytes(R) bytes, no initialisation needed (every forward clears the flags it reads). */
 size_t gsaj_binning_workspace_bytes(int R);
 
 /* ---- per-call flags of the forward entry points (the library keeps NO process-wide mode: two threads may render
@@ -562,7 +570,7 @@ int gsaj_pose_gn8_step(const float *gn8_partials, int n_partials, float lambda_i
  * against a fixed map, or K start poses of one frame.  The loss-fused forms only; a tile band on any view is not supported.
  * gsaj_rasterize_pose_jacobian_loss_batch / _loss8_batch -- the arguments of gsaj_rasterize_backward_loss_batch up to the loss
  *   group (on a FINISHED gsaj_rasterize_forward[_loss]_batch of the same K views: 256-byte aligned blocks, `capacity` as there),
- *   then jac_ws (gsaj_pose_jac_batch_workspace_bytes(K, P, W, H) bytes, 256-byte aligned), irls_delta, gn_partials
+ *   then jac_ws (gsaj_pose_jac_batch_workspace_bytes(K, P, W, H) bytes, 256-byte aligned, no initialisation needed), irls_delta, gn_partials
  *   [K][gsaj_pose_jac_partial_rows(W, H)][GSAJ_GN_PARTIAL_FLOATS | GSAJ_GN8_PARTIAL_FLOATS] and jac_out [K,H,W,4,6] or NULL.
  *   View v's rows are the bits of the single-view entry point on view v's blocks.  cov3D is read from the caller's cov3D_precomp
  *   or from view 0's geometry block, the only one a batched forward writes.  A view aborted on the device keeps its rows.
@@ -622,7 +630,7 @@ int gsaj_pose_gn_select(int K, const float *gn_states, int state_floats, const u
  *   the pyramid does not have); every output pointer may be NULL.
  * gsaj_pyramid_build -- all levels in ONE launch on `stream`, no host read, no atomics: every input element is read once, every
  *   output element written once, the bits are the same run to run.  `pyramid`: gsaj_pyramid_bytes(W, H, levels, depth != NULL,
- *   mask != NULL) bytes, 256-byte aligned.
+ *   mask != NULL) bytes, 256-byte aligned, no initialisation needed.
  * gsaj_pose_gn_relevel -- a gn_state / gn8_state (above) taken to the next resolution: one launch of one wave, no host read.  If a
  *   pose has been accepted ([82] != 0), W2C [0:16) <- the accepted W2C [88:104) and, in the joint form, the exposure [33:35) <-
  *   [148:150): the last proposed pose, which no step has judged, is discarded -- a loss at another resolution cannot judge it;
@@ -757,7 +765,7 @@ int gsaj_stereo_match(int W, int H, const uint8_t *left /*dev*/, size_t left_str
  * simple_knn._C.distCUDA2 (reference submodules/simple-knn/simple_knn.cu:45-220, spatial.cu): for P points
  * [P,3] the mean of the squared distances to the 3 nearest other points -> mean_dists [P].  Exact search;
  * fewer than 3 neighbours leaves FLT_MAX terms (-> inf) as in the reference.  No host synchronisation.
- * knn_ws: gsaj_dist2_workspace_bytes(P) bytes. */
+ * knn_ws: gsaj_dist2_workspace_bytes(P) bytes, no initialisation needed (the call zeroes its ticket on the stream). */
 size_t gsaj_dist2_workspace_bytes(int P);
 int gsaj_dist2(int P, const float *points, float *mean_dists, void *knn_ws, void *stream);
 /* Tests only: the Morton order gsaj_dist2 left in its workspace -- the 30-bit codes in sorted order and the point index of every
@@ -830,7 +838,8 @@ int gsaj_debug_seed_pixels(int W, int H, int m, const void *seed_ws, uint32_t *p
  * gsaj_grad_mask, blocks == 0 (every dataset type but "replica"): t = med * edge_threshold with med the LOWER median of all H W
  *   intensities, zeros included (order statistic (H W - 1) / 2, torch.median); mask = I > t.  out_mask_u8 [H,W] = 0 / 1;
  *   out_mask_f32 [H,W] (may be NULL) = 0.0 / 1.0.  An intensity pass, a radix select and one threshold kernel that reads the
- *   selected value from device memory: no host read, no synchronisation.  ws: gsaj_grad_mask_workspace_bytes(W, H).
+ *   selected value from device memory: no host read, no synchronisation.  ws: gsaj_grad_mask_workspace_bytes(W, H) bytes, no
+ *   initialisation needed.
  * blocks != 0 ("replica"): a 32 x 32 grid of blocks of bh = H / 32 rows and bw = W / 32 columns (integer division) anchored at
  *   (0, 0); per block t = med * edge_threshold with med the lower median of the block's bh bw intensities; out_mask_f32 is what the
  *   reference leaves in Camera.grad_mask, a FLOAT image: 1 where I > t and t < 1 (the reference writes the ones first and then
@@ -884,7 +893,7 @@ int gsaj_covis_prune_mask(int P, const uint32_t *words, uint32_t window_mask, co
  * is set; P' = number of kept rows.
  *
  * gsaj_compact_plan: counts the kept rows per block of 256 and scans the counts into block offsets.  No host read.
- *   compact_ws: gsaj_compact_workspace_bytes(P) bytes, P / 256 + O(1) words.  The plan remembers the mask's ADDRESS: the mask
+ *   compact_ws: gsaj_compact_workspace_bytes(P) bytes, P / 256 + O(1) words, no initialisation needed.  The plan remembers the mask's ADDRESS: the mask
  *   must stay where it is, unchanged, until the last gsaj_compact_rows of the plan has run.
  * gsaj_compact_count: *n_kept = P' (host).  The one blocking read, 4 bytes; a caller who knows P' already need not call it.
  * gsaj_compact_rows: for every t < n_tensors, dst[t] = the kept rows of src[t], row_bytes[t] bytes each, in the STABLE order
@@ -941,6 +950,7 @@ int gsaj_compact_rows(int P, int n_tensors, const void *const *src /*host [n] of
 #define GSAJ_DENSIFY_CLONE 1
 #define GSAJ_DENSIFY_SPLIT 2
 #define GSAJ_DENSIFY_PRUNE 4
+/* densify_ws: gsaj_densify_workspace_bytes(P, N) bytes, no initialisation needed; gsaj_densify_plan writes it and `code`, the other calls read both. */
 size_t gsaj_densify_workspace_bytes(int P, int N);
 int gsaj_densify_plan(int P, int S, int N, int stages, const float *accum /*dev [P]*/, const float *denom /*dev [P] or NULL*/,
                       int n_grads, const float *scaling /*dev [P,S]*/, const float *opacity /*dev [P]*/, float grad_threshold,
@@ -1034,6 +1044,7 @@ int gsaj_eval_frame(int C, int W, int H, int flags, const float *image, const fl
                     uint32_t *out_count /*[1] dev*/, uint8_t *image_u8 /*[H,W,C] dev or NULL*/, void *eval_ws, void *stream);
 
 /* ---- dense analytic path (NumPy-path semantics) ------------------ */
+/* dense_ws: gsaj_dense_workspace_bytes(N, W, H) bytes (the per-workgroup partials of gsaj_dense_backward), no initialisation needed. */
 size_t gsaj_dense_workspace_bytes(int N, int W, int H);
 /* N depth-sorted Gaussians: means2D [N,2] (pixels), covs2D [N,2,2], colors [N,3], depths [N], opac [N];
  * per-pixel seeds seed_color [H,W,3], seed_depth [H,W]  ->
@@ -1058,7 +1069,8 @@ int gsaj_dense_backward(int N, int W, int H, const float *means2D, const float *
  * global STABLE order by view-space z.  means3D [N,3], cov3D [N,6] (xx,xy,xz,yy,yz,zz), shs [N,sh_coeffs,3]; viewmatrix /
  * projmatrix as for the rasteriser (W2C^T, (P W2C)^T); campos [3].  Outputs (device): order [N] int32 (order[i] = original
  * index of sorted position i) and, IN SORTED ORDER, mean2D [N,2] pixels, cov2D [N,2,2] pixels^2 (+0.3 dilation), color [N,3],
- * color_raw [N,3] (before the clamp; may be NULL), depth [N].  project_ws: gsaj_dense_project_workspace_bytes(N). */
+ * color_raw [N,3] (before the clamp; may be NULL), depth [N].  project_ws: gsaj_dense_project_workspace_bytes(N) bytes, no
+ * initialisation needed. */
 size_t gsaj_dense_project_workspace_bytes(int N);
 int gsaj_dense_project(int N, int sh_coeffs, int sh_degree, int W, int H, const float *means3D, const float *cov3D,
                        const float *shs, const float *viewmatrix, const float *projmatrix, const float *campos, double fx,
