@@ -95,7 +95,7 @@ int gsaj_profile_end(float *stage_ms, int *stage_launches) {
 }
 
 const char *gsaj_last_error(void) { return g_err; }
-int gsaj_version(void) { return 109; }
+int gsaj_version(void) { return 110; }
 
 size_t gsaj_geom_workspace_bytes(int P) { return geom_carve(nullptr, (size_t)(P > 0 ? P : 0), nullptr) + 256; }
 size_t gsaj_image_workspace_bytes(int W, int H) { return image_carve(nullptr, W, H, nullptr) + 256; }
@@ -566,6 +566,18 @@ int gsaj_rasterize_forward_loss_batch(int K, int P, int D, int M, const float *b
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------------
+// k_render_bwd finds an instance's gradient row from the Gaussian's tile rectangle as k_preprocess packed it: 10 bits for x0, 10 for
+// y0.  Beyond 1024 tiles a side x0 spills into y0 and the row lands elsewhere, past the arena at worst: such a call is refused here,
+// behind the argument checks of the backward at hand and before it carves or launches anything.
+static int check_rect_range(const Views &v) {
+  if (v.W > GSAJ_BWD_MAX_SIDE || v.H > GSAJ_BWD_MAX_SIDE) {
+    gsaj_set_error("backward: W=%d H=%d is above the %d pixels (%d tiles) a side that the packed tile rectangle's 10-bit fields hold",
+                   v.W, v.H, GSAJ_BWD_MAX_SIDE, GSAJ_BWD_MAX_SIDE / TILE);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  return GSAJ_OK;
+}
+
 static int backward_batch(BwdParams *p, const Scene &sc, const Views &v, const Arenas &a, const PixelSeeds &seeds, int flags,
                           hipStream_t s) {
   if (v.K <= 0 || sc.P <= 0 || a.instances <= 0 || v.W <= 0 || v.H <= 0 || !v.bg || !sc.means3D || !v.viewmatrix || !v.projmatrix ||
@@ -579,9 +591,10 @@ static int backward_batch(BwdParams *p, const Scene &sc, const Views &v, const A
     gsaj_set_error("gsaj_rasterize_backward_batch: missing gradient buffer for a provided input");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  Carved c;
-  int rc = carve(a, sc.P, v.W, v.H, v.K, &c);
+  int rc = check_rect_range(v);
   if (rc != GSAJ_OK) return rc;
+  Carved c;
+  if ((rc = carve(a, sc.P, v.W, v.H, v.K, &c)) != GSAJ_OK) return rc;
   bwd_params(p, sc, v, c.g);
   // the whole window in one call: the chain kernel sums the reverse compositor's instance rows itself (no gather launch, no gsum
   // round trip); the two halves called separately go through gsum as before
@@ -662,11 +675,13 @@ static int backward_frame(BwdParams *p, const Scene &sc, const Views &v, const A
     gsaj_set_error("gsaj_rasterize_backward: missing gradient buffer for a provided input");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
+  int rc = check_rect_range(v);
+  if (rc != GSAJ_OK) return rc;
   Carved c;
   carve(a, sc.P, v.W, v.H, 0, &c);
   bwd_params(p, sc, v, c.g);
   // every output row is written by the kernels (zeros for culled Gaussians): no memsets
-  int rc = launch_render_backward(a.instances, v.W, v.H, p->grid_x, p->grid_y, v.bg, c.g, c.b, c.im, seeds.dL_dpix, seeds.dL_dpix_depth,
+  rc = launch_render_backward(a.instances, v.W, v.H, p->grid_x, p->grid_y, v.bg, c.g, c.b, c.im, seeds.dL_dpix, seeds.dL_dpix_depth,
                                   1, c.vs, s, seeds.fl);
   if (rc != GSAJ_OK) return rc;
   return launch_gaussian_backward(*p, c.g, c.b, c.im, s);
@@ -949,6 +964,23 @@ int gsaj_debug_export(int P, int R, int W, int H, const void *geom_ws, const voi
     CP(n_contrib, im.n_contrib, sizeof(uint32_t) * N);
   }
 #undef CP
+  return GSAJ_OK;
+}
+
+int gsaj_debug_launch_plan(int P, int views, int W, int H, int *plan) {
+  if (P <= 0 || views <= 0 || W <= 0 || H <= 0 || !plan) {
+    gsaj_set_error("gsaj_debug_launch_plan: invalid argument (P=%d views=%d W=%d H=%d)", P, views, W, H);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;  // (as fwd_params and composite form them)
+  const PreprocessPlan pre = plan_preprocess(P, views, gx, gy);
+  const ScatterPlan sc = plan_scatter(P, views, gx, gy);
+  plan[GSAJ_PLAN_BPW] = pre.bpw;
+  plan[GSAJ_PLAN_PRE_WORKGROUPS] = pre.workgroups;
+  plan[GSAJ_PLAN_HIST_LDS] = pre.hist_lds ? 1 : 0;
+  plan[GSAJ_PLAN_GPT] = sc.gpt;
+  plan[GSAJ_PLAN_SCAT_WORKGROUPS] = sc.workgroups;
+  plan[GSAJ_PLAN_SCAT_LDS] = sc.counters_lds ? 1 : 0;
   return GSAJ_OK;
 }
 

@@ -216,6 +216,21 @@ struct FwdParams {
                  // campos + 3 v and writes radii + P v, n_touched + P v
 };
 
+// The variants launch_preprocess / launch_tile_binning choose by the size of the launch (preprocess.hip; host only, pure functions
+// of P, the views of the launch and the tile grid).  gsaj_debug_launch_plan hands them to tests.
+struct PreprocessPlan {
+  int bpw;         // blocks of 256 Gaussians per k_preprocess workgroup (> 1: the MULTI instantiations)
+  int workgroups;  // gridDim.x of k_preprocess
+  bool hist_lds;   // the workgroup's tile histogram is in LDS (tiles <= LDS_TILES_MAX)
+};
+struct ScatterPlan {
+  int gpt;            // blocks of 256 Gaussians per k_scatter_instances workgroup
+  int workgroups;     // gridDim.x of k_scatter_instances (per view)
+  bool counters_lds;  // the class-local tile counters are in LDS (ceil(grid_y / 8) * grid_x <= SCAT_LDS_TILES)
+};
+PreprocessPlan plan_preprocess(int P, int views, int grid_x, int grid_y);
+ScatterPlan plan_scatter(int P, int views, int grid_x, int grid_y);
+
 int launch_preprocess(const FwdParams &p, int *radii, int *n_touched, const GeomWS &g, const ImageWS &im, ViewStrides vs,
                       hipStream_t s);
 // tile binning of `views` frames: instance scatter -> per-tile (depth, id) sort -> point_list, ranges, cleared `reached` flags.

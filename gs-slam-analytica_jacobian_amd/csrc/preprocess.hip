@@ -214,6 +214,9 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_preprocess(FwdParams p, int *__re
             if constexpr (sh_regs) rgb = sh_to_rgb(p.D, p_orig, cam, shv, cl);
             else rgb = sh_to_rgb(p.D, p_orig, cam, p.shs + (size_t)idx * p.M * 3, cl);
           }
+          // 10-bit x0 and y0: right for grids up to 1024 x 1024 tiles (GSAJ_BWD_MAX_SIDE = 16384 pixels a side).  Only
+          // k_render_bwd unpacks this word, so the backward entry points refuse a larger image (api.hip: check_rect_range);
+          // a forward of one leaves x0 spilled into y0 here, and nothing reads it
           rect_pack = (uint32_t)x0 | ((uint32_t)y0 << 10) | ((uint32_t)(x1 - x0) << 20);
           rect_x = (uint32_t)x0 | ((uint32_t)x1 << 16);
           rect_y = (uint32_t)y0 | ((uint32_t)y1 << 16);
@@ -931,15 +934,48 @@ __global__ __launch_bounds__(256) void k_zero_frame_state(uint32_t *__restrict__
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) c[i] = 0u;
 }
 
+// ---- the launch variants the size of a launch selects (host only, pure: gsaj_common.h) -------------------------------------------
+// The launchers below take their variant from these two and gsaj_debug_launch_plan reports what they return, so a test that
+// pins or asserts a variant asks the code that launches it.
+PreprocessPlan plan_preprocess(int P, int views, int grid_x, int grid_y) {
+  PreprocessPlan pl;
+  const int nblk = (P + PRE_BLOCK - 1) / PRE_BLOCK;
+  // blocks of 256 Gaussians per workgroup: 1 unless the launch has far more workgroups than the chip holds (k_preprocess)
+  pl.bpw = 1;
+  while (pl.bpw < 8 && (long long)nblk * views / (2 * pl.bpw) >= 4096) pl.bpw *= 2;
+  pl.workgroups = (nblk + pl.bpw - 1) / pl.bpw;
+  pl.hist_lds = grid_x * grid_y <= LDS_TILES_MAX;
+  return pl;
+}
+
+ScatterPlan plan_scatter(int P, int views, int grid_x, int grid_y) {
+  ScatterPlan pl;
+  // Gaussians per thread: as many as still leave ~1500 workgroups in the launch (4 .. 8; 8 x 256 Gaussians put ~2000-3000
+  // instances of one class into the 4096-entry staging area): the longer a workgroup's run of ids per tile, the fewer partial
+  // 64-byte pieces leave L2
+  int gpt = 4;
+  while (gpt < 8 && (long long)P * views * SCAT_CLS / ((long long)PRE_BLOCK * gpt * 2) >= 1536) gpt *= 2;
+  // (a launch that misses ONE resident generation -- 6 workgroups x 256 CUs -- by a few workgroups: one or two more blocks each)
+  for (int g2 = 9; gpt == 8 && g2 <= 10; g2++) {
+    const long long wg8 = (long long)((P + PRE_BLOCK * 8 - 1) / (PRE_BLOCK * 8)) * SCAT_CLS * views;
+    const long long wg2 = (long long)((P + PRE_BLOCK * g2 - 1) / (PRE_BLOCK * g2)) * SCAT_CLS * views;
+    if (wg8 > 1536 && wg2 <= 1536) gpt = g2;
+  }
+  const int per = PRE_BLOCK * gpt;
+  pl.gpt = gpt;
+  pl.workgroups = ((P + per - 1) / per) * SCAT_CLS;
+  pl.counters_lds = ((grid_y + SCAT_CLS - 1) / SCAT_CLS) * grid_x <= SCAT_LDS_TILES;
+  return pl;
+}
+
 int launch_preprocess(const FwdParams &p0, int *radii, int *n_touched, const GeomWS &g, const ImageWS &im, ViewStrides vs,
                       hipStream_t s) {
   FwdParams p = p0;
   const int nblk = (p.P + PRE_BLOCK - 1) / PRE_BLOCK;
   const int views = p.views > 0 ? p.views : 1;
-  // blocks of 256 Gaussians per workgroup: 1 unless the launch has far more workgroups than the chip holds (k_preprocess)
-  p.bpw = 1;
-  while (p.bpw < 8 && (long long)nblk * views / (2 * p.bpw) >= 4096) p.bpw *= 2;
-  const int nwg = (nblk + p.bpw - 1) / p.bpw;
+  const PreprocessPlan pl = plan_preprocess(p.P, views, p.grid_x, p.grid_y);
+  p.bpw = pl.bpw;
+  const int nwg = pl.workgroups;
   {
     const size_t words = im.zero_bytes / sizeof(uint32_t);
     hipLaunchKernelGGL(k_zero_frame_state, dim3((unsigned)((words + 1023) / 1024), views), dim3(256), 0, s, im.counters, words,
@@ -948,7 +984,7 @@ int launch_preprocess(const FwdParams &p0, int *radii, int *n_touched, const Geo
   {
     GsajProfScope ps(ST_PREPROCESS, s);
     const int tiles = p.grid_x * p.grid_y;
-    const size_t lds = tiles <= LDS_TILES_MAX ? sizeof(uint32_t) * (size_t)tiles : 0;
+    const size_t lds = pl.hist_lds ? sizeof(uint32_t) * (size_t)tiles : 0;
 #ifndef GSAJ_PRE_NO_SHREGS
     if (!p.colors_precomp && p.M == 16)
 #else
@@ -970,21 +1006,10 @@ int launch_tile_binning(int P, int sort_cap, int rec16, int grid_x, int grid_y, 
   {
     GsajProfScope ps(ST_SCATTER, s);
     const int ltiles = ((grid_y + SCAT_CLS - 1) / SCAT_CLS) * grid_x;
-    const size_t lds = ltiles <= SCAT_LDS_TILES ? 3 * sizeof(uint32_t) * (size_t)ltiles : 0;
-    // Gaussians per thread: as many as still leave ~1500 workgroups in the launch (4 .. 8; 8 x 256 Gaussians put ~2000-3000
-    // instances of one class into the 4096-entry staging area): the longer a workgroup's run of ids per tile, the fewer partial
-    // 64-byte pieces leave L2
-    int gpt = 4;
-    while (gpt < 8 && (long long)P * views * SCAT_CLS / ((long long)PRE_BLOCK * gpt * 2) >= 1536) gpt *= 2;
-    // (a launch that misses ONE resident generation -- 6 workgroups x 256 CUs -- by a few workgroups: one or two more blocks each)
-    for (int g2 = 9; gpt == 8 && g2 <= 10; g2++) {
-      const long long wg8 = (long long)((P + PRE_BLOCK * 8 - 1) / (PRE_BLOCK * 8)) * SCAT_CLS * views;
-      const long long wg2 = (long long)((P + PRE_BLOCK * g2 - 1) / (PRE_BLOCK * g2)) * SCAT_CLS * views;
-      if (wg8 > 1536 && wg2 <= 1536) gpt = g2;
-    }
-    const int per = PRE_BLOCK * gpt;
-    hipLaunchKernelGGL(k_scatter_instances, dim3((unsigned)((P + per - 1) / per) * SCAT_CLS, views), dim3(PRE_BLOCK), lds, s, P, grid_x,
-                       grid_y, gpt, g, im, b.point_list, vs);
+    const ScatterPlan pl = plan_scatter(P, views, grid_x, grid_y);  // (gpt: Gaussians per thread)
+    const size_t lds = pl.counters_lds ? 3 * sizeof(uint32_t) * (size_t)ltiles : 0;
+    hipLaunchKernelGGL(k_scatter_instances, dim3((unsigned)pl.workgroups, views), dim3(PRE_BLOCK), lds, s, P, grid_x, grid_y, pl.gpt,
+                       g, im, b.point_list, vs);
     if (rec16)
       hipLaunchKernelGGL(k_pack_splat16, dim3((P + 255) / 256, views), dim3(256), 0, s, P, g, im.counters, vs);
   }

@@ -66,6 +66,7 @@ SIGNATURES = {
     "gsaj_rasterize_backward": (c_int, _BWD + [P, P] + _GRADS + [P]),
     "gsaj_mark_visible": (c_int, [c_int, P, P, P, P, P]),
     "gsaj_debug_export": (c_int, [c_int] * 4 + [P] * 3 + [P] * 11 + [P]),
+    "gsaj_debug_launch_plan": (c_int, [c_int] * 4 + [ctypes.POINTER(c_int)]),
     "gsaj_debug_export_taken": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
     "gsaj_debug_export_view_sums": (c_int, [c_int, P, P, P]),
     "gsaj_debug_export_view_sums_gather": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P]),

@@ -333,6 +333,17 @@ def debug_export(P, R, W, H, geomBuffer, binningBuffer, imageBuffer):
     return out
 
 
+PLAN_FIELDS = ("bpw", "pre_workgroups", "hist_lds", "gpt", "scat_workgroups", "scat_lds")  # GSAJ_PLAN_* of include/gsaj.h, in order
+
+
+def launch_plan(P, views, W, H):
+    """The variants the binning front end selects for ONE call with `views` views of P Gaussians at W x H, as the launchers
+    themselves compute them (gsaj_debug_launch_plan; host only, no device needed): dict of PLAN_FIELDS."""
+    plan = (ctypes.c_int * len(PLAN_FIELDS))()
+    _lib.check(_lib.load().gsaj_debug_launch_plan(int(P), int(views), int(W), int(H), plan), "gsaj_debug_launch_plan")
+    return dict(zip(PLAN_FIELDS, (int(x) for x in plan)))
+
+
 def debug_export_taken(R, W, H, binningBuffer, imageBuffer):
     """(taken [R] int32 by list position, reached [R] uint8 by emission slot) of one view: which entries the forward compositor
     took per quadrant (byte q of a word), cleared beyond each quadrant's furthest last contributor as the reverse compositor

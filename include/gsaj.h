@@ -181,7 +181,7 @@ int gsaj_forward_preprocess_cap(int P, int D, int M, int W, int H,
  * (may be NULL; replaces torch.sum in diff_gaussian_rasterization/__init__.py:162).
  * Pose-only mode (tracking, where only the camera is optimised): pass NULL for ALL ten per-Gaussian outputs
  * dL_dmean2D .. dL_drot and a dL_dtau_sum; the per-Gaussian parameter gradients are then neither finished nor stored.
- * The three workspaces must be the ones the forward filled. */
+ * The three workspaces must be the ones the forward filled.  W, H <= GSAJ_BWD_MAX_SIDE = 16384 ("image size of a backward", below). */
 int gsaj_rasterize_backward(int P, int D, int M, int R, const float *bg, int W, int H,
                             const float *means3D, const float *shs, const float *colors_precomp,
                             const float *scales, float scale_modifier, const float *rotations,
@@ -212,7 +212,7 @@ int gsaj_rasterize_backward(int P, int D, int M, int R, const float *bg, int W, 
  * Backward outputs.  Summed over the views: dL_dopacity [P], dL_dmean3D [P,3], dL_dcov3D [P,6], dL_dsh [P,M,3], dL_dscale
  * [P,3], dL_drot [P,4].  Per view (each may be NULL): dL_dmean2D [K,P,3] (what densification reads as
  * viewspace_points.grad, gaussian_model.py:767-771), dL_dconic [K,P,2,2], dL_dcolor [K,P,3], dL_ddepth [K,P], dL_dtau [K,P,6];
- * and dL_dtau_sum [K,6].  SH storage of 1, 4, 9 or 16 coefficients. */
+ * and dL_dtau_sum [K,6].  SH storage of 1, 4, 9 or 16 coefficients.  Backward: W, H <= GSAJ_BWD_MAX_SIDE; forward: any size. */
 int gsaj_rasterize_forward_batch(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D,
                                  const float *shs, const float *colors_precomp, const float *opacities, const float *scales,
                                  float scale_modifier, const float *rotations, const float *cov3D_precomp,
@@ -320,7 +320,7 @@ int gsaj_loss_seeds(int W, int H, int flags, float alpha, float rgb_boundary_thr
  * scalars, with the arithmetic of gsaj_loss_seeds bit for bit -- the gradients equal those of forward -> gsaj_loss_seeds ->
  * backward exactly; the loss scalars differ from gsaj_loss_seeds' only by the order of their sums.  loss_flags: GSAJ_LOSS_TRACKING,
  * _MONOCULAR, _NO_EXPOSURE (GSAJ_LOSS_COMPUTE_LOSS has no fused form).  loss_ws: gsaj_fused_loss_workspace_bytes(W, H) bytes, no
- * initialisation needed.  An aborted frame leaves out_scalars as they were. */
+ * initialisation needed.  An aborted frame leaves out_scalars as they were.  Backward forms: W, H <= GSAJ_BWD_MAX_SIDE. */
 size_t gsaj_fused_loss_workspace_bytes(int W, int H);
 int gsaj_rasterize_forward_loss(int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
                                 const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
@@ -1091,6 +1091,34 @@ int gsaj_dense_tau(int N, int sh_coeffs, int sh_degree, const int *order, const 
                    const double *dmu_dtau, const double *dcov_dtau, const double *mu_w, const double *T_cw,
                    const double *campos, const double *shs /*[N,sh_coeffs,3]*/, double *dL_dtau /*dev [6]*/,
                    double *parts /*dev [4,6] mu,cov,depth,sh or NULL*/, void *stream);
+
+/* ---- image size of a backward ------------------------------------------------------------------------------------------
+ * W and H up to GSAJ_BWD_MAX_SIDE (16384 pixels = 1024 tiles a side).  The reverse compositor finds the row an instance's
+ * partial gradients go to from the Gaussian's tile rectangle, which the forward packs with 10 bits for each of its first column
+ * and first row.  A larger W or H is GSAJ_ERR_INVALID_ARGUMENT, before anything is launched, in all four backward entry points
+ * (gsaj_rasterize_backward, _backward_loss, _backward_batch, _backward_loss_batch); the forward entry points and the Jacobian
+ * walk do not read the packed rectangle and take wider images. */
+#define GSAJ_BWD_MAX_SIDE 16384
+
+/* ---- the launch variants of the binning front end (tests, debugging) ------------------------------------------------------
+ * Host only, touches no device: the variants the binning front end selects by the size of a launch, for `views` views of P
+ * Gaussians at W x H in ONE call (a single-frame entry point: views = 1; a batched one: its K) -- computed by the functions the
+ * launchers themselves call.  plan [GSAJ_PLAN_COUNT] (host memory):
+ *   GSAJ_PLAN_BPW               blocks of 256 Gaussians per per-Gaussian forward workgroup (1, 2, 4 or 8)
+ *   GSAJ_PLAN_PRE_WORKGROUPS    workgroups of that kernel per view: ceil(ceil(P / 256) / bpw)
+ *   GSAJ_PLAN_HIST_LDS          1: its tile histogram is kept in LDS (at most 8192 tiles), 0: global atomics
+ *   GSAJ_PLAN_GPT               blocks of 256 Gaussians per instance-scatter workgroup (4, 8, 9 or 10)
+ *   GSAJ_PLAN_SCAT_WORKGROUPS   scatter workgroups per view: 8 row classes x ceil(P / (256 gpt))
+ *   GSAJ_PLAN_SCAT_LDS          1: the scatter's tile counters are in LDS (ceil(tile rows / 8) x tile columns <= 4096)
+ * GSAJ_ERR_INVALID_ARGUMENT: P, views, W or H <= 0, or plan NULL. */
+#define GSAJ_PLAN_BPW 0
+#define GSAJ_PLAN_PRE_WORKGROUPS 1
+#define GSAJ_PLAN_HIST_LDS 2
+#define GSAJ_PLAN_GPT 3
+#define GSAJ_PLAN_SCAT_WORKGROUPS 4
+#define GSAJ_PLAN_SCAT_LDS 5
+#define GSAJ_PLAN_COUNT 6
+int gsaj_debug_launch_plan(int P, int views, int W, int H, int *plan /*host [GSAJ_PLAN_COUNT]*/);
 
 #ifdef __cplusplus
 }
