@@ -95,7 +95,7 @@ int gsaj_profile_end(float *stage_ms, int *stage_launches) {
 }
 
 const char *gsaj_last_error(void) { return g_err; }
-int gsaj_version(void) { return 110; }
+int gsaj_version(void) { return 111; }
 
 size_t gsaj_geom_workspace_bytes(int P) { return geom_carve(nullptr, (size_t)(P > 0 ? P : 0), nullptr) + 256; }
 size_t gsaj_image_workspace_bytes(int W, int H) { return image_carve(nullptr, W, H, nullptr) + 256; }

@@ -149,6 +149,8 @@ SIGNATURES = {
     "gsaj_debug_stereo_offsets": (c_int, [c_int] * 4 + [ctypes.POINTER(c_size_t)] * 2),
     "gsaj_rectify_u8": (c_int, [c_int] * 4 + [c_size_t, P, P, P, P, c_size_t, P, P]),
     "gsaj_stereo_match": (c_int, [c_int, c_int, P, c_size_t, P, c_size_t] + [c_int] * 8 + [P, c_size_t, P, P, c_double, P]),
+    "gsaj_rgbd_align_partial_rows": (c_int, [c_int, c_int]),
+    "gsaj_rgbd_align": (c_int, [c_int, c_int] + [c_float] * 4 + [P] * 6 + [c_float] * 7 + [P] * 6),
 }
 
 _lib = None

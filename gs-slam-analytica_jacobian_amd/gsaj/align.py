@@ -1,0 +1,232 @@
+"""Frame-to-frame RGB-D alignment on the device (C ABI gsaj_rgbd_align, csrc/align.hip): the start pose of a new frame from the last
+tracked frame alone -- its colour, its depth and its pose -- before the map is touched.  include/gsaj.h states the arithmetic.
+
+One iteration is two C-ABI calls that touch no host state: gsaj_rgbd_align (one pass over the pixels of a level: warp, photometric
+and depth residual, their pose Jacobians, the 6x6 normal equations of the iteratively reweighted terms, normalised by the number of
+valid pixels) -> gsaj_pose_gn_step on that ONE row (accept / reject, damping, the Cholesky solve, W2C <- Exp(tau) W2C).  The levels of
+both frames come from gsaj.pyramid.ImagePyramid, the state goes from level to level through gsaj_pose_gn_relevel, exactly as in
+gsaj.PyramidGaussNewtonTracker.  There is no CPU path and no host read before result().
+"""
+import torch
+
+from . import _lib
+from .pyramid import MAX_LEVELS, ImagePyramid, level_camera
+
+_STATE_FLOATS = 136   # GSAJ_GN_STATE_FLOATS
+_ROW_FLOATS = 32      # GSAJ_GN_PARTIAL_FLOATS
+
+
+def _stream(al):
+    return torch.cuda.current_stream(al.dev).cuda_stream
+
+
+def _residuals(al, l, depth):  # (the device work of one iteration, first half: host-logic tests replace it)
+    """gsaj_rgbd_align at level l: the reference level against the current level at the state's pose -> al.row."""
+    W, H, fx, fy, cx, cy = al.cams[l]
+    rc, rd, cc, cd = al._level(al._ref, l) + al._level(al._cur, l)
+    with torch.cuda.device(al.dev):
+        _lib.check(al.lib.gsaj_rgbd_align(W, H, fx, fy, cx, cy, rc.data_ptr(), rd.data_ptr(), al.ref_w2c.data_ptr(), cc.data_ptr(),
+                                          cd.data_ptr() if depth else None, al.state.data_ptr(), al.w_depth, al.delta_photo, al.delta_depth,
+                                          al.depth_edge_ratio, al.min_depth, al.max_depth, al.min_overlap, al.rows.data_ptr(),
+                                          al.row.data_ptr(), None, None, None, _stream(al)), "gsaj_rgbd_align")
+
+
+def _step(al, l):  # (device work too)
+    with torch.cuda.device(al.dev):
+        _lib.check(al.lib.gsaj_pose_gn_step(al.row.data_ptr(), 1, *al.lm_args, al.projections[l].data_ptr(), al.state.data_ptr(), None,
+                                            _stream(al)), "gsaj_pose_gn_step")
+
+
+def _relevel(al, l):  # (device work too)
+    with torch.cuda.device(al.dev):
+        _lib.check(al.lib.gsaj_pose_gn_relevel(al.state.data_ptr(), _STATE_FLOATS, al.projections[l].data_ptr(), al.lm_args[0], None,
+                                               _stream(al)), "gsaj_pose_gn_relevel")
+
+
+class _Frame:
+    """One frame's level 0 (buffers the aligner owns) and its pyramid."""
+
+    def __init__(self, W, H, levels, dev):
+        self.color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+        self.depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+        self.pyramid = ImagePyramid(W, H, levels, dev, has_depth=True) if levels else None
+        self.has_depth = False
+        self.filled = False
+
+
+class RgbdAligner:
+    """Aligns the last tracked frame (the reference: colour, depth, pose) against a new frame (colour, optionally depth), coarse to
+    fine, and leaves the new frame's pose on the device: aligner.w2c is what a map tracker's set_frame(..., w2c=) takes.  Pre-allocated
+    for one image size.  w_depth weighs the depth term against the photometric one; delta_photo / delta_depth: the residual below which
+    an L1 term is a quadratic; depth_edge_ratio: the relative spread of the four depth taps (and of a coarse pixel's children) beyond
+    which a pixel straddles a discontinuity and carries no depth term; min_overlap: the share of valid pixels below which a level
+    gives no step.  The Levenberg-Marquardt arguments are GaussNewtonTracker's."""
+
+    def __init__(self, W, H, fx, fy, cx, cy, device, levels=2, w_depth=1.0, delta_photo=0.01, delta_depth=0.01, depth_edge_ratio=0.1,
+                 min_depth=0.01, max_depth=100.0, min_overlap=0.0, znear=0.01, zfar=100.0, lambda_init=1e-3, nu=4.0, lambda_min=1e-7,
+                 lambda_max=1e7, converged_threshold=1e-4):
+        if torch.device(device).type != "cuda":
+            raise _lib.GsajError("RgbdAligner needs a HIP device (there is no CPU path)")
+        self._init_host(W, H, (fx, fy, cx, cy), device, levels, (w_depth, delta_photo, delta_depth, depth_edge_ratio, min_depth, max_depth,
+                                                                  min_overlap), (znear, zfar),
+                        (lambda_init, nu, lambda_min, lambda_max, converged_threshold))
+
+    def _init_host(self, W, H, intrinsics, device, levels, terms, clip, lm_args):
+        """Everything that is not a kernel: the argument checks, the level cameras, the buffers."""
+        self.lib = _lib.load()
+        self.W, self.H, self.dev, self.levels = int(W), int(H), torch.device(device), int(levels)
+        fx, fy, cx, cy = (float(v) for v in intrinsics)
+        (self.w_depth, self.delta_photo, self.delta_depth, self.depth_edge_ratio, self.min_depth, self.max_depth,
+         self.min_overlap) = (float(v) for v in terms)
+        self.lm_args = tuple(float(v) for v in lm_args)
+        if not 0 <= self.levels <= MAX_LEVELS:
+            raise _lib.GsajError("RgbdAligner: levels must be 0..%d, got %d" % (MAX_LEVELS, self.levels))
+        if (self.W >> self.levels) < 2 or (self.H >> self.levels) < 2 or self.lib.gsaj_rgbd_align_partial_rows(self.W, self.H) == 0:
+            raise _lib.GsajError("RgbdAligner: every level must be at least 2x2 and the frame at most 16384 a side (W=%d H=%d levels=%d)" % (
+                self.W, self.H, self.levels))
+        if not (fx > 0 and fy > 0):
+            raise _lib.GsajError("RgbdAligner: fx and fy must be positive (fx=%g fy=%g)" % (fx, fy))
+        if not (self.delta_photo > 0 and self.delta_depth > 0 and self.w_depth >= 0 and self.depth_edge_ratio >= 0):
+            raise _lib.GsajError("RgbdAligner: delta_photo, delta_depth > 0 and w_depth, depth_edge_ratio >= 0 (got %g, %g, %g, %g)" % (
+                self.delta_photo, self.delta_depth, self.w_depth, self.depth_edge_ratio))
+        if not (0 < self.min_depth < self.max_depth and 0 <= self.min_overlap <= 1):
+            raise _lib.GsajError("RgbdAligner: 0 < min_depth < max_depth and min_overlap in [0, 1] (got %g, %g, %g)" % (
+                self.min_depth, self.max_depth, self.min_overlap))
+        li, nu, lmin, lmax, _ = self.lm_args
+        if not (nu > 1 and 0 < lmin <= li <= lmax):
+            raise _lib.GsajError("RgbdAligner: nu > 1 and 0 < lambda_min <= lambda_init <= lambda_max")
+        self.cams, self.projections = [], []
+        for l in range(self.levels + 1):   # the exact intrinsics of the cropped, box-filtered image (pyramid.level_camera)
+            wl, hl, proj, _, _ = level_camera(self.W, self.H, l, fx, fy, cx, cy, *clip)
+            s = float(1 << l)
+            self.cams.append((wl, hl, fx / s, fy / s, cx / s, cy / s))
+            self.projections.append(proj.to(torch.float32).contiguous().to(self.dev))
+        self._ref = _Frame(self.W, self.H, self.levels, self.dev)
+        self._cur = _Frame(self.W, self.H, self.levels, self.dev)
+        self.ref_w2c = torch.zeros(16, dtype=torch.float32, device=self.dev)
+        self.state = torch.zeros(_STATE_FLOATS, dtype=torch.float32, device=self.dev)
+        self.rows = torch.empty(self.lib.gsaj_rgbd_align_partial_rows(self.W, self.H), _ROW_FLOATS, dtype=torch.float32, device=self.dev)
+        self.row = torch.zeros(_ROW_FLOATS, dtype=torch.float32, device=self.dev)
+        self._pixels = self.W * self.H   # of the level the row was last formed at
+        self.iterations = 0
+
+    # ---- frames ----------------------------------------------------------------------------------------------------------------------
+    def _level(self, frame, l):
+        if l == 0:
+            return frame.color, frame.depth
+        return frame.pyramid.color(l), frame.pyramid.depth(l)
+
+    def _take(self, frame, color, depth, who):
+        n = self.W * self.H
+        for name, t, numel in (("color", color, 3 * n), ("depth", depth, n)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.device != self.state.device:
+                raise _lib.GsajError("%s: %s must be a tensor on %s (there is no CPU path)" % (who, name, self.state.device))
+            if t.numel() != numel:
+                raise _lib.GsajError("%s: %s must have %d elements for a %dx%d frame, got %d" % (who, name, numel, self.W, self.H, t.numel()))
+        frame.color.copy_(color.reshape(3, self.H, self.W))
+        if depth is None:
+            frame.depth.zero_()   # (no valid depth anywhere: the levels carry none either)
+        else:
+            frame.depth.copy_(depth.reshape(self.H, self.W))
+        frame.has_depth = depth is not None
+        frame.filled = True
+        if frame.pyramid is not None:
+            frame.pyramid.build(frame.color, frame.depth, None, self.depth_edge_ratio)
+
+    def _pose(self, w2c, who):
+        t = torch.as_tensor(w2c, dtype=torch.float32) if not torch.is_tensor(w2c) else w2c
+        if t.numel() != 16:
+            raise _lib.GsajError("%s: w2c must be a 4x4 matrix" % who)
+        return t.detach().to(self.dev, torch.float32).reshape(16)
+
+    def set_reference(self, color, depth, w2c):
+        """The frame to align against: colour [3,H,W], depth [H,W] (device, fp32; copied) and its world-to-camera pose, a host array or
+        a device tensor such as tracker.accepted_w2c (copied device to device)."""
+        if depth is None:
+            raise _lib.GsajError("set_reference: the reference frame needs depth")
+        pose = self._pose(w2c, "set_reference")
+        self._take(self._ref, color, depth, "set_reference")
+        self.ref_w2c.copy_(pose)
+
+    def promote(self, w2c=None):
+        """The current frame becomes the reference (the pyramids are swapped, nothing is copied or rebuilt); its pose becomes w2c --
+        the map tracker's refined pose, device to device -- or, by default, the aligned pose."""
+        if not self._cur.filled:
+            raise _lib.GsajError("promote: align() a frame first")
+        if not self._cur.has_depth:
+            raise _lib.GsajError("promote: the frame was aligned without depth, and the reference frame needs depth")
+        pose = self._pose(self.w2c if w2c is None else w2c, "promote").clone()
+        self._ref, self._cur = self._cur, self._ref
+        self._cur.filled = False
+        self.ref_w2c.copy_(pose)
+
+    # ---- the solve -------------------------------------------------------------------------------------------------------------------
+    def default_schedule(self):
+        """8 iterations at the coarsest level, 6 at every level below it."""
+        return [8] + [6] * self.levels
+
+    def _reset(self, w2c):
+        """A new solve: pose, camera matrices of the coarsest level, no accepted step, lambda_init -- device operations only."""
+        s = self.state
+        s.zero_()
+        s[0:16] = w2c
+        w = s[0:16].view(4, 4)
+        s[35:51] = w.t().reshape(16)
+        s[51:67] = (w.t() @ self.projections[self.levels]).reshape(16)
+        s[67:70] = -(w[:3, :3].t() @ w[:3, 3])   # the camera centre of a rigid pose
+        s[80] = self.lm_args[0]
+        s[88:104] = s[0:16]
+
+    def align(self, color, depth=None, w2c_init=None, schedule=None):
+        """Aligns the reference against this frame (colour [3,H,W], depth [H,W] or None: the photometric term alone).  w2c_init: the
+        start pose, by default the reference's -- the start the frontend takes.  schedule: the iteration counts from the coarsest level
+        to level 0 (levels + 1 of them).  No host read; returns the numbers run per level."""
+        if not self._ref.filled:
+            raise _lib.GsajError("set_reference() first")
+        schedule = self.default_schedule() if schedule is None else [int(n) for n in (schedule if isinstance(schedule, (list, tuple)) else [schedule])]
+        if len(schedule) != self.levels + 1 or min(schedule) < 0:
+            raise _lib.GsajError("align: schedule must hold %d non-negative counts, coarsest level first (got %r)" % (self.levels + 1, schedule))
+        start = self.ref_w2c if w2c_init is None else self._pose(w2c_init, "align")
+        self._take(self._cur, color, depth, "align")
+        self._reset(start)
+        at = self.levels
+        for l, n in zip(range(self.levels, -1, -1), schedule):
+            if not n:   # (a level with no iterations is passed over)
+                continue
+            if at != l:
+                _relevel(self, l)
+                at = l
+            for _ in range(n):
+                _residuals(self, l, depth is not None)
+                _step(self, l)
+            self._pixels = self.cams[l][0] * self.cams[l][1]
+        self.iterations += sum(schedule)
+        return schedule
+
+    # ---- results (device) ------------------------------------------------------------------------------------------------------------
+    w2c = property(lambda s: s.state[88:104].view(4, 4))
+    converged = property(lambda s: s.state[77])
+
+    @property
+    def overlap(self):
+        """The share of valid pixels at the last level evaluated (device scalar)."""
+        return self.row[30] / float(self._pixels)
+
+    @property
+    def loss_terms(self):
+        """[loss, L_photo, L_depth] of the last iteration, per valid pixel (device)."""
+        return self.state[85:88]
+
+    @property
+    def lm(self):
+        """dict(lam, accepted, rejected, accepted_loss: device scalars; H [6,6], g [6]: the accepted normal equations)."""
+        from .rasterizer import unpack_sym6
+        return dict(lam=self.state[80], accepted=self.state[83], rejected=self.state[84], accepted_loss=self.state[81],
+                    H=unpack_sym6(self.state[104:125]), g=self.state[125:131])
+
+    def result(self):
+        """The one host read: (w2c [4,4] ndarray, overlap, accepted loss, converged)."""
+        s = torch.cat([self.state, self.row]).cpu().numpy()
+        return s[88:104].reshape(4, 4).copy(), float(s[_STATE_FLOATS + 30]) / float(self._pixels), float(s[81]), bool(s[77] != 0.0)

@@ -1120,6 +1120,69 @@ int gsaj_dense_tau(int N, int sh_coeffs, int sh_degree, const int *order, const 
 #define GSAJ_PLAN_COUNT 6
 int gsaj_debug_launch_plan(int P, int views, int W, int H, int *plan /*host [GSAJ_PLAN_COUNT]*/);
 
+/* ---- frame-to-frame RGB-D alignment: the start pose of a new frame (csrc/align.hip) --------------------------------------------
+ * The reference starts a new frame's tracking at the previous frame's pose (utils/slam_frontend.py:129-130) and has NO counterpart of
+ * what follows: direct image alignment of the last tracked frame (colour, depth, known pose) against the new frame (colour, optionally
+ * depth).  No map, no binning, no lists: one iteration is one pass over the pixels, and it ends in the normal equations
+ * gsaj_pose_gn_step solves.  tau = [rho, theta] is that step's left increment, W2C_cur <- Exp(tau) W2C_cur.
+ *
+ * gsaj_rgbd_align -- two launches on `stream` (the pixel pass, a one-workgroup fold), no host read, no float atomics: the same bits
+ *   run to run and on any stream.  Colour [3,H,W], depth [H,W], fp32, contiguous.  Per REFERENCE pixel (i, j) = (column, row), all
+ *   fp32, one rounding per operation (no contraction), every sum left to right as written:
+ *   0. T = W2C_cur inverse(W2C_ref), W2C_cur = gn_state[0:16) read on the device, the inverse the rigid one [R^T, -R^T t]:
+ *        T[a][b] = (C[a][0] R[b][0] + C[a][1] R[b][1]) + C[a][2] R[b][2]                       (C: W2C_cur, R: W2C_ref, 3 x 3 blocks)
+ *        ti[k] = -((R[0][k] t[0] + R[1][k] t[1]) + R[2][k] t[2]);   T[a][3] = ((C[a][0] ti[0] + C[a][1] ti[1]) + C[a][2] ti[2]) + C[a][3]
+ *   1. I_r = ((r + g) + b) (float)(1.0 / 3.0), Z_r = ref_depth.  Invalid unless both are finite and min_depth <= Z_r <= max_depth.
+ *      This project's pixel convention (gsaj/pyramid.py level_camera): pixel index = fx X / Z + cx - 0.5, so
+ *        xn = (((float)i + 0.5f) - cx) / fx,  yn likewise;   X_r = xn Z_r,  Y_r = yn Z_r
+ *   2. X_c = ((T[0][0] X_r + T[0][1] Y_r) + T[0][2] Z_r) + T[0][3], Y_c, Z_c likewise.  Invalid unless all three are finite and
+ *      Z_c >= min_depth.
+ *   3. iz = 1.0f / Z_c;  fxz = fx iz;  px = fxz X_c;  u = (px + cx) - 0.5f;  v likewise;  x0 = floorf(u), y0 = floorf(v).
+ *      Valid iff 0 <= x0, x0 + 1 <= W - 1, 0 <= y0, y0 + 1 <= H - 1 (u = W - 1 exactly is invalid).  a = u - x0, b = v - y0; the taps
+ *      p00 p01 / p10 p11 at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), each the grey of line 1; invalid unless all four
+ *      are finite.  With oma = 1.0f - a, omb = 1.0f - b:
+ *        I_c = (p00 oma + p01 a) omb + (p10 oma + p11 a) b
+ *        gx = omb (p01 - p00) + b (p11 - p10);   gy = oma (p10 - p00) + a (p11 - p01)
+ *      -- the exact derivative of that interpolant; there is no gradient image.
+ *   4. r_I = I_c - I_r.  With duz = -(px iz), dvz = -(py iz):  j0 = gx fxz, j1 = gy fyz, j2 = gx duz + gy dvz and
+ *        J_I = [j0, j1, j2, j2 Y_c - j1 Z_c, j0 Z_c - j2 X_c, j1 X_c - j0 Y_c]                      (= [j0 j1 j2] [I, -[X_c]x])
+ *   5. With cur_depth: the gate is open iff the four depth taps are finite, in [min_depth, max_depth], and
+ *      dmax - dmin <= depth_edge_ratio dmin.  D_c and its gradient (hx, hy) as I_c and (gx, gy); r_Z = D_c - Z_c;
+ *      k0 = hx fxz, k1 = hy fyz, k2 = hx duz + hy dvz and
+ *        J_Z = [k0, k1, k2 - 1, (k2 Y_c - k1 Z_c) - Y_c, (k0 Z_c - k2 X_c) + X_c, k1 X_c - k0 Y_c]
+ *   6. Per term, kappa = 1 (photometric) or w_depth, delta = delta_photo or delta_depth (iteratively reweighted least squares, as
+ *      gsaj_rasterize_pose_jacobian_loss):  s = kappa min(max(r / delta, -1), 1);  h = kappa / max(|r|, delta);
+ *      l = kappa (|r| >= delta ? |r| - 0.5f delta : (r r) / (2.0f delta)).
+ *      The pixel's terms:  H_kl = (h_I J_I[k]) J_I[l] + (h_Z J_Z[k]) J_Z[l]  (k <= l),  g_k = s_I J_I[k] + s_Z J_Z[k],  l_I + l_Z, l_I,
+ *      l_Z, 1, and 1 if the depth gate is open (a closed gate: s_Z = h_Z = l_Z = 0, J_Z = 0).
+ *   7. A NaN or an inf anywhere in an input makes that pixel (colour, reference depth, pose) or that term (current depth) invalid; it
+ *      never reaches a sum.
+ *   rows [gsaj_rgbd_align_partial_rows(W, H)][GSAJ_GN_PARTIAL_FLOATS]: scratch, one row per workgroup of 64 x 4 pixels, no
+ *   initialisation needed.  gn_row [GSAJ_GN_PARTIAL_FLOATS]: the rows added in a fixed order in fp64, then with n = the number of
+ *   valid pixels:  [0:21) H / n, [21:27) g / n, [27] loss / n, [28] L_photo / n, [29] L_depth / n, [30] n, [31] the number of open
+ *   depth gates -- the ONE row gsaj_pose_gn_step is given, n_partials = 1.  If n < max(1, ceil(min_overlap W H)): H and g are zero and
+ *   the three losses +inf, so the step rejects the proposal, or on a first call leaves the pose where it is.
+ *   pix_out (may be NULL) [H,W,GSAJ_ALIGN_PIXEL_FLOATS]: u, v, X_c, Y_c, Z_c, I_c, gx, gy, r_I, s_I, h_I, then D_c, r_Z, s_Z, h_Z, 1.0
+ *   (zeros with a closed gate); all zeros at an invalid pixel.  valid_out (may be NULL) [H,W]: bit 0 valid, bit 1 depth gate open.
+ *   skip: as in gsaj_pose_gn_step -- a non-zero word changes nothing (neither launch writes).
+ * gsaj_rgbd_align_partial_rows -- ceil(W / 64) ceil(H / 4); 0 for sizes the call refuses.
+ * GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: W or H < 2 or > 16384; a NULL ref_color, ref_depth, ref_w2c, cur_color,
+ * gn_state, rows or gn_row; fx or fy not positive; delta_photo or delta_depth <= 0; w_depth < 0; depth_edge_ratio < 0; min_depth <= 0
+ * or >= max_depth; min_overlap outside [0, 1]. */
+#define GSAJ_ALIGN_PIXEL_FLOATS 16
+int gsaj_rgbd_align_partial_rows(int W, int H);      /* 0 for sizes the call refuses */
+int gsaj_rgbd_align(int W, int H, float fx, float fy, float cx, float cy,
+                    const float *ref_color /*[3,H,W]*/, const float *ref_depth /*[H,W]*/,
+                    const float *ref_w2c   /*[16] device, row-major*/,
+                    const float *cur_color /*[3,H,W]*/, const float *cur_depth /*[H,W], NULL: photometric only*/,
+                    const float *gn_state  /*device; only W2C [0:16) is read*/,
+                    float w_depth, float delta_photo, float delta_depth, float depth_edge_ratio,
+                    float min_depth, float max_depth, float min_overlap,
+                    float *rows      /*[partial_rows][GSAJ_GN_PARTIAL_FLOATS], no initialisation needed*/,
+                    float *gn_row    /*[GSAJ_GN_PARTIAL_FLOATS]: the ONE row gsaj_pose_gn_step is given, n_partials = 1*/,
+                    float *pix_out   /*[H,W,GSAJ_ALIGN_PIXEL_FLOATS] NULL ok*/, uint8_t *valid_out /*[H,W] NULL ok*/,
+                    const uint32_t *skip /*NULL ok, as in gsaj_pose_gn_step*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
