@@ -8,10 +8,10 @@
 //                       gate -> the one row gsaj_pose_gn_step takes with n_partials = 1
 // Compiled without FMA contraction: tests/align_restated.py mirrors the per-pixel arithmetic one fp32 rounding at a time.
 #include "gsaj_common.h"
-#include "pose_se3.h"
+#include "gn_state.h"
 #include "wave_reduce.h"
 
-#define AL_ROW GSAJ_GN_PARTIAL_FLOATS
+#define AL_ROW GN_ROW
 #define AL_PIX GSAJ_ALIGN_PIXEL_FLOATS
 #define AL_MAX_SIDE 16384
 static_assert(AL_ROW == 32 && AL_PIX == 16, "row / pixel record layout");
@@ -179,34 +179,13 @@ __global__ __launch_bounds__(256) void k_rgbd_align(AlignParams p) {
   }
 }
 
-// ---- the fold: pose_jac.hip's gn_sum_rows restated for this file (1024 threads = 32 row groups x 32 columns: thread (r, c) adds rows
-// r, r + 32, ... of column c in row order, four loads in flight, then the groups are added in order), then the normalisation ----------
-#define AL_FOLD_THREADS 1024
-#define AL_GROUPS (AL_FOLD_THREADS / AL_ROW)
-__global__ __launch_bounds__(AL_FOLD_THREADS) void k_rgbd_align_fold(const float *__restrict__ rows, int n, double need, float *__restrict__ out,
-                                                                     const uint32_t *__restrict__ skip) {
-  __shared__ double red[AL_GROUPS][AL_ROW], sums[AL_ROW];
+// ---- the fold: the step kernels' own gn_sum_rows (gn_state.h: the rows added in a fixed order in fp64), then the normalisation -------
+__global__ __launch_bounds__(GN_SUM_THREADS) void k_rgbd_align_fold(const float *__restrict__ rows, int n, double need, float *__restrict__ out,
+                                                                    const uint32_t *__restrict__ skip) {
+  __shared__ double red[GN_SUM_THREADS / AL_ROW][AL_ROW], sums[AL_ROW];
   if (skip && *skip != 0u) return;
-  const int c = threadIdx.x & (AL_ROW - 1), r = threadIdx.x / AL_ROW;
-  double acc = 0.0;
-  for (int i0 = r; i0 < n; i0 += 4 * AL_GROUPS) {
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int i = i0 + u * AL_GROUPS;
-      v[u] = i < n ? rows[(size_t)i * AL_ROW + c] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) acc += (double)v[u];
-  }
-  red[r][c] = acc;
-  __syncthreads();
-  if (r == 0) {
-    double s = red[0][c];
-    for (int q = 1; q < AL_GROUPS; q++) s += red[q][c];
-    sums[c] = s;
-  }
-  __syncthreads();
+  gn_sum_rows<AL_ROW>(rows, n, red, sums);
+  const int c = threadIdx.x & (AL_ROW - 1);
   if (threadIdx.x < AL_ROW) {
     const double cnt = sums[30];   // an exact integer: every row's count is, and their sum stays below 2^53
     float o;
@@ -253,7 +232,7 @@ extern "C" int gsaj_rgbd_align(int W, int H, float fx, float fy, float cx, float
   const dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4));
   hipLaunchKernelGGL(k_rgbd_align, grid, dim3(256), 0, (hipStream_t)stream, p);
   GSAJ_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_rgbd_align_fold, dim3(1), dim3(AL_FOLD_THREADS), 0, (hipStream_t)stream, rows, n, need, gn_row, skip);
+  hipLaunchKernelGGL(k_rgbd_align_fold, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, rows, n, need, gn_row, skip);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }

@@ -33,33 +33,13 @@
 #include "gsaj_common.h"
 #include "gaussian_chain.h"
 #include "loss_terms.h"
-#include "pose_se3.h"
+#include "gn_state.h"
 #include "wave_reduce.h"
 
 #define JROW_F 48      // floats per derivative row: m2x[6] m2y[6] conic a[6] b[6] c[6] depth[6] colour r[3] g[3] b[3], 3 unused
 #define JROW_F4 (JROW_F / 4)
 #define JAC_CHUNK 32   // list positions examined (and at most that many entries staged) per wave and trip: 1.5 KB of splat rows + 6 KB
                        // of derivative rows + the ids = 7.8 KB of LDS per wave
-#define GN_ROW GSAJ_GN_PARTIAL_FLOATS  // H (21, upper triangle by rows), g (6), loss, L_rgb, L_depth, d/da, d/db partials
-#define GN8_ROW GSAJ_GN8_PARTIAL_FLOATS  // joint form: H8 (36), g8 (8), loss, L_rgb, L_depth, d/da, d/db partials, 15 zeros
-
-// gn_state fields behind the pose state (include/gsaj.h)
-#define GN_LAMBDA 80
-#define GN_ACC_LOSS 81
-#define GN_HAS 82
-#define GN_ACCEPTED 83
-#define GN_REJECTED 84
-#define GN_LAST 85      // loss, L_rgb, L_depth of the last call
-#define GN_ACC_W2C 88
-#define GN_H 104
-#define GN_G 125
-static_assert(GN_G + 6 <= GSAJ_GN_STATE_FLOATS, "gn_state layout");
-// joint form: [0:104) as above, then H8, g8 and the accepted exposure; the exposure step x[6], x[7] of the last call goes into the
-// two floats the pose state leaves unused behind `converged`
-#define GN8_G (GN_H + 36)
-#define GN8_ACC_EXP (GN8_G + 8)
-#define GN8_DEXP 78
-static_assert(GN8_ACC_EXP + 2 <= GSAJ_GN8_STATE_FLOATS && GN8_ROW == 64, "gn8_state layout");
 
 // ---- per-Gaussian derivative rows ----------------------------------------------------------------------------------------
 // The chain is linear in the ten sums the reverse compositor hands it, so its transpose is the chain applied to unit sums:
@@ -431,41 +411,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   render_jac_body<true, JOINT>(W, H, gx, tiles, P, im, splat, splat16, bg, point_list, taken, rows, jo, fl);
 }
 
-// ---- the partial rows summed in slot order, in fp64 ------------------------------------------------------------------------
-// GN_SUM_THREADS threads = GROUPS row groups x ROW columns (32 groups of the 32-float row, 16 of the joint form's 64-float row): thread
-// (r, c) adds rows r, r + GROUPS, ... of column c, four loads in flight at a time and added in row order, then the groups are added in
-// order.  (A frame of 640x480 has 4800 rows: eight groups with one dependent load after the other took 158 us, as long as the
-// compositor.)  sums: [ROW] doubles in LDS, complete after the call's barrier.
-#define GN_SUM_THREADS 1024
-#define GN_GROUPS (GN_SUM_THREADS / 32)
-template <int ROW>
-__device__ __forceinline__ void gn_sum_rows(const float *__restrict__ partials, int n, double (*red)[ROW], double *sums) {
-  constexpr int GROUPS = GN_SUM_THREADS / ROW;
-  const int c = threadIdx.x & (ROW - 1), r = threadIdx.x / ROW;
-  double acc = 0.0;
-  for (int i0 = r; i0 < n; i0 += 4 * GROUPS) {
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int i = i0 + u * GROUPS;
-      v[u] = i < n ? partials[(size_t)i * ROW + c] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) acc += (double)v[u];
-  }
-  red[r][c] = acc;
-  __syncthreads();
-  if (r == 0) {
-    double t = red[0][c];
-    for (int q = 1; q < GROUPS; q++) t += red[q][c];
-    sums[c] = t;
-  }
-  __syncthreads();
-}
-
+// ---- the partial rows summed in slot order, in fp64 (gn_sum_rows: gn_state.h) ----------------------------------------------------
 __global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_reduce(const float *__restrict__ partials, int n, const uint32_t *__restrict__ counters,
                                                    float *__restrict__ H_out, float *__restrict__ g_out) {
-  __shared__ double red[GN_GROUPS][GN_ROW], sums[GN_ROW];
+  __shared__ double red[GN_SUM_THREADS / GN_ROW][GN_ROW], sums[GN_ROW];
   if (counters[4]) return;  // aborted async frame
   gn_sum_rows<GN_ROW>(partials, n, red, sums);
   const int t = threadIdx.x;

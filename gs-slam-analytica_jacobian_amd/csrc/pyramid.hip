@@ -5,7 +5,7 @@
 //                  no host read
 // Compiled without FMA contraction: tests/pyramid_restated.py restates the pyramid one fp32 rounding at a time.
 #include "gsaj_common.h"
-#include "pose_se3.h"
+#include "gn_state.h"
 
 // ---- the packed pyramid: levels 1..L one after the other, each colour [3,H_l,W_l], depth [H_l,W_l], mask [H_l,W_l], every plane
 // at a 256-byte aligned offset (bytes between planes are never written) ----------------------------------------------------------
@@ -148,16 +148,7 @@ __global__ __launch_bounds__(256) void k_pyramid(PyrParams p) {
 }
 
 // ---- the Levenberg-Marquardt state at the next resolution ---------------------------------------------------------------------------
-// gn_state / gn8_state (include/gsaj.h; the offsets of pose_jac.hip)
-#define GN_LAMBDA 80
-#define GN_ACC_LOSS 81
-#define GN_HAS 82
-#define GN_LAST 85
-#define GN_ACC_W2C 88
-#define GN_H 104
-#define GN8_DEXP 78
-#define GN8_ACC_EXP 148
-static_assert(GSAJ_GN_STATE_FLOATS == 136 && GSAJ_GN8_STATE_FLOATS == 152 && GN8_ACC_EXP + 2 <= GSAJ_GN8_STATE_FLOATS, "gn_state layout");
+// gn_state / gn8_state: gn_state.h
 
 // One wave, lane 0 (as the step kernels' tail): back to the accepted pose (and exposure) -- the last proposal was never judged, and
 // a loss at another resolution cannot judge it --, the camera matrices from W2C and the NEXT level's projection matrix with the step

@@ -10,10 +10,8 @@ gsaj.PyramidGaussNewtonTracker.  There is no CPU path and no host read before re
 import torch
 
 from . import _lib
+from ._gn_state import ROW_VALID, GnViews, check_schedule, init_state
 from .pyramid import MAX_LEVELS, ImagePyramid, level_camera
-
-_STATE_FLOATS = 136   # GSAJ_GN_STATE_FLOATS
-_ROW_FLOATS = 32      # GSAJ_GN_PARTIAL_FLOATS
 
 
 def _stream(al):
@@ -39,7 +37,7 @@ def _step(al, l):  # (device work too)
 
 def _relevel(al, l):  # (device work too)
     with torch.cuda.device(al.dev):
-        _lib.check(al.lib.gsaj_pose_gn_relevel(al.state.data_ptr(), _STATE_FLOATS, al.projections[l].data_ptr(), al.lm_args[0], None,
+        _lib.check(al.lib.gsaj_pose_gn_relevel(al.state.data_ptr(), al.state.numel(), al.projections[l].data_ptr(), al.lm_args[0], None,
                                                _stream(al)), "gsaj_pose_gn_relevel")
 
 
@@ -54,7 +52,7 @@ class _Frame:
         self.filled = False
 
 
-class RgbdAligner:
+class RgbdAligner(GnViews):
     """Aligns the last tracked frame (the reference: colour, depth, pose) against a new frame (colour, optionally depth), coarse to
     fine, and leaves the new frame's pose on the device: aligner.w2c is what a map tracker's set_frame(..., w2c=) takes.  Pre-allocated
     for one image size.  w_depth weighs the depth term against the photometric one; delta_photo / delta_depth: the residual below which
@@ -104,9 +102,9 @@ class RgbdAligner:
         self._ref = _Frame(self.W, self.H, self.levels, self.dev)
         self._cur = _Frame(self.W, self.H, self.levels, self.dev)
         self.ref_w2c = torch.zeros(16, dtype=torch.float32, device=self.dev)
-        self.state = torch.zeros(_STATE_FLOATS, dtype=torch.float32, device=self.dev)
-        self.rows = torch.empty(self.lib.gsaj_rgbd_align_partial_rows(self.W, self.H), _ROW_FLOATS, dtype=torch.float32, device=self.dev)
-        self.row = torch.zeros(_ROW_FLOATS, dtype=torch.float32, device=self.dev)
+        self.state = torch.zeros(self._layout.floats, dtype=torch.float32, device=self.dev)
+        self.rows = torch.empty(self.lib.gsaj_rgbd_align_partial_rows(self.W, self.H), self._layout.row, dtype=torch.float32, device=self.dev)
+        self.row = torch.zeros(self._layout.row, dtype=torch.float32, device=self.dev)
         self._pixels = self.W * self.H   # of the level the row was last formed at
         self.iterations = 0
 
@@ -169,15 +167,7 @@ class RgbdAligner:
 
     def _reset(self, w2c):
         """A new solve: pose, camera matrices of the coarsest level, no accepted step, lambda_init -- device operations only."""
-        s = self.state
-        s.zero_()
-        s[0:16] = w2c
-        w = s[0:16].view(4, 4)
-        s[35:51] = w.t().reshape(16)
-        s[51:67] = (w.t() @ self.projections[self.levels]).reshape(16)
-        s[67:70] = -(w[:3, :3].t() @ w[:3, 3])   # the camera centre of a rigid pose
-        s[80] = self.lm_args[0]
-        s[88:104] = s[0:16]
+        init_state(self.state, self._layout, w2c, self.projections[self.levels], None, self.lm_args[0], rigid=True)
 
     def align(self, color, depth=None, w2c_init=None, schedule=None):
         """Aligns the reference against this frame (colour [3,H,W], depth [H,W] or None: the photometric term alone).  w2c_init: the
@@ -185,9 +175,8 @@ class RgbdAligner:
         to level 0 (levels + 1 of them).  No host read; returns the numbers run per level."""
         if not self._ref.filled:
             raise _lib.GsajError("set_reference() first")
-        schedule = self.default_schedule() if schedule is None else [int(n) for n in (schedule if isinstance(schedule, (list, tuple)) else [schedule])]
-        if len(schedule) != self.levels + 1 or min(schedule) < 0:
-            raise _lib.GsajError("align: schedule must hold %d non-negative counts, coarsest level first (got %r)" % (self.levels + 1, schedule))
+        schedule = self.default_schedule() if schedule is None else schedule if isinstance(schedule, (list, tuple)) else [schedule]
+        schedule = check_schedule(schedule, self.levels, "align")
         start = self.ref_w2c if w2c_init is None else self._pose(w2c_init, "align")
         self._take(self._cur, color, depth, "align")
         self._reset(start)
@@ -206,27 +195,15 @@ class RgbdAligner:
         return schedule
 
     # ---- results (device) ------------------------------------------------------------------------------------------------------------
-    w2c = property(lambda s: s.state[88:104].view(4, 4))
-    converged = property(lambda s: s.state[77])
+    w2c = GnViews.accepted_w2c   # the aligned pose is the accepted one: the last proposal was never judged
 
     @property
     def overlap(self):
         """The share of valid pixels at the last level evaluated (device scalar)."""
-        return self.row[30] / float(self._pixels)
-
-    @property
-    def loss_terms(self):
-        """[loss, L_photo, L_depth] of the last iteration, per valid pixel (device)."""
-        return self.state[85:88]
-
-    @property
-    def lm(self):
-        """dict(lam, accepted, rejected, accepted_loss: device scalars; H [6,6], g [6]: the accepted normal equations)."""
-        from .rasterizer import unpack_sym6
-        return dict(lam=self.state[80], accepted=self.state[83], rejected=self.state[84], accepted_loss=self.state[81],
-                    H=unpack_sym6(self.state[104:125]), g=self.state[125:131])
+        return self.row[ROW_VALID] / float(self._pixels)
 
     def result(self):
         """The one host read: (w2c [4,4] ndarray, overlap, accepted loss, converged)."""
-        s = torch.cat([self.state, self.row]).cpu().numpy()
-        return s[88:104].reshape(4, 4).copy(), float(s[_STATE_FLOATS + 30]) / float(self._pixels), float(s[81]), bool(s[77] != 0.0)
+        s, o = torch.cat([self.state, self.row]).cpu().numpy(), self._layout.o
+        return (s[slice(*o["acc_w2c"])].reshape(4, 4).copy(), float(s[self._layout.floats + ROW_VALID]) / float(self._pixels),
+                float(s[o["acc_loss"][0]]), bool(s[o["conv"][0]] != 0.0))

@@ -21,19 +21,16 @@ tracker per level on one shared state, re-levelled between levels on the device 
 import torch
 
 from . import _lib
+from ._gn_state import SPANS, GnViews, check_schedule, init_state, matrices
 from .grad_mask import GradMask
 from .losses import MONOCULAR, TRACKING
-from .rasterizer import FrameContext, unpack_sym6, unpack_sym8
+from .rasterizer import FrameContext
 
-# gn_state (include/gsaj.h): [0:80) the pose-state layout, then the Levenberg-Marquardt fields
-_O = dict(w2c=(0, 16), exposure=(33, 35), view=(35, 51), proj=(51, 67), campos=(67, 70), tau=(70, 76), norm=(76, 77), conv=(77, 78),
-          lam=(80, 81), acc_loss=(81, 82), has=(82, 83), accepted=(83, 84), rejected=(84, 85), last=(85, 88), acc_w2c=(88, 104),
-          H=(104, 125), g=(125, 131))
-# the joint form's state: [0:104) as above, then the accepted H8, g8 and exposure; the last exposure step behind `converged`
-_O8 = dict(_O, H=(104, 140), g=(140, 148), acc_exposure=(148, 150), dexposure=(78, 80))
+# field -> (a, b) of the two forms, under the names the host-logic tests know: a tracker they assemble by hand carries one as `_o`
+_O, _O8 = SPANS["gn"], SPANS["gn8"]
 
 
-class GaussNewtonTracker:
+class GaussNewtonTracker(GnViews):
     def __init__(self, P, W, H, M, device, w2c, projection_matrix, tanfovx, tanfovy, bg, means3D, opacities, sh_degree=0, shs=None,
                  colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, monocular=False, alpha=0.95,
                  rgb_boundary_threshold=0.01, record_bits=32, irls_delta=0.01, lambda_init=1e-3, nu=4.0, lambda_min=1e-7,
@@ -48,11 +45,9 @@ class GaussNewtonTracker:
         self.lib = _lib.load()
         self.ctx = FrameContext(P, W, H, M, self.dev, has_scales=scales is not None, record_bits=record_bits)
         self.solve_exposure = bool(solve_exposure)
-        self._o = _O8 if self.solve_exposure else _O
         self._step, self._step_name = ((self.lib.gsaj_pose_gn8_step, "gsaj_pose_gn8_step") if self.solve_exposure else
                                        (self.lib.gsaj_pose_gn_step, "gsaj_pose_gn_step"))
-        n_state = self.lib.gsaj_gn8_state_floats() if self.solve_exposure else self.lib.gsaj_gn_state_floats()
-        self.state = torch.zeros(n_state, dtype=torch.float32, device=self.dev)
+        self.state = torch.zeros(self._layout.floats, dtype=torch.float32, device=self.dev)
         self.projection = torch.as_tensor(projection_matrix, dtype=torch.float32).reshape(4, 4).contiguous().to(self.dev)
         self.praw = self.projection
         self.tanfov = (float(tanfovx), float(tanfovy))
@@ -71,51 +66,7 @@ class GaussNewtonTracker:
 
     def reset(self, w2c, exposure=(0.0, 0.0)):
         """A new frame: pose, no accepted step, lambda back to lambda_init -- in place."""
-        s = self.state
-        s.zero_()
-        s[0:16] = torch.as_tensor(w2c, dtype=torch.float32).reshape(16).to(self.dev)
-        s[33] = float(exposure[0])
-        s[34] = float(exposure[1])
-        w = s[0:16].view(4, 4)
-        s[35:51] = w.t().reshape(16)
-        s[51:67] = (w.t() @ self.projection).reshape(16)
-        s[67:70] = -(torch.linalg.inv(w[:3, :3].double().cpu()) @ w[:3, 3].double().cpu()).float().to(self.dev)
-        s[80] = self.lm_args[0]
-        s[88:104] = s[0:16]
-        if self.solve_exposure:
-            s[148:150] = s[33:35]
-
-    def _v(self, name, shape=None):
-        a, b = self._o[name]
-        t = self.state[a:b]
-        return t.view(*shape) if shape else t
-
-    w2c = property(lambda s: s._v("w2c", (4, 4)))
-    viewmatrix = property(lambda s: s._v("view", (4, 4)))
-    projmatrix = property(lambda s: s._v("proj", (4, 4)))
-    campos = property(lambda s: s._v("campos"))
-    exposure_a = property(lambda s: s.state[33:34])
-    exposure_b = property(lambda s: s.state[34:35])
-    tau = property(lambda s: s._v("tau"))
-    converged = property(lambda s: s.state[77])
-    accepted_w2c = property(lambda s: s._v("acc_w2c", (4, 4)))
-
-    @property
-    def accepted_exposure(self):
-        """[a, b] of the last accepted step (device).  Without solve_exposure the exposure never moves: the state's own [a, b]."""
-        return self._v("acc_exposure") if self.solve_exposure else self.state[33:35]
-
-    @property
-    def loss_terms(self):
-        """[loss, L_rgb, L_depth] of the last iteration's render (device)."""
-        return self._v("last")
-
-    @property
-    def lm(self):
-        """dict(lam, accepted, rejected, accepted_loss: device scalars; H [6,6], g [6]: the accepted normal equations -- [8,8], [8] over
-        [rho, theta, a, b] with solve_exposure)."""
-        return dict(lam=self.state[80], accepted=self.state[83], rejected=self.state[84], accepted_loss=self.state[81],
-                    H=(unpack_sym8 if self.solve_exposure else unpack_sym6)(self._v("H")), g=self._v("g"))
+        init_state(self.state, self._layout, w2c, self.projection, exposure, self.lm_args[0])
 
     def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2c=None, edge_threshold=None, grad_blocks=False):
         """New frame: ground truth (device, [3,H,W] / [H,W]; grad_mask [1,H,W] or None) and optionally a new initial pose; copied into
@@ -146,13 +97,12 @@ class GaussNewtonTracker:
             self.reset(w2c)
 
     def _iteration(self, sync):
-        c = self.ctx
-        c.forward(self.bg, self.means, self.opac, self.viewmatrix, self.projmatrix, self.campos, self.tanfov[0], self.tanfov[1], sync=sync,
-                  **self.kw)
+        c, view, proj, campos = self.ctx, self.viewmatrix, self.projmatrix, self.campos   # (the views are made once per iteration)
+        c.forward(self.bg, self.means, self.opac, view, proj, campos, self.tanfov[0], self.tanfov[1], sync=sync, **self.kw)
         L = dict(flags=self.flags, alpha=self.alpha, rgb_boundary_threshold=self.thr, gt_color=self.gt_color, gt_depth=self.gt_depth,
                  grad_mask=self.grad_mask, exposure_a=self.exposure_a, exposure_b=self.exposure_b)
-        o = c.pose_jacobian_loss(L, self.bg, self.means, self.viewmatrix, self.projmatrix, self.praw, self.campos, self.tanfov[0],
-                                 self.tanfov[1], irls_delta=self.delta, solve_exposure=self.solve_exposure, **self.kw)
+        o = c.pose_jacobian_loss(L, self.bg, self.means, view, proj, self.praw, campos, self.tanfov[0], self.tanfov[1],
+                                 irls_delta=self.delta, solve_exposure=self.solve_exposure, **self.kw)
         _lib.check(self._step(o["partials"].data_ptr(), o["partials"].shape[0], *self.lm_args, self.projection.data_ptr(),
                               self.state.data_ptr(), self._abort_ptr, torch.cuda.current_stream(self.dev).cuda_stream), self._step_name)
 
@@ -181,11 +131,11 @@ class GaussNewtonTracker:
 # ---- K independent solves against ONE map, in one set of launches ------------------------------------------------------------------
 def _launch(win, sync):  # (the one iteration's device work: host-logic tests replace it)
     """Batched forward at the K proposed poses -> BatchContext.pose_jacobian_loss -> gsaj_pose_gn[8]_step_batch."""
-    c, n = win.ctx, win.state.shape[1]
+    c, n, exposure = win.ctx, win.state.shape[1], win.exposure
     views, projs, cps = win.matrices()
     c.forward(win.bg, win.means, win.opac, views, projs, cps, win.tanfov[0], win.tanfov[1], sync=sync, **win.kw)
     L = dict(flags=win.flags, alpha=win.alpha, rgb_boundary_threshold=win.thr, gt_color=win.gt_color, gt_depth=win.gt_depth,
-             grad_mask=win.grad_mask, exposure_a=win.state[:, 33], exposure_b=win.state[:, 34], exposure_stride=n)
+             grad_mask=win.grad_mask, exposure_a=exposure[:, 0], exposure_b=exposure[:, 1], exposure_stride=n)
     o = c.pose_jacobian_loss(L, win.bg, win.means, views, projs, win.praw, cps, win.tanfov[0], win.tanfov[1], irls_delta=win.delta,
                              solve_exposure=win.solve_exposure, **win.kw)
     skip, skip_stride = c.abort_flags()
@@ -201,7 +151,7 @@ def _select(win):  # (device work too)
                                            win._best.data_ptr() + 4, torch.cuda.current_stream(win.dev).cuda_stream), "gsaj_pose_gn_select")
 
 
-class GaussNewtonWindow:
+class GaussNewtonWindow(GnViews):
     """GaussNewtonTracker for K views of ONE fixed map, solved together: every kernel of an iteration runs once with gridDim.y = K
     (batched forward, Jacobian walk, K Levenberg-Marquardt steps in one launch).  With the map fixed the K poses decouple, so the K
     solves are exact, and each view's arithmetic is the single tracker's.  Two uses:
@@ -230,9 +180,7 @@ class GaussNewtonWindow:
         self.ctx, self.lib = ctx, _lib.load()
         self.K, self.W, self.H, self.dev = ctx.K, ctx.W, ctx.H, ctx.dev
         self.solve_exposure = bool(solve_exposure)
-        self._o = _O8 if self.solve_exposure else _O
-        n_state = self.lib.gsaj_gn8_state_floats() if self.solve_exposure else self.lib.gsaj_gn_state_floats()
-        self.state = torch.zeros((self.K, n_state), dtype=torch.float32, device=self.dev)
+        self.state = torch.zeros((self.K, self._layout.floats), dtype=torch.float32, device=self.dev)
         self.projection = torch.as_tensor(projection_matrix, dtype=torch.float32).reshape(4, 4).contiguous().to(self.dev)
         self.praw = self.projection
         self.tanfov = (float(tanfov[0]), float(tanfov[1]))
@@ -262,19 +210,7 @@ class GaussNewtonWindow:
 
     def reset(self, slot, w2c, exposure=(0.0, 0.0)):
         """Slot `slot` starts over: pose (and exposure), no accepted step, lambda back to lambda_init -- as GaussNewtonTracker.reset."""
-        s = self.state[self._slot(slot)]
-        s.zero_()
-        s[0:16] = torch.as_tensor(w2c, dtype=torch.float32).reshape(16).to(self.dev)
-        s[33] = float(exposure[0])
-        s[34] = float(exposure[1])
-        w = s[0:16].view(4, 4)
-        s[35:51] = w.t().reshape(16)
-        s[51:67] = (w.t() @ self.projection).reshape(16)
-        s[67:70] = -(torch.linalg.inv(w[:3, :3].double().cpu()) @ w[:3, 3].double().cpu()).float().to(self.dev)
-        s[80] = self.lm_args[0]
-        s[88:104] = s[0:16]
-        if self.solve_exposure:
-            s[148:150] = s[33:35]
+        init_state(self.state[self._slot(slot)], self._layout, w2c, self.projection, exposure, self.lm_args[0])
 
     def set_view(self, slot, gt_color, gt_depth=None, grad_mask=None, w2c=None, exposure=None):
         """The window use: slot `slot` gets its own frame -- ground truth (device, [3,H,W] / [H,W]; grad_mask [1,H,W] or None), copied
@@ -301,7 +237,7 @@ class GaussNewtonWindow:
                 m.copy_(grad_mask.to(self.dev, torch.uint8).reshape(-1))
         self._filled[k] = True
         if w2c is not None or exposure is not None:
-            self.reset(k, self.state[k, 0:16].clone() if w2c is None else w2c, (0.0, 0.0) if exposure is None else exposure)
+            self.reset(k, self.w2c[k].clone() if w2c is None else w2c, (0.0, 0.0) if exposure is None else exposure)
 
     def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2cs=None, exposure=None):
         """The multi-start use: ONE frame copied into all K slots, with K start poses w2cs [K,4,4] (None: the slots keep theirs)."""
@@ -314,35 +250,7 @@ class GaussNewtonWindow:
 
     def matrices(self):
         """(viewmatrices [K,4,4], projmatrices [K,4,4], campos [K,3]) of the poses the next render is at, gathered from the state."""
-        s = self.state
-        return s[:, 35:51].reshape(self.K, 4, 4).contiguous(), s[:, 51:67].reshape(self.K, 4, 4).contiguous(), s[:, 67:70].contiguous()
-
-    def _v(self, name, shape=()):
-        a, b = self._o[name]
-        return self.state[:, a:b].view(self.K, *shape) if shape else self.state[:, a:b]
-
-    w2c = property(lambda s: s.state[:, 0:16].view(s.K, 4, 4))
-    exposure = property(lambda s: s.state[:, 33:35])
-    tau = property(lambda s: s._v("tau"))
-    converged = property(lambda s: s.state[:, 77])
-    accepted_w2c = property(lambda s: s.state[:, 88:104].view(s.K, 4, 4))
-
-    @property
-    def accepted_exposure(self):
-        """[K,2]: a, b of each view's last accepted step (without solve_exposure the exposure never moves: the state's own)."""
-        return self._v("acc_exposure") if self.solve_exposure else self.state[:, 33:35]
-
-    @property
-    def loss_terms(self):
-        """[K,3]: loss, L_rgb, L_depth of each view's last render."""
-        return self._v("last")
-
-    @property
-    def lm(self):
-        """GaussNewtonTracker.lm with [K,...] entries: lam, accepted, rejected, accepted_loss [K]; H [K,6,6] / [K,8,8], g [K,6] / [K,8]."""
-        s = self.state
-        return dict(lam=s[:, 80], accepted=s[:, 83], rejected=s[:, 84], accepted_loss=s[:, 81],
-                    H=(unpack_sym8 if self.solve_exposure else unpack_sym6)(self._v("H")), g=self._v("g"))
+        return matrices(self.state)
 
     def iterate(self, n, check_every=0):
         """Up to n iterations of all K views.  The first is synchronous (it sizes the arena); after it an iteration contains no host
@@ -357,7 +265,7 @@ class GaussNewtonWindow:
             _launch(self, not self._sized)
             self._sized = True
             done += 1
-            if check_every and done % check_every == 0 and bool(((self.state[:, 77] != 0) | (self.active == 0)).all().item()):
+            if check_every and done % check_every == 0 and bool(((self.converged != 0) | (self.active == 0)).all().item()):
                 break
         self.iterations += done
         aborted = self.ctx.clear_aborts()
@@ -500,9 +408,7 @@ class PyramidGaussNewtonTracker:
             done = self.trackers[0].iterate(n, check_every)
             self.iterations += done
             return [done]
-        schedule = [int(n) for n in schedule]
-        if len(schedule) != self.levels + 1 or min(schedule) < 0:
-            raise _lib.GsajError("iterate: schedule must hold %d non-negative counts, coarsest level first (got %r)" % (self.levels + 1, schedule))
+        schedule = check_schedule(schedule, self.levels, "iterate")
         self._snapshot.copy_(self.state)
         done, prev, at = [], None, self._at
         for l, n in zip(range(self.levels, -1, -1), schedule):

@@ -119,7 +119,7 @@ class DeviceMapper:
                 one.reset(w2c, exposure)
             self.poses.state[slot].copy_(one.state)
         elif exposure is not None:
-            self.poses.state[slot, 33], self.poses.state[slot, 34] = float(exposure[0]), float(exposure[1])
+            self.poses.exposure[slot, 0], self.poses.exposure[slot, 1] = float(exposure[0]), float(exposure[1])
 
     # ---- one iteration --------------------------------------------------------------------------------------------------
     def _iteration(self, reset, initialization):
@@ -139,7 +139,7 @@ class DeviceMapper:
             rendered = False
         if self.fused:  # 2., 3.
             L = dict(flags=flags, alpha=self.alpha, rgb_boundary_threshold=self.thr, gt_color=self.gt_color, gt_depth=self.gt_depth,
-                     exposure_a=None if initialization else p.state[:, 33], exposure_b=None if initialization else p.state[:, 34],
+                     exposure_a=None if initialization else p.exposure[:, 0], exposure_b=None if initialization else p.exposure[:, 1],
                      exposure_stride=p.state.stride(0), scalars=self.scalars, dexposure=self.dexposure)
             c.forward_loss(L, self.bg, xyz, opac, views, projs, cps, tx, ty, **geo)
             g = c.backward_loss(L, self.bg, xyz, views, projs, self.praw, cps, tx, ty, split=self.split, **geo)

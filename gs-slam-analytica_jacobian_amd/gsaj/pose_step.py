@@ -8,20 +8,18 @@ scalar, so N tracking iterations can be enqueued without a host round trip."""
 import torch
 
 from . import _lib
-
-_O = dict(w2c=(0, 16), m=(16, 24), v=(24, 32), step=(32, 33), exposure=(33, 35), view=(35, 51), proj=(51, 67), campos=(67, 70),
-          tau=(70, 76), norm=(76, 77), conv=(77, 78))
+from ._gn_state import StateViews, init_state, layout, matrices
 
 
-class PoseTracker:
+class PoseTracker(StateViews):
     def __init__(self, w2c, projection_matrix, device, lr_rot=0.003, lr_trans=0.001, lr_exposure_a=0.01, lr_exposure_b=0.01,
                  betas=(0.9, 0.999), eps=1e-8, converged_threshold=1e-4):
         self.lib = _lib.load()
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
             raise _lib.GsajError("PoseTracker needs a HIP device (there is no CPU path)")
-        n = self.lib.gsaj_pose_state_floats()
-        self.state = torch.zeros(n, dtype=torch.float32, device=self.dev)
+        self._layout = layout("pose")
+        self.state = torch.zeros(self._layout.floats, dtype=torch.float32, device=self.dev)
         self.projection = torch.as_tensor(projection_matrix, dtype=torch.float32).reshape(4, 4).contiguous().to(self.dev)
         self.lr = (float(lr_rot), float(lr_trans), float(lr_exposure_a), float(lr_exposure_b))
         self.betas, self.eps, self.thr = (float(betas[0]), float(betas[1])), float(eps), float(converged_threshold)
@@ -30,29 +28,7 @@ class PoseTracker:
     def reset(self, w2c, exposure=(0.0, 0.0)):
         """A new frame: pose, zero Adam moments and step count -- IN PLACE, so that views of the state handed out earlier
         (and hipGraphs captured over them, gsaj.tracking) stay valid."""
-        self.state.zero_()
-        self.state[0:16] = torch.as_tensor(w2c, dtype=torch.float32).reshape(16).to(self.dev)
-        self.state[33] = float(exposure[0])
-        self.state[34] = float(exposure[1])
-        # matrices for the first render
-        w = self.state[0:16].view(4, 4)
-        self.state[35:51] = w.t().reshape(16)
-        self.state[51:67] = (w.t() @ self.projection).reshape(16)
-        self.state[67:70] = -(torch.linalg.inv(w[:3, :3].double().cpu()) @ w[:3, 3].double().cpu()).float().to(self.dev)
-
-    def _v(self, name, shape=None):
-        a, b = _O[name]
-        t = self.state[a:b]
-        return t.view(*shape) if shape else t
-
-    w2c = property(lambda s: s._v("w2c", (4, 4)))
-    viewmatrix = property(lambda s: s._v("view", (4, 4)))        # world_view_transform = W2C^T
-    projmatrix = property(lambda s: s._v("proj", (4, 4)))        # full_proj_transform
-    campos = property(lambda s: s._v("campos"))
-    exposure_a = property(lambda s: s.state[33:34])
-    exposure_b = property(lambda s: s.state[34:35])
-    tau = property(lambda s: s._v("tau"))
-    converged = property(lambda s: s.state[77])                   # device scalar: 1.0 when |tau| < threshold
+        init_state(self.state, self._layout, w2c, self.projection, exposure)
 
     def step(self, dL_dtau_sum, dL_dexposure=None, skip=None):
         """dL_dtau_sum: device float32 [6] = [rho, theta] (gsaj_rasterize_backward); dL_dexposure: device [2] or None.
@@ -68,7 +44,7 @@ class PoseTracker:
                    "gsaj_pose_adam_step")
 
 
-class PoseTrackerBatch:
+class PoseTrackerBatch(StateViews):
     """K poses stepped in one launch (C ABI gsaj_pose_adam_step_batch): the keyframe poses of a mapping window, each with its own
     Adam state (utils/slam_backend.py:255-262 steps the keyframe optimiser and calls update_pose per keyframe).  `state` is
     [K, 80]; the matrices the next batched render needs come out as [K,4,4] / [K,3] views of it gathered by `matrices()`."""
@@ -82,6 +58,7 @@ class PoseTrackerBatch:
         self.singles = [PoseTracker(w, projection_matrix, device, lr_rot, lr_trans, lr_exposure_a, lr_exposure_b, betas, eps,
                                     converged_threshold) for w in w2cs]  # (initialises every state exactly as the single tracker does)
         self.K = len(self.singles)
+        self._layout = self.singles[0]._layout
         self.state = torch.stack([s.state for s in self.singles]).contiguous()
         self.projection = self.singles[0].projection
         self.lr, self.betas, self.eps, self.thr = self.singles[0].lr, self.singles[0].betas, self.singles[0].eps, self.singles[0].thr
@@ -102,9 +79,4 @@ class PoseTrackerBatch:
 
     def matrices(self):
         """(viewmatrices [K,4,4], projmatrices [K,4,4], campos [K,3]) as contiguous tensors for BatchContext.forward / backward."""
-        s = self.state
-        return s[:, 35:51].reshape(self.K, 4, 4).contiguous(), s[:, 51:67].reshape(self.K, 4, 4).contiguous(), s[:, 67:70].contiguous()
-
-    w2c = property(lambda s: s.state[:, 0:16].view(s.K, 4, 4))
-    exposure = property(lambda s: s.state[:, 33:35])
-    converged = property(lambda s: s.state[:, 77])
+        return matrices(self.state)

@@ -119,7 +119,7 @@ def seed_from_keyframe(image, depth, w2c, fx, fy, cx, cy, downsample_factor, poi
 
     image [3,H,W] (the keyframe's colour; exposure_ab = device tensor {a, b} applies exp(a) * image + b first), depth [H,W], w2c = 16
     device floats, row-major W2C (a [4,4] tensor, or a DeviceTracker pose_state, whose first 16 floats are that; exposure_ab may be
-    pose_state[33:35]).  A pixel seeds a Gaussian if 0 < depth < depth_trunc (and, with gt_image, its colour sum exceeds the
+    the pose tracker's `exposure` view of it).  A pixel seeds a Gaussian if 0 < depth < depth_trunc (and, with gt_image, its colour sum exceeds the
     threshold) and it is among the m = int(n_valid / downsample_factor) pixels the seed picks."""
     lib = _lib.load()
     d = _plane("depth", depth)

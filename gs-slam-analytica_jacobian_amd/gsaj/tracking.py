@@ -70,21 +70,22 @@ class DeviceTracker:
     # ---- one iteration, in the two halves a collective may sit between -------------------------------------------------
     def _render_and_grads(self, sync):
         p, c = self.pose, self.ctx
+        view, proj, campos = p.viewmatrix, p.projmatrix, p.campos   # (the views are made once per iteration)
         if self.fused and not sync:
             L = dict(flags=self.flags, alpha=self.alpha, rgb_boundary_threshold=self.thr, gt_color=self.gt_color, gt_depth=self.gt_depth,
                      grad_mask=self.grad_mask, exposure_a=p.exposure_a, exposure_b=p.exposure_b, scalars=self.packed[6:11])
-            c.forward_loss(L, self.bg, self.means, self.opac, p.viewmatrix, p.projmatrix, p.campos, self.tanfov[0], self.tanfov[1], **self.kw)
-            g = c.backward_loss(L, self.bg, self.means, p.viewmatrix, p.projmatrix, self.praw, p.campos, self.tanfov[0], self.tanfov[1],
+            c.forward_loss(L, self.bg, self.means, self.opac, view, proj, campos, self.tanfov[0], self.tanfov[1], **self.kw)
+            g = c.backward_loss(L, self.bg, self.means, view, proj, self.praw, campos, self.tanfov[0], self.tanfov[1],
                                 pose_only=True, **self.kw)
             assert g["tau_sum"].data_ptr() == self.packed.data_ptr()
             if self._sharded():
                 self.packed[tbs.ABORTED].copy_(self._abort_word)
             return
-        c.forward(self.bg, self.means, self.opac, p.viewmatrix, p.projmatrix, p.campos, self.tanfov[0], self.tanfov[1], sync=sync,
+        c.forward(self.bg, self.means, self.opac, view, proj, campos, self.tanfov[0], self.tanfov[1], sync=sync,
                   **self.kw)
         L = self.loss(self.flags, self.alpha, self.thr, c.color, c.depth, c.opacity, self.gt_color, self.gt_depth, self.grad_mask,
                       p.exposure_a, p.exposure_b)
-        g = c.backward(self.bg, self.means, p.viewmatrix, p.projmatrix, self.praw, p.campos, self.tanfov[0], self.tanfov[1],
+        g = c.backward(self.bg, self.means, view, proj, self.praw, campos, self.tanfov[0], self.tanfov[1],
                        L["dL_dcolor"], L["dL_ddepth"], pose_only=True, **self.kw)
         assert g["tau_sum"].data_ptr() == self.packed.data_ptr()
         if self._sharded():  # the abort word joins the sum: any rank's abort reaches every rank

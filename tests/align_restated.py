@@ -459,6 +459,7 @@ def parity_case(W, H, mode):
 
 
 MODES = ("depth", "photo", "w0")
+LONG_FOLD = (70, 260)   # 2 x 65 = 130 rows: past one trip of the fold's four-deep load loop (32 groups x 4 = 128 rows of 32 floats)
 
 
 # ---- planted cases -------------------------------------------------------------------------------------------------------------------

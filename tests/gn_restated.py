@@ -252,6 +252,21 @@ def sym6(h21):
     return out
 
 
+def fold_rows(rows, groups):
+    """The step kernels' sum of the partial rows [n, ROW] (csrc/gn_state.h gn_sum_rows) in its stated order, in float64: row group r
+    of `groups` (1024 threads / ROW: 32 for the 32-float row, 16 for the joint form's 64) adds rows r, r + groups, ... in order, then
+    the groups are added in order -> [ROW] float64.  Float64 addition in a fixed order is reproducible, so the float32 cast of this is
+    the device's value bit for bit."""
+    rows = np.asarray(rows, F).astype(np.float64)
+    acc = np.zeros((groups, rows.shape[1]))
+    for i in range(rows.shape[0]):
+        acc[i % groups] += rows[i]
+    total = acc[0].copy()
+    for q in range(1, groups):
+        total += acc[q]
+    return total
+
+
 def lm_new_state(w2c, lambda_init):
     w = np.array(w2c, np.float64).reshape(4, 4)
     return dict(w2c=w.copy(), lam=float(lambda_init), has=False, acc_loss=0.0, acc_w2c=w.copy(), H=np.zeros((6, 6)), g=np.zeros(6),

@@ -175,6 +175,7 @@ def _committed_cases():
     for W, H in ar.parity_sizes():
         for mode in ar.MODES:
             yield "%dx%d %s" % (W, H, mode), ar.parity_case(W, H, mode)
+    yield "%dx%d depth" % ar.LONG_FOLD, ar.parity_case(*ar.LONG_FOLD, "depth")
     for sign in (1, -1):
         yield "planted %+d" % sign, ar.planted_case(sign)[0]
     yield "planted near", ar.planted_near_case()[0]

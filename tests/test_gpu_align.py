@@ -87,6 +87,17 @@ def test_pixels_equal_the_mirror_bit_for_bit_and_the_row_is_their_sum(W, H, mode
         assert out["row"][29] == 0 and (out["row"][31] == mir["gate"].sum() or border.any()), "w_depth = 0: the gates are counted, the term is nothing"
 
 
+def test_a_frame_of_more_rows_than_one_trip_of_the_folds_load_loop():
+    """70 x 260 with depth: 2 x 65 = 130 rows, so row group 0 and 1 of the fold (gn_sum_rows: csrc/gn_state.h) take a second trip of
+    the four-deep load loop, and the last trip of every group is a partial one.  The comparisons of the parity test."""
+    W, H = ar.LONG_FOLD
+    case, mir, border = _expect((W, H, "depth"), lambda: ar.parity_case(W, H, "depth"))
+    out, _ = _run(case)
+    assert out["rows"].shape == (130, 32)
+    _compare(case, mir, border, out, "%dx%d depth" % (W, H))
+    assert out["row"][30] >= 1 and out["row"][31] >= 1
+
+
 @pytest.mark.parametrize("sign", [1, -1])
 def test_planted_pixels_on_every_gate(sign):
     """u exactly W - 1 (sign +1) and exactly 0 (sign -1), a reference depth of 0, NaN and +inf in each of the four inputs, a tap on
