@@ -14,6 +14,7 @@
 // contiguous run (emission-slot order), and the [64][M*3] SH blocks are staged through LDS so that the
 // global loads / stores of dL_dsh are fully coalesced (padded LDS rows, conflict-free per-lane reads).
 #include "gsaj_common.h"
+#include "last_block.h"
 #include "wave_reduce.h"
 __constant__ float bSH_C0 = 0.28209479177387814f;
 __constant__ float bSH_C1 = 0.4886025119029199f;
@@ -24,42 +25,6 @@ __constant__ float bSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.457
 #define GSAJ_SH_CONSTANTS_DEFINED
 #include "gaussian_chain.h"
 
-// Four workgroups' dL/dtau partials (8 floats each, 6 used) as seen by ANOTHER workgroup after the ticket: 16-byte loads that
-// bypass this CU's L1 and this XCD's L2 (sc0 sc1).  The partials were stored write-through (agent-scope atomic stores) by CUs of
-// any XCD.  Coherent loads cost ~100 ns EACH on this part and do not overlap (tools/chain_trace.py: 6 dword loads per partial
-// made the last workgroup's sum 20 us of the batched kernel's 80; two dwordx4 loads: 8 us), so they are as wide as the ISA allows,
-// eight to a batch, and the batch's s_waitcnt sits in the SAME asm statement: the compiler takes an asm's outputs for ready when
-// the statement ends and may copy them at once.
-__device__ __forceinline__ void gsaj_load_partials4(const float *p0, const float *p1, const float *p2, const float *p3,
-                                                    float4 (&lo)[4], float4 (&hi)[4]) {
-  asm volatile(
-      "global_load_dwordx4 %0, %8, off sc0 sc1\n\tglobal_load_dwordx4 %1, %8, off offset:16 sc0 sc1\n\t"
-      "global_load_dwordx4 %2, %9, off sc0 sc1\n\tglobal_load_dwordx4 %3, %9, off offset:16 sc0 sc1\n\t"
-      "global_load_dwordx4 %4, %10, off sc0 sc1\n\tglobal_load_dwordx4 %5, %10, off offset:16 sc0 sc1\n\t"
-      "global_load_dwordx4 %6, %11, off sc0 sc1\n\tglobal_load_dwordx4 %7, %11, off offset:16 sc0 sc1\n\t"
-      "s_waitcnt vmcnt(0)"
-      : "=&v"(lo[0]), "=&v"(hi[0]), "=&v"(lo[1]), "=&v"(hi[1]), "=&v"(lo[2]), "=&v"(hi[2]), "=&v"(lo[3]), "=&v"(hi[3])
-      : "v"(p0), "v"(p1), "v"(p2), "v"(p3)
-      : "memory");
-}
-// sum over workgroups i = lane, lane + 64, ... < nblk of the 6 components, in that order, in fp64
-__device__ __forceinline__ void gsaj_sum_partials(const float *partials, int nblk, int lane, double (&acc)[6]) {
-  for (int i0 = lane; i0 < nblk; i0 += 4 * 64) {
-    float4 lo[4], hi[4];
-    const float *src[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) src[u] = partials + (size_t)min(i0 + u * 64, nblk - 1) * 8;  // unconditional loads, masked below
-    gsaj_load_partials4(src[0], src[1], src[2], src[3], lo, hi);
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const bool in = i0 + u * 64 < nblk;
-      const float t6[6] = {lo[u].x, lo[u].y, lo[u].z, lo[u].w, hi[u].x, hi[u].y};
-#pragma unroll
-      for (int k = 0; k < 6; k++) acc[k] += in ? (double)t6[k] : 0.0;
-    }
-  }
-}
-
 // SHW = 3*M as a compile-time constant (0: runtime) -- the staging loops divide by it per element
 GSAJ_TRACE_DEFINE(gbwd)
 
@@ -68,7 +33,7 @@ __global__ __launch_bounds__(GB_BLOCK) void k_gaussian_bwd(BwdParams p, GeomWS g
                                                            const float4 *__restrict__ inst_grad,
                                                            const uint8_t *__restrict__ reached) {
   extern __shared__ float sh_lds[];  // [GB_BLOCK][3M+1]: SH coefficients in, overwritten in place by dL/dSH (padded rows)
-  __shared__ uint32_t s_ticket;
+  __shared__ bool s_last;
   if (counters[4]) return;  // aborted async frame
   GSAJ_TRACE_BEGIN(gbwd)
 #ifdef GSAJ_BLOCK_TRACE
@@ -190,33 +155,19 @@ __global__ __launch_bounds__(GB_BLOCK) void k_gaussian_bwd(BwdParams p, GeomWS g
 #pragma unroll
   for (int k = 0; k < 6; k++) {
     const float v = wave_sum(tau[k]);
-    if (tid == 0)  // write-through (sc1) store: part of the fence-free hand-off below
-      __hip_atomic_store(&g.tau_partials[(size_t)blockIdx.x * 8 + k], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) lb_publish(&g.tau_partials[(size_t)blockIdx.x * 8 + k], v);  // (6 floats in an 8-float slot: two 16-byte loads)
   }
-  if (p.dL_dtau_sum) {
-  // ---- 8. the last workgroup to arrive sums the partials in workgroup order (fp64): deterministic,
-  // no extra launch (replaces torch.sum over [P,6], diff_gaussian_rasterization/__init__.py:162).
-  // Hand-off without fences (MI355X_MICROARCH.md, hand-offs measured with sc1 loads in place of the
-  // acquire): the 6 partials are stored write-through (sc1) by lane 0, drained with vmcnt(0), then
-  // the ticket is drawn with a relaxed agent-scope atomic; the workgroup that draws the last ticket
-  // reads every partial with sc1 loads only after its add has returned.  An agent release here
-  // (buffer_wbl2) would write back this kernel's ~25 MB of dirty output once per workgroup.
-  if (tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_ticket = __hip_atomic_fetch_add(&counters[3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (s_ticket == gridDim.x - 1) {
-  const int nblk = (int)gridDim.x;
-  double acc6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  gsaj_sum_partials(g.tau_partials, nblk, tid, acc6);
+  // ---- 8. the last workgroup to arrive sums the partials in workgroup order (fp64): deterministic, no extra launch (replaces
+  // torch.sum over [P,6], diff_gaussian_rasterization/__init__.py:162).  The hand-off is last_block.h's, the ticket counters[3].
+  if (p.dL_dtau_sum && lb_arrive(&counters[3], &s_last)) {
+    double acc6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    lb_sum_partials(g.tau_partials, (int)gridDim.x, tid, acc6);
 #pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const double v = wave_sum(acc6[k]);
-    if (tid == 0) p.dL_dtau_sum[k] = (float)v;
-  }
-  if (tid == 0) counters[3] = 0u;  // ready for the next backward over this workspace
-  }
+    for (int k = 0; k < 6; k++) {
+      const double v = wave_sum(acc6[k]);
+      if (tid == 0) p.dL_dtau_sum[k] = (float)v;
+    }
+    if (tid == 0) lb_reset(&counters[3]);  // ready for the next backward over this workspace
   }
   TRM(3)
   // ---- 9. outputs: one row per Gaussian, zeros for culled ones (the reference's binding memsets first) ----

@@ -424,10 +424,7 @@ __device__ __forceinline__ void gsaj_load_row(const float4 *__restrict__ splat, 
 #endif
 
 #ifdef __HIPCC__
-// Four consecutive words written by OTHER workgroups of this launch (L2 atomics / write-through stores): one 16-byte load that
-// bypasses this CU's L1 and this XCD's L2 (sc0 sc1), with its wait inside the statement (the compiler takes an asm's outputs
-// for ready when the statement ends).  Coherent loads cost ~100 ns each and do not overlap (tools/chain_trace.py), so the
-// "last workgroup sums the partials" tails use as few and as wide ones as they can.
+// (Loads of what OTHER workgroups of the same launch wrote: last_block.h.)
 // 16 bytes from a 4-byte-aligned address (global_load_dwordx4 needs no more): one load instruction where the C++ type system would
 // want four.
 // The pointer is stated to be GLOBAL memory (a flat load is counted by the LDS counter too, so every LDS wait would wait for it).
@@ -440,16 +437,11 @@ __device__ __forceinline__ uint32_t gsaj_load_u32_global(const uint32_t *src) {
   return *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>((unsigned long long)src);
 }
 // Eight bytes written earlier in this kernel (by this workgroup, made visible by a barrier): a device-scope load, which is served
-// by the L2 -- never by a line this CU's L1 took before the store -- and, unlike the coherent load below, is not waited for here.
+// by the L2 -- never by a line this CU's L1 took before the store -- and, unlike the coherent loads of last_block.h, is not waited for here.
 __device__ __forceinline__ uint2 gsaj_load_u64_device(const uint2 *src) {
   const unsigned long long v = __hip_atomic_load(reinterpret_cast<const __attribute__((address_space(1))) unsigned long long *>((unsigned long long)src),
                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-}
-__device__ __forceinline__ uint4 gsaj_coherent_load_x4(const void *src) {
-  uint4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(src) : "memory");
-  return v;
 }
 #endif
 

@@ -12,6 +12,7 @@
 // points = spatial neighbours) scans the UNION of the boxes its lanes accept, so a box's points are fetched once per
 // wave through LDS and every lane tests them (a superset of candidates keeps the result exact).
 #include "gsaj_common.h"
+#include "last_block.h"
 #include "wave_reduce.h"
 #include <cfloat>
 #include <cstring>
@@ -48,6 +49,18 @@ static size_t knn_carve(void *base, int P, KnnWS *w) {
   return (size_t)(p - (char *)base) + 256;
 }
 
+// A box {min xyz, max xyz} of a workgroup through the ordered fold of wave_reduce.h: three minima and three maxima put into the six
+// rows of red, the caller's ONE barrier, then component c folded over the waves in order.
+template <int NWAVES>
+__device__ __forceinline__ void knn_box_put(float *v, float (*red)[NWAVES]) {
+  block_fold_put<NWAVES, 3>(v, red, lane_min());
+  block_fold_put<NWAVES, 3>(v + 3, red + 3, lane_max());
+}
+template <int NWAVES>
+__device__ __forceinline__ float knn_box_get(const float (*red)[NWAVES], int c) {
+  return c < 3 ? block_fold_get<NWAVES>(red[c], lane_min()) : block_fold_get<NWAVES>(red[c], lane_max());
+}
+
 // bounding box incl. the origin (simple_knn.cu:194-203: Reduce with init {0,0,0}); last workgroup combines the partials
 __global__ __launch_bounds__(256) void k_knn_bbox(int P, const float *__restrict__ pts, KnnWS w) {
   __shared__ float red[6][4];
@@ -59,46 +72,27 @@ __global__ __launch_bounds__(256) void k_knn_bbox(int P, const float *__restrict
     v[0] = fminf(0.f, x); v[1] = fminf(0.f, y); v[2] = fminf(0.f, z);
     v[3] = fmaxf(0.f, x); v[4] = fmaxf(0.f, y); v[5] = fmaxf(0.f, z);
   }
-#pragma unroll
-  for (int c = 0; c < 6; c++) v[c] = c < 3 ? wave_min(v[c]) : wave_max(v[c]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int c = 0; c < 6; c++) red[c][threadIdx.x >> 6] = v[c];
+  knn_box_put<4>(v, red);
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0) {  // the workgroup's box, handed to the last workgroup (last_block.h)
 #pragma unroll
-    for (int c = 0; c < 6; c++) {
-      float s = red[c][0];
-      for (int k = 1; k < 4; k++) s = c < 3 ? fminf(s, red[c][k]) : fmaxf(s, red[c][k]);
-      __hip_atomic_store(&w.bpart[(size_t)blockIdx.x * 6 + c], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    is_last = __hip_atomic_fetch_add(w.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    for (int c = 0; c < 6; c++) lb_publish(&w.bpart[(size_t)blockIdx.x * 6 + c], knn_box_get<4>(red, c));
   }
-  __syncthreads();
-  if (!is_last) return;
+  if (!lb_arrive(w.ticket, &is_last)) return;
   float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (unsigned b = threadIdx.x; b < gridDim.x; b += 256)
 #pragma unroll
     for (int c = 0; c < 6; c++) {
-      const float t = __hip_atomic_load(&w.bpart[(size_t)b * 6 + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const float t = lb_load(&w.bpart[(size_t)b * 6 + c]);
       a[c] = c < 3 ? fminf(a[c], t) : fmaxf(a[c], t);
     }
-#pragma unroll
-  for (int c = 0; c < 6; c++) a[c] = c < 3 ? wave_min(a[c]) : wave_max(a[c]);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int c = 0; c < 6; c++) red[c][threadIdx.x >> 6] = a[c];
+  __syncthreads();  // (red is written again)
+  knn_box_put<4>(a, red);
   __syncthreads();
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int c = 0; c < 6; c++) {
-      float s = red[c][0];
-      for (int k = 1; k < 4; k++) s = c < 3 ? fminf(s, red[c][k]) : fmaxf(s, red[c][k]);
-      w.bbox[c] = s;
-    }
-    *w.ticket = 0u;
+    for (int c = 0; c < 6; c++) w.bbox[c] = knn_box_get<4>(red, c);
+    lb_reset(w.ticket);
   }
 }
 
@@ -228,18 +222,9 @@ __global__ __launch_bounds__(KNN_BOX) void k_knn_boxes(int P, const float *__res
     w.sorted[i] = make_float4(x, y, z, 0.f);
     v[0] = x; v[1] = y; v[2] = z; v[3] = x; v[4] = y; v[5] = z;
   }
-#pragma unroll
-  for (int c = 0; c < 6; c++) v[c] = c < 3 ? wave_min(v[c]) : wave_max(v[c]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int c = 0; c < 6; c++) red[c][threadIdx.x >> 6] = v[c];
+  knn_box_put<KNN_BOX / 64>(v, red);
   __syncthreads();
-  if (threadIdx.x < 6) {
-    const int c = threadIdx.x;
-    float s = red[c][0];
-    for (int k = 1; k < KNN_BOX / 64; k++) s = c < 3 ? fminf(s, red[c][k]) : fmaxf(s, red[c][k]);
-    w.boxes[(size_t)blockIdx.x * 6 + c] = s;
-  }
+  if (threadIdx.x < 6) w.boxes[(size_t)blockIdx.x * 6 + threadIdx.x] = knn_box_get<KNN_BOX / 64>(red, (int)threadIdx.x);
 }
 
 __device__ __forceinline__ void k_best3(float d, float &b0, float &b1, float &b2) {  // simple_knn.cu:134-147

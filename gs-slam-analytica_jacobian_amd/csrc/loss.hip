@@ -8,8 +8,9 @@
 // torch kernels plus their autograd backward; here one kernel reads colour/depth/opacity + ground truth once
 // and writes dL/dcolour, dL/ddepth (what gsaj_rasterize_backward consumes) and, deterministically, the loss value
 // and dL/d(exposure a, b): workgroup partials are summed in workgroup order, in fp64, by the last-arriving
-// workgroup (ticket; no float atomics).
+// workgroup (last_block.h; no float atomics).
 #include "gsaj_common.h"
+#include "last_block.h"
 #include "loss_terms.h"
 #include "wave_reduce.h"
 
@@ -75,54 +76,25 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_loss_seeds(LossParams p) {
     if (p.dL_dopacity) p.dL_dopacity[pix] = o.dop;
     p.dL_ddepth[pix] = o.gD;
   }
-  // workgroup partials: wave butterfly, then the four waves in order
+  // the workgroup's four partials, handed to the last workgroup (last_block.h; fenced, this kernel took 78 us instead of 6)
   float v[4] = {s_rgb, s_d, s_a, s_b};
-#pragma unroll
-  for (int c = 0; c < 4; c++) v[c] = wave_sum(v[c]);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) {
-#pragma unroll
-    for (int c = 0; c < 4; c++) red[c][wave] = v[c];
-  }
-  __syncthreads();
-  // Hand-off without fences (as in k_gaussian_bwd): lane 0 stores the four workgroup partials write-through
-  // (agent-scope atomic stores = sc1), drains them with vmcnt(0) and only then draws its ticket; the workgroup
-  // that draws the last ticket reads every partial with sc1 loads.  A __threadfence() here costs a buffer_wbl2
-  // of this kernel's 5 MB of dirty seed rows per workgroup (measured: 78 us instead of 6).
+  block_fold<LOSS_BLOCK / 64, 4>(v, red, lane_add());
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
-      float s = red[c][0];
-      for (int w = 1; w < LOSS_BLOCK / 64; w++) s += red[c][w];
-      __hip_atomic_store(&p.partials[(size_t)blockIdx.x * 4 + c], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    is_last = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    for (int c = 0; c < 4; c++) lb_publish(&p.partials[(size_t)blockIdx.x * 4 + c], v[c]);
   }
-  __syncthreads();
-  if (!is_last) return;
+  if (!lb_arrive(p.ticket, &is_last)) return;
   __shared__ double fin[4][LOSS_BLOCK / 64];
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  double t[4] = {0.0, 0.0, 0.0, 0.0};
   for (unsigned b = threadIdx.x; b < gridDim.x; b += LOSS_BLOCK) {  // a workgroup's four partials = one 16-byte coherent load
-    const uint4 u = gsaj_coherent_load_x4(p.partials + (size_t)b * 4);
-    acc[0] += (double)__uint_as_float(u.x);
-    acc[1] += (double)__uint_as_float(u.y);
-    acc[2] += (double)__uint_as_float(u.z);
-    acc[3] += (double)__uint_as_float(u.w);
+    const uint4 u = lb_load_x4(p.partials + (size_t)b * 4);
+    t[0] += (double)__uint_as_float(u.x);
+    t[1] += (double)__uint_as_float(u.y);
+    t[2] += (double)__uint_as_float(u.z);
+    t[3] += (double)__uint_as_float(u.w);
   }
-#pragma unroll
-  for (int c = 0; c < 4; c++) acc[c] = wave_sum(acc[c]);
-  if (lane == 0) {
-#pragma unroll
-    for (int c = 0; c < 4; c++) fin[c][wave] = acc[c];
-  }
-  __syncthreads();
+  block_fold<LOSS_BLOCK / 64, 4>(t, fin, lane_add());
   if (threadIdx.x == 0) {
-    double t[4];
-    for (int c = 0; c < 4; c++) {
-      t[c] = fin[c][0];
-      for (int w = 1; w < LOSS_BLOCK / 64; w++) t[c] += fin[c][w];
-    }
     const double n_rgb = 3.0 * (double)HW;
     const double l_rgb = t[0] / n_rgb, l_d = mono ? 0.0 : t[1] / (cl ? (double)max(p.n_valid[0], 1u) : (double)HW);
     p.out[0] = (float)(cl ? (mono ? l_rgb : l_rgb + l_d) : mono ? l_rgb : (double)p.alpha * l_rgb + (1.0 - (double)p.alpha) * l_d);
@@ -130,7 +102,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_loss_seeds(LossParams p) {
     p.out[2] = (float)l_d;
     p.out[3] = noexp ? 0.f : (float)((double)k_rgb * t[2]);
     p.out[4] = noexp ? 0.f : (float)((double)k_rgb * t[3]);
-    *p.ticket = 0u;
+    lb_reset(p.ticket);
   }
 }
 
@@ -271,7 +243,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_isotropic(int P, int C, float we
                                                           float *__restrict__ dL_dscales, int accumulate,
                                                           double *__restrict__ partials, uint32_t *__restrict__ ticket,
                                                           float *__restrict__ out) {
-  __shared__ double red[LOSS_BLOCK / 64];
+  __shared__ double red[1][LOSS_BLOCK / 64];
   __shared__ bool is_last;
   const int i = blockIdx.x * LOSS_BLOCK + threadIdx.x;
   const float k = weight / ((float)P * (float)C);
@@ -293,22 +265,13 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_isotropic(int P, int C, float we
         dL_dscales[(size_t)i * C + c] = accumulate ? dL_dscales[(size_t)i * C + c] + gq : gq;
       }
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = red[0];
-    for (int w = 1; w < LOSS_BLOCK / 64; w++) t += red[w];
-    __hip_atomic_store(&partials[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    is_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!is_last || threadIdx.x != 0) return;
+  block_fold<LOSS_BLOCK / 64, 1>(&s, red, lane_add());
+  if (threadIdx.x == 0) lb_publish(&partials[blockIdx.x], s);
+  if (!lb_arrive(ticket, &is_last) || threadIdx.x != 0) return;
   double t = 0.0;
-  for (unsigned b = 0; b < gridDim.x; b++) t += __hip_atomic_load(&partials[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (unsigned b = 0; b < gridDim.x; b++) t += lb_load(&partials[b]);  // (one thread, one load per workgroup: DESIGN.md section 8)
   out[0] = (float)((double)k * t);
-  *ticket = 0u;
+  lb_reset(ticket);
 }
 
 extern "C" size_t gsaj_isotropic_workspace_bytes(int P) {

@@ -10,13 +10,14 @@
 // staged in LDS (zeros outside the image), the five blurred quantities x, y, x^2, y^2, xy are formed, and per pixel
 // S = A B / (C D) together with the three partials of S w.r.t. the blurred quantities that depend on img -- dS/dmu1,
 // dS/dE[x^2], dS/dE[xy] -- which the backward consumes from the workspace.  Per-workgroup sums of S and |x - y| are reduced
-// in a fixed order by the last-arriving workgroup (ticket, as in loss.hip: no float atomics, bit-reproducible).
+// in a fixed order by the last-arriving workgroup (last_block.h: no float atomics, bit-reproducible).
 // Backward (k_ssim_bwd): the same tile geometry blurs the three partial maps (zeros outside: the adjoint of a zero-padded
 // correlation with a symmetric window is the same correlation) and forms
 //   dL/dx = w_n (blur(dS/dmu1) + 2 x blur(dS/dE[x^2]) + y blur(dS/dE[xy])) + l1_w sign(x - y).
 // LDS: lane = column in every pass, so each 32-lane half of a wave reads 32 consecutive dwords of one row: conflict-free
 // without padding (ds_read_b32 banks are dword % 32, serviced per 32-lane half).
 #include "gsaj_common.h"
+#include "last_block.h"
 #include "wave_reduce.h"
 
 #define SSIM_TW 32           // output tile width (= the 32 lanes of a wave half)
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(SSIM_BLOCK) void k_ssim_fwd(SsimFwdParams p) {
   }
   __syncthreads();
   // vertical pass + the per-pixel SSIM terms: SSIM_TH x SSIM_TW outputs, two per thread
-  float s_ssim = 0.f, s_l1 = 0.f;
+  float s[2] = {0.f, 0.f};  // sums of S and of |x - y|
 #pragma unroll
   for (int q = 0; q < (SSIM_TH * SSIM_TW) / SSIM_BLOCK; q++) {
     const int i = threadIdx.x + q * SSIM_BLOCK, r = i / SSIM_TW, c = i - r * SSIM_TW;
@@ -162,50 +163,33 @@ __global__ __launch_bounds__(SSIM_BLOCK) void k_ssim_fwd(SsimFwdParams p) {
     p.L.dmu[pix] = 2.f * m2 * (B - A) / CD + 2.f * m1 * S * (1.f / D - 1.f / Cc);
     p.L.dxx[pix] = -S / D;
     p.L.dxy[pix] = 2.f * A / CD;
-    s_ssim += S;
-    s_l1 += fabsf(sx[r + SSIM_R][c + SSIM_R] - sy[r + SSIM_R][c + SSIM_R]);
+    s[0] += S;
+    s[1] += fabsf(sx[r + SSIM_R][c + SSIM_R] - sy[r + SSIM_R][c + SSIM_R]);
   }
-  // workgroup partials: wave butterfly, then the four waves in order
-  s_ssim = wave_sum(s_ssim);
-  s_l1 = wave_sum(s_l1);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) { red[0][wave] = s_ssim; red[1][wave] = s_l1; }
-  __syncthreads();
-  // hand-off as in k_loss_seeds: write-through partials, drain, then the ticket; the last workgroup reads them coherently
+  // the workgroup's two partials (in a 4-float slot: one coherent load each), handed to the last workgroup (last_block.h)
+  block_fold<SSIM_BLOCK / 64, 2>(s, red, lane_add());
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int c = 0; c < 2; c++) {
-      float s = red[c][0];
-      for (int w = 1; w < SSIM_BLOCK / 64; w++) s += red[c][w];
-      __hip_atomic_store(&p.L.partials[(size_t)blockIdx.x * 4 + c], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    is_last = __hip_atomic_fetch_add(p.L.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    for (int c = 0; c < 2; c++) lb_publish(&p.L.partials[(size_t)blockIdx.x * 4 + c], s[c]);
   }
-  __syncthreads();
-  if (!is_last) return;
+  if (!lb_arrive(p.L.ticket, &is_last)) return;
   // per image: its C * tiles workgroups are contiguous in blockIdx order; fp64, fixed tree
   const unsigned per_img = gridDim.x / (unsigned)p.N;
   double tot_s = 0.0, tot_l1 = 0.0;
   for (int n = 0; n < p.N; n++) {
     double acc[2] = {0.0, 0.0};
     for (unsigned b = threadIdx.x; b < per_img; b += SSIM_BLOCK) {
-      const uint4 u = gsaj_coherent_load_x4(p.L.partials + ((size_t)n * per_img + b) * 4);
+      const uint4 u = lb_load_x4(p.L.partials + ((size_t)n * per_img + b) * 4);
       acc[0] += (double)__uint_as_float(u.x);
       acc[1] += (double)__uint_as_float(u.y);
     }
-    acc[0] = wave_sum(acc[0]);
-    acc[1] = wave_sum(acc[1]);
-    if (lane == 0) { fin[0][wave] = acc[0]; fin[1][wave] = acc[1]; }
-    __syncthreads();
+    block_fold<SSIM_BLOCK / 64, 2>(acc, fin, lane_add());
     if (threadIdx.x == 0) {
-      double a = fin[0][0], l = fin[1][0];
-      for (int w = 1; w < SSIM_BLOCK / 64; w++) { a += fin[0][w]; l += fin[1][w]; }
-      if (p.ssim_out) p.ssim_out[n] = (float)(a / ((double)p.C * (double)HW));
-      tot_s += a;
-      tot_l1 += l;
+      if (p.ssim_out) p.ssim_out[n] = (float)(acc[0] / ((double)p.C * (double)HW));
+      tot_s += acc[0];
+      tot_l1 += acc[1];
     }
-    __syncthreads();
+    __syncthreads();  // (fin is written again for the next image)
   }
   if (threadIdx.x == 0) {
     const double cnt = (double)p.N * (double)p.C * (double)HW;
@@ -216,7 +200,7 @@ __global__ __launch_bounds__(SSIM_BLOCK) void k_ssim_fwd(SsimFwdParams p) {
       p.refine_out[1] = (float)l1;
       p.refine_out[2] = (float)ssim;
     }
-    *p.L.ticket = 0u;
+    lb_reset(p.L.ticket);
   }
 }
 

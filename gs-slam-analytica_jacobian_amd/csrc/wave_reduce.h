@@ -10,6 +10,7 @@
 //   block_excl_scan_add              workgroup exclusive scan: wave scans + one LDS hop for the wave totals, ONE barrier;
 //   block_scan_total                 the workgroup's total from the same LDS words
 //   block_excl_scan_runs             the same over n items, a contiguous run per lane, with the largest item
+//   block_fold (_put / _get)         workgroup reduction: butterflies + one LDS hop, ONE barrier, the waves folded in wave order
 //   reduce4 / store4                 four per-lane partials through one tree (7 cross-lane steps where four butterflies take 24)
 //   reduce10 / store10               ten per-lane partials at once, register-only:
 //
@@ -132,6 +133,36 @@ __device__ __forceinline__ uint32_t block_excl_scan_runs(In in, uint32_t *out, i
     run += v;
   }
   return total;
+}
+
+// ---- ordered workgroup fold of N values per lane, NWAVES waves (every lane must call) ----------------------------------------
+// slots: N rows of NWAVES words of the caller's LDS.  block_fold_put: the butterfly of each value, then lane 0 of each wave
+// writes its wave's N results; block_fold_get, behind a barrier: row by row, the waves folded in order 0, 1, 2, ... -- a fixed
+// tree, whatever the value type.  block_fold is the two around ONE barrier, the result in thread 0 only.  A caller whose values
+// do not share one operation (a bounding box: three minima, three maxima) puts each group, has its own barrier, and gets.
+template <int NWAVES, int N, typename T, typename Op>
+__device__ __forceinline__ void block_fold_put(T *v, T (*slots)[NWAVES], Op op) {
+#pragma unroll
+  for (int c = 0; c < N; c++) v[c] = wave_allreduce(v[c], op);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int c = 0; c < N; c++) slots[c][threadIdx.x >> 6] = v[c];
+  }
+}
+template <int NWAVES, typename T, typename Op>
+__device__ __forceinline__ T block_fold_get(const T *row, Op op) {
+  T s = row[0];
+  for (int w = 1; w < NWAVES; w++) s = op(s, row[w]);
+  return s;
+}
+template <int NWAVES, int N, typename T, typename Op>
+__device__ __forceinline__ void block_fold(T *v, T (*slots)[NWAVES], Op op) {
+  block_fold_put<NWAVES, N>(v, slots, op);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < N; c++) v[c] = block_fold_get<NWAVES>(slots[c], op);
+  }
 }
 
 // ---- ten values at once -----------------------------------------------------------------------------------------------------
