@@ -11,11 +11,8 @@ import torch
 
 from . import _lib
 from ._gn_state import ROW_VALID, GnViews, check_schedule, init_state
+from ._loop import require_device, stream
 from .pyramid import MAX_LEVELS, ImagePyramid, level_camera
-
-
-def _stream(al):
-    return torch.cuda.current_stream(al.dev).cuda_stream
 
 
 def _residuals(al, l, depth):  # (the device work of one iteration, first half: host-logic tests replace it)
@@ -26,19 +23,19 @@ def _residuals(al, l, depth):  # (the device work of one iteration, first half: 
         _lib.check(al.lib.gsaj_rgbd_align(W, H, fx, fy, cx, cy, rc.data_ptr(), rd.data_ptr(), al.ref_w2c.data_ptr(), cc.data_ptr(),
                                           cd.data_ptr() if depth else None, al.state.data_ptr(), al.w_depth, al.delta_photo, al.delta_depth,
                                           al.depth_edge_ratio, al.min_depth, al.max_depth, al.min_overlap, al.rows.data_ptr(),
-                                          al.row.data_ptr(), None, None, None, _stream(al)), "gsaj_rgbd_align")
+                                          al.row.data_ptr(), None, None, None, stream(al.dev)), "gsaj_rgbd_align")
 
 
 def _step(al, l):  # (device work too)
     with torch.cuda.device(al.dev):
         _lib.check(al.lib.gsaj_pose_gn_step(al.row.data_ptr(), 1, *al.lm_args, al.projections[l].data_ptr(), al.state.data_ptr(), None,
-                                            _stream(al)), "gsaj_pose_gn_step")
+                                            stream(al.dev)), "gsaj_pose_gn_step")
 
 
 def _relevel(al, l):  # (device work too)
     with torch.cuda.device(al.dev):
         _lib.check(al.lib.gsaj_pose_gn_relevel(al.state.data_ptr(), al.state.numel(), al.projections[l].data_ptr(), al.lm_args[0], None,
-                                               _stream(al)), "gsaj_pose_gn_relevel")
+                                               stream(al.dev)), "gsaj_pose_gn_relevel")
 
 
 class _Frame:
@@ -63,8 +60,7 @@ class RgbdAligner(GnViews):
     def __init__(self, W, H, fx, fy, cx, cy, device, levels=2, w_depth=1.0, delta_photo=0.01, delta_depth=0.01, depth_edge_ratio=0.1,
                  min_depth=0.01, max_depth=100.0, min_overlap=0.0, znear=0.01, zfar=100.0, lambda_init=1e-3, nu=4.0, lambda_min=1e-7,
                  lambda_max=1e7, converged_threshold=1e-4):
-        if torch.device(device).type != "cuda":
-            raise _lib.GsajError("RgbdAligner needs a HIP device (there is no CPU path)")
+        require_device(device, "RgbdAligner")
         self._init_host(W, H, (fx, fy, cx, cy), device, levels, (w_depth, delta_photo, delta_depth, depth_edge_ratio, min_depth, max_depth,
                                                                   min_overlap), (znear, zfar),
                         (lambda_init, nu, lambda_min, lambda_max, converged_threshold))

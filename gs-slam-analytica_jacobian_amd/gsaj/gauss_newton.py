@@ -22,15 +22,16 @@ import torch
 
 from . import _lib
 from ._gn_state import SPANS, GnViews, check_schedule, init_state, matrices
-from .grad_mask import GradMask
-from .losses import MONOCULAR, TRACKING
-from .rasterizer import FrameContext
+from ._loop import FrameTarget, ViewTargets, check_slot, finish_frame, finish_window, loss_description, loss_terms, map_args, require_device, run, stream
+from .losses import TRACKING
+from .pyramid import MAX_LEVELS, ImagePyramid, level_camera
+from .rasterizer import BatchContext, FrameContext
 
 # field -> (a, b) of the two forms, under the names the host-logic tests know: a tracker they assemble by hand carries one as `_o`
 _O, _O8 = SPANS["gn"], SPANS["gn8"]
 
 
-class GaussNewtonTracker(GnViews):
+class GaussNewtonTracker(GnViews, FrameTarget):
     def __init__(self, P, W, H, M, device, w2c, projection_matrix, tanfovx, tanfovy, bg, means3D, opacities, sh_degree=0, shs=None,
                  colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, monocular=False, alpha=0.95,
                  rgb_boundary_threshold=0.01, record_bits=32, irls_delta=0.01, lambda_init=1e-3, nu=4.0, lambda_min=1e-7,
@@ -39,9 +40,7 @@ class GaussNewtonTracker(GnViews):
         residual below which an L1 term is treated as a quadratic (0: pure IRLS weights 1 / |r|).  lambda_init / nu / lambda_min /
         lambda_max: the damping and its factor; converged_threshold: |tau| below which the device reports convergence.
         solve_exposure: solve for the exposure (a, b) together with the pose (then convergence also needs |da|, |db| below the threshold)."""
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise _lib.GsajError("GaussNewtonTracker needs a HIP device (there is no CPU path)")
+        self.dev = require_device(device, "GaussNewtonTracker")
         self.lib = _lib.load()
         self.ctx = FrameContext(P, W, H, M, self.dev, has_scales=scales is not None, record_bits=record_bits)
         self.solve_exposure = bool(solve_exposure)
@@ -51,13 +50,10 @@ class GaussNewtonTracker(GnViews):
         self.projection = torch.as_tensor(projection_matrix, dtype=torch.float32).reshape(4, 4).contiguous().to(self.dev)
         self.praw = self.projection
         self.tanfov = (float(tanfovx), float(tanfovy))
-        self.flags = TRACKING | (MONOCULAR if monocular else 0)
-        self.alpha, self.thr = float(alpha), float(rgb_boundary_threshold)
-        self.delta = float(irls_delta)
+        self.flags, self.alpha, self.thr, self.delta = loss_terms(monocular, alpha, rgb_boundary_threshold, irls_delta, TRACKING)
         self.lm_args = (float(lambda_init), float(nu), float(lambda_min), float(lambda_max), float(converged_threshold))
         self.bg, self.means, self.opac = bg, means3D, opacities
-        self.kw = dict(sh_degree=sh_degree, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
-                       cov3D_precomp=cov3D_precomp)
+        self.kw = map_args(sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp)
         self._abort_ptr = self.ctx.abort_flag_ptr()
         self.gt_color = self.gt_depth = self.grad_mask = None
         self._grad_op = None
@@ -68,43 +64,16 @@ class GaussNewtonTracker(GnViews):
         """A new frame: pose, no accepted step, lambda back to lambda_init -- in place."""
         init_state(self.state, self._layout, w2c, self.projection, exposure, self.lm_args[0])
 
-    def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2c=None, edge_threshold=None, grad_blocks=False):
-        """New frame: ground truth (device, [3,H,W] / [H,W]; grad_mask [1,H,W] or None) and optionally a new initial pose; copied into
-        buffers the tracker owns.  edge_threshold (with grad_mask None): the tracker computes the frame's gradient mask itself
-        (gsaj.grad_mask) from its own copy of gt_color.  A mask, given or computed, is there for every frame of a tracker or for none."""
-        masked = grad_mask is not None or edge_threshold is not None
-        if self.gt_color is None:
-            self.gt_color = gt_color.to(self.dev, torch.float32).contiguous().clone()
-            self.gt_depth = None if gt_depth is None else gt_depth.to(self.dev, torch.float32).contiguous().clone()
-            if grad_mask is not None:
-                self.grad_mask = grad_mask.to(self.dev, torch.uint8).contiguous().view(-1).clone()
-            elif masked:
-                self.grad_mask = torch.empty(self.gt_color[0].numel(), dtype=torch.uint8, device=self.dev)
-        else:
-            if (gt_depth is None) != (self.gt_depth is None) or masked != (self.grad_mask is not None):
-                raise _lib.GsajError("set_frame: depth / mask must be given for every frame of a tracker or for none")
-            self.gt_color.copy_(gt_color)
-            if gt_depth is not None:
-                self.gt_depth.copy_(gt_depth)
-            if grad_mask is not None:
-                self.grad_mask.copy_(grad_mask.to(self.dev, torch.uint8).view(-1))
-        if grad_mask is None and masked:
-            if self._grad_op is None:
-                _, H, W = self.gt_color.shape
-                self._grad_op = GradMask(W, H, self.dev)
-            self._grad_op(self.gt_color, edge_threshold, blocks=grad_blocks, out=self.grad_mask)
-        if w2c is not None:
-            self.reset(w2c)
+    _start_pose = reset   # (FrameTarget.set_frame's new start pose)
 
     def _iteration(self, sync):
         c, view, proj, campos = self.ctx, self.viewmatrix, self.projmatrix, self.campos   # (the views are made once per iteration)
         c.forward(self.bg, self.means, self.opac, view, proj, campos, self.tanfov[0], self.tanfov[1], sync=sync, **self.kw)
-        L = dict(flags=self.flags, alpha=self.alpha, rgb_boundary_threshold=self.thr, gt_color=self.gt_color, gt_depth=self.gt_depth,
-                 grad_mask=self.grad_mask, exposure_a=self.exposure_a, exposure_b=self.exposure_b)
+        L = loss_description(self, self.exposure_a, self.exposure_b)
         o = c.pose_jacobian_loss(L, self.bg, self.means, view, proj, self.praw, campos, self.tanfov[0], self.tanfov[1],
                                  irls_delta=self.delta, solve_exposure=self.solve_exposure, **self.kw)
         _lib.check(self._step(o["partials"].data_ptr(), o["partials"].shape[0], *self.lm_args, self.projection.data_ptr(),
-                              self.state.data_ptr(), self._abort_ptr, torch.cuda.current_stream(self.dev).cuda_stream), self._step_name)
+                              self.state.data_ptr(), self._abort_ptr, stream(self.dev)), self._step_name)
 
     def iterate(self, n, check_every=0):
         """Up to n iterations; check_every > 0: stop once the device reports |tau| (and, with solve_exposure, |da|, |db|) < converged_threshold, looked at every check_every
@@ -112,19 +81,10 @@ class GaussNewtonTracker(GnViews):
         (those iterations changed nothing); the next call re-sizes the arena with one synchronous iteration."""
         if self.gt_color is None:
             raise _lib.GsajError("set_frame() first")
-        done = 0
-        with torch.cuda.device(self.dev):
-            while done < n:
-                self._iteration(self.ctx.capacity == 0)  # the very first iteration sizes the binning arena: synchronous forward
-                done += 1
-                if check_every and done % check_every == 0 and bool(self.converged.item() != 0.0):
-                    break
+        with torch.cuda.device(self.dev):   # the very first iteration sizes the binning arena: synchronous forward
+            done = run(n, check_every, lambda: self._iteration(self.ctx.capacity == 0), lambda: self.converged)
         self.iterations += done
-        try:
-            self.ctx.status()
-        except _lib.GsajError:
-            self.ctx.capacity = 0
-            raise
+        finish_frame(self.ctx)
         return done
 
 
@@ -134,24 +94,23 @@ def _launch(win, sync):  # (the one iteration's device work: host-logic tests re
     c, n, exposure = win.ctx, win.state.shape[1], win.exposure
     views, projs, cps = win.matrices()
     c.forward(win.bg, win.means, win.opac, views, projs, cps, win.tanfov[0], win.tanfov[1], sync=sync, **win.kw)
-    L = dict(flags=win.flags, alpha=win.alpha, rgb_boundary_threshold=win.thr, gt_color=win.gt_color, gt_depth=win.gt_depth,
-             grad_mask=win.grad_mask, exposure_a=exposure[:, 0], exposure_b=exposure[:, 1], exposure_stride=n)
+    L = loss_description(win, exposure[:, 0], exposure[:, 1], exposure_stride=n)
     o = c.pose_jacobian_loss(L, win.bg, win.means, views, projs, win.praw, cps, win.tanfov[0], win.tanfov[1], irls_delta=win.delta,
                              solve_exposure=win.solve_exposure, **win.kw)
     skip, skip_stride = c.abort_flags()
     name = "gsaj_pose_gn8_step_batch" if win.solve_exposure else "gsaj_pose_gn_step_batch"
     _lib.check(getattr(win.lib, name)(win.K, o["partials"].data_ptr(), o["partials"].shape[1], win.active.data_ptr(), *win.lm_args,
                                       win.projection.data_ptr(), win.state.data_ptr(), skip, skip_stride,
-                                      torch.cuda.current_stream(win.dev).cuda_stream), name)
+                                      stream(win.dev)), name)
 
 
 def _select(win):  # (device work too)
     """gsaj_pose_gn_select into win._best: int32 [2] = the index, the bits of its loss."""
     _lib.check(win.lib.gsaj_pose_gn_select(win.K, win.state.data_ptr(), win.state.shape[1], win.active.data_ptr(), win._best.data_ptr(),
-                                           win._best.data_ptr() + 4, torch.cuda.current_stream(win.dev).cuda_stream), "gsaj_pose_gn_select")
+                                           win._best.data_ptr() + 4, stream(win.dev)), "gsaj_pose_gn_select")
 
 
-class GaussNewtonWindow(GnViews):
+class GaussNewtonWindow(GnViews, ViewTargets):
     """GaussNewtonTracker for K views of ONE fixed map, solved together: every kernel of an iteration runs once with gridDim.y = K
     (batched forward, Jacobian walk, K Levenberg-Marquardt steps in one launch).  With the map fixed the K poses decouple, so the K
     solves are exact, and each view's arithmetic is the single tracker's.  Two uses:
@@ -165,13 +124,10 @@ class GaussNewtonWindow(GnViews):
                  rgb_boundary_threshold=0.01, record_bits=32, irls_delta=0.01, lambda_init=1e-3, nu=4.0, lambda_min=1e-7,
                  lambda_max=1e7, converged_threshold=1e-4, solve_exposure=False, streams=1):
         """The arguments of GaussNewtonTracker with K and w2cs [K,4,4]; streams: BatchContext's view groups."""
-        if torch.device(device).type != "cuda":
-            raise _lib.GsajError("GaussNewtonWindow needs a HIP device (there is no CPU path)")
-        from .rasterizer import BatchContext
+        require_device(device, "GaussNewtonWindow")
         ctx = BatchContext(K, P, W, H, M, device, has_scales=scales is not None, record_bits=record_bits, streams=streams)
         self._init_host(ctx, w2cs, projection_matrix, (tanfovx, tanfovy), bg, means3D, opacities,
-                        dict(sh_degree=sh_degree, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
-                             cov3D_precomp=cov3D_precomp),
+                        map_args(sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp),
                         dict(monocular=monocular, alpha=alpha, rgb_boundary_threshold=rgb_boundary_threshold, irls_delta=irls_delta),
                         (lambda_init, nu, lambda_min, lambda_max, converged_threshold), solve_exposure)
 
@@ -184,13 +140,10 @@ class GaussNewtonWindow(GnViews):
         self.projection = torch.as_tensor(projection_matrix, dtype=torch.float32).reshape(4, 4).contiguous().to(self.dev)
         self.praw = self.projection
         self.tanfov = (float(tanfov[0]), float(tanfov[1]))
-        self.flags = TRACKING | (MONOCULAR if loss["monocular"] else 0)
-        self.alpha, self.thr, self.delta = float(loss["alpha"]), float(loss["rgb_boundary_threshold"]), float(loss["irls_delta"])
+        self.flags, self.alpha, self.thr, self.delta = loss_terms(flags=TRACKING, **loss)
         self.lm_args = tuple(float(x) for x in lm_args)
         self.bg, self.means, self.opac, self.kw = bg, means3D, opacities, kw
-        f = dict(dtype=torch.float32, device=self.dev)
-        self.gt_color = torch.zeros((self.K, 3, self.H, self.W), **f)
-        self.gt_depth = None if loss["monocular"] else torch.zeros((self.K, self.H, self.W), **f)
+        self._alloc_views(loss["monocular"])
         self.grad_mask = None  # uint8 [K*H*W] once a slot was given a mask (the other slots: all ones, which is no mask)
         self.active = torch.ones(self.K, dtype=torch.uint8, device=self.dev)
         self._best = torch.zeros(2, dtype=torch.int32, device=self.dev)
@@ -203,30 +156,17 @@ class GaussNewtonWindow(GnViews):
         for k in range(self.K):
             self.reset(k, w2cs[k])
 
-    def _slot(self, slot):
-        if not 0 <= int(slot) < self.K:
-            raise _lib.GsajError("GaussNewtonWindow: slot %r is not one of the window's %d" % (slot, self.K))
-        return int(slot)
-
     def reset(self, slot, w2c, exposure=(0.0, 0.0)):
         """Slot `slot` starts over: pose (and exposure), no accepted step, lambda back to lambda_init -- as GaussNewtonTracker.reset."""
-        init_state(self.state[self._slot(slot)], self._layout, w2c, self.projection, exposure, self.lm_args[0])
+        init_state(self.state[check_slot(slot, self.K, "GaussNewtonWindow")], self._layout, w2c, self.projection, exposure, self.lm_args[0])
 
     def set_view(self, slot, gt_color, gt_depth=None, grad_mask=None, w2c=None, exposure=None):
         """The window use: slot `slot` gets its own frame -- ground truth (device, [3,H,W] / [H,W]; grad_mask [1,H,W] or None), copied
         into the window's [K,...] buffers -- and optionally a new start pose (with `exposure` (a, b), default (0, 0))."""
-        k, H, W = self._slot(slot), self.H, self.W
-        if tuple(gt_color.shape) != (3, H, W):
-            raise _lib.GsajError("set_view: gt_color must be [3,%d,%d], got %r" % (H, W, tuple(gt_color.shape)))
-        if (gt_depth is None) != (self.gt_depth is None):
-            raise _lib.GsajError("set_view: a monocular window takes no depth, every other window needs it")
-        if gt_depth is not None and gt_depth.numel() != H * W:
-            raise _lib.GsajError("set_view: gt_depth must have %d elements, got %d" % (H * W, gt_depth.numel()))
+        H, W = self.H, self.W
         if grad_mask is not None and grad_mask.numel() != H * W:
             raise _lib.GsajError("set_view: grad_mask must have %d elements, got %d" % (H * W, grad_mask.numel()))
-        self.gt_color[k].copy_(gt_color)
-        if gt_depth is not None:
-            self.gt_depth[k].copy_(gt_depth.reshape(H, W))
+        k = self._take_view(slot, gt_color, gt_depth)
         if grad_mask is not None and self.grad_mask is None:
             self.grad_mask = torch.ones(self.K * H * W, dtype=torch.uint8, device=self.dev)
         if self.grad_mask is not None:
@@ -252,6 +192,10 @@ class GaussNewtonWindow(GnViews):
         """(viewmatrices [K,4,4], projmatrices [K,4,4], campos [K,3]) of the poses the next render is at, gathered from the state."""
         return matrices(self.state)
 
+    def _one(self):
+        _launch(self, not self._sized)
+        self._sized = True
+
     def iterate(self, n, check_every=0):
         """Up to n iterations of all K views.  The first is synchronous (it sizes the arena); after it an iteration contains no host
         read.  check_every > 0: every check_every iterations the K converged flags are read once, and the loop stops when every
@@ -260,19 +204,13 @@ class GaussNewtonWindow(GnViews):
         if not all(self._filled):
             raise _lib.GsajError("set_view() every slot (or set_frame()) first: slots %r have no frame" %
                                  [k for k, ok in enumerate(self._filled) if not ok])
-        done = 0
-        while done < n:
-            _launch(self, not self._sized)
-            self._sized = True
-            done += 1
-            if check_every and done % check_every == 0 and bool(((self.converged != 0) | (self.active == 0)).all().item()):
-                break
+        done = run(n, check_every, self._one, lambda: ((self.converged != 0) | (self.active == 0)).all())
         self.iterations += done
-        aborted = self.ctx.clear_aborts()
-        if aborted:
+        try:
+            finish_window(self.ctx, "those views' states were skipped")
+        except _lib.GsajError:
             self._sized = False
-            raise _lib.GsajError("%d asynchronous forward(s) of the window were aborted on the device (binning arena too small for a "
-                                 "view's instances): those views' states were skipped" % aborted)
+            raise
         return done
 
     def best(self):
@@ -292,7 +230,7 @@ def _relevel(pt, level, skip):  # (device work too)
     """gsaj_pose_gn_relevel of the shared state to level `level`'s projection matrix; skip: a device address or None."""
     with torch.cuda.device(pt.dev):
         _lib.check(pt.lib.gsaj_pose_gn_relevel(pt.state.data_ptr(), pt.state.numel(), pt.trackers[level].projection.data_ptr(), pt.lambda_init,
-                                               skip, torch.cuda.current_stream(pt.dev).cuda_stream), "gsaj_pose_gn_relevel")
+                                               skip, stream(pt.dev)), "gsaj_pose_gn_relevel")
 
 
 def _level_iteration(t, sync):  # (device work too)
@@ -314,14 +252,12 @@ class PyramidGaussNewtonTracker:
         """The arguments of GaussNewtonTracker (projection_matrix, tanfovx, tanfovy: level 0's), then levels, the intrinsics of the
         frame, from which every coarser level's camera follows (ImagePyramid.level_camera), and depth_edge_ratio: the relative depth
         spread beyond which a coarse pixel counts as a depth discontinuity and carries no depth."""
-        if torch.device(device).type != "cuda":
-            raise _lib.GsajError("PyramidGaussNewtonTracker needs a HIP device (there is no CPU path)")
+        require_device(device, "PyramidGaussNewtonTracker")
         self._init_host(P, W, H, M, device, w2c, projection_matrix, (tanfovx, tanfovy), bg, means3D, opacities, levels,
                         (fx, fy, cx, cy, znear, zfar), depth_edge_ratio, kw)
 
     def _init_host(self, P, W, H, M, device, w2c, projection_matrix, tanfov, bg, means3D, opacities, levels, intrinsics, depth_edge_ratio, kw):
         """Everything that is not a kernel: the level cameras, one tracker per level (through _level_tracker), the shared state."""
-        from .pyramid import MAX_LEVELS, level_camera
         self.lib = _lib.load()
         self.P, self.W, self.H, self.M, self.dev = int(P), int(W), int(H), int(M), torch.device(device)
         self.levels = int(levels)
@@ -363,26 +299,19 @@ class PyramidGaussNewtonTracker:
         """GaussNewtonTracker.set_frame, then the pyramid of the frame in one launch.  A given grad_mask is OR-reduced with the
         images; with edge_threshold every level's mask is computed by gsaj.grad_mask on that level's colour: the gradient is taken
         at that scale.  w2c: the start pose; the solve starts at the coarsest level."""
-        from .pyramid import ImagePyramid
         t0 = self.trackers[0]
         t0.set_frame(gt_color, gt_depth, grad_mask, None, edge_threshold, grad_blocks)
         if self.levels:
             given = grad_mask is not None
             if self.pyramid is None:
                 self.pyramid = ImagePyramid(self.W, self.H, self.levels, self.dev, has_depth=t0.gt_depth is not None, has_mask=given)
-                for l in range(1, self.levels + 1):
-                    t = self.trackers[l]
-                    t.gt_color = self.pyramid.color(l)
-                    t.gt_depth = self.pyramid.depth(l) if t0.gt_depth is not None else None
-                    if given:
-                        t.grad_mask = self.pyramid.mask(l).view(-1)
-                    elif edge_threshold is not None:
-                        t.grad_mask = torch.empty(t.gt_color[0].numel(), dtype=torch.uint8, device=self.dev)
-                        t._grad_op = GradMask(t.gt_color.shape[2], t.gt_color.shape[1], self.dev)
+                for l in range(1, self.levels + 1):   # the coarse levels read the pyramid's planes in place
+                    self.trackers[l].frame_views(self.pyramid.color(l), self.pyramid.depth(l) if t0.gt_depth is not None else None,
+                                                 self.pyramid.mask(l) if given else None, own_mask=edge_threshold is not None)
             self.pyramid.build(t0.gt_color, t0.gt_depth, t0.grad_mask if given else None, self.depth_edge_ratio)
             if not given and edge_threshold is not None:
                 for t in self.trackers[1:]:
-                    t._grad_op(t.gt_color, edge_threshold, blocks=grad_blocks, out=t.grad_mask)
+                    t.compute_mask(edge_threshold, grad_blocks)
         if w2c is not None:
             self.trackers[-1].reset(w2c)
             self._at = self.levels
@@ -417,11 +346,7 @@ class PyramidGaussNewtonTracker:
                 t = self.trackers[l]
                 if self._at != l:
                     self.relevel(l, None if prev is None else prev._abort_ptr)
-                while k < n:
-                    _level_iteration(t, t.ctx.capacity == 0)
-                    k += 1
-                    if check_every and k % check_every == 0 and bool(self.converged.item() != 0.0):
-                        break
+                k = run(n, check_every, lambda: _level_iteration(t, t.ctx.capacity == 0), lambda: self.converged)
                 t.iterations += k
                 prev = t
             done.append(k)
@@ -430,9 +355,8 @@ class PyramidGaussNewtonTracker:
         for l, k in zip(range(self.levels, -1, -1), done):
             if k:
                 try:
-                    self.trackers[l].ctx.status()
+                    finish_frame(self.trackers[l].ctx)
                 except _lib.GsajError as e:
-                    self.trackers[l].ctx.capacity = 0
                     errors.append("level %d: %s" % (l, e))
         if errors:
             self.state.copy_(self._snapshot)

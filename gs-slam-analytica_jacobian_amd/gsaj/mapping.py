@@ -36,12 +36,13 @@ pruning stay the caller's calls (they have a designed host read); call refresh()
 import torch
 
 from . import _lib
-from .losses import MONOCULAR, NO_EXPOSURE, IsotropicLoss, LossSeedsBatch
+from ._loop import ViewTargets, finish_window, loss_description, loss_terms, require_device
+from .losses import NO_EXPOSURE, IsotropicLoss, LossSeedsBatch
 from .pose_step import PoseTracker, PoseTrackerBatch
 from .rasterizer import BatchContext
 
 
-class DeviceMapper:
+class DeviceMapper(ViewTargets):
     def __init__(self, model, K, W, H, projection_matrix, tanfovx, tanfovy, bg, device=None, w2cs=None, n_window=None, uids=None,
                  pose_window=3, monocular=False, alpha=0.95, rgb_boundary_threshold=0.01, isotropic_weight=10.0, fused=False,
                  streams=1, split=False, record_bits=32, **pose_kw):
@@ -51,9 +52,7 @@ class DeviceMapper:
         numbers) -- the keyframe with uid 0 anchors the map and is never moved.  Poses and exposures of the first `pose_window`
         window slots are optimised (one mask for both: PoseTrackerBatch steps a view's pose and exposure together); extras never.
         pose_kw: learning rates / betas / eps of PoseTrackerBatch.  streams / split: as BatchContext."""
-        self.dev = torch.device(model.get_xyz.device if device is None else device)
-        if self.dev.type != "cuda":
-            raise _lib.GsajError("DeviceMapper needs a HIP device (there is no CPU path)")
+        self.dev = require_device(model.get_xyz.device if device is None else device, "DeviceMapper")
         self.model, self.K, self.W, self.H = model, int(K), int(W), int(H)
         self.n_window = self.K if n_window is None else int(n_window)
         if not 0 < self.n_window <= self.K or self.K - self.n_window > 2:
@@ -64,12 +63,10 @@ class DeviceMapper:
             raise _lib.GsajError("DeviceMapper: uids must name all %d slots" % self.K)
         self.tanfov = (float(tanfovx), float(tanfovy))
         self.bg = bg.to(self.dev, torch.float32).contiguous()
-        self.flags = MONOCULAR if monocular else 0
-        self.alpha, self.thr, self.iso_weight = float(alpha), float(rgb_boundary_threshold), float(isotropic_weight)
+        (self.flags, self.alpha, self.thr), self.iso_weight = loss_terms(monocular, alpha, rgb_boundary_threshold), float(isotropic_weight)
         self.fused, self.split, self._streams, self._record_bits = bool(fused), bool(split), int(streams), int(record_bits)
         f = dict(dtype=torch.float32, device=self.dev)
-        self.gt_color = torch.zeros((self.K, 3, self.H, self.W), **f)
-        self.gt_depth = None if monocular else torch.zeros((self.K, self.H, self.W), **f)
+        self._alloc_views(monocular)
         eye = torch.eye(4)
         self._pose_args = (projection_matrix, pose_kw)
         self.poses = PoseTrackerBatch([eye] * self.K if w2cs is None else list(w2cs), projection_matrix, self.dev, **pose_kw)
@@ -101,18 +98,7 @@ class DeviceMapper:
     def set_view(self, slot, gt_color, gt_depth=None, w2c=None, exposure=None):
         """Slot `slot` shows another keyframe: its ground truth ([3,H,W], [H,W]) is copied into the mapper's own buffers; w2c
         (and exposure = (a, b)) given: the slot's pose state starts afresh from them, Adam moments zero."""
-        slot = int(slot)
-        if not 0 <= slot < self.K:
-            raise _lib.GsajError("set_view: slot %d is not one of the %d views" % (slot, self.K))
-        if tuple(gt_color.shape) != (3, self.H, self.W):
-            raise _lib.GsajError("set_view: gt_color must be [3,%d,%d], got %s" % (self.H, self.W, tuple(gt_color.shape)))
-        if (gt_depth is None) != (self.gt_depth is None):
-            raise _lib.GsajError("set_view: a depth image is needed for every view of an RGB-D mapper and for none of a monocular one")
-        if gt_depth is not None and gt_depth.numel() != self.H * self.W:
-            raise _lib.GsajError("set_view: gt_depth must be [%d,%d], got %s" % (self.H, self.W, tuple(gt_depth.shape)))
-        self.gt_color[slot].copy_(gt_color)
-        if gt_depth is not None:
-            self.gt_depth[slot].copy_(gt_depth.reshape(self.H, self.W))
+        slot = self._take_view(slot, gt_color, gt_depth)
         if w2c is not None:
             one = PoseTracker(w2c, self._pose_args[0], self.dev, **self._pose_args[1])  # (initialises the row as the batch's were)
             if exposure is not None:
@@ -138,9 +124,8 @@ class DeviceMapper:
         else:
             rendered = False
         if self.fused:  # 2., 3.
-            L = dict(flags=flags, alpha=self.alpha, rgb_boundary_threshold=self.thr, gt_color=self.gt_color, gt_depth=self.gt_depth,
-                     exposure_a=None if initialization else p.exposure[:, 0], exposure_b=None if initialization else p.exposure[:, 1],
-                     exposure_stride=p.state.stride(0), scalars=self.scalars, dexposure=self.dexposure)
+            L = loss_description(self, None if initialization else p.exposure[:, 0], None if initialization else p.exposure[:, 1],
+                                 flags=flags, masked=False, exposure_stride=p.state.stride(0), scalars=self.scalars, dexposure=self.dexposure)
             c.forward_loss(L, self.bg, xyz, opac, views, projs, cps, tx, ty, **geo)
             g = c.backward_loss(L, self.bg, xyz, views, projs, self.praw, cps, tx, ty, split=self.split, **geo)
             dexp = self.dexposure
@@ -175,11 +160,11 @@ class DeviceMapper:
         with torch.cuda.device(self.dev):
             for i in range(int(n)):
                 self._iteration(reset if i == int(n) - 1 else None, initialization)
-            aborted = self.ctx.clear_aborts()
-        if aborted:
-            self._sized = False  # the next call re-sizes with one synchronous forward
-            raise _lib.GsajError("%d asynchronous forward(s) of the window were aborted on the device (binning arena too small for a view's "
-                                 "instances): those views added nothing to the gradient sums and their poses were skipped" % aborted)
+            try:
+                finish_window(self.ctx, "those views added nothing to the gradient sums and their poses were skipped")
+            except _lib.GsajError:
+                self._sized = False  # the next call re-sizes with one synchronous forward
+                raise
         return int(n)
 
     # ---- results (device tensors; reading them is the caller's synchronisation) ------------------------------------------

@@ -9,15 +9,14 @@ import torch
 
 from . import _lib
 from ._gn_state import StateViews, init_state, layout, matrices
+from ._loop import require_device, stream
 
 
 class PoseTracker(StateViews):
     def __init__(self, w2c, projection_matrix, device, lr_rot=0.003, lr_trans=0.001, lr_exposure_a=0.01, lr_exposure_b=0.01,
                  betas=(0.9, 0.999), eps=1e-8, converged_threshold=1e-4):
         self.lib = _lib.load()
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise _lib.GsajError("PoseTracker needs a HIP device (there is no CPU path)")
+        self.dev = require_device(device, "PoseTracker")
         self._layout = layout("pose")
         self.state = torch.zeros(self._layout.floats, dtype=torch.float32, device=self.dev)
         self.projection = torch.as_tensor(projection_matrix, dtype=torch.float32).reshape(4, 4).contiguous().to(self.dev)
@@ -37,10 +36,9 @@ class PoseTracker(StateViews):
         for t in (dL_dtau_sum, dL_dexposure):
             if t is not None and (t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous()):
                 raise _lib.GsajError("gradients must be contiguous float32 device tensors")
-        st = torch.cuda.current_stream(self.dev).cuda_stream
         _lib.check(self.lib.gsaj_pose_adam_step(dL_dtau_sum.data_ptr(), None if dL_dexposure is None else dL_dexposure.data_ptr(),
                                                 self.lr[0], self.lr[1], self.lr[2], self.lr[3], self.betas[0], self.betas[1], self.eps,
-                                                self.thr, self.projection.data_ptr(), self.state.data_ptr(), skip, st),
+                                                self.thr, self.projection.data_ptr(), self.state.data_ptr(), skip, stream(self.dev)),
                    "gsaj_pose_adam_step")
 
 
@@ -52,9 +50,7 @@ class PoseTrackerBatch(StateViews):
     def __init__(self, w2cs, projection_matrix, device, lr_rot=0.003, lr_trans=0.001, lr_exposure_a=0.01, lr_exposure_b=0.01,
                  betas=(0.9, 0.999), eps=1e-8, converged_threshold=1e-4):
         self.lib = _lib.load()
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise _lib.GsajError("PoseTrackerBatch needs a HIP device (there is no CPU path)")
+        self.dev = require_device(device, "PoseTrackerBatch")
         self.singles = [PoseTracker(w, projection_matrix, device, lr_rot, lr_trans, lr_exposure_a, lr_exposure_b, betas, eps,
                                     converged_threshold) for w in w2cs]  # (initialises every state exactly as the single tracker does)
         self.K = len(self.singles)
@@ -75,7 +71,7 @@ class PoseTrackerBatch(StateViews):
                                                       None if act is None else act.data_ptr(), self.lr[0], self.lr[1], self.lr[2],
                                                       self.lr[3], self.betas[0], self.betas[1], self.eps, self.thr,
                                                       self.projection.data_ptr(), self.state.data_ptr(), skip, int(skip_stride),
-                                                      torch.cuda.current_stream(self.dev).cuda_stream), "gsaj_pose_adam_step_batch")
+                                                      stream(self.dev)), "gsaj_pose_adam_step_batch")
 
     def matrices(self):
         """(viewmatrices [K,4,4], projmatrices [K,4,4], campos [K,3]) as contiguous tensors for BatchContext.forward / backward."""

@@ -11,6 +11,7 @@ import os
 import torch
 
 from . import _lib
+from ._loop import stream as _stream
 
 _F32 = torch.float32
 # tests flip this (or set the variable) to push every tile list longer than 128 entries through the chunk + merge path of the
@@ -35,10 +36,6 @@ def _prep(t, device, name):
     if t.dtype != _F32:
         t = t.to(_F32)
     return t.contiguous()
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _require_cuda(t, what):

@@ -24,13 +24,13 @@ iterations and iterate() raises on every rank together.
 import torch
 
 from . import _lib, tile_band_shard as tbs
-from .grad_mask import GradMask
-from .losses import MONOCULAR, TRACKING, LossSeeds
+from ._loop import FrameTarget, finish_frame, loss_description, loss_terms, map_args, require_device, run
+from .losses import TRACKING, LossSeeds
 from .pose_step import PoseTracker
 from .rasterizer import FrameContext
 
 
-class DeviceTracker:
+class DeviceTracker(FrameTarget):
     def __init__(self, P, W, H, M, device, w2c, projection_matrix, tanfovx, tanfovy, bg, means3D, opacities, sh_degree=0, shs=None,
                  colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, monocular=False, alpha=0.95,
                  rgb_boundary_threshold=0.01, record_bits=32, band=None, group=None, use_graph=False, fused=True, **pose_kw):
@@ -39,9 +39,7 @@ class DeviceTracker:
         fused=True (default): the loss is evaluated inside the compositors (gsaj_rasterize_forward_loss / _backward_loss): the
         forward's epilogue sums the loss terms, the reverse compositor derives its pixel seeds itself -- no loss kernel, no seed
         images; the pose follows the unfused loop bit for bit (same per-pixel arithmetic), the loss scalars to rounding."""
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise _lib.GsajError("DeviceTracker needs a HIP device (there is no CPU path)")
+        self.dev = require_device(device, "DeviceTracker")
         self.ctx = FrameContext(P, W, H, M, self.dev, has_scales=scales is not None, record_bits=record_bits)
         if band is not None:
             self.ctx.set_tile_band(*band)
@@ -49,11 +47,9 @@ class DeviceTracker:
         self.pose = PoseTracker(w2c, projection_matrix, self.dev, **pose_kw)
         self.praw = self.pose.projection
         self.tanfov = (float(tanfovx), float(tanfovy))
-        self.flags = TRACKING | (MONOCULAR if monocular else 0)
-        self.alpha, self.thr = float(alpha), float(rgb_boundary_threshold)
+        self.flags, self.alpha, self.thr = loss_terms(monocular, alpha, rgb_boundary_threshold, flags=TRACKING)
         self.bg, self.means, self.opac = bg, means3D, opacities
-        self.kw = dict(sh_degree=sh_degree, shs=shs, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
-                       cov3D_precomp=cov3D_precomp)
+        self.kw = map_args(sh_degree, shs, colors_precomp, scales, rotations, cov3D_precomp)
         self.group, self.use_graph, self.fused = group, bool(use_graph), bool(fused)
         # dL/dtau and the loss kernel's five scalars land side by side in ONE buffer (the backward and gsaj_loss_seeds are handed
         # views of it): nothing to pack before the all-reduce / the pose step -- three launches fewer per iteration
@@ -71,22 +67,16 @@ class DeviceTracker:
     def _render_and_grads(self, sync):
         p, c = self.pose, self.ctx
         view, proj, campos = p.viewmatrix, p.projmatrix, p.campos   # (the views are made once per iteration)
+        tx, ty = self.tanfov
         if self.fused and not sync:
-            L = dict(flags=self.flags, alpha=self.alpha, rgb_boundary_threshold=self.thr, gt_color=self.gt_color, gt_depth=self.gt_depth,
-                     grad_mask=self.grad_mask, exposure_a=p.exposure_a, exposure_b=p.exposure_b, scalars=self.packed[6:11])
-            c.forward_loss(L, self.bg, self.means, self.opac, view, proj, campos, self.tanfov[0], self.tanfov[1], **self.kw)
-            g = c.backward_loss(L, self.bg, self.means, view, proj, self.praw, campos, self.tanfov[0], self.tanfov[1],
-                                pose_only=True, **self.kw)
-            assert g["tau_sum"].data_ptr() == self.packed.data_ptr()
-            if self._sharded():
-                self.packed[tbs.ABORTED].copy_(self._abort_word)
-            return
-        c.forward(self.bg, self.means, self.opac, view, proj, campos, self.tanfov[0], self.tanfov[1], sync=sync,
-                  **self.kw)
-        L = self.loss(self.flags, self.alpha, self.thr, c.color, c.depth, c.opacity, self.gt_color, self.gt_depth, self.grad_mask,
-                      p.exposure_a, p.exposure_b)
-        g = c.backward(self.bg, self.means, view, proj, self.praw, campos, self.tanfov[0], self.tanfov[1],
-                       L["dL_dcolor"], L["dL_ddepth"], pose_only=True, **self.kw)
+            L = loss_description(self, p.exposure_a, p.exposure_b, scalars=self.packed[6:11])
+            c.forward_loss(L, self.bg, self.means, self.opac, view, proj, campos, tx, ty, **self.kw)
+            g = c.backward_loss(L, self.bg, self.means, view, proj, self.praw, campos, tx, ty, pose_only=True, **self.kw)
+        else:
+            c.forward(self.bg, self.means, self.opac, view, proj, campos, tx, ty, sync=sync, **self.kw)
+            L = self.loss(self.flags, self.alpha, self.thr, c.color, c.depth, c.opacity, self.gt_color, self.gt_depth, self.grad_mask,
+                          p.exposure_a, p.exposure_b)
+            g = c.backward(self.bg, self.means, view, proj, self.praw, campos, tx, ty, L["dL_dcolor"], L["dL_ddepth"], pose_only=True, **self.kw)
         assert g["tau_sum"].data_ptr() == self.packed.data_ptr()
         if self._sharded():  # the abort word joins the sum: any rank's abort reaches every rank
             self.packed[tbs.ABORTED].copy_(self._abort_word)
@@ -95,35 +85,8 @@ class DeviceTracker:
         skip = self.packed[tbs.ABORTED].data_ptr() if self._sharded() else self._abort_ptr
         self.pose.step(self.packed[tbs.TAU], self.packed[tbs.EXPOSURE_GRADS], skip=skip)
 
-    def set_frame(self, gt_color, gt_depth=None, grad_mask=None, w2c=None, edge_threshold=None, grad_blocks=False):
-        """New frame: ground truth (device, [3,H,W] / [H,W]; grad_mask [1,H,W] or None) and optionally a new initial pose.
-        Everything is copied into buffers the tracker owns, so a captured graph stays valid from frame to frame.
-        edge_threshold (with grad_mask None): the tracker computes the frame's gradient mask itself (gsaj.grad_mask: the reference's
-        Camera.compute_grad_mask; grad_blocks=True: its "replica" block form) from its own copy of gt_color into its own mask
-        buffer, on the current stream.  A mask, given or computed, is there for every frame of a tracker or for none."""
-        masked = grad_mask is not None or edge_threshold is not None
-        if self.gt_color is None:
-            self.gt_color = gt_color.to(self.dev, torch.float32).contiguous().clone()
-            self.gt_depth = None if gt_depth is None else gt_depth.to(self.dev, torch.float32).contiguous().clone()
-            if grad_mask is not None:
-                self.grad_mask = grad_mask.to(self.dev, torch.uint8).contiguous().view(-1).clone()
-            elif masked:
-                self.grad_mask = torch.empty(self.gt_color[0].numel(), dtype=torch.uint8, device=self.dev)
-        else:
-            if (gt_depth is None) != (self.gt_depth is None) or masked != (self.grad_mask is not None):
-                raise _lib.GsajError("set_frame: depth / mask must be given for every frame of a tracker or for none")
-            self.gt_color.copy_(gt_color)
-            if gt_depth is not None:
-                self.gt_depth.copy_(gt_depth)
-            if grad_mask is not None:
-                self.grad_mask.copy_(grad_mask.to(self.dev, torch.uint8).view(-1))
-        if grad_mask is None and masked:
-            if self._grad_op is None:
-                _, H, W = self.gt_color.shape
-                self._grad_op = GradMask(W, H, self.dev)
-            self._grad_op(self.gt_color, edge_threshold, blocks=grad_blocks, out=self.grad_mask)
-        if w2c is not None:
-            self.pose.reset(w2c)
+    def _start_pose(self, w2c):   # (FrameTarget.set_frame's new start pose)
+        self.pose.reset(w2c)
 
     def _sharded(self):
         import torch.distributed as dist
@@ -149,35 +112,33 @@ class DeviceTracker:
         tbs.allreduce_pose_terms(self.packed, self.group)
         self._step()
 
+    def _one(self):
+        if self.ctx.capacity == 0:
+            self._eager(True)  # the very first iteration sizes the binning arena: synchronous forward
+        elif not self.use_graph:
+            self._eager(False)
+        else:
+            self.ctx._grow_ahead()  # (a replayed graph calls no forward: the arena watch runs here, outside the capture)
+            if self._graphs is None or self._graphs[2] != self.ctx.binning.data_ptr():
+                self._capture()  # (again if the arena was re-allocated: the graph holds its address)
+            self._graphs[0].replay()
+            if self.ctx.auto_grow:
+                self.ctx.watch.post()
+            if self._graphs[1] is not None:
+                tbs.allreduce_pose_terms(self.packed, self.group)
+                self._graphs[1].replay()
+
     def iterate(self, n, check_every=0):
         """Up to n tracking iterations; check_every > 0: stop once the device reports |tau| < converged_threshold, looked at
         every check_every iterations (the reference looks every iteration, slam_frontend.py:176-178).  Returns the number run."""
         if self.gt_color is None:
             raise _lib.GsajError("set_frame() first")
-        done = 0
         with torch.cuda.device(self.dev):
-            while done < n:
-                if self.ctx.capacity == 0:
-                    self._eager(True)  # the very first iteration sizes the binning arena: synchronous forward
-                elif not self.use_graph:
-                    self._eager(False)
-                else:
-                    self.ctx._grow_ahead()  # (a replayed graph calls no forward: the arena watch runs here, outside the capture)
-                    if self._graphs is None or self._graphs[2] != self.ctx.binning.data_ptr():
-                        self._capture()  # (again if the arena was re-allocated: the graph holds its address)
-                    self._graphs[0].replay()
-                    if self.ctx.auto_grow:
-                        self.ctx.watch.post()
-                    if self._graphs[1] is not None:
-                        tbs.allreduce_pose_terms(self.packed, self.group)
-                        self._graphs[1].replay()
-                done += 1
-                if check_every and done % check_every == 0 and bool(self.pose.converged.item() != 0.0):
-                    break
+            done = run(n, check_every, self._one, lambda: self.pose.converged)
         self.iterations += done
         err = None
         try:
-            self.ctx.status()
+            finish_frame(self.ctx)
         except _lib.GsajError as e:
             err = e
         if self._sharded():  # a rank whose own share fitted must raise with the others (they all skipped the same pose steps)
@@ -185,12 +146,9 @@ class DeviceTracker:
             flag = torch.tensor([1.0 if err else 0.0], device=self.dev)
             dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=self.group)
             if err is None and float(flag.item()) > 0.0:
+                self.ctx.capacity = 0  # (as finish_frame leaves it on the ranks that aborted)
                 err = _lib.GsajError("an asynchronous forward of another rank's tile band was aborted on the device (binning arena too small)")
         if err is not None:
-            # an asynchronous frame did not fit the arena sized earlier (the view moved onto more Gaussians): those iterations
-            # rendered nothing and moved nothing (the pose step skips an aborted frame).  The next call re-sizes with one
-            # synchronous iteration; the caller sees the error and decides.
-            self.ctx.capacity = 0
             raise err
         return done
 
