@@ -97,13 +97,10 @@ int gsaj_profile_end(float *stage_ms, int *stage_launches) {
 const char *gsaj_last_error(void) { return g_err; }
 int gsaj_version(void) { return 111; }
 
-size_t gsaj_geom_workspace_bytes(int P) { return geom_carve(nullptr, (size_t)(P > 0 ? P : 0), nullptr) + 256; }
-size_t gsaj_image_workspace_bytes(int W, int H) { return image_carve(nullptr, W, H, nullptr) + 256; }
-size_t gsaj_binning_workspace_bytes(int R) {
-  return bin_carve(nullptr, (size_t)(R > 0 ? R : 0), nullptr) + 256;
-}
-
-static char *align_base(void *p) { return reinterpret_cast<char *>(gsaj_align(reinterpret_cast<size_t>(p))); }
+// (+ 256: the base slack of a workspace carved from its next 256-byte boundary, workspace.h)
+size_t gsaj_geom_workspace_bytes(int P) { GeomWS g; return geom_carve(Carver(nullptr, ALIGN_BASE), (size_t)(P > 0 ? P : 0), &g) + 256; }
+size_t gsaj_image_workspace_bytes(int W, int H) { ImageWS im; return image_carve(Carver(nullptr, ALIGN_BASE), W, H, &im) + 256; }
+size_t gsaj_binning_workspace_bytes(int R) { BinWS b; return bin_carve(Carver(nullptr, ALIGN_BASE), (size_t)(R > 0 ? R : 0), &b) + 256; }
 
 // ---- argument groups of the rasteriser entry points (host only; DESIGN.md "Argument groups") --------------------------------
 // Every extern "C" rasteriser function fills these once from its own parameters -- members in the order of the ABI, so that an
@@ -164,9 +161,9 @@ static int carve(const Arenas &a, int P, int W, int H, int batch_K, Carved *c) {
       return GSAJ_ERR_WORKSPACE_TOO_SMALL;
     }
   }
-  geom_carve(align_base(a.geom), (size_t)P, &c->g);
-  image_carve(align_base(a.image), W, H, &c->im);
-  bin_carve(align_base(a.binning), (size_t)a.instances, &c->b);
+  geom_carve(Carver(a.geom, ALIGN_BASE), (size_t)P, &c->g);
+  image_carve(Carver(a.image, ALIGN_BASE), W, H, &c->im);
+  bin_carve(Carver(a.binning, ALIGN_BASE), (size_t)a.instances, &c->b);
   return GSAJ_OK;
 }
 
@@ -329,7 +326,7 @@ int gsaj_forward_num_rendered(int W, int H, const void *image_ws, void *stream, 
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   ImageWS im;
-  image_carve(align_base(const_cast<void *>(image_ws)), W, H, &im);
+  image_carve(Carver(image_ws, ALIGN_BASE), W, H, &im);
   uint32_t host[4] = {0, 0, 0, 0};
   GSAJ_HIP_CHECK(hipMemcpyAsync(host, im.counters, sizeof(host), hipMemcpyDeviceToHost, (hipStream_t)stream));
   GSAJ_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
@@ -356,7 +353,7 @@ int gsaj_forward_aborted_count(int W, int H, void *image_ws, void *stream, int *
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   ImageWS im;
-  image_carve(align_base(image_ws), W, H, &im);
+  image_carve(Carver(image_ws, ALIGN_BASE), W, H, &im);
   uint32_t host = 0;
   GSAJ_HIP_CHECK(hipMemcpyAsync(&host, im.sticky, sizeof(host), hipMemcpyDeviceToHost, (hipStream_t)stream));
   GSAJ_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
@@ -372,7 +369,7 @@ const uint32_t *gsaj_forward_abort_flag(int W, int H, void *image_ws) {
     return nullptr;
   }
   ImageWS im;
-  image_carve(align_base(image_ws), W, H, &im);
+  image_carve(Carver(image_ws, ALIGN_BASE), W, H, &im);
   return im.counters + 4;
 }
 
@@ -384,7 +381,7 @@ int gsaj_set_tile_band(int W, int H, void *image_ws, int tile_row_begin, int til
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   ImageWS im;
-  image_carve(align_base(image_ws), W, H, &im);
+  image_carve(Carver(image_ws, ALIGN_BASE), W, H, &im);
   // 0 = the whole frame; an empty band [b, b) with b > 0 is kept as such (the rank renders nothing); [0, 0) cannot be
   // told from "whole frame" and is refused
   const bool whole = tile_row_begin == 0 && tile_row_end == gy;
@@ -486,6 +483,7 @@ int gsaj_rasterize_forward_async(int P, int D, int M, const float *bg, int W, in
   return forward_async(sc, v, prefiltered, flags, o, a, nullptr, (hipStream_t)stream);
 }
 
+// (one array at the aligned base, the forward's partial slots [slots][4], not rounded)
 size_t gsaj_fused_loss_workspace_bytes(int W, int H) { return (size_t)gsaj_fwd_loss_slots(W, H) * 4 * sizeof(float) + 256; }
 
 int gsaj_rasterize_forward_loss(int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
@@ -540,9 +538,9 @@ int gsaj_rasterize_forward_batch(int K, int P, int D, int M, const float *bg, in
   return forward_batch(sc, v, prefiltered, flags, o, a, nullptr, (hipStream_t)stream);
 }
 
-static size_t fused_loss_view_bytes(int W, int H) { return (gsaj_fused_loss_workspace_bytes(W, H) + 255) & ~(size_t)255; }
-
-size_t gsaj_fused_loss_batch_workspace_bytes(int K, int W, int H) { return (size_t)(K > 0 ? K : 0) * fused_loss_view_bytes(W, H); }
+size_t gsaj_fused_loss_batch_workspace_bytes(int K, int W, int H) {
+  return (size_t)(K > 0 ? K : 0) * view_stride(gsaj_fused_loss_workspace_bytes(W, H));
+}
 
 int gsaj_rasterize_forward_loss_batch(int K, int P, int D, int M, const float *bg, int W, int H, const float *means3D, const float *shs,
                                       const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier,
@@ -734,9 +732,13 @@ int gsaj_rasterize_backward_loss(int P, int D, int M, int R, const float *bg, in
 }
 
 // ---- Gauss-Newton tracking: per-pixel pose Jacobians and normal equations (pose_jac.hip) ------------------------------------
-size_t gsaj_pose_jac_workspace_bytes(int P, int W, int H) {
-  return gsaj_jac_rows_bytes(P) + gsaj_align((size_t)gsaj_jac_slots(W, H) * GSAJ_GN_PARTIAL_FLOATS * sizeof(float)) + 256;
+struct JacWS { float *rows, *partials; };  // the derivative rows | the explicit form's partial rows (the fused forms: the caller's)
+static size_t jac_carve(Carver c, int P, int W, int H, JacWS *w) {
+  w->rows = reinterpret_cast<float *>(c.take<char>(gsaj_jac_rows_bytes(P)));
+  w->partials = c.take<float>((size_t)gsaj_jac_slots(W, H) * GSAJ_GN_PARTIAL_FLOATS);
+  return c.used();
 }
+size_t gsaj_pose_jac_workspace_bytes(int P, int W, int H) { JacWS w; return jac_carve(Carver(nullptr, ALIGN_BASE), P, W, H, &w) + 256; }
 int gsaj_pose_jac_partial_rows(int W, int H) { return gsaj_jac_slots(W, H); }
 
 // the fused form's loss arguments (fl arrives as the caller gave them), in the order a caller is told about them
@@ -773,14 +775,15 @@ static int pose_jac(const char *who, BwdParams *p, const Scene &sc, const Views 
   Carved c;
   carve(a, sc.P, v.W, v.H, 0, &c);
   bwd_params(p, sc, v, c.g);
-  float *rows = reinterpret_cast<float *>(align_base(jac_ws));
-  rc = launch_splat_jac(*p, c.g, c.im, rows, s);
+  JacWS w;
+  jac_carve(Carver(jac_ws, ALIGN_BASE), sc.P, v.W, v.H, &w);
+  rc = launch_splat_jac(*p, c.g, c.im, w.rows, s);
   if (rc != GSAJ_OK) return rc;
   const bool sums = gn.fl || gn.H_out || gn.g_out;
   if (!gn.g_out) jo.seed_c = jo.seed_d = nullptr;
   if (!gn.H_out) jo.curv_c = jo.curv_d = nullptr;
-  if (!gn.fl) jo.partials = sums ? reinterpret_cast<float *>(reinterpret_cast<char *>(rows) + gsaj_jac_rows_bytes(sc.P)) : nullptr;
-  rc = launch_render_jac(*p, v.bg, c.g, c.b, c.im, rows, jo, gn.fl, gn.joint ? 1 : 0, s);
+  if (!gn.fl) jo.partials = sums ? w.partials : nullptr;
+  rc = launch_render_jac(*p, v.bg, c.g, c.b, c.im, w.rows, jo, gn.fl, gn.joint ? 1 : 0, s);
   if (rc != GSAJ_OK || gn.fl || !sums) return rc;
   return launch_gn_reduce(jo.partials, gsaj_jac_slots(v.W, v.H), c.im, gn.H_out, gn.g_out, s);
 }
@@ -844,11 +847,9 @@ int gsaj_rasterize_pose_jacobian_loss8(int P, int D, int M, int R, const float *
 }
 
 // ---- the same for K views of one map: gridDim.y = K, K consecutive blocks of every workspace (the loss-fused forms only) ----------
-static size_t jac_rows_view_bytes(int P) { return gsaj_jac_rows_bytes(P); }  // (a multiple of 256: view v's rows are v of these on)
-
 size_t gsaj_pose_jac_batch_workspace_bytes(int K, int P, int W, int H) {
   (void)W; (void)H;  // (the batched forms keep no partial rows of their own: the caller owns gn_partials)
-  return (size_t)(K > 0 ? K : 0) * jac_rows_view_bytes(P);
+  return (size_t)(K > 0 ? K : 0) * view_stride(gsaj_jac_rows_bytes(P));  // (view v's rows are v strides on: pose_jac.hip)
 }
 
 static int pose_jac_batch(const char *who, BwdParams *p, const Scene &sc, const Views &v, const Arenas &a, void *jac_ws, JacOut jo,
@@ -938,7 +939,7 @@ int gsaj_debug_export(int P, int R, int W, int H, const void *geom_ws, const voi
   if (dst) GSAJ_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s))
   if (geom_ws) {
     GeomWS g;
-    geom_carve(align_base(const_cast<void *>(geom_ws)), Pz, &g);
+    geom_carve(Carver(geom_ws, ALIGN_BASE), Pz, &g);
     // means2D, conic_opacity, rgb live in the 48-byte splat rows only: strided copies
 #define CP2D(dst, src, width) \
   if (dst) GSAJ_HIP_CHECK(hipMemcpy2DAsync(dst, width, src, sizeof(float4) * REC_F4, width, Pz, hipMemcpyDeviceToDevice, s))
@@ -953,12 +954,12 @@ int gsaj_debug_export(int P, int R, int W, int H, const void *geom_ws, const voi
   }
   if (binning_ws && R > 0) {
     BinWS b;
-    bin_carve(align_base(const_cast<void *>(binning_ws)), (size_t)R, &b);
+    bin_carve(Carver(binning_ws, ALIGN_BASE), (size_t)R, &b);
     CP(point_list, b.point_list, sizeof(uint32_t) * (size_t)R);
   }
   if (image_ws) {
     ImageWS im;
-    image_carve(align_base(const_cast<void *>(image_ws)), W, H, &im);
+    image_carve(Carver(image_ws, ALIGN_BASE), W, H, &im);
     CP(ranges, im.ranges, sizeof(uint2) * tiles);
     CP(final_T, im.final_T, sizeof(float) * N);
     CP(n_contrib, im.n_contrib, sizeof(uint32_t) * N);
@@ -992,9 +993,9 @@ int gsaj_debug_export_taken(int R, int W, int H, const void *binning_ws, const v
   }
   hipStream_t s = (hipStream_t)stream;
   BinWS b;
-  bin_carve(align_base(const_cast<void *>(binning_ws)), (size_t)R, &b);
+  bin_carve(Carver(binning_ws, ALIGN_BASE), (size_t)R, &b);
   ImageWS im;
-  image_carve(align_base(const_cast<void *>(image_ws)), W, H, &im);
+  image_carve(Carver(image_ws, ALIGN_BASE), W, H, &im);
   if (reached) GSAJ_HIP_CHECK(hipMemcpyAsync(reached, b.reached, (size_t)R, hipMemcpyDeviceToDevice, s));
   if (taken) return launch_export_taken(W, H, (W + TILE - 1) / TILE, (H + TILE - 1) / TILE, b, im, taken, s);
   return GSAJ_OK;
@@ -1007,7 +1008,7 @@ int gsaj_debug_export_view_sums(int P, const void *geom_ws, float *sums, void *s
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   GeomWS g;
-  geom_carve(align_base(const_cast<void *>(geom_ws)), (size_t)P, &g);
+  geom_carve(Carver(geom_ws, ALIGN_BASE), (size_t)P, &g);
   GSAJ_HIP_CHECK(hipMemcpyAsync(sums, g.gsum, sizeof(float4) * 3 * (size_t)P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return GSAJ_OK;
 }

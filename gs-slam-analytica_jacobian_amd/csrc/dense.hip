@@ -464,10 +464,16 @@ __global__ __launch_bounds__(256) void k_dense_tau(int N, int M, int deg, const 
 
 extern "C" {
 
+static size_t dense_nblk(int W, int H) { return ((size_t)W * H + 255) / 256; }
+struct DenseWS { float *slab, *Tplane; };  // the workgroup slab [nblk][N][IGRAD_F] | the transmittance plane [N][nblk * 256], unpadded
+static size_t dense_carve(Carver c, size_t N, int W, int H, DenseWS *w) {
+  w->slab = c.pack<float>(dense_nblk(W, H) * N * IGRAD_F);
+  w->Tplane = c.pack<float>(dense_nblk(W, H) * N * 256);
+  return c.used();
+}
 size_t gsaj_dense_workspace_bytes(int N, int W, int H) {
-  const size_t nblk = ((size_t)W * H + 255) / 256;
-  // the workgroup slab [nblk][N][IGRAD_F] and the transmittance plane [N][nblk * 256]
-  return nblk * (size_t)(N > 0 ? N : 1) * (IGRAD_F + 256) * sizeof(float) + 256;
+  DenseWS w;
+  return dense_carve(Carver(nullptr, ALIGN_BASE), (size_t)(N > 0 ? N : 1), W, H, &w) + 256;
 }
 
 int gsaj_dense_backward(int N, int W, int H, const float *means2D, const float *covs2D, const float *colors,
@@ -488,16 +494,16 @@ int gsaj_dense_backward(int N, int W, int H, const float *means2D, const float *
     pm = DensePixelMap{1, intrinsics[0], intrinsics[1], intrinsics[2], intrinsics[3]};
   }
   hipStream_t s = (hipStream_t)stream;
-  const int nblk = (int)(((size_t)W * H + 255) / 256);
-  float *slab = reinterpret_cast<float *>(gsaj_align(reinterpret_cast<size_t>(dense_ws)));
-  float *Tplane = slab + (size_t)nblk * N * IGRAD_F;
+  const int nblk = (int)dense_nblk(W, H);
+  DenseWS w;
+  dense_carve(Carver(dense_ws, ALIGN_BASE), (size_t)N, W, H, &w);
   {
     GsajProfScope ps(ST_DENSE_BWD, s);
     hipLaunchKernelGGL(k_dense_bwd, dim3(nblk), dim3(256), 0, s, N, W, H, means2D, covs2D, colors, depths, opac, seed_color,
-                       seed_depth, slab, Tplane, (flags & GSAJ_DENSE_NAIVE_GUARDS) ? 1 : 0, pm);
+                       seed_depth, w.slab, w.Tplane, (flags & GSAJ_DENSE_NAIVE_GUARDS) ? 1 : 0, pm);
   }
   GsajProfScope ps(ST_DENSE_REDUCE, s);
-  hipLaunchKernelGGL(k_dense_reduce, dim3((N * 10 + 255) / 256), dim3(256), 0, s, N, nblk, slab, grad_mu, grad_Sigma,
+  hipLaunchKernelGGL(k_dense_reduce, dim3((N * 10 + 255) / 256), dim3(256), 0, s, N, nblk, w.slab, grad_mu, grad_Sigma,
                      grad_depth, grad_color);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
@@ -509,14 +515,23 @@ int gsaj_dense_render(int N, int W, int H, const float *means2D, const float *co
     gsaj_set_error("gsaj_dense_render: invalid argument");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  const int nblk = (int)(((size_t)W * H + 255) / 256);
+  const int nblk = (int)dense_nblk(W, H);
   hipLaunchKernelGGL(k_dense_render, dim3(nblk), dim3(256), 0, (hipStream_t)stream, N, W, H, means2D, covs2D, colors,
                      depths, opac, out_color, out_depth);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }
 
-size_t gsaj_dense_project_workspace_bytes(int N) { return sizeof(double) * 13 * (size_t)(N > 0 ? N : 1) + 256; }
+struct ProjectWS { double *mean, *cov, *col, *raw, *dep; };  // the unsorted columns [N][2 | 4 | 3 | 3 | 1], unpadded
+static size_t project_carve(Carver c, size_t n, ProjectWS *w) {
+  w->mean = c.pack<double>(2 * n); w->cov = c.pack<double>(4 * n); w->col = c.pack<double>(3 * n);
+  w->raw = c.pack<double>(3 * n); w->dep = c.pack<double>(n);
+  return c.used();
+}
+size_t gsaj_dense_project_workspace_bytes(int N) {
+  ProjectWS w;
+  return project_carve(Carver(nullptr, ALIGN_BASE), (size_t)(N > 0 ? N : 1), &w) + 256;
+}
 
 int gsaj_dense_project(int N, int sh_coeffs, int sh_degree, int W, int H, const float *means3D, const float *cov3D,
                        const float *shs, const float *viewmatrix, const float *projmatrix, const float *campos, double fx,
@@ -529,15 +544,14 @@ int gsaj_dense_project(int N, int sh_coeffs, int sh_degree, int W, int H, const 
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   hipStream_t s = (hipStream_t)stream;
-  double *w = reinterpret_cast<double *>(gsaj_align(reinterpret_cast<size_t>(project_ws)));
-  const size_t n = (size_t)N;
-  double *u_mean = w, *u_cov = w + 2 * n, *u_col = w + 6 * n, *u_raw = w + 9 * n, *u_dep = w + 12 * n;
+  ProjectWS u;
+  project_carve(Carver(project_ws, ALIGN_BASE), (size_t)N, &u);
   hipLaunchKernelGGL(k_dense_project, dim3((N + 127) / 128), dim3(128), 0, s, N, sh_coeffs, sh_degree, means3D, cov3D, shs,
-                     viewmatrix, projmatrix, campos, fx, fy, W / (2.0 * fx), H / (2.0 * fy), W, H, u_mean, u_cov, u_col, u_raw,
-                     u_dep);
-  hipLaunchKernelGGL(k_dense_rank, dim3((N + 255) / 256), dim3(256), 0, s, N, u_dep, order);
+                     viewmatrix, projmatrix, campos, fx, fy, W / (2.0 * fx), H / (2.0 * fy), W, H, u.mean, u.cov, u.col, u.raw,
+                     u.dep);
+  hipLaunchKernelGGL(k_dense_rank, dim3((N + 255) / 256), dim3(256), 0, s, N, u.dep, order);
   const struct { const double *in; double *out; int width; } cols[5] = {
-      {u_mean, mean2D, 2}, {u_cov, cov2D, 4}, {u_col, color, 3}, {u_raw, color_raw, 3}, {u_dep, depth, 1}};
+      {u.mean, mean2D, 2}, {u.cov, cov2D, 4}, {u.col, color, 3}, {u.raw, color_raw, 3}, {u.dep, depth, 1}};
   for (int k = 0; k < 5; k++)
     if (cols[k].out)
       hipLaunchKernelGGL(k_dense_gather, dim3((N * cols[k].width + 255) / 256), dim3(256), 0, s, N, order, cols[k].in, cols[k].out,

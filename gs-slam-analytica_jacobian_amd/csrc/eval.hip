@@ -34,19 +34,13 @@ struct EvalLayout {  // the workspace: clamped image [C,H,W] | partials [nblk] |
 
 static size_t eval_nblk(size_t total) { return (total + EV_RUN - 1) / EV_RUN; }
 
-static size_t eval_carve(void *ws, int C, int W, int H, EvalLayout *L) {
+static size_t eval_carve(Carver c, int C, int W, int H, EvalLayout *L) {
   const size_t total = (size_t)C * W * H;
-  char *base = (char *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  size_t off = 0;
-  if (L) L->clamped = (float *)(base + off);
-  off += gsaj_align(sizeof(float) * total);
-  if (L) L->partials = (EvalPartial *)(base + off);
-  off += gsaj_align(sizeof(EvalPartial) * eval_nblk(total));
-  if (L) L->ssim_out = (float *)(base + off);
-  off += 256;
-  if (L) L->ssim_ws = base + off;
-  off += gsaj_ssim_workspace_bytes(1, C, W, H);
-  return 256 + off;  // (256: the alignment of base)
+  L->clamped = c.take<float>(total);
+  L->partials = c.take<EvalPartial>(eval_nblk(total));
+  L->ssim_out = c.take<float>(2);
+  L->ssim_ws = c.pack<char>(gsaj_ssim_workspace_bytes(1, C, W, H));  // (last, not rounded)
+  return c.used();
 }
 
 struct EvalPixelParams {
@@ -181,7 +175,8 @@ static bool eval_dims_ok(int C, int W, int H) {
 
 extern "C" size_t gsaj_eval_workspace_bytes(int C, int W, int H) {
   if (!eval_dims_ok(C, W, H)) return 0;
-  return eval_carve(nullptr, C, W, H, nullptr);
+  EvalLayout L;
+  return eval_carve(Carver(nullptr, ALIGN_BASE), C, W, H, &L) + 256;
 }
 
 extern "C" int gsaj_eval_frame(int C, int W, int H, int flags, const float *image, const float *gt, float *out_row,
@@ -197,7 +192,7 @@ extern "C" int gsaj_eval_frame(int C, int W, int H, int flags, const float *imag
   }
   const hipStream_t s = (hipStream_t)stream;
   EvalLayout L;
-  eval_carve(eval_ws, C, W, H, &L);
+  eval_carve(Carver(eval_ws, ALIGN_BASE), C, W, H, &L);
   const size_t total = (size_t)C * W * H, nblk = eval_nblk(total);
   EvalPixelParams p;
   p.image = image; p.gt = gt; p.clamped = L.clamped; p.u8 = image_u8; p.partials = L.partials;

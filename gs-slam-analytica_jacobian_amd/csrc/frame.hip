@@ -192,20 +192,17 @@ struct GradWS {
   void *select;   // gsaj_seed_workspace_bytes(W, H): the radix select's workspace
 };
 
-static size_t gm_carve(void *base, int W, int H, GradWS *w) {
-  char *p = (char *)(((uintptr_t)base + 255) & ~(uintptr_t)255);
-  const size_t N = (size_t)W * H;
-  auto take = [&](size_t bytes) { char *r = p; p += (bytes + 255) & ~(size_t)255; return r; };
-  w->key = (uint32_t *)take(16);
-  w->I = (float *)take((N + 4) * 4);
-  w->select = (void *)take(gsaj_seed_workspace_bytes(W, H));
-  return (size_t)(p - (char *)base) + 256;
+static size_t gm_carve(Carver c, int W, int H, GradWS *w) {
+  w->key = c.take<uint32_t>(4);
+  w->I = c.take<float>((size_t)W * H + 4);
+  w->select = c.take<char>(gsaj_seed_workspace_bytes(W, H));
+  return c.used();
 }
 
 extern "C" size_t gsaj_grad_mask_workspace_bytes(int W, int H) {
   if (gm_bad_image(W, H)) return 0;
   GradWS w;
-  return gm_carve(nullptr, W, H, &w);
+  return gm_carve(Carver(nullptr, ALIGN_BASE), W, H, &w) + 256;
 }
 
 static void gm_launch_intensity(int W, int H, const float *image, float *out, hipStream_t s) {
@@ -247,7 +244,7 @@ extern "C" int gsaj_grad_mask(int W, int H, const float *image, float edge_thres
     return GSAJ_OK;
   }
   GradWS w;
-  gm_carve(ws, W, H, &w);
+  gm_carve(Carver(ws, ALIGN_BASE), W, H, &w);
   const int n = W * H;
   gm_launch_intensity(W, H, image, w.I, s);
   const int rc = launch_select_rank_f32(W, H, w.I, (uint32_t)((n - 1) / 2), w.key, w.select, s);  // torch.median: the LOWER median

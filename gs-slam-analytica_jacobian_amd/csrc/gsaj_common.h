@@ -28,47 +28,37 @@
 // as one contiguous run.
 
 // ---- workspace layouts ------------------------------------------------------------------
-static inline __host__ __device__ size_t gsaj_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// GeomWS, ImageWS and BinWS state their arrays ONCE, as a list of X(field, type, count): the struct's members, the carve (host) and
+// the per-view shift of a batched launch (device; geom_view / image_view) are all generated from the list, in its order.
+#include "workspace.h"
+#define WS_MEMBER(field, type, count) type *field;
+#define WS_TAKE(field, type, count) w->field = c.take<type>(count);
+#define WS_SHIFT(field, type, count) w.field = gsaj_shift(w.field, off);
 
-struct GeomWS {  // per-Gaussian state (reference: GeometryState, rasterizer_impl.h:29-44)
-  float *depths;          // [P] view-space depth: the tile sort gathers it by id for its (depth, id) keys
-  float *cov3D;           // [P*6] (a batched launch writes view 0's only: Sigma = R S^2 R^T does not depend on the view)
-  uint8_t *clamped;       // [P*3]
-  uint32_t *tiles_touched;  // [P]
-  uint32_t *point_offsets;  // [P] inclusive scan of tiles_touched INSIDE the Gaussian's block of PRE_BLOCK; + block_sums[block] = global
-  int *internal_radii;      // [P]
-  uint32_t *block_sums;     // [nblk] per-workgroup totals, then (frame scan) their exclusive offsets
-  float *tau_partials;      // [nblk*8] per-workgroup dL/dtau partial sums
-  float4 *splat;            // [P*3] the per-Gaussian row both compositors gather through the sorted id list (above)
-  float4 *splat16;          // [P*2] fp16-storage form of the row (GSAJ_FWD_RECORDS_FP16; written by k_pack_splat16):
-                            //   (mean2D.x, mean2D.y, depth, first emission slot) (half2 a b, half2 c o, half2 r g, half2 b 0)
-  uint2 *scat;              // [P] what the instance scatter reads: the tile rectangle (x0 | x1 << 16, y0 | y1 << 16); x1 == x0: no tile
-  float4 *gsum;             // [P*3] batched backward: the Gaussian's 10 reverse-compositor sums (its instance rows added in
-                            //   emission order by k_gather_sums), read by k_chain_window
-};
+// per-Gaussian state (reference: GeometryState, rasterizer_impl.h:29-44); nblk: blocks of PRE_BLOCK Gaussians, at least one
+#define GEOM_WS_FIELDS(X)                                                                                                          \
+  X(depths, float, P)             /* view-space depth: the tile sort gathers it by id for its (depth, id) keys */                  \
+  X(cov3D, float, P * 6)          /* (a batched launch writes view 0's only: Sigma = R S^2 R^T does not depend on the view) */     \
+  X(clamped, uint8_t, P * 3)                                                                                                       \
+  X(tiles_touched, uint32_t, P)                                                                                                    \
+  X(point_offsets, uint32_t, P)   /* inclusive scan of tiles_touched INSIDE the Gaussian's block; + block_sums[block] = global */  \
+  X(internal_radii, int, P)                                                                                                        \
+  X(block_sums, uint32_t, nblk)   /* per-workgroup totals, then (frame scan) their exclusive offsets */                            \
+  X(tau_partials, float, ((P + 31) / 32 + 1) * 8) /* per-workgroup dL/dtau partial sums (a slot per 64 Gaussians, 32 batched) */   \
+  X(splat, float4, P * 3)         /* the per-Gaussian row both compositors gather through the sorted id list (above) */            \
+  X(splat16, float4, P * 2)       /* fp16-storage form of the row (GSAJ_FWD_RECORDS_FP16; written by k_pack_splat16): (mean2D.x, */ \
+                                  /*   mean2D.y, depth, first emission slot) (half2 a b, half2 c o, half2 r g, half2 b 0) */        \
+  X(scat, uint2, P)               /* what the instance scatter reads: the tile rectangle (x0 | x1 << 16, y0 | y1 << 16); */         \
+                                  /*   x1 == x0: no tile */                                                                         \
+  X(gsum, float4, P * 3)          /* batched backward: the Gaussian's 10 reverse-compositor sums (its instance rows added in */     \
+                                  /*   emission order by k_gather_sums), read by k_chain_window */
+struct GeomWS { GEOM_WS_FIELDS(WS_MEMBER) };
 
-static inline __host__ __device__ size_t geom_carve(char *base, size_t P, GeomWS *g) {
-  size_t off = 0;
+static inline size_t geom_carve(Carver c, size_t P, GeomWS *w) {
   size_t nblk = (P + PRE_BLOCK - 1) / PRE_BLOCK;
   if (nblk == 0) nblk = 1;
-#define CARVE(field, type, count)                                \
-  do {                                                           \
-    if (g) g->field = reinterpret_cast<type *>(base + off);      \
-    off += gsaj_align(sizeof(type) * (size_t)(count));           \
-  } while (0)
-  CARVE(depths, float, P);
-  CARVE(cov3D, float, P * 6);
-  CARVE(clamped, uint8_t, P * 3);
-  CARVE(tiles_touched, uint32_t, P);
-  CARVE(point_offsets, uint32_t, P);
-  CARVE(internal_radii, int, P);
-  CARVE(block_sums, uint32_t, nblk);
-  CARVE(tau_partials, float, ((P + 31) / 32 + 1) * 8);  // (one slot per 64 Gaussians single view, per 32 batched)
-  CARVE(splat, float4, P * 3);
-  CARVE(splat16, float4, P * 2);
-  CARVE(scat, uint2, P);
-  CARVE(gsum, float4, P * 3);
-  return off;
+  GEOM_WS_FIELDS(WS_TAKE)
+  return c.used();
 }
 
 #define TILE_REP 1        // replicas of each tile's instance counter (1: contention is removed by LDS aggregation)
@@ -82,51 +72,60 @@ static inline __host__ __device__ size_t geom_carve(char *base, size_t P, GeomWS
 #define ERR_CAPACITY 4u   // async forward: R exceeds the binning arena the caller provided
 #define ERR_TILE_LIST 8u  // (no longer raised: tile lists of any length are sorted on the device)
 
-struct ImageWS {  // reference: ImageState, rasterizer_impl.h:46-53
-  float *final_T;         // [H*W]
-  uint32_t *n_contrib;    // [H*W]
-  uint2 *ranges;          // [tiles]
-  uint32_t *counters;     // [N_COUNTERS]            -+
-  uint32_t *tile_count;   // [tiles*TILE_REP]         | zeroed by ONE memset per forward
-  uint32_t *tile_cursor;  // [tiles*TILE_REP]        -+
-  uint32_t *tile_offset;  // [tiles*TILE_REP + 1] exclusive scan of tile_count (tile-major)
-  uint32_t *sticky;       // [16] never zeroed by a forward: [0] number of aborted async forwards, [1] tile band, [2] its complement (gsaj_tile_band)
-  uint32_t *tile_order;   // [tiles] tile indices, longest list first (frame_scan): the order both compositors take their tiles in
-  size_t zero_bytes;      // bytes from counters to the end of tile_cursor
+// reference: ImageState, rasterizer_impl.h:46-53.  Three lists: the arrays from counters to tile_cursor are zeroed by ONE memset
+// per forward (ImageWS.zero_bytes)
+#define IMAGE_WS_HEAD(X)                                                                                                           \
+  X(final_T, float, N)                                                                                                             \
+  X(n_contrib, uint32_t, N)                                                                                                        \
+  X(ranges, uint2, tiles)
+#define IMAGE_WS_ZEROED(X)                                                                                                         \
+  X(counters, uint32_t, N_COUNTERS)                                                                                                \
+  X(tile_count, uint32_t, tiles * TILE_REP)                                                                                        \
+  X(tile_cursor, uint32_t, tiles * TILE_REP)
+#define IMAGE_WS_TAIL(X)                                                                                                           \
+  X(tile_offset, uint32_t, tiles * TILE_REP + 1) /* exclusive scan of tile_count (tile-major) */                                   \
+  X(sticky, uint32_t, 16)         /* never zeroed by a forward: [0] number of aborted async forwards, [1] tile band, [2] its */    \
+                                  /*   complement (gsaj_tile_band) */                                                              \
+  X(tile_order, uint32_t, tiles)  /* tile indices, longest list first (frame_scan): the order both compositors take their tiles in */
+#define IMAGE_WS_FIELDS(X) IMAGE_WS_HEAD(X) IMAGE_WS_ZEROED(X) IMAGE_WS_TAIL(X)
+struct ImageWS {
+  IMAGE_WS_FIELDS(WS_MEMBER)
+  size_t zero_bytes;  // bytes from counters to the end of tile_cursor
 };
 
-static inline __host__ __device__ size_t image_carve(char *base, int W, int H, ImageWS *s) {
-  size_t off = 0;
-  size_t N = (size_t)W * H;
-  size_t tiles = (size_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
-  ImageWS *g = s;
-  CARVE(final_T, float, N);
-  CARVE(n_contrib, uint32_t, N);
-  CARVE(ranges, uint2, tiles);
-  const size_t z0 = off;
-  CARVE(counters, uint32_t, N_COUNTERS);
-  CARVE(tile_count, uint32_t, tiles * TILE_REP);
-  CARVE(tile_cursor, uint32_t, tiles * TILE_REP);
-  if (g) g->zero_bytes = off - z0;
-  CARVE(tile_offset, uint32_t, tiles * TILE_REP + 1);
-  CARVE(sticky, uint32_t, 16);
-  CARVE(tile_order, uint32_t, tiles);
-  return off;
+static inline size_t image_carve(Carver c, int W, int H, ImageWS *w) {
+  const size_t N = (size_t)W * H;
+  const size_t tiles = (size_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
+  IMAGE_WS_HEAD(WS_TAKE)
+  const size_t z0 = c.used();
+  IMAGE_WS_ZEROED(WS_TAKE)
+  w->zero_bytes = c.used() - z0;
+  IMAGE_WS_TAIL(WS_TAKE)
+  return c.used();
 }
 
-struct BinWS {  // reference: BinningState, rasterizer_impl.h:55-66
-  uint64_t *keys_unsorted;  // [R] the two key buffers of tile lists longer than the LDS sort capacity (chunk sort -> merge passes);
-  uint64_t *keys;           // [R]   keys are (depth bits << 32 | id).  Idle once the lists are sorted: the reverse compositor keeps
-                            //   each tile's compacted list of LIVE entries in the tile's segment of `keys` (render_bwd.hip)
-  uint32_t *point_list;     // [R] Gaussian ids grouped by tile: as scattered (k_scatter_instances), then sorted in place (k_tile_sort)
-  float4 *inst_grad;        // [R*3] per-instance partial gradients (backward), indexed by emission slot
-  uint8_t *reached;         // [R] by emission slot: 1 = the reverse compositor wrote that row, 0 = no pixel of the tile got that far
-                            //   (zeroed by the tile sort, set by the reverse compositor)
-  uint32_t *taken;          // [R] by list position: byte q = 1 if some pixel of quadrant q of the position's tile composited the
-                            //   entry (written by the forward compositor, one byte per quadrant wave; a wave writes the bytes of
-                            //   the 64-entry chunks it processed and no others, so bytes at or beyond a quadrant's furthest last
-                            //   contributor may be stale and are ignored by every reader)
-};
+// reference: BinningState, rasterizer_impl.h:55-66; R: at least one
+#define BIN_WS_FIELDS(X)                                                                                                           \
+  X(keys_unsorted, uint64_t, R)   /* the two key buffers of tile lists longer than the LDS sort capacity (chunk sort -> merge */   \
+  X(keys, uint64_t, R)            /*   passes); keys are (depth bits << 32 | id).  Idle once the lists are sorted: the reverse */  \
+                                  /*   compositor keeps each tile's compacted list of LIVE entries in the tile's segment of */     \
+                                  /*   `keys` (render_bwd.hip) */                                                                  \
+  X(point_list, uint32_t, R)      /* Gaussian ids grouped by tile: as scattered (k_scatter_instances), then sorted in place */     \
+                                  /*   (k_tile_sort) */                                                                            \
+  X(inst_grad, float4, R * REC_F4) /* per-instance partial gradients (backward), indexed by emission slot */                       \
+  X(reached, uint8_t, R)          /* by emission slot: 1 = the reverse compositor wrote that row, 0 = no pixel of the tile got */  \
+                                  /*   that far (zeroed by the tile sort, set by the reverse compositor) */                        \
+  X(taken, uint32_t, R)           /* by list position: byte q = 1 if some pixel of quadrant q of the position's tile composited */ \
+                                  /*   the entry (written by the forward compositor, one byte per quadrant wave; a wave writes */  \
+                                  /*   the bytes of the 64-entry chunks it processed and no others, so bytes at or beyond a */     \
+                                  /*   quadrant's furthest last contributor may be stale and are ignored by every reader) */
+struct BinWS { BIN_WS_FIELDS(WS_MEMBER) };
+
+static inline size_t bin_carve(Carver c, size_t R, BinWS *w) {
+  if (R == 0) R = 1;
+  BIN_WS_FIELDS(WS_TAKE)
+  return c.used();
+}
 
 // ---- batched multi-view launches (gsaj_rasterize_*_batch): K views of ONE Gaussian map -------------------------------
 // Every per-view workspace is one of K consecutive, identically carved blocks; kernels run with gridDim.y = K and shift
@@ -144,35 +143,15 @@ __device__ __forceinline__ T *gsaj_shift(T *p, size_t bytes) {
   typedef typename std::conditional<std::is_const<T>::value, const char, char>::type byte_t;
   return reinterpret_cast<T *>(reinterpret_cast<byte_t *>(p) + bytes);
 }
-__device__ __forceinline__ GeomWS geom_view(GeomWS g, size_t off) {
-  g.depths = gsaj_shift(g.depths, off); g.cov3D = gsaj_shift(g.cov3D, off); g.clamped = gsaj_shift(g.clamped, off);
-  g.tiles_touched = gsaj_shift(g.tiles_touched, off); g.point_offsets = gsaj_shift(g.point_offsets, off);
-  g.internal_radii = gsaj_shift(g.internal_radii, off); g.block_sums = gsaj_shift(g.block_sums, off);
-  g.tau_partials = gsaj_shift(g.tau_partials, off); g.splat = gsaj_shift(g.splat, off); g.gsum = gsaj_shift(g.gsum, off);
-  g.splat16 = gsaj_shift(g.splat16, off); g.scat = gsaj_shift(g.scat, off);
-  return g;
+__device__ __forceinline__ GeomWS geom_view(GeomWS w, size_t off) {
+  GEOM_WS_FIELDS(WS_SHIFT)
+  return w;
 }
-__device__ __forceinline__ ImageWS image_view(ImageWS m, size_t off) {
-  m.final_T = gsaj_shift(m.final_T, off); m.n_contrib = gsaj_shift(m.n_contrib, off); m.ranges = gsaj_shift(m.ranges, off);
-  m.counters = gsaj_shift(m.counters, off); m.tile_count = gsaj_shift(m.tile_count, off);
-  m.tile_cursor = gsaj_shift(m.tile_cursor, off); m.tile_offset = gsaj_shift(m.tile_offset, off);
-  m.sticky = gsaj_shift(m.sticky, off); m.tile_order = gsaj_shift(m.tile_order, off);
-  return m;
+__device__ __forceinline__ ImageWS image_view(ImageWS w, size_t off) {
+  IMAGE_WS_FIELDS(WS_SHIFT)
+  return w;
 }
 #endif
-
-static inline size_t bin_carve(char *base, size_t R, BinWS *g) {
-  size_t off = 0;
-  size_t Rn = R ? R : 1;
-  CARVE(keys_unsorted, uint64_t, Rn);
-  CARVE(keys, uint64_t, Rn);
-  CARVE(point_list, uint32_t, Rn);
-  CARVE(inst_grad, float4, Rn * REC_F4);
-  CARVE(reached, uint8_t, Rn);
-  CARVE(taken, uint32_t, Rn);
-  return off;
-}
-#undef CARVE
 
 // the three workspaces of a call as carved (api.hip: carve()); batched calls: view 0's blocks and the strides to the next view's
 struct Carved { GeomWS g; BinWS b; ImageWS im; ViewStrides vs; };

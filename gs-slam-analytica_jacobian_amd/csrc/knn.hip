@@ -32,21 +32,19 @@ struct KnnWS {
   uint32_t *hist;      // [RS_BUCKETS][ntile] digit counts of the radix pass under way, bucket-major; exclusive offsets after the scan
 };
 
-static size_t knn_carve(void *base, int P, KnnWS *w) {
-  char *p = (char *)(((uintptr_t)base + 255) & ~(uintptr_t)255);
+static size_t knn_carve(Carver c, int P, KnnWS *w) {
   const size_t Pz = (size_t)P, nblk = (Pz + 255) / 256, nbox = (Pz + KNN_BOX - 1) / KNN_BOX;
-  auto take = [&](size_t bytes) { char *r = p; p += (bytes + 255) & ~(size_t)255; return r; };
-  w->bbox = (float *)take(6 * sizeof(float));
-  w->ticket = (uint32_t *)take(sizeof(uint32_t));
-  w->bpart = (float *)take(nblk * 6 * sizeof(float));
-  w->codes = (uint32_t *)take(Pz * 4);
-  w->codes_sorted = (uint32_t *)take(Pz * 4);
-  w->idx = (uint32_t *)take(Pz * 4);
-  w->idx_sorted = (uint32_t *)take(Pz * 4);
-  w->sorted = (float4 *)take(Pz * sizeof(float4));
-  w->boxes = (float *)take(nbox * 6 * sizeof(float));
-  w->hist = (uint32_t *)take((size_t)RS_BUCKETS * ((Pz + RS_TILE - 1) / RS_TILE) * 4);
-  return (size_t)(p - (char *)base) + 256;
+  w->bbox = c.take<float>(6);
+  w->ticket = c.take<uint32_t>(1);
+  w->bpart = c.take<float>(nblk * 6);
+  w->codes = c.take<uint32_t>(Pz);
+  w->codes_sorted = c.take<uint32_t>(Pz);
+  w->idx = c.take<uint32_t>(Pz);
+  w->idx_sorted = c.take<uint32_t>(Pz);
+  w->sorted = c.take<float4>(Pz);
+  w->boxes = c.take<float>(nbox * 6);
+  w->hist = c.take<uint32_t>((size_t)RS_BUCKETS * ((Pz + RS_TILE - 1) / RS_TILE));
+  return c.used();
 }
 
 // A box {min xyz, max xyz} of a workgroup through the ordered fold of wave_reduce.h: three minima and three maxima put into the six
@@ -283,7 +281,7 @@ __global__ __launch_bounds__(64) void k_knn_mean_dist(int P, KnnWS w, float *__r
 extern "C" size_t gsaj_dist2_workspace_bytes(int P) {
   if (P <= 0) return 512;
   KnnWS w;
-  return knn_carve(nullptr, P, &w);
+  return knn_carve(Carver(nullptr, ALIGN_BASE), P, &w) + 256;
 }
 
 extern "C" int gsaj_dist2(int P, const float *points, float *mean_dists, void *knn_ws, void *stream) {
@@ -294,7 +292,7 @@ extern "C" int gsaj_dist2(int P, const float *points, float *mean_dists, void *k
   if (P == 0) return GSAJ_OK;
   hipStream_t s = (hipStream_t)stream;
   KnnWS w;
-  knn_carve(knn_ws, P, &w);
+  knn_carve(Carver(knn_ws, ALIGN_BASE), P, &w);
   GSAJ_HIP_CHECK(hipMemsetAsync(w.ticket, 0, sizeof(uint32_t), s));
   const unsigned nblk = (unsigned)((P + 255) / 256), nbox = (unsigned)((P + KNN_BOX - 1) / KNN_BOX);
   hipLaunchKernelGGL(k_knn_bbox, dim3(nblk), dim3(256), 0, s, P, points, w);
@@ -316,7 +314,7 @@ extern "C" int gsaj_debug_dist2_order(int P, void *knn_ws, uint32_t *codes_sorte
   }
   hipStream_t s = (hipStream_t)stream;
   KnnWS w;
-  knn_carve(knn_ws, P, &w);
+  knn_carve(Carver(knn_ws, ALIGN_BASE), P, &w);
   // (where knn_radix_sort leaves the result: passes alternate between the two pairs of arrays)
   int passes = 0;
   for (int shift = 0; shift < 30; shift += RS_BITS) passes++;

@@ -168,9 +168,29 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_count_valid(size_t HW, const flo
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
 }
 
-extern "C" size_t gsaj_loss_workspace_bytes(int W, int H) {
-  const size_t nblk = ((size_t)W * H + LOSS_BLOCK * LOSS_PPT - 1) / (LOSS_BLOCK * LOSS_PPT);
-  return 256 + nblk * 4 * sizeof(float) + 256;
+static size_t loss_nblk(int W, int H) { return ((size_t)W * H + LOSS_BLOCK * LOSS_PPT - 1) / (LOSS_BLOCK * LOSS_PPT); }
+
+struct LossWS { uint32_t *ticket, *n_valid; float *partials; };  // a 256-byte head (ticket at byte 0, n_valid at 64) | partials, not rounded
+static size_t loss_carve(Carver c, int W, int H, LossWS *w) {
+  w->ticket = c.pack<uint32_t>(16);   // the caller zeroes the workspace once, when it allocates it
+  w->n_valid = c.pack<uint32_t>(48);
+  w->partials = c.pack<float>(loss_nblk(W, H) * 4);
+  return c.used();
+}
+extern "C" size_t gsaj_loss_workspace_bytes(int W, int H) { LossWS w; return loss_carve(Carver(nullptr, ALIGN_BASE), W, H, &w) + 256; }
+
+// what gsaj_loss_seeds and gsaj_loss_seeds_batch share: every argument of the loss, view 0's workspace, the stride to the next view's
+static LossParams loss_params(int W, int H, int flags, float alpha, float rgb_boundary_threshold, const float *color,
+                              const float *depth, const float *opacity, const float *gt_color, const float *gt_depth,
+                              const uint8_t *grad_mask, const float *exposure_a, const float *exposure_b, float *dL_dcolor,
+                              float *dL_ddepth, float *dL_dopacity, float *out_scalars, const LossWS &w, size_t ws_stride) {
+  LossParams p;
+  p.W = W; p.H = H; p.flags = flags; p.alpha = alpha; p.rgb_thr = rgb_boundary_threshold;
+  p.color = color; p.depth = depth; p.opacity = opacity; p.gt_color = gt_color; p.gt_depth = gt_depth;
+  p.grad_mask = grad_mask; p.exp_a = exposure_a; p.exp_b = exposure_b;
+  p.dL_dcolor = dL_dcolor; p.dL_ddepth = dL_ddepth; p.dL_dopacity = dL_dopacity;
+  p.ticket = w.ticket; p.partials = w.partials; p.n_valid = w.n_valid; p.out = out_scalars; p.ws_stride = ws_stride;
+  return p;
 }
 
 extern "C" int gsaj_loss_seeds(int W, int H, int flags, float alpha, float rgb_boundary_threshold, const float *color,
@@ -185,24 +205,15 @@ extern "C" int gsaj_loss_seeds(int W, int H, int flags, float alpha, float rgb_b
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   if (flags & GSAJ_LOSS_COMPUTE_LOSS) flags |= GSAJ_LOSS_NO_EXPOSURE;
-  LossParams p;
-  p.W = W; p.H = H; p.flags = flags; p.alpha = alpha; p.rgb_thr = rgb_boundary_threshold;
-  p.color = color; p.depth = depth; p.opacity = opacity; p.gt_color = gt_color; p.gt_depth = gt_depth;
-  p.grad_mask = grad_mask; p.exp_a = exposure_a; p.exp_b = exposure_b;
-  p.dL_dcolor = dL_dcolor; p.dL_ddepth = dL_ddepth; p.dL_dopacity = dL_dopacity;
-  char *base = (char *)(((uintptr_t)loss_ws + 255) & ~(uintptr_t)255);
-  p.ticket = (uint32_t *)base;          // the caller zeroes the workspace once, when it allocates it
-  p.partials = (float *)(base + 256);
-  p.out = out_scalars;
-  p.n_valid = (uint32_t *)(base + 64);
-  p.ws_stride = 0;
+  LossWS w;
+  loss_carve(Carver(loss_ws, ALIGN_BASE), W, H, &w);
+  const LossParams p = loss_params(W, H, flags, alpha, rgb_boundary_threshold, color, depth, opacity, gt_color, gt_depth, grad_mask,
+                                   exposure_a, exposure_b, dL_dcolor, dL_ddepth, dL_dopacity, out_scalars, w, 0);
   if ((flags & GSAJ_LOSS_COMPUTE_LOSS) && !mono) {
-    GSAJ_HIP_CHECK(hipMemsetAsync(base + 64, 0, sizeof(uint32_t), (hipStream_t)stream));
-    hipLaunchKernelGGL(k_count_valid, dim3(64), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, (size_t)W * H, gt_depth, grad_mask,
-                       (uint32_t *)(base + 64));
+    GSAJ_HIP_CHECK(hipMemsetAsync(w.n_valid, 0, sizeof(uint32_t), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_count_valid, dim3(64), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, (size_t)W * H, gt_depth, grad_mask, w.n_valid);
   }
-  const unsigned nblk = (unsigned)(((size_t)W * H + LOSS_BLOCK * LOSS_PPT - 1) / (LOSS_BLOCK * LOSS_PPT));
-  hipLaunchKernelGGL(k_loss_seeds, dim3(nblk), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(k_loss_seeds, dim3((unsigned)loss_nblk(W, H)), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, p);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }
@@ -219,19 +230,12 @@ extern "C" int gsaj_loss_seeds_batch(int K, int W, int H, int flags, float alpha
                    "GSAJ_LOSS_COMPUTE_LOSS has no batched form)", K, W, H, flags);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  LossParams p;
-  p.W = W; p.H = H; p.flags = flags; p.alpha = alpha; p.rgb_thr = rgb_boundary_threshold;
-  p.color = color; p.depth = depth; p.opacity = opacity; p.gt_color = gt_color; p.gt_depth = gt_depth;
-  p.grad_mask = grad_mask; p.exp_a = exposure_a; p.exp_b = exposure_b;
-  p.dL_dcolor = dL_dcolor; p.dL_ddepth = dL_ddepth; p.dL_dopacity = dL_dopacity;
-  char *base = (char *)loss_ws;
-  p.ticket = (uint32_t *)base;
-  p.partials = (float *)(base + 256);
-  p.out = out_scalars;
-  p.n_valid = (uint32_t *)(base + 64);
-  p.ws_stride = (gsaj_loss_workspace_bytes(W, H) + 255) & ~(size_t)255;
-  const unsigned nblk = (unsigned)(((size_t)W * H + LOSS_BLOCK * LOSS_PPT - 1) / (LOSS_BLOCK * LOSS_PPT));
-  hipLaunchKernelGGL(k_loss_seeds, dim3(nblk, (unsigned)K), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, p);
+  LossWS w;
+  loss_carve(Carver(loss_ws, BASE_AS_GIVEN), W, H, &w);
+  const LossParams p = loss_params(W, H, flags, alpha, rgb_boundary_threshold, color, depth, opacity, gt_color, gt_depth, grad_mask,
+                                   exposure_a, exposure_b, dL_dcolor, dL_ddepth, dL_dopacity, out_scalars, w,
+                                   view_stride(gsaj_loss_workspace_bytes(W, H)));
+  hipLaunchKernelGGL(k_loss_seeds, dim3((unsigned)loss_nblk(W, H), (unsigned)K), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, p);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }
@@ -274,9 +278,14 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_isotropic(int P, int C, float we
   lb_reset(ticket);
 }
 
-extern "C" size_t gsaj_isotropic_workspace_bytes(int P) {
-  return 512 + sizeof(double) * (size_t)((P + LOSS_BLOCK - 1) / LOSS_BLOCK + 1);
+static int iso_nblk(int P) { return (P + LOSS_BLOCK - 1) / LOSS_BLOCK; }
+struct IsoWS { uint32_t *ticket; double *partials; };  // ticket [1] (zeroed once by the caller) | partials [nblk + 1], not rounded
+static size_t iso_carve(Carver c, int P, IsoWS *w) {
+  w->ticket = c.take<uint32_t>(1);
+  w->partials = c.pack<double>((size_t)(iso_nblk(P) + 1));
+  return c.used();
 }
+extern "C" size_t gsaj_isotropic_workspace_bytes(int P) { IsoWS w; return iso_carve(Carver(nullptr, ALIGN_BASE), P, &w) + 256; }
 
 extern "C" int gsaj_isotropic_loss(int P, int C, float weight, const float *scales, float *dL_dscales, int accumulate,
                                    float *out_loss, void *iso_ws, void *stream) {
@@ -284,9 +293,10 @@ extern "C" int gsaj_isotropic_loss(int P, int C, float weight, const float *scal
     gsaj_set_error("gsaj_isotropic_loss: invalid argument (P=%d C=%d)", P, C);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  char *base = (char *)(((uintptr_t)iso_ws + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_isotropic, dim3((P + LOSS_BLOCK - 1) / LOSS_BLOCK), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, P, C, weight,
-                     scales, dL_dscales, accumulate, (double *)(base + 256), (uint32_t *)base, out_loss);
+  IsoWS w;
+  iso_carve(Carver(iso_ws, ALIGN_BASE), P, &w);
+  hipLaunchKernelGGL(k_isotropic, dim3(iso_nblk(P)), dim3(LOSS_BLOCK), 0, (hipStream_t)stream, P, C, weight, scales, dL_dscales,
+                     accumulate, w.partials, w.ticket, out_loss);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }

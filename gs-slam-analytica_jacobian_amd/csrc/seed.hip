@@ -52,22 +52,21 @@ struct SeedWS {
   size_t zero_bytes;
 };
 
-static size_t seed_carve(void *base, int W, int H, SeedWS *w) {
-  char *p = (char *)(((uintptr_t)base + 255) & ~(uintptr_t)255);
+static size_t seed_carve(Carver c, int W, int H, SeedWS *w) {
   const size_t N = (size_t)W * H, ntile = (N + SD_TILE - 1) / SD_TILE, ctile = (N + SD_CTILE - 1) / SD_CTILE;
-  auto take = [&](size_t bytes) { char *r = p; p += (bytes + 255) & ~(size_t)255; return r; };
-  w->res = (uint32_t *)take(16 * 4);
-  w->hist = (uint32_t *)take(4 * 256 * 4);
-  w->st = (uint32_t *)take(16 * 4);
-  w->dstat = (double *)take(4 * 8);
-  w->zero_bytes = (size_t)(p - (char *)w->hist);
-  w->part = (double *)take((ntile + 1) * 8);
-  w->keys = (uint32_t *)take((N + 4) * 4);
-  w->flags = (uint8_t *)take(N + 4);
-  w->tcount = (uint32_t *)take((ctile + 1) * 4);
-  w->sel = (uint32_t *)take((N + 4) * 4);
-  w->dist2 = (float *)take((N + 4) * 4);
-  return (size_t)(p - (char *)base) + 256;
+  w->res = c.take<uint32_t>(16);
+  const size_t z0 = c.used();
+  w->hist = c.take<uint32_t>(4 * 256);
+  w->st = c.take<uint32_t>(16);
+  w->dstat = c.take<double>(4);
+  w->zero_bytes = c.used() - z0;
+  w->part = c.take<double>(ntile + 1);
+  w->keys = c.take<uint32_t>(N + 4);
+  w->flags = c.take<uint8_t>(N + 4);
+  w->tcount = c.take<uint32_t>(ctile + 1);
+  w->sel = c.take<uint32_t>(N + 4);
+  w->dist2 = c.take<float>(N + 4);
+  return c.used();
 }
 
 // ---- keys -------------------------------------------------------------------------------------------------------------
@@ -468,7 +467,7 @@ static bool sd_bad_image(int W, int H) { return W <= 0 || H <= 0 || (long long)W
 extern "C" size_t gsaj_seed_workspace_bytes(int W, int H) {
   if (sd_bad_image(W, H)) return 0;
   SeedWS w;
-  return seed_carve(nullptr, W, H, &w);
+  return seed_carve(Carver(nullptr, ALIGN_BASE), W, H, &w) + 256;
 }
 
 extern "C" int gsaj_depth_stats(int W, int H, const float *depth, const float *opacity, float opacity_min, const uint8_t *mask,
@@ -479,7 +478,7 @@ extern "C" int gsaj_depth_stats(int W, int H, const float *depth, const float *o
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   SeedWS w;
-  seed_carve(seed_ws, W, H, &w);
+  seed_carve(Carver(seed_ws, ALIGN_BASE), W, H, &w);
   SdSrc src;
   src.n = W * H; src.kind = SD_KIND_STATS; src.depth = depth; src.opacity = opacity; src.gt = gt_image; src.mask = mask;
   src.opacity_min = opacity_min; src.rgb_thr = rgb_threshold; src.trunc = 0.f; src.seedmix = 0u; src.out_valid = out_valid;
@@ -496,7 +495,7 @@ extern "C" int gsaj_keyframe_depth_prior(int W, int H, const float *depth, const
   const int rc = gsaj_depth_stats(W, H, depth, opacity, 0.95f, nullptr, gt_image, rgb_threshold, out_stats, nullptr, seed_ws, stream);
   if (rc != GSAJ_OK) return rc;
   SeedWS w;
-  seed_carve(seed_ws, W, H, &w);
+  seed_carve(Carver(seed_ws, ALIGN_BASE), W, H, &w);
   const int n = W * H;
   hipLaunchKernelGGL(k_sd_prior, dim3((n + 1023) / 1024), dim3(256), 0, (hipStream_t)stream, n, depth, gt_image, rgb_threshold, noise,
                      out_stats, w.flags, out_depth);
@@ -513,7 +512,7 @@ extern "C" int gsaj_seed_select(int W, int H, const float *depth, const float *g
   }
   hipStream_t s = (hipStream_t)stream;
   SeedWS w;
-  seed_carve(seed_ws, W, H, &w);
+  seed_carve(Carver(seed_ws, ALIGN_BASE), W, H, &w);
   const int n = W * H, ctile = (n + SD_CTILE - 1) / SD_CTILE;
   SdSrc src;
   src.n = n; src.kind = SD_KIND_SEED; src.depth = depth; src.opacity = nullptr; src.gt = gt_image; src.mask = nullptr;
@@ -530,7 +529,7 @@ extern "C" int gsaj_seed_select(int W, int H, const float *depth, const float *g
 // the key (sd_float_key) of the order statistic `rank` of ALL W * H floats of `values`; for frame.hip, through gsaj_common.h
 int launch_select_rank_f32(int W, int H, const float *values, uint32_t rank, uint32_t *out_key, void *seed_ws, hipStream_t s) {
   SeedWS w;
-  seed_carve(seed_ws, W, H, &w);
+  seed_carve(Carver(seed_ws, ALIGN_BASE), W, H, &w);
   SdSrc src;
   src.n = W * H; src.kind = SD_KIND_ALL; src.depth = values; src.opacity = nullptr; src.gt = nullptr; src.mask = nullptr;
   src.opacity_min = 0.f; src.rgb_thr = 0.f; src.trunc = 0.f; src.seedmix = 0u; src.out_valid = nullptr;
@@ -543,7 +542,7 @@ extern "C" int gsaj_seed_count(const void *seed_ws, void *stream, int *n_valid, 
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   SeedWS w;
-  seed_carve(const_cast<void *>(seed_ws), 1, 1, &w);  // (res comes first: its place does not depend on the image size)
+  seed_carve(Carver(seed_ws, ALIGN_BASE), 1, 1, &w);  // (res comes first: its place does not depend on the image size)
   uint32_t host[2] = {0u, 0u};
   GSAJ_HIP_CHECK(hipMemcpyAsync(host, w.res + RES_NVALID, sizeof(host), hipMemcpyDeviceToHost, (hipStream_t)stream));
   GSAJ_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
@@ -559,7 +558,7 @@ extern "C" int gsaj_debug_seed_pixels(int W, int H, int m, const void *seed_ws, 
   }
   if (m == 0) return GSAJ_OK;
   SeedWS w;
-  seed_carve(const_cast<void *>(seed_ws), W, H, &w);
+  seed_carve(Carver(seed_ws, ALIGN_BASE), W, H, &w);
   GSAJ_HIP_CHECK(hipMemcpyAsync(pixels, w.sel, (size_t)m * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return GSAJ_OK;
 }
@@ -577,7 +576,7 @@ extern "C" int gsaj_seed_gaussians(int m, int W, int H, const float *depth, cons
   if (m == 0) return GSAJ_OK;
   hipStream_t s = (hipStream_t)stream;
   SeedWS w;
-  seed_carve(seed_ws, W, H, &w);
+  seed_carve(Carver(seed_ws, ALIGN_BASE), W, H, &w);
   const int n = W * H;
   if (adaptive) {  // the two middle order statistics of the whole depth image, zeros included (np.median)
     int rc = launch_select_rank_f32(W, H, depth, (uint32_t)((n - 1) / 2), w.res + RES_MED_LO, seed_ws, s);

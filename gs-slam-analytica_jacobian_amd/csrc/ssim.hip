@@ -44,17 +44,14 @@ static size_t ssim_nblk(int N, int C, int W, int H) {
   return (size_t)((W + SSIM_TW - 1) / SSIM_TW) * (size_t)((H + SSIM_TH - 1) / SSIM_TH) * (size_t)N * (size_t)C;
 }
 
-static SsimLayout ssim_layout(void *ws, int N, int C, int W, int H) {
-  char *base = (char *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  const size_t nblk = ssim_nblk(N, C, W, H), plane = (size_t)N * C * W * H;
-  SsimLayout L;
-  L.ticket = (uint32_t *)base;  // the caller zeroes the workspace once, when it allocates it; the last workgroup resets it
-  L.partials = (float *)(base + 256);
-  char *maps = base + 256 + ((nblk * 4 * sizeof(float) + 255) & ~(size_t)255);
-  L.dmu = (float *)maps;
-  L.dxx = L.dmu + plane;
-  L.dxy = L.dxx + plane;
-  return L;
+static size_t ssim_carve(Carver c, int N, int C, int W, int H, SsimLayout *L) {
+  const size_t plane = (size_t)N * C * W * H;
+  L->ticket = c.take<uint32_t>(1);  // the caller zeroes the workspace once, when it allocates it; the last workgroup resets it
+  L->partials = c.take<float>(ssim_nblk(N, C, W, H) * 4);
+  L->dmu = c.pack<float>(plane);    // (the three maps follow each other unpadded)
+  L->dxx = c.pack<float>(plane);
+  L->dxy = c.pack<float>(plane);
+  return c.used();
 }
 
 struct SsimTile {
@@ -265,8 +262,8 @@ __global__ __launch_bounds__(SSIM_BLOCK) void k_ssim_bwd(SsimBwdParams p) {
 
 extern "C" size_t gsaj_ssim_workspace_bytes(int N, int C, int W, int H) {
   if (N <= 0 || C <= 0 || W <= 0 || H <= 0) return 0;
-  const size_t nblk = ssim_nblk(N, C, W, H);
-  return 256 + 256 + ((nblk * 4 * sizeof(float) + 255) & ~(size_t)255) + 3 * sizeof(float) * (size_t)N * C * W * H;
+  SsimLayout L;
+  return ssim_carve(Carver(nullptr, ALIGN_BASE), N, C, W, H, &L) + 256;
 }
 
 static bool ssim_dims_ok(int N, int C, int W, int H) {
@@ -278,7 +275,7 @@ static int launch_ssim_fwd(int N, int C, int W, int H, const float *img, const f
                            float *refine_out, float lambda, void *ws, hipStream_t s) {
   SsimFwdParams p;
   p.N = N; p.C = C; p.W = W; p.H = H; p.img = img; p.gt = gt; p.ssim_map = ssim_map;
-  p.L = ssim_layout(ws, N, C, W, H);
+  ssim_carve(Carver(ws, ALIGN_BASE), N, C, W, H, &p.L);
   p.ssim_out = ssim_out; p.refine_out = refine_out; p.lambda = lambda;
   hipLaunchKernelGGL(k_ssim_fwd, dim3((unsigned)ssim_nblk(N, C, W, H)), dim3(SSIM_BLOCK), 0, s, p);
   GSAJ_HIP_CHECK(hipGetLastError());
@@ -290,7 +287,7 @@ static int launch_ssim_bwd(int N, int C, int W, int H, const float *img, const f
   SsimBwdParams p;
   p.N = N; p.C = C; p.W = W; p.H = H; p.img = img; p.gt = gt; p.dL_dssim = dL_dssim; p.w_const = w_const; p.l1_w = l1_w;
   p.dL_dimg = dL_dimg;
-  p.L = ssim_layout(ws, N, C, W, H);
+  ssim_carve(Carver(ws, ALIGN_BASE), N, C, W, H, &p.L);
   hipLaunchKernelGGL(k_ssim_bwd, dim3((unsigned)ssim_nblk(N, C, W, H)), dim3(SSIM_BLOCK), 0, s, p);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;

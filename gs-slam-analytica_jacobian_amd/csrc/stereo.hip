@@ -25,20 +25,16 @@ struct StereoWS {
   uint32_t *S;        // [H,W,D]
 };
 
-static size_t stereo_carve(char *base, int W, int H, int D, StereoWS *w, size_t *c_off, size_t *s_off) {
+// (the workspace must be 256-byte aligned as handed over: carved BASE_AS_GIVEN, no base slack in its size)
+static size_t stereo_carve(Carver c, int W, int H, int D, StereoWS *w, size_t *c_off = nullptr, size_t *s_off = nullptr) {
   const size_t n = (size_t)W * H;
-  size_t off = 0;
-  if (w) w->pl = reinterpret_cast<uint8_t *>(base + off);
-  off += gsaj_align(n);
-  if (w) w->pr = reinterpret_cast<uint8_t *>(base + off);
-  off += gsaj_align(n);
-  if (w) w->C = reinterpret_cast<uint16_t *>(base + off);
-  if (c_off) *c_off = off;
-  off += gsaj_align(n * D * sizeof(uint16_t));
-  if (w) w->S = reinterpret_cast<uint32_t *>(base + off);
-  if (s_off) *s_off = off;
-  off += gsaj_align(n * D * sizeof(uint32_t));
-  return off;
+  w->pl = c.take<uint8_t>(n);
+  w->pr = c.take<uint8_t>(n);
+  if (c_off) *c_off = c.used();
+  w->C = c.take<uint16_t>(n * D);
+  if (s_off) *s_off = c.used();
+  w->S = c.take<uint32_t>(n * D);
+  return c.used();
 }
 
 // ---- a. prefilter ------------------------------------------------------------------------------------------------------------------
@@ -289,13 +285,15 @@ extern "C" int gsaj_stereo_workspace_bytes(int W, int H, int D, int paths, size_
     gsaj_set_error("gsaj_stereo_workspace_bytes: bytes is required");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  *bytes = stereo_carve(nullptr, W, H, D, nullptr, nullptr, nullptr);
+  StereoWS ws;
+  *bytes = stereo_carve(Carver(nullptr, BASE_AS_GIVEN), W, H, D, &ws);
   return GSAJ_OK;
 }
 
 extern "C" int gsaj_debug_stereo_offsets(int W, int H, int D, int paths, size_t *cost_off, size_t *sum_off) {
   if (!stereo_sizes_ok("gsaj_debug_stereo_offsets", W, H, D, paths)) return GSAJ_ERR_INVALID_ARGUMENT;
-  stereo_carve(nullptr, W, H, D, nullptr, cost_off, sum_off);
+  StereoWS ws;
+  stereo_carve(Carver(nullptr, BASE_AS_GIVEN), W, H, D, &ws, cost_off, sum_off);
   return GSAJ_OK;
 }
 
@@ -356,7 +354,8 @@ extern "C" int gsaj_stereo_match(int W, int H, const uint8_t *left, size_t left_
     gsaj_set_error("gsaj_stereo_match: a row stride is less than W (left_stride=%zu right_stride=%zu W=%d)", left_stride, right_stride, W);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  const size_t need = stereo_carve(nullptr, W, H, D, nullptr, nullptr, nullptr);
+  StereoWS ws;
+  const size_t need = stereo_carve(Carver(workspace, BASE_AS_GIVEN), W, H, D, &ws);
   if (workspace_bytes < need) {
     gsaj_set_error("gsaj_stereo_match: the workspace has %zu bytes, gsaj_stereo_workspace_bytes says %zu", workspace_bytes, need);
     return GSAJ_ERR_WORKSPACE_TOO_SMALL;
@@ -370,8 +369,6 @@ extern "C" int gsaj_stereo_match(int W, int H, const uint8_t *left, size_t left_
     gsaj_set_error("gsaj_stereo_match: with out_depth, bf must be positive and finite (bf=%g)", bf);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  StereoWS ws;
-  stereo_carve(static_cast<char *>(workspace), W, H, D, &ws, nullptr, nullptr);
   StereoPaths pp;
   pp.W = W; pp.H = H; pp.P1 = P1; pp.P2 = P2; pp.paths = paths; pp.C = ws.C; pp.S = ws.S;
   StereoWinner wp;
