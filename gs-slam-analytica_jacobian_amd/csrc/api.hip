@@ -206,6 +206,18 @@ static FwdParams fwd_params(const Scene &sc, const Views &v, int prefiltered, co
   return p;
 }
 
+// what a backward's caller gives BwdParams directly, in the order of the ABI: radii and the twelve gradient outputs
+static BwdParams grad_outputs(const int *radii, float *dL_dmean2D, float *dL_dconic, float *dL_dopacity, float *dL_dcolor, float *dL_ddepth,
+                              float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh, float *dL_dscale, float *dL_drot, float *dL_dtau,
+                              float *dL_dtau_sum) {
+  BwdParams p{};
+  p.radii = radii;
+  p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
+  p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
+  p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
+  return p;
+}
+
 // p arrives with what the caller gave it directly: the twelve gradient outputs (none for the Jacobian walk) and radii
 static void bwd_params(BwdParams *p, const Scene &sc, const Views &v, const GeomWS &g) {
   p->P = sc.P; p->D = sc.D; p->M = sc.M; p->W = v.W; p->H = v.H;
@@ -619,11 +631,8 @@ int gsaj_rasterize_backward_batch(int K, int P, int D, int M, int capacity, cons
   const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
   const Views v{K, bg, W, H, viewmatrices, projmatrices, projmatrix_raw, campos, tanfovx, tanfovy};
   const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, capacity, 0, image_ws};
-  BwdParams p{};
-  p.radii = radii;
-  p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
-  p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
-  p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
+  BwdParams p = grad_outputs(radii, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                             dL_dtau, dL_dtau_sum);
   return backward_batch(&p, sc, v, a, PixelSeeds{dL_dpix, dL_dpix_depth, nullptr}, flags, (hipStream_t)stream);
 }
 
@@ -649,11 +658,8 @@ int gsaj_rasterize_backward_loss_batch(int K, int P, int D, int M, int capacity,
     if (rc != GSAJ_OK) return rc;
     if ((rc = check_loss_images("gsaj_rasterize_backward_loss_batch", fl)) != GSAJ_OK) return rc;
   }
-  BwdParams p{};
-  p.radii = radii;
-  p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
-  p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
-  p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
+  BwdParams p = grad_outputs(radii, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                             dL_dtau, dL_dtau_sum);
   return backward_batch(&p, sc, v, a, PixelSeeds{nullptr, nullptr, &fl}, flags, (hipStream_t)stream);
 }
 
@@ -697,11 +703,8 @@ int gsaj_rasterize_backward(int P, int D, int M, int R, const float *bg, int W, 
   const Scene sc{P, D, M, means3D, shs, colors_precomp, nullptr, scales, scale_modifier, rotations, cov3D_precomp};
   const Views v{1, bg, W, H, viewmatrix, projmatrix, projmatrix_raw, campos, tanfovx, tanfovy};
   const Arenas a{geom_ws, binning_ws, SIZE_NOT_GIVEN, R, 0, image_ws};
-  BwdParams p{};
-  p.radii = radii;
-  p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
-  p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
-  p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
+  BwdParams p = grad_outputs(radii, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                             dL_dtau, dL_dtau_sum);
   return backward_frame(&p, sc, v, a, PixelSeeds{dL_dpix, dL_dpix_depth, nullptr}, (hipStream_t)stream);
 }
 
@@ -723,11 +726,8 @@ int gsaj_rasterize_backward_loss(int P, int D, int M, int R, const float *bg, in
   int rc = fused_loss("gsaj_rasterize_backward_loss", &fl);
   if (rc != GSAJ_OK) return rc;
   if ((rc = check_loss_images("gsaj_rasterize_backward_loss", fl)) != GSAJ_OK) return rc;
-  BwdParams p{};
-  p.radii = radii;
-  p.dL_dmean2D = dL_dmean2D; p.dL_dconic = dL_dconic; p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
-  p.dL_ddepth = dL_ddepth; p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = dL_dsh;
-  p.dL_dscale = dL_dscale; p.dL_drot = dL_drot; p.dL_dtau = dL_dtau; p.dL_dtau_sum = dL_dtau_sum;
+  BwdParams p = grad_outputs(radii, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                             dL_dtau, dL_dtau_sum);
   return backward_frame(&p, sc, v, a, PixelSeeds{nullptr, nullptr, &fl}, (hipStream_t)stream);
 }
 
@@ -741,8 +741,14 @@ static size_t jac_carve(Carver c, int P, int W, int H, JacWS *w) {
 size_t gsaj_pose_jac_workspace_bytes(int P, int W, int H) { JacWS w; return jac_carve(Carver(nullptr, ALIGN_BASE), P, W, H, &w) + 256; }
 int gsaj_pose_jac_partial_rows(int W, int H) { return gsaj_jac_slots(W, H); }
 
+// (the batched forms keep no partial rows of their own -- the caller owns gn_partials -- so W and H do not count)
+size_t gsaj_pose_jac_batch_workspace_bytes(int K, int P, int W, int H) {
+  (void)W; (void)H;
+  return (size_t)(K > 0 ? K : 0) * view_stride(gsaj_jac_rows_bytes(P));  // (view v's rows are v strides on: pose_jac.hip)
+}
+
 // the fused form's loss arguments (fl arrives as the caller gave them), in the order a caller is told about them
-static int pose_jac_loss_args(const char *who, bool joint, FusedLoss *fl, const float *gn_partials, float irls_delta, int K = 1) {
+static int pose_jac_loss_args(const char *who, bool joint, FusedLoss *fl, const float *gn_partials, float irls_delta, int K) {
   int rc = fused_loss(who, fl, K);
   if (rc != GSAJ_OK) return rc;
   if (joint && ((fl->flags & GSAJ_LOSS_NO_EXPOSURE) || !fl->exp_a || !fl->exp_b)) {
@@ -756,15 +762,20 @@ static int pose_jac_loss_args(const char *who, bool joint, FusedLoss *fl, const 
   return GSAJ_OK;
 }
 
-// p: radii only (no gradient output).  jo: the walk's outputs as the caller named them; the explicit form's seed / curvature images
-// are dropped where their sum was not asked for, and its partial rows live in the Jacobian workspace behind the derivative rows.
+// The five Jacobian entry points: v.K views of one map (the single forms: K = 1).  p: radii only (no gradient output).  jo: the walk's
+// outputs as the caller named them; the explicit form's seed / curvature images are dropped where their sum was not asked for, and its
+// partial rows live in the Jacobian workspace behind the derivative rows.  What differs between the single and the batched forms:
+//   single   run behind a synchronous forward: R may be 0 and radii may be the workspace's own; every workspace is carved from the
+//            aligned base of whatever the caller gave; jac_ws holds the rows, then the explicit form's partial rows (jac_carve)
+//   batched  (the loss-fused forms only) a capacity > 0 and the caller's radii [K,P]; K blocks of every workspace, 256-byte aligned
+//            themselves; jac_ws is K row blocks view_stride apart and nothing else (gsaj_pose_jac_batch_workspace_bytes)
 static int pose_jac(const char *who, BwdParams *p, const Scene &sc, const Views &v, const Arenas &a, void *jac_ws, JacOut jo,
-                    const GnSums &gn, hipStream_t s) {
-  int rc = gn.fl ? pose_jac_loss_args(who, gn.joint, gn.fl, jo.partials, jo.delta) : GSAJ_OK;
+                    const GnSums &gn, bool batched, hipStream_t s) {
+  int rc = gn.fl ? pose_jac_loss_args(who, gn.joint, gn.fl, jo.partials, jo.delta, v.K) : GSAJ_OK;
   if (rc != GSAJ_OK) return rc;
-  if (sc.P <= 0 || a.instances < 0 || v.W <= 0 || v.H <= 0 || !v.bg || !sc.means3D || !v.viewmatrix || !v.projmatrix ||
-      !v.projmatrix_raw || !a.geom || !a.binning || !a.image || !jac_ws || (sc.shs && !v.campos) || (sc.scales && !sc.rotations) ||
-      (!sc.scales && !sc.cov3D_precomp)) {
+  if (sc.P <= 0 || (batched ? a.instances <= 0 || !p->radii : a.instances < 0) || v.W <= 0 || v.H <= 0 || !v.bg || !sc.means3D ||
+      !v.viewmatrix || !v.projmatrix || !v.projmatrix_raw || !a.geom || !a.binning || !a.image || !jac_ws || (sc.shs && !v.campos) ||
+      (sc.scales && !sc.rotations) || (!sc.scales && !sc.cov3D_precomp)) {
     gsaj_set_error("%s: invalid argument", who);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
@@ -773,17 +784,22 @@ static int pose_jac(const char *who, BwdParams *p, const Scene &sc, const Views 
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   Carved c;
-  carve(a, sc.P, v.W, v.H, 0, &c);
-  bwd_params(p, sc, v, c.g);
-  JacWS w;
+  if ((rc = carve(a, sc.P, v.W, v.H, batched ? v.K : 0, &c)) != GSAJ_OK) return rc;
+  if (batched && ((uintptr_t)jac_ws & 255)) {
+    gsaj_set_error("batched entry points need 256-byte aligned workspaces");
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  bwd_params(p, sc, v, c.g);  // (cov3Ds: the caller's, or view 0's geometry block -- the only one a batched forward writes)
+  JacWS w;  // (batched: jac_ws is aligned, so w.rows is the first of the K row blocks; w.partials is not used)
   jac_carve(Carver(jac_ws, ALIGN_BASE), sc.P, v.W, v.H, &w);
-  rc = launch_splat_jac(*p, c.g, c.im, w.rows, s);
+  const size_t rows_stride = view_stride(gsaj_jac_rows_bytes(sc.P));
+  rc = launch_splat_jac(*p, v.K, c.g, c.im, w.rows, c.vs, rows_stride, s);
   if (rc != GSAJ_OK) return rc;
   const bool sums = gn.fl || gn.H_out || gn.g_out;
   if (!gn.g_out) jo.seed_c = jo.seed_d = nullptr;
   if (!gn.H_out) jo.curv_c = jo.curv_d = nullptr;
   if (!gn.fl) jo.partials = sums ? w.partials : nullptr;
-  rc = launch_render_jac(*p, v.bg, c.g, c.b, c.im, w.rows, jo, gn.fl, gn.joint ? 1 : 0, s);
+  rc = launch_render_jac(*p, v.K, v.bg, c, w.rows, rows_stride, jo, gn.fl, gn.joint ? 1 : 0, s);
   if (rc != GSAJ_OK || gn.fl || !sums) return rc;
   return launch_gn_reduce(jo.partials, gsaj_jac_slots(v.W, v.H), c.im, gn.H_out, gn.g_out, s);
 }
@@ -801,7 +817,7 @@ int gsaj_rasterize_pose_jacobian(int P, int D, int M, int R, const float *bg, in
   const JacOut jo{jac_out, out_color, out_depth, seed_color, seed_depth, curv_color, curv_depth, nullptr, 0.f};
   BwdParams p{};
   p.radii = radii;
-  return pose_jac("gsaj_rasterize_pose_jacobian", &p, sc, v, a, jac_ws, jo, GnSums{H_out, g_out, nullptr, false}, (hipStream_t)stream);
+  return pose_jac("gsaj_rasterize_pose_jacobian", &p, sc, v, a, jac_ws, jo, GnSums{H_out, g_out, nullptr, false}, false, (hipStream_t)stream);
 }
 
 int gsaj_rasterize_pose_jacobian_loss(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
@@ -822,7 +838,7 @@ int gsaj_rasterize_pose_jacobian_loss(int P, int D, int M, int R, const float *b
   fl.color = color; fl.depth = depth; fl.opacity = opacity;
   BwdParams p{};
   p.radii = radii;
-  return pose_jac(who, &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, false}, (hipStream_t)stream);
+  return pose_jac(who, &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, false}, false, (hipStream_t)stream);
 }
 
 int gsaj_rasterize_pose_jacobian_loss8(int P, int D, int M, int R, const float *bg, int W, int H, const float *means3D,
@@ -843,37 +859,10 @@ int gsaj_rasterize_pose_jacobian_loss8(int P, int D, int M, int R, const float *
   fl.color = color; fl.depth = depth; fl.opacity = opacity;
   BwdParams p{};
   p.radii = radii;
-  return pose_jac(who, &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, true}, (hipStream_t)stream);
+  return pose_jac(who, &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, true}, false, (hipStream_t)stream);
 }
 
 // ---- the same for K views of one map: gridDim.y = K, K consecutive blocks of every workspace (the loss-fused forms only) ----------
-size_t gsaj_pose_jac_batch_workspace_bytes(int K, int P, int W, int H) {
-  (void)W; (void)H;  // (the batched forms keep no partial rows of their own: the caller owns gn_partials)
-  return (size_t)(K > 0 ? K : 0) * view_stride(gsaj_jac_rows_bytes(P));  // (view v's rows are v strides on: pose_jac.hip)
-}
-
-static int pose_jac_batch(const char *who, BwdParams *p, const Scene &sc, const Views &v, const Arenas &a, void *jac_ws, JacOut jo,
-                          const GnSums &gn, hipStream_t s) {
-  int rc = pose_jac_loss_args(who, gn.joint, gn.fl, jo.partials, jo.delta, v.K);
-  if (rc != GSAJ_OK) return rc;
-  if (sc.P <= 0 || a.instances <= 0 || v.W <= 0 || v.H <= 0 || !v.bg || !sc.means3D || !v.viewmatrix || !v.projmatrix ||
-      !v.projmatrix_raw || !p->radii || !a.geom || !a.binning || !a.image || !jac_ws || (sc.shs && !v.campos) ||
-      (sc.scales && !sc.rotations) || (!sc.scales && !sc.cov3D_precomp)) {
-    gsaj_set_error("%s: invalid argument", who);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  Carved c;
-  if ((rc = carve(a, sc.P, v.W, v.H, v.K, &c)) != GSAJ_OK) return rc;
-  if ((uintptr_t)jac_ws & 255) {
-    gsaj_set_error("batched entry points need 256-byte aligned workspaces");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  bwd_params(p, sc, v, c.g);  // (cov3Ds: the caller's, or view 0's geometry block -- the only one a batched forward writes)
-  float *rows = reinterpret_cast<float *>(jac_ws);
-  if ((rc = launch_splat_jac_batch(*p, v.K, c.g, c.im, rows, c.vs, s)) != GSAJ_OK) return rc;
-  return launch_render_jac_batch(*p, v.K, v.bg, c, rows, jo, *gn.fl, gn.joint ? 1 : 0, s);
-}
-
 int gsaj_rasterize_pose_jacobian_loss_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
                                             const float *shs, const float *colors_precomp, const float *scales, float scale_modifier,
                                             const float *rotations, const float *cov3D_precomp, const float *viewmatrices,
@@ -892,8 +881,8 @@ int gsaj_rasterize_pose_jacobian_loss_batch(int K, int P, int D, int M, int capa
   fl.color = color; fl.depth = depth; fl.opacity = opacity;
   BwdParams p{};
   p.radii = radii;
-  return pose_jac_batch("gsaj_rasterize_pose_jacobian_loss_batch", &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, false},
-                        (hipStream_t)stream);
+  return pose_jac("gsaj_rasterize_pose_jacobian_loss_batch", &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, false}, true,
+                  (hipStream_t)stream);
 }
 
 int gsaj_rasterize_pose_jacobian_loss8_batch(int K, int P, int D, int M, int capacity, const float *bg, int W, int H, const float *means3D,
@@ -914,8 +903,8 @@ int gsaj_rasterize_pose_jacobian_loss8_batch(int K, int P, int D, int M, int cap
   fl.color = color; fl.depth = depth; fl.opacity = opacity;
   BwdParams p{};
   p.radii = radii;
-  return pose_jac_batch("gsaj_rasterize_pose_jacobian_loss8_batch", &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, true},
-                        (hipStream_t)stream);
+  return pose_jac("gsaj_rasterize_pose_jacobian_loss8_batch", &p, sc, v, a, jac_ws, jo, GnSums{nullptr, nullptr, &fl, true}, true,
+                  (hipStream_t)stream);
 }
 
 int gsaj_mark_visible(int P, const float *means3D, const float *viewmatrix, const float *projmatrix, uint8_t *present,

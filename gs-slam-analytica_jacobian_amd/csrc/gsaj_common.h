@@ -255,29 +255,27 @@ int launch_gaussian_backward(const BwdParams &p, const GeomWS &g, const BinWS &b
 int launch_gather_sums(int P, int K, const int *radii, const GeomWS &g, const BinWS &b, const ImageWS &im, ViewStrides vs, hipStream_t s);
 int launch_gaussian_backward_batch(const BwdParams &p, int K, const GeomWS &g, const BinWS &b, const ImageWS &im, ViewStrides vs,
                                    int accumulate, int gather, hipStream_t s);
-// pose_jac.hip: per-Gaussian derivative rows (`rows`: gsaj_jac_rows_bytes(P) bytes), the forward-mode compositor over a finished
-// forward's state (every output may be NULL; fl != NULL: seeds and curvatures from the tracking loss with IRLS delta, else from the
-// seed / curvature images; partials [gsaj_jac_slots(W, H)][GSAJ_GN_PARTIAL_FLOATS]; joint (with fl): the exposure columns too, partials
-// [gsaj_jac_slots(W, H)][GSAJ_GN8_PARTIAL_FLOATS]) and the explicit form's fixed-order sum
+// pose_jac.hip, K views of one map (a single frame: K = 1, c.vs zero): per-Gaussian derivative rows (`rows`: K blocks of
+// gsaj_jac_rows_bytes(P) bytes, rows_stride apart), the forward-mode compositor over a finished forward's state (every output may be
+// NULL; fl != NULL: seeds and curvatures from the tracking loss with IRLS delta, view 0's pointers; else, K = 1 only, from the seed /
+// curvature images; partials [K][gsaj_jac_slots(W, H)][GSAJ_GN_PARTIAL_FLOATS]; joint (with fl): the exposure columns too, partials
+// [K][gsaj_jac_slots(W, H)][GSAJ_GN8_PARTIAL_FLOATS]) and the explicit form's fixed-order sum.  p.viewmatrix / projmatrix / campos
+// [K,.], p.radii [K,P].
 size_t gsaj_jac_rows_bytes(int P);
 int gsaj_jac_slots(int W, int H);
-int launch_splat_jac(const BwdParams &p, const GeomWS &g, const ImageWS &im, float *rows, hipStream_t s);
+int launch_splat_jac(const BwdParams &p, int K, const GeomWS &g, const ImageWS &im, float *rows, ViewStrides vs, size_t rows_stride,
+                     hipStream_t s);
 struct JacOut {
-  float *jac;                       // [H,W,4,6] or NULL
+  float *jac;                       // [K,H,W,4,6] or NULL
   float *color, *depth;             // re-derived images [3,H,W], [H,W] or NULL
   const float *seed_c, *seed_d;     // explicit form: seed images [3,H,W], [H,W] (NULL: no g)
   const float *curv_c, *curv_d;     // explicit form: curvature images (NULL: no H)
-  float *partials;                  // [workgroups][GN_ROW] or NULL
+  float *partials;                  // [K][workgroups][GN_ROW] or NULL
   float delta;                      // fused form: the IRLS delta
 };
-int launch_render_jac(const BwdParams &p, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im, const float *rows,
-                      const JacOut &jo, const FusedLoss *fl, int joint, hipStream_t s);
+int launch_render_jac(const BwdParams &p, int K, const float *bg, const Carved &c, const float *rows, size_t rows_stride, const JacOut &jo,
+                      const FusedLoss *fl, int joint, hipStream_t s);
 int launch_gn_reduce(const float *partials, int n, const ImageWS &im, float *H_out, float *g_out, hipStream_t s);
-// K views of one map, the loss-fused forms: p.viewmatrix / projmatrix / campos [K,.], p.radii [K,P]; rows: K blocks of
-// gsaj_jac_rows_bytes(P); jo.partials [K][gsaj_jac_slots(W, H)][row], jo.jac [K,H,W,4,6] or NULL; fl: view 0's pointers
-int launch_splat_jac_batch(const BwdParams &p, int K, const GeomWS &g, const ImageWS &im, float *rows, ViewStrides vs, hipStream_t s);
-int launch_render_jac_batch(const BwdParams &p, int K, const float *bg, const Carved &c, const float *rows, const JacOut &jo,
-                            const FusedLoss &fl, int joint, hipStream_t s);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 // in-place exclusive scan of n counters by ONE workgroup (knn.hip; the radix sort's digit offsets, seed.hip's compaction offsets)
 void launch_exclusive_scan_u32(int n, uint32_t *v, hipStream_t s);

@@ -92,6 +92,23 @@ __global__ void k_pose_adam_step(PoseStepParams p) {
 
 extern "C" int gsaj_pose_state_floats(void) { return GSAJ_POSE_STATE_FLOATS; }
 
+// K poses in one launch (checked by the entry point); the single-pose entry point is K = 1, no mask, no skip stride
+static int pose_adam_launch(int K, const float *dL_dtau, const float *dL_dexposure, const uint8_t *active, float lr_rot, float lr_trans,
+                            float lr_exp_a, float lr_exp_b, float beta1, float beta2, float eps, float converged_threshold,
+                            const float *projection_matrix, float *pose_states, const uint32_t *skip, size_t skip_stride, hipStream_t s) {
+  PoseStepParams p;
+  p.g_tau = dL_dtau; p.g_exp = dL_dexposure; p.projection = projection_matrix;
+  for (int i = 0; i < 3; i++) { p.lr[i] = lr_trans; p.lr[3 + i] = lr_rot; }
+  p.lr[6] = lr_exp_a; p.lr[7] = lr_exp_b;
+  p.beta1 = beta1; p.beta2 = beta2; p.eps = eps; p.threshold = converged_threshold;
+  p.st = pose_states;
+  p.active = active;
+  p.skip = skip; p.skip_stride = skip_stride;
+  hipLaunchKernelGGL(k_pose_adam_step, dim3((unsigned)K), dim3(64), 0, s, p);
+  GSAJ_HIP_CHECK(hipGetLastError());
+  return GSAJ_OK;
+}
+
 extern "C" int gsaj_pose_adam_step(const float *dL_dtau, const float *dL_dexposure, float lr_rot, float lr_trans, float lr_exp_a,
                                    float lr_exp_b, float beta1, float beta2, float eps, float converged_threshold,
                                    const float *projection_matrix, float *pose_state, const uint32_t *skip, void *stream) {
@@ -99,17 +116,8 @@ extern "C" int gsaj_pose_adam_step(const float *dL_dtau, const float *dL_dexposu
     gsaj_set_error("gsaj_pose_adam_step: dL_dtau and pose_state are required");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  PoseStepParams p;
-  p.g_tau = dL_dtau; p.g_exp = dL_dexposure; p.projection = projection_matrix;
-  for (int i = 0; i < 3; i++) { p.lr[i] = lr_trans; p.lr[3 + i] = lr_rot; }
-  p.lr[6] = lr_exp_a; p.lr[7] = lr_exp_b;
-  p.beta1 = beta1; p.beta2 = beta2; p.eps = eps; p.threshold = converged_threshold;
-  p.st = pose_state;
-  p.active = nullptr;
-  p.skip = skip; p.skip_stride = 0;
-  hipLaunchKernelGGL(k_pose_adam_step, dim3(1), dim3(64), 0, (hipStream_t)stream, p);
-  GSAJ_HIP_CHECK(hipGetLastError());
-  return GSAJ_OK;
+  return pose_adam_launch(1, dL_dtau, dL_dexposure, nullptr, lr_rot, lr_trans, lr_exp_a, lr_exp_b, beta1, beta2, eps, converged_threshold,
+                          projection_matrix, pose_state, skip, 0, (hipStream_t)stream);
 }
 
 extern "C" int gsaj_pose_adam_step_batch(int K, const float *dL_dtau, const float *dL_dexposure, const uint8_t *active, float lr_rot,
@@ -120,15 +128,6 @@ extern "C" int gsaj_pose_adam_step_batch(int K, const float *dL_dtau, const floa
     gsaj_set_error("gsaj_pose_adam_step_batch: K > 0, dL_dtau and pose_states are required");
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  PoseStepParams p;
-  p.g_tau = dL_dtau; p.g_exp = dL_dexposure; p.projection = projection_matrix;
-  for (int i = 0; i < 3; i++) { p.lr[i] = lr_trans; p.lr[3 + i] = lr_rot; }
-  p.lr[6] = lr_exp_a; p.lr[7] = lr_exp_b;
-  p.beta1 = beta1; p.beta2 = beta2; p.eps = eps; p.threshold = converged_threshold;
-  p.st = pose_states;
-  p.active = active;
-  p.skip = skip; p.skip_stride = skip_stride_bytes;
-  hipLaunchKernelGGL(k_pose_adam_step, dim3((unsigned)K), dim3(64), 0, (hipStream_t)stream, p);
-  GSAJ_HIP_CHECK(hipGetLastError());
-  return GSAJ_OK;
+  return pose_adam_launch(K, dL_dtau, dL_dexposure, active, lr_rot, lr_trans, lr_exp_a, lr_exp_b, beta1, beta2, eps, converged_threshold,
+                          projection_matrix, pose_states, skip, skip_stride_bytes, (hipStream_t)stream);
 }

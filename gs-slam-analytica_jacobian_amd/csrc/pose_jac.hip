@@ -20,15 +20,15 @@
 //  k_gn_reduce     the explicit form's tail: the rows summed in slot order (fp64) -> H [21], g [6].
 //  k_gn_step       the fused form's tail: the same sum, then accept / reject, damping, a 6x6 Cholesky solve in fp64 and
 //                  Exp(tau) W2C with the Adam pose step's own device functions (pose_se3.h).  One launch, no host read.
-//  k_render_jac8 / k_gn8_step   the joint form: the unknowns are x = [rho, theta, a, b] with the exposure e^a C + b of the tracking
-//                  loss.  r_ch = m (e^a C_ch + b - gt_ch), so relative to the rendered colour the exposure parameters are two more
+//  k_render_jac<true, true> / k_gn_step<8>   the joint form: the unknowns are x = [rho, theta, a, b] with the exposure e^a C + b of the
+//                  tracking loss.  r_ch = m (e^a C_ch + b - gt_ch), so relative to the rendered colour the exposure parameters are two more
 //                  Jacobian columns, J8[ch] = [J[ch][0..5], C_ch, 1 / e^a] (0, 0 in the depth row), under the same seeds and
 //                  curvatures: H8 (36, upper triangle by rows) and g8 (8) in ONE 64-float row per workgroup, 8x8 solve, a and b
 //                  stepped, saved and restored with the pose.  The same body and the same step, instantiated for 8 unknowns.
-//  k_splat_jac_batch / k_render_jac_batch / k_gn_step_batch / k_gn8_step_batch   K views of ONE map (gridDim.y = K, or one workgroup per
-//                  view): the same bodies on view v's blocks -- every per-view pointer moved on by blockIdx.y x its stride -- for K
-//                  independent solves in one set of launches (a keyframe window's poses against a fixed map; K start poses of one
-//                  frame).  Only cov3D is not per view: a batched forward writes it into view 0's geometry block only.
+//  K views of ONE map are the same kernels with gridDim.y = K (k_splat_jac, the loss-fused k_render_jac) or one workgroup per view
+//                  (k_gn_step): every per-view pointer is moved on by the view's index x its stride, for K independent solves in one set
+//                  of launches (a keyframe window's poses against a fixed map; K start poses of one frame).  A single view is K = 1 with
+//                  zero strides.  Only cov3D is not per view: a batched forward writes it into view 0's geometry block only.
 //  k_gn_select     one wave: the view of smallest accepted loss among the active views that have accepted a pose.
 #include "gsaj_common.h"
 #include "gaussian_chain.h"
@@ -45,62 +45,12 @@
 // The chain is linear in the ten sums the reverse compositor hands it, so its transpose is the chain applied to unit sums:
 // row j of d(.)/dtau = the tau the chain returns for sum j = 1, all others 0.  Opacity does not depend on tau.  The colour
 // rows are the view-direction term of the SH colour (rho columns only, masked by the clamp flags: sh_backward).
-// (The rows' code is a macro, not a function: written into k_splat_jac it compiles to the instructions that kernel always had --
-// inlined from a function it did not -- and the batched kernel gets the same text.)
-#define SPLAT_JAC_ROWS(p, clamped, counters, rows) \
-  if (counters[4]) return; \
-  const int idx = blockIdx.x * 64 + threadIdx.x; \
-  if (idx >= p.P) return; \
-  const size_t ii = (size_t)idx; \
-  const int radius = p.radii[ii]; \
-  const float3 mean = make_float3(p.means3D[3 * ii], p.means3D[3 * ii + 1], p.means3D[3 * ii + 2]); \
-  float c6[6]; \
-  _Pragma("unroll") \
-  for (int k = 0; k < 6; k++) c6[k] = p.cov3Ds[6 * ii + k]; \
-  uint8_t cl[3] = {0, 0, 0}; \
-  if (p.shs) { \
-    cl[0] = clamped[3 * ii]; cl[1] = clamped[3 * ii + 1]; cl[2] = clamped[3 * ii + 2]; \
-  } \
-  if (radius <= 0) return; \
-  float *row = rows + ii * JROW_F; \
-  _Pragma("unroll 1") \
-  for (int u = 0; u < 6; u++) { \
-    const float4 s0 = make_float4(u == 0 ? 1.f : 0.f, u == 1 ? 1.f : 0.f, u == 2 ? 1.f : 0.f, u == 3 ? 1.f : 0.f); \
-    const float4 s1 = make_float4(u == 4 ? 1.f : 0.f, 0.f, 0.f, 0.f); \
-    const float4 s2 = make_float4(0.f, u == 5 ? 1.f : 0.f, 0.f, 0.f); \
-    GaussianGrads o; \
-    float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; \
-    gaussian_chain_geom(p, mean, c6, s0, s1, s2, o, tau); \
-  _Pragma("unroll") \
-    for (int k = 0; k < 6; k++) row[6 * u + k] = tau[k]; \
-  } \
-  float col[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; \
-  if (p.shs) { \
-    const float3 cam = make_float3(p.campos[0], p.campos[1], p.campos[2]); \
-    const float *sh_row = p.shs + ii * 3 * (size_t)p.M; \
-    float w_unused[16]; \
-  _Pragma("unroll") \
-    for (int ch = 0; ch < 3; ch++) { \
-      const float3 unit = make_float3(ch == 0 ? 1.f : 0.f, ch == 1 ? 1.f : 0.f, ch == 2 ? 1.f : 0.f); \
-      const float3 dmean = sh_backward<1>(p.D, p.M, mean, cam, sh_row, w_unused, cl, unit); \
-      col[3 * ch] = -dmean.x; col[3 * ch + 1] = -dmean.y; col[3 * ch + 2] = -dmean.z; \
-    } \
-  } \
-  float4 *row4 = reinterpret_cast<float4 *>(row + 36); \
-  row4[0] = make_float4(col[0], col[1], col[2], col[3]); \
-  row4[1] = make_float4(col[4], col[5], col[6], col[7]); \
-  row4[2] = make_float4(col[8], 0.f, 0.f, 0.f);
-
+//
+// K views of one map (gridDim.y = K; one view: K = 1 and zero strides): view v's camera, radii, clamp flags, abort word and rows come
+// from view v's blocks.  p.cov3Ds is NOT moved on: Sigma does not depend on the view, and a batched forward writes it into view 0's
+// geometry block only (or the caller gave it) -- as k_chain_window reads it.  projmatrix_raw is shared.
 __global__ __launch_bounds__(64) void k_splat_jac(BwdParams p, const uint8_t *__restrict__ clamped, const uint32_t *__restrict__ counters,
-                                                  float *__restrict__ rows) {
-  SPLAT_JAC_ROWS(p, clamped, counters, rows)
-}
-
-// K views of one map (gridDim.y = K): view v's camera, radii, clamp flags, abort word and rows come from view v's blocks.  p.cov3Ds
-// is NOT moved on: Sigma does not depend on the view, and a batched forward writes it into view 0's geometry block only (or the
-// caller gave it) -- as k_chain_window reads it.  projmatrix_raw is shared.
-__global__ __launch_bounds__(64) void k_splat_jac_batch(BwdParams p, const uint8_t *__restrict__ clamped, const uint32_t *__restrict__ counters,
-                                                        float *__restrict__ rows, ViewStrides vs, size_t rows_stride) {
+                                                  float *__restrict__ rows, ViewStrides vs, size_t rows_stride) {
   const size_t view = blockIdx.y;
   p.viewmatrix += 16 * view;
   p.projmatrix += 16 * view;
@@ -109,7 +59,48 @@ __global__ __launch_bounds__(64) void k_splat_jac_batch(BwdParams p, const uint8
   clamped = gsaj_shift(clamped, view * vs.geom);
   counters = gsaj_shift(counters, view * vs.image);
   rows = gsaj_shift(rows, view * rows_stride);
-  SPLAT_JAC_ROWS(p, clamped, counters, rows)
+  if (counters[4]) return;
+  const int idx = blockIdx.x * 64 + threadIdx.x;
+  if (idx >= p.P) return;
+  const size_t ii = (size_t)idx;
+  const int radius = p.radii[ii];
+  const float3 mean = make_float3(p.means3D[3 * ii], p.means3D[3 * ii + 1], p.means3D[3 * ii + 2]);
+  float c6[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) c6[k] = p.cov3Ds[6 * ii + k];
+  uint8_t cl[3] = {0, 0, 0};
+  if (p.shs) {
+    cl[0] = clamped[3 * ii]; cl[1] = clamped[3 * ii + 1]; cl[2] = clamped[3 * ii + 2];
+  }
+  if (radius <= 0) return;
+  float *row = rows + ii * JROW_F;
+#pragma unroll 1
+  for (int u = 0; u < 6; u++) {
+    const float4 s0 = make_float4(u == 0 ? 1.f : 0.f, u == 1 ? 1.f : 0.f, u == 2 ? 1.f : 0.f, u == 3 ? 1.f : 0.f);
+    const float4 s1 = make_float4(u == 4 ? 1.f : 0.f, 0.f, 0.f, 0.f);
+    const float4 s2 = make_float4(0.f, u == 5 ? 1.f : 0.f, 0.f, 0.f);
+    GaussianGrads o;
+    float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    gaussian_chain_geom(p, mean, c6, s0, s1, s2, o, tau);
+#pragma unroll
+    for (int k = 0; k < 6; k++) row[6 * u + k] = tau[k];
+  }
+  float col[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (p.shs) {
+    const float3 cam = make_float3(p.campos[0], p.campos[1], p.campos[2]);
+    const float *sh_row = p.shs + ii * 3 * (size_t)p.M;
+    float w_unused[16];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      const float3 unit = make_float3(ch == 0 ? 1.f : 0.f, ch == 1 ? 1.f : 0.f, ch == 2 ? 1.f : 0.f);
+      const float3 dmean = sh_backward<1>(p.D, p.M, mean, cam, sh_row, w_unused, cl, unit);
+      col[3 * ch] = -dmean.x; col[3 * ch + 1] = -dmean.y; col[3 * ch + 2] = -dmean.z;
+    }
+  }
+  float4 *row4 = reinterpret_cast<float4 *>(row + 36);
+  row4[0] = make_float4(col[0], col[1], col[2], col[3]);
+  row4[1] = make_float4(col[4], col[5], col[6], col[7]);
+  row4[2] = make_float4(col[8], 0.f, 0.f, 0.f);
 }
 
 // ---- forward-mode compositor ----------------------------------------------------------------------------------------------
@@ -374,29 +365,15 @@ __device__ __forceinline__ void render_jac_body(
   }
 }
 
-template <bool LOSS>
+// K views of one map (gridDim.y = K; one view: K = 1 and zero strides), the loss-fused forms: the body on view v's blocks.  Every
+// per-view pointer is moved on by blockIdx.y x its stride (workgroup-uniform: scalar adds), as k_render_fwd / k_render_bwd do; view v
+// owns gridDim.x partial rows.  The explicit form (LOSS = false) is one view's: launched with gridDim.y = 1 only, it moves nothing.
+template <bool LOSS, bool JOINT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_render_jac(
     int W, int H, int gx, int tiles, int P, ImageWS im, const float4 *__restrict__ splat, const float4 *__restrict__ splat16,
     const float *__restrict__ bg, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ taken,
-    const float4 *__restrict__ rows, JacOut jo, FusedLoss fl) {
-  render_jac_body<LOSS, false>(W, H, gx, tiles, P, im, splat, splat16, bg, point_list, taken, rows, jo, fl);
-}
-
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_render_jac8(
-    int W, int H, int gx, int tiles, int P, ImageWS im, const float4 *__restrict__ splat, const float4 *__restrict__ splat16,
-    const float *__restrict__ bg, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ taken,
-    const float4 *__restrict__ rows, JacOut jo, FusedLoss fl) {
-  render_jac_body<true, true>(W, H, gx, tiles, P, im, splat, splat16, bg, point_list, taken, rows, jo, fl);
-}
-
-// K views of one map (gridDim.y = K), the loss-fused forms only: the same body on view v's blocks.  Every per-view pointer is moved on
-// by blockIdx.y x its stride (workgroup-uniform: scalar adds), as k_render_fwd / k_render_bwd do; view v owns gridDim.x partial rows.
-template <bool JOINT>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_render_jac_batch(
-    int W, int H, int gx, int tiles, int P, ImageWS im, const float4 *__restrict__ splat, const float4 *__restrict__ splat16,
-    const float *__restrict__ bg, const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ taken,
     const float4 *__restrict__ rows, JacOut jo, FusedLoss fl, ViewStrides vs, size_t rows_stride) {
-  {
+  if (LOSS) {
     const size_t view = blockIdx.y, HWv = (size_t)H * W;
     im = image_view(im, view * vs.image);
     splat = gsaj_shift(splat, view * vs.geom);
@@ -408,7 +385,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     jo.partials += view * (size_t)gridDim.x * (JOINT ? GN8_ROW : GN_ROW);
     fused_loss_view(fl, view, HWv, 0);  // (no loss partials here: the sums are slots of jo.partials)
   }
-  render_jac_body<true, JOINT>(W, H, gx, tiles, P, im, splat, splat16, bg, point_list, taken, rows, jo, fl);
+  render_jac_body<LOSS, JOINT>(W, H, gx, tiles, P, im, splat, splat16, bg, point_list, taken, rows, jo, fl);
 }
 
 // ---- the partial rows summed in slot order, in fp64 (gn_sum_rows: gn_state.h) ----------------------------------------------------
@@ -529,11 +506,10 @@ __device__ __forceinline__ void gn_step_body(const GnStepParams &p) {
   if (!ok) st[PS_CONV] = 0.f;
 }
 
-__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_step(GnStepParams p) { gn_step_body<6>(p); }
-__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn8_step(GnStepParams p) { gn_step_body<8>(p); }
-
-// K states in one launch: workgroup v is k_gn_step / k_gn8_step on view v's rows (p.n of them), state and skip word.  active [K]
-// bytes or NULL: an inactive view's state is not touched.  The projection matrix and the LM scalars are shared.
+// K states in one launch (one state: K = 1): workgroup v steps view v's rows (p.n of them), state and skip word.  active [K] bytes or
+// NULL: an inactive view's state is not touched.  The projection matrix and the LM scalars are shared.
+// (gn_step_view works on its own copy of the kernel's argument: moved on in place, in the kernel's own text, the state's accepted count
+// is fetched by a vector load where this form has a scalar one -- the instructions the batched step always had.)
 template <int NX>
 __device__ __forceinline__ void gn_step_view(GnStepParams p, const uint8_t *__restrict__ active, size_t skip_stride) {
   constexpr int ROW = NX == 8 ? GN8_ROW : GN_ROW, STATE = NX == 8 ? GSAJ_GN8_STATE_FLOATS : GSAJ_GN_STATE_FLOATS;
@@ -544,11 +520,9 @@ __device__ __forceinline__ void gn_step_view(GnStepParams p, const uint8_t *__re
   if (p.skip) p.skip = gsaj_shift(p.skip, v * skip_stride);
   gn_step_body<NX>(p);
 }
-__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_step_batch(GnStepParams p, const uint8_t *__restrict__ active, size_t skip_stride) {
-  gn_step_view<6>(p, active, skip_stride);
-}
-__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn8_step_batch(GnStepParams p, const uint8_t *__restrict__ active, size_t skip_stride) {
-  gn_step_view<8>(p, active, skip_stride);
+template <int NX>
+__global__ __launch_bounds__(GN_SUM_THREADS) void k_gn_step(GnStepParams p, const uint8_t *__restrict__ active, size_t skip_stride) {
+  gn_step_view<NX>(p, active, skip_stride);
 }
 
 // One wave: the view of smallest accepted loss among the views that are active, have accepted a pose and whose loss is finite; ties
@@ -580,48 +554,21 @@ __global__ __launch_bounds__(64) void k_gn_select(int K, const float *__restrict
 size_t gsaj_jac_rows_bytes(int P) { return gsaj_align(sizeof(float) * JROW_F * (size_t)(P > 0 ? P : 1)); }
 int gsaj_jac_slots(int W, int H) { return gsaj_fwd_loss_slots(W, H); }
 
-int launch_splat_jac(const BwdParams &p, const GeomWS &g, const ImageWS &im, float *rows, hipStream_t s) {
+int launch_splat_jac(const BwdParams &p, int K, const GeomWS &g, const ImageWS &im, float *rows, ViewStrides vs, size_t rows_stride,
+                     hipStream_t s) {
   const int nblk = (p.P + 63) / 64;
-  hipLaunchKernelGGL(k_splat_jac, dim3(nblk), dim3(64), 0, s, p, g.clamped, im.counters, rows);
+  hipLaunchKernelGGL(k_splat_jac, dim3(nblk, K), dim3(64), 0, s, p, g.clamped, im.counters, rows, vs, rows_stride);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }
 
-int launch_render_jac(const BwdParams &p, const float *bg, const GeomWS &g, const BinWS &b, const ImageWS &im, const float *rows,
-                      const JacOut &jo, const FusedLoss *fl, int joint, hipStream_t s) {
-  const int W = p.W, H = p.H, P = p.P, grid_x = p.grid_x, tiles = p.grid_x * p.grid_y;
-  const unsigned nblk = (unsigned)gsaj_jac_slots(W, H);
-  if (fl && joint)
-    hipLaunchKernelGGL(k_render_jac8, dim3(nblk), dim3(64), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg, b.point_list, b.taken,
-                       reinterpret_cast<const float4 *>(rows), jo, *fl);
-  else if (fl)
-    hipLaunchKernelGGL(k_render_jac<true>, dim3(nblk), dim3(64), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg, b.point_list, b.taken,
-                       reinterpret_cast<const float4 *>(rows), jo, *fl);
-  else
-    hipLaunchKernelGGL(k_render_jac<false>, dim3(nblk), dim3(64), 0, s, W, H, grid_x, tiles, P, im, g.splat, g.splat16, bg, b.point_list, b.taken,
-                       reinterpret_cast<const float4 *>(rows), jo, FusedLoss{});
-  GSAJ_HIP_CHECK(hipGetLastError());
-  return GSAJ_OK;
-}
-
-int launch_splat_jac_batch(const BwdParams &p, int K, const GeomWS &g, const ImageWS &im, float *rows, ViewStrides vs, hipStream_t s) {
-  const int nblk = (p.P + 63) / 64;
-  hipLaunchKernelGGL(k_splat_jac_batch, dim3(nblk, K), dim3(64), 0, s, p, g.clamped, im.counters, rows, vs, gsaj_jac_rows_bytes(p.P));
-  GSAJ_HIP_CHECK(hipGetLastError());
-  return GSAJ_OK;
-}
-
-int launch_render_jac_batch(const BwdParams &p, int K, const float *bg, const Carved &c, const float *rows, const JacOut &jo,
-                            const FusedLoss &fl, int joint, hipStream_t s) {
-  const int W = p.W, H = p.H, P = p.P, grid_x = p.grid_x, tiles = p.grid_x * p.grid_y;
-  const dim3 grid((unsigned)gsaj_jac_slots(W, H), (unsigned)K);
-  const size_t rows_stride = gsaj_jac_rows_bytes(P);
-  if (joint)
-    hipLaunchKernelGGL(k_render_jac_batch<true>, grid, dim3(64), 0, s, W, H, grid_x, tiles, P, c.im, c.g.splat, c.g.splat16, bg, c.b.point_list,
-                       c.b.taken, reinterpret_cast<const float4 *>(rows), jo, fl, c.vs, rows_stride);
-  else
-    hipLaunchKernelGGL(k_render_jac_batch<false>, grid, dim3(64), 0, s, W, H, grid_x, tiles, P, c.im, c.g.splat, c.g.splat16, bg, c.b.point_list,
-                       c.b.taken, reinterpret_cast<const float4 *>(rows), jo, fl, c.vs, rows_stride);
+// fl == NULL: the explicit form (K = 1: its kernel moves no pointer on)
+int launch_render_jac(const BwdParams &p, int K, const float *bg, const Carved &c, const float *rows, size_t rows_stride, const JacOut &jo,
+                      const FusedLoss *fl, int joint, hipStream_t s) {
+  const dim3 grid((unsigned)gsaj_jac_slots(p.W, p.H), (unsigned)K);
+  const auto kernel = !fl ? k_render_jac<false, false> : joint ? k_render_jac<true, true> : k_render_jac<true, false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(64), 0, s, p.W, p.H, p.grid_x, p.grid_x * p.grid_y, p.P, c.im, c.g.splat, c.g.splat16, bg,
+                     c.b.point_list, c.b.taken, reinterpret_cast<const float4 *>(rows), jo, fl ? *fl : FusedLoss{}, c.vs, rows_stride);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }
@@ -636,72 +583,50 @@ extern "C" int gsaj_gn_state_floats(void) { return GSAJ_GN_STATE_FLOATS; }
 
 extern "C" int gsaj_gn8_state_floats(void) { return GSAJ_GN8_STATE_FLOATS; }
 
-static int gn_step_launch(const char *who, bool joint, const float *gn_partials, int n_partials, float lambda_init, float nu, float lambda_min,
-                          float lambda_max, float converged_threshold, const float *projection_matrix, float *gn_state,
-                          const uint32_t *skip, void *stream) {
-  if (!gn_partials || n_partials <= 0 || !gn_state || !(nu > 1.f) || !(lambda_min > 0.f) || !(lambda_max >= lambda_min) ||
-      !(lambda_init >= lambda_min) || !(lambda_init <= lambda_max)) {
-    gsaj_set_error("%s: gn_partials, n_partials > 0 and gn_state are required; nu > 1, 0 < lambda_min <= lambda_init <= lambda_max", who);
+// the one launcher of the four step entry points; `required`: the caller's words for what it requires (the K of a batched call included)
+static int gn_step_launch(const char *who, const char *required, bool joint, int K, const uint8_t *active, size_t skip_stride,
+                          const GnStepParams &p, hipStream_t s) {
+  if (K <= 0 || !p.partials || p.n <= 0 || !p.st || !(p.nu > 1.f) || !(p.lambda_min > 0.f) || !(p.lambda_max >= p.lambda_min) ||
+      !(p.lambda_init >= p.lambda_min) || !(p.lambda_init <= p.lambda_max)) {
+    gsaj_set_error("%s: %s are required; nu > 1, 0 < lambda_min <= lambda_init <= lambda_max", who, required);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  GnStepParams p;
-  p.partials = gn_partials; p.n = n_partials; p.lambda_init = lambda_init; p.nu = nu; p.lambda_min = lambda_min; p.lambda_max = lambda_max;
-  p.threshold = converged_threshold; p.projection = projection_matrix; p.st = gn_state; p.skip = skip;
   if (joint)
-    hipLaunchKernelGGL(k_gn8_step, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_gn_step<8>, dim3((unsigned)K), dim3(GN_SUM_THREADS), 0, s, p, active, skip_stride);
   else
-    hipLaunchKernelGGL(k_gn_step, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_gn_step<6>, dim3((unsigned)K), dim3(GN_SUM_THREADS), 0, s, p, active, skip_stride);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }
+static const char *const GN_STEP_REQUIRED = "gn_partials, n_partials > 0 and gn_state";
+static const char *const GN_STEP_BATCH_REQUIRED = "K > 0, gn_partials, n_partials > 0 and gn_states";
 
 extern "C" int gsaj_pose_gn_step(const float *gn_partials, int n_partials, float lambda_init, float nu, float lambda_min, float lambda_max,
                                  float converged_threshold, const float *projection_matrix, float *gn_state, const uint32_t *skip,
                                  void *stream) {
-  return gn_step_launch("gsaj_pose_gn_step", false, gn_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold,
-                        projection_matrix, gn_state, skip, stream);
+  const GnStepParams p{gn_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold, projection_matrix, gn_state, skip};
+  return gn_step_launch("gsaj_pose_gn_step", GN_STEP_REQUIRED, false, 1, nullptr, 0, p, (hipStream_t)stream);
 }
 
 extern "C" int gsaj_pose_gn8_step(const float *gn8_partials, int n_partials, float lambda_init, float nu, float lambda_min, float lambda_max,
                                   float converged_threshold, const float *projection_matrix, float *gn8_state, const uint32_t *skip,
                                   void *stream) {
-  return gn_step_launch("gsaj_pose_gn8_step", true, gn8_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold,
-                        projection_matrix, gn8_state, skip, stream);
-}
-
-// ---- K states in one launch ----------------------------------------------------------------------------------------------------
-struct GnBatch {  // what the batched step adds to the single one's arguments
-  int K;
-  const uint8_t *active;
-  size_t skip_stride;
-};
-
-static int gn_step_batch_launch(const char *who, bool joint, const GnBatch &b, const GnStepParams &p, hipStream_t s) {
-  if (b.K <= 0 || !p.partials || p.n <= 0 || !p.st || !(p.nu > 1.f) || !(p.lambda_min > 0.f) || !(p.lambda_max >= p.lambda_min) ||
-      !(p.lambda_init >= p.lambda_min) || !(p.lambda_init <= p.lambda_max)) {
-    gsaj_set_error("%s: K > 0, gn_partials, n_partials > 0 and gn_states are required; nu > 1, 0 < lambda_min <= lambda_init <= lambda_max", who);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (joint)
-    hipLaunchKernelGGL(k_gn8_step_batch, dim3((unsigned)b.K), dim3(GN_SUM_THREADS), 0, s, p, b.active, b.skip_stride);
-  else
-    hipLaunchKernelGGL(k_gn_step_batch, dim3((unsigned)b.K), dim3(GN_SUM_THREADS), 0, s, p, b.active, b.skip_stride);
-  GSAJ_HIP_CHECK(hipGetLastError());
-  return GSAJ_OK;
+  const GnStepParams p{gn8_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold, projection_matrix, gn8_state, skip};
+  return gn_step_launch("gsaj_pose_gn8_step", GN_STEP_REQUIRED, true, 1, nullptr, 0, p, (hipStream_t)stream);
 }
 
 extern "C" int gsaj_pose_gn_step_batch(int K, const float *gn_partials, int n_partials, const uint8_t *active, float lambda_init, float nu,
                                        float lambda_min, float lambda_max, float converged_threshold, const float *projection_matrix,
                                        float *gn_states, const uint32_t *skip, size_t skip_stride_bytes, void *stream) {
   const GnStepParams p{gn_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold, projection_matrix, gn_states, skip};
-  return gn_step_batch_launch("gsaj_pose_gn_step_batch", false, GnBatch{K, active, skip_stride_bytes}, p, (hipStream_t)stream);
+  return gn_step_launch("gsaj_pose_gn_step_batch", GN_STEP_BATCH_REQUIRED, false, K, active, skip_stride_bytes, p, (hipStream_t)stream);
 }
 
 extern "C" int gsaj_pose_gn8_step_batch(int K, const float *gn8_partials, int n_partials, const uint8_t *active, float lambda_init, float nu,
                                         float lambda_min, float lambda_max, float converged_threshold, const float *projection_matrix,
                                         float *gn8_states, const uint32_t *skip, size_t skip_stride_bytes, void *stream) {
   const GnStepParams p{gn8_partials, n_partials, lambda_init, nu, lambda_min, lambda_max, converged_threshold, projection_matrix, gn8_states, skip};
-  return gn_step_batch_launch("gsaj_pose_gn8_step_batch", true, GnBatch{K, active, skip_stride_bytes}, p, (hipStream_t)stream);
+  return gn_step_launch("gsaj_pose_gn8_step_batch", GN_STEP_BATCH_REQUIRED, true, K, active, skip_stride_bytes, p, (hipStream_t)stream);
 }
 
 extern "C" int gsaj_pose_gn_select(int K, const float *gn_states, int state_floats, const uint8_t *active, int *best, float *best_loss,

@@ -1,4 +1,4 @@
-"""NumPy restatements (float64) of the JOINT Gauss-Newton tracking path -- csrc/pose_jac.hip: k_render_jac8, k_gn8_step -- built on
+"""NumPy restatements (float64) of the JOINT Gauss-Newton tracking path -- csrc/pose_jac.hip: k_render_jac<true, true>, k_gn_step<8> -- built on
 tests/gn_restated.py, with the comparators the GPU tests use and a `mutant=` switch for the canaries.  TEST INFRASTRUCTURE ONLY;
 shared by tests/test_cpu_gn8.py, tests/test_gpu_pose_jacobian8.py and tests/test_gpu_gn8_tracker.py.
 
@@ -25,7 +25,7 @@ EPS, F = gn.EPS, gn.F
 MUTANTS = ("b_without_inv_ea", "a_from_ground_truth", "exposure_in_depth_row", "exposure_not_restored_on_reject")
 SYM8 = [(k, l) for k in range(8) for l in range(k, 8)]
 
-# Roundings between a pixel's (s, h, J, C, a) and an element of the kernel's H8 / g8 (k_render_jac8's epilogue, k_gn8_step).
+# Roundings between a pixel's (s, h, J, C, a) and an element of the kernel's H8 / g8 (the epilogue of k_render_jac<true, true>, k_gn_step<8>).
 # The reduction goes through two half-wave swaps and four row rotations instead of the 6-form's six butterfly steps: the SAME depth 6,
 # so the base counts are gn_restated's: g 12, H 13.  What the new columns add:
 #   the a column is the forward's colour C_ch, an fp32 INPUT of both sides: its product with s (or h J) is the term's own product,

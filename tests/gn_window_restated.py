@@ -1,5 +1,5 @@
-"""NumPy restatements (float64) for the batched Gauss-Newton path -- csrc/pose_jac.hip: k_splat_jac_batch, k_render_jac_batch,
-k_gn_step_batch / k_gn8_step_batch, k_gn_select -- TEST INFRASTRUCTURE ONLY; shared by tests/test_cpu_gn_window.py,
+"""NumPy restatements (float64) for the batched Gauss-Newton path -- csrc/pose_jac.hip: k_splat_jac, k_render_jac and
+k_gn_step<6> / k_gn_step<8> launched over K views, k_gn_select -- TEST INFRASTRUCTURE ONLY; shared by tests/test_cpu_gn_window.py,
 tests/test_gpu_pose_jacobian_batch.py and tests/test_gpu_gn_window.py.
 
 K views of one map are K independent single-view problems, so the per-view restatement is tests/gn_restated.py / gn8_restated.py
