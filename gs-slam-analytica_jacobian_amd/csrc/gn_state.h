@@ -26,6 +26,11 @@ static_assert(GN_G + 6 <= GSAJ_GN_STATE_FLOATS && GSAJ_GN_STATE_FLOATS == 136 &&
 #define GN8_ACC_EXP (GN8_G + 8)
 #define GN8_DEXP 78
 static_assert(GN8_ACC_EXP + 2 <= GSAJ_GN8_STATE_FLOATS && GSAJ_GN8_STATE_FLOATS == 152 && GN8_ROW == 64, "gn8_state layout");
+// A row's slots behind H and g: loss, L_rgb, L_depth, then the two floats the step does not read.  The frame-to-frame alignment
+// (align.hip) keeps the number of valid pixels in the first of them (gsaj/_gn_state.py: ROW_VALID, Layout.row_valid).  Constants of
+// the ROW, not offsets of the state: the #defines of this file are the state's table.
+constexpr int GN_ROW_VALID = 21 + 6 + 3, GN8_ROW_VALID = 36 + 8 + 3;
+static_assert(GN_ROW_VALID + 2 == GN_ROW && GN8_ROW_VALID + 2 <= GN8_ROW, "the rows' count slots");
 
 // ---- the partial rows summed in slot order, in fp64 ------------------------------------------------------------------------
 // GN_SUM_THREADS threads = GROUPS row groups x ROW columns (32 groups of the 32-float row, 16 of the joint form's 64-float row): thread

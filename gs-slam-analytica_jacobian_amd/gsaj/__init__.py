@@ -1,6 +1,7 @@
 """gsaj -- torch-tensor front end of libgsaj_hip.so.  Submodules are imported by name (gsaj.rasterizer, gsaj.tracking, ...);
 the package itself imports nothing, so that `from gsaj import synthetic` needs neither torch nor the library."""
-__all__ = ["GaussNewtonTracker", "GaussNewtonWindow", "PyramidGaussNewtonTracker", "StereoMatcher", "StereoIngest", "RgbdAligner"]
+__all__ = ["GaussNewtonTracker", "GaussNewtonWindow", "PyramidGaussNewtonTracker", "StereoMatcher", "StereoIngest", "RgbdAligner",
+           "JointRgbdAligner"]
 
 
 def __getattr__(name):
@@ -16,7 +17,7 @@ def __getattr__(name):
     if name in ("StereoMatcher", "StereoIngest"):  # a stereo pair to disparity, depth and the left colour (gsaj.stereo)
         from . import stereo
         return getattr(stereo, name)
-    if name == "RgbdAligner":  # the start pose of a new frame from the last tracked frame alone (gsaj.align)
-        from .align import RgbdAligner
-        return RgbdAligner
+    if name in ("RgbdAligner", "JointRgbdAligner"):  # the start pose of a new frame from the last tracked frame alone (gsaj.align);
+        from . import align                           # Joint: its brightness change against that frame solved with the pose
+        return getattr(align, name)
     raise AttributeError("module 'gsaj' has no attribute %r" % name)

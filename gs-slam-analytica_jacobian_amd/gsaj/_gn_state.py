@@ -25,7 +25,7 @@ _GN = dict(_POSE, lam=("GN_LAMBDA", 80, 1), acc_loss=("GN_ACC_LOSS", 81, 1), has
 _GN8 = dict(_GN, H=("GN_H", 104, 36), g=("GN8_G", 140, 8), acc_exposure=("GN8_ACC_EXP", 148, 2), dexposure=("GN8_DEXP", 78, 2))
 FIELDS = dict(pose=_POSE, gn=_GN, gn8=_GN8)
 SPANS = {kind: {k: (a, a + n) for k, (_, a, n) in fields.items()} for kind, fields in FIELDS.items()}   # kind: field -> (a, b)
-ROW_VALID = 30   # gsaj_rgbd_align's gn_row: the slot that holds the number of valid pixels
+ROW_VALID = 30   # gsaj_rgbd_align's gn_row: the slot that holds the number of valid pixels (gsaj_rgbd_align8's: Layout.row_valid)
 
 
 class Layout:
@@ -49,6 +49,9 @@ class Layout:
                 self.row = int(re.search(r"#define GSAJ_%s_PARTIAL_FLOATS (\d+)" % kind.upper(), fh.read()).group(1))
             if self.row < fields["H"][2] + fields["g"][2] + 5:
                 raise _lib.GsajError("gsaj._gn_state: a %s row of %d floats does not hold H, g and the five sums" % (kind, self.row))
+            # gsaj_rgbd_align / gsaj_rgbd_align8: the slot of the row that holds the number of valid pixels (csrc/gn_state.h
+            # GN_ROW_VALID, GN8_ROW_VALID) -- behind H, g and the three losses
+            self.row_valid = fields["H"][2] + fields["g"][2] + 3
 
 
 _LAYOUTS = {}

@@ -151,6 +151,7 @@ SIGNATURES = {
     "gsaj_stereo_match": (c_int, [c_int, c_int, P, c_size_t, P, c_size_t] + [c_int] * 8 + [P, c_size_t, P, P, c_double, P]),
     "gsaj_rgbd_align_partial_rows": (c_int, [c_int, c_int]),
     "gsaj_rgbd_align": (c_int, [c_int, c_int] + [c_float] * 4 + [P] * 6 + [c_float] * 7 + [P] * 6),
+    "gsaj_rgbd_align8": (c_int, [c_int, c_int] + [c_float] * 4 + [P] * 6 + [c_float] * 7 + [P] * 7),
 }
 
 _lib = None

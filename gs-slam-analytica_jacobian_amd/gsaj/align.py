@@ -6,11 +6,14 @@ and depth residual, their pose Jacobians, the 6x6 normal equations of the iterat
 valid pixels) -> gsaj_pose_gn_step on that ONE row (accept / reject, damping, the Cholesky solve, W2C <- Exp(tau) W2C).  The levels of
 both frames come from gsaj.pyramid.ImagePyramid, the state goes from level to level through gsaj_pose_gn_relevel, exactly as in
 gsaj.PyramidGaussNewtonTracker.  There is no CPU path and no host read before result().
+
+JointRgbdAligner is the joint form: the affine brightness change of the new frame against the reference, I_c = e^a I_r + b, is
+solved with the pose -- gsaj_rgbd_align8 -> gsaj_pose_gn8_step on the gn8 state, the same two calls per iteration.
 """
 import torch
 
 from . import _lib
-from ._gn_state import ROW_VALID, GnViews, check_schedule, init_state
+from ._gn_state import GnViews, check_schedule, init_state
 from ._loop import require_device, stream
 from .pyramid import MAX_LEVELS, ImagePyramid, level_camera
 
@@ -20,6 +23,13 @@ def _residuals(al, l, depth):  # (the device work of one iteration, first half: 
     W, H, fx, fy, cx, cy = al.cams[l]
     rc, rd, cc, cd = al._level(al._ref, l) + al._level(al._cur, l)
     with torch.cuda.device(al.dev):
+        if al.solve_exposure:   # (the joint form: the state's exposure is read on the device, the gain it used is not asked for)
+            _lib.check(al.lib.gsaj_rgbd_align8(W, H, fx, fy, cx, cy, rc.data_ptr(), rd.data_ptr(), al.ref_w2c.data_ptr(), cc.data_ptr(),
+                                               cd.data_ptr() if depth else None, al.state.data_ptr(), al.w_depth, al.delta_photo,
+                                               al.delta_depth, al.depth_edge_ratio, al.min_depth, al.max_depth, al.min_overlap,
+                                               al.rows.data_ptr(), al.row.data_ptr(), None, None, None, None, stream(al.dev)),
+                       "gsaj_rgbd_align8")
+            return
         _lib.check(al.lib.gsaj_rgbd_align(W, H, fx, fy, cx, cy, rc.data_ptr(), rd.data_ptr(), al.ref_w2c.data_ptr(), cc.data_ptr(),
                                           cd.data_ptr() if depth else None, al.state.data_ptr(), al.w_depth, al.delta_photo, al.delta_depth,
                                           al.depth_edge_ratio, al.min_depth, al.max_depth, al.min_overlap, al.rows.data_ptr(),
@@ -27,9 +37,10 @@ def _residuals(al, l, depth):  # (the device work of one iteration, first half: 
 
 
 def _step(al, l):  # (device work too)
+    step = al.lib.gsaj_pose_gn8_step if al.solve_exposure else al.lib.gsaj_pose_gn_step
     with torch.cuda.device(al.dev):
-        _lib.check(al.lib.gsaj_pose_gn_step(al.row.data_ptr(), 1, *al.lm_args, al.projections[l].data_ptr(), al.state.data_ptr(), None,
-                                            stream(al.dev)), "gsaj_pose_gn_step")
+        _lib.check(step(al.row.data_ptr(), 1, *al.lm_args, al.projections[l].data_ptr(), al.state.data_ptr(), None, stream(al.dev)),
+                   "gsaj_pose_gn8_step" if al.solve_exposure else "gsaj_pose_gn_step")
 
 
 def _relevel(al, l):  # (device work too)
@@ -55,7 +66,9 @@ class RgbdAligner(GnViews):
     for one image size.  w_depth weighs the depth term against the photometric one; delta_photo / delta_depth: the residual below which
     an L1 term is a quadratic; depth_edge_ratio: the relative spread of the four depth taps (and of a coarse pixel's children) beyond
     which a pixel straddles a discontinuity and carries no depth term; min_overlap: the share of valid pixels below which a level
-    gives no step.  The Levenberg-Marquardt arguments are GaussNewtonTracker's."""
+    gives no step.  The Levenberg-Marquardt arguments are GaussNewtonTracker's.  The photometric term has no exposure model: for frames
+    whose brightness changes (auto-exposure), JointRgbdAligner below.  (solve_exposure, False here, is GnViews' switch between the gn
+    and the gn8 layout: the state, the rows and the calls of an iteration follow it.)"""
 
     def __init__(self, W, H, fx, fy, cx, cy, device, levels=2, w_depth=1.0, delta_photo=0.01, delta_depth=0.01, depth_edge_ratio=0.1,
                  min_depth=0.01, max_depth=100.0, min_overlap=0.0, znear=0.01, zfar=100.0, lambda_init=1e-3, nu=4.0, lambda_min=1e-7,
@@ -161,21 +174,28 @@ class RgbdAligner(GnViews):
         """8 iterations at the coarsest level, 6 at every level below it."""
         return [8] + [6] * self.levels
 
-    def _reset(self, w2c):
-        """A new solve: pose, camera matrices of the coarsest level, no accepted step, lambda_init -- device operations only."""
+    def _reset(self, w2c, exposure=None):
+        """A new solve: pose, camera matrices of the coarsest level, no accepted step, lambda_init -- device operations only.  exposure
+        (joint form): the start (a, b), a device tensor of 2; None: (0, 0)."""
         init_state(self.state, self._layout, w2c, self.projections[self.levels], None, self.lm_args[0], rigid=True)
+        if exposure is not None:
+            self.state[self._layout.sl["exposure"]] = exposure
+            self.state[self._layout.sl["acc_exposure"]] = exposure
 
     def align(self, color, depth=None, w2c_init=None, schedule=None):
         """Aligns the reference against this frame (colour [3,H,W], depth [H,W] or None: the photometric term alone).  w2c_init: the
         start pose, by default the reference's -- the start the frontend takes.  schedule: the iteration counts from the coarsest level
         to level 0 (levels + 1 of them).  No host read; returns the numbers run per level."""
+        return self._align(color, depth, w2c_init, schedule)
+
+    def _align(self, color, depth, w2c_init, schedule, exposure=None):
         if not self._ref.filled:
             raise _lib.GsajError("set_reference() first")
         schedule = self.default_schedule() if schedule is None else schedule if isinstance(schedule, (list, tuple)) else [schedule]
         schedule = check_schedule(schedule, self.levels, "align")
         start = self.ref_w2c if w2c_init is None else self._pose(w2c_init, "align")
         self._take(self._cur, color, depth, "align")
-        self._reset(start)
+        self._reset(start, exposure)
         at = self.levels
         for l, n in zip(range(self.levels, -1, -1), schedule):
             if not n:   # (a level with no iterations is passed over)
@@ -196,10 +216,45 @@ class RgbdAligner(GnViews):
     @property
     def overlap(self):
         """The share of valid pixels at the last level evaluated (device scalar)."""
-        return self.row[ROW_VALID] / float(self._pixels)
+        return self.row[self._layout.row_valid] / float(self._pixels)
 
     def result(self):
         """The one host read: (w2c [4,4] ndarray, overlap, accepted loss, converged)."""
         s, o = torch.cat([self.state, self.row]).cpu().numpy(), self._layout.o
-        return (s[slice(*o["acc_w2c"])].reshape(4, 4).copy(), float(s[self._layout.floats + ROW_VALID]) / float(self._pixels),
+        return (s[slice(*o["acc_w2c"])].reshape(4, 4).copy(), float(s[self._layout.floats + self._layout.row_valid]) / float(self._pixels),
                 float(s[o["acc_loss"][0]]), bool(s[o["conv"][0]] != 0.0))
+
+
+class JointRgbdAligner(RgbdAligner):
+    """RgbdAligner with the affine brightness change of the new frame solved together with the pose: the new frame is modelled as
+    e^a I_ref + b, the unknowns are [rho, theta, a, b] (gsaj_rgbd_align8 -> gsaj_pose_gn8_step on the gn8 state).  (a, b) is the new
+    frame's brightness RELATIVE TO THE REFERENCE FRAME -- auto-exposure between the two frames -- not an absolute camera exposure;
+    exposure_for() turns it into one.  The constructor, set_reference, promote, overlap, result and lm are RgbdAligner's (lm["H"] is
+    8 x 8 over [rho, theta, a, b]).  A class of its own, not a keyword of RgbdAligner: the signatures of the existing loops are kept."""
+    solve_exposure = True
+
+    def _exposure(self, exposure, who):
+        """(a, b) as a device tensor of 2: a pair of numbers, a host array or a device tensor (copied device to device)."""
+        t = torch.as_tensor(exposure, dtype=torch.float32) if not torch.is_tensor(exposure) else exposure
+        if t.numel() != 2:
+            raise _lib.GsajError("%s: an exposure is the pair (a, b), got %d values" % (who, t.numel()))
+        return t.detach().to(self.dev, torch.float32).reshape(2)
+
+    def align(self, color, depth=None, w2c_init=None, schedule=None, exposure_init=None):
+        """RgbdAligner.align; exposure_init: the start (a, b) -- a pair of numbers or a device tensor -- by default (0, 0), the
+        brightness of the reference."""
+        return self._align(color, depth, w2c_init, schedule, None if exposure_init is None else self._exposure(exposure_init, "align"))
+
+    @property
+    def relative_exposure(self):
+        """Device [2]: the accepted (a, b) -- the new frame's brightness as e^a I_ref + b."""
+        return self.accepted_exposure
+
+    def exposure_for(self, ref_exposure):
+        """Device [2]: the new frame's exposure (a_r + a, e^a b_r + b) from the reference frame's (a_r, b_r) -- a pair of numbers or a
+        device tensor such as tracker.accepted_exposure -- and the accepted (a, b); no host read.  With obs = e^a' render + b' for both
+        frames of one scene, obs_c = e^a obs_r + b = e^(a_r + a) render + (e^a b_r + b): the start exposure of the map tracker, as
+        GaussNewtonTracker.reset(w2c, exposure=) and GaussNewtonWindow.set_view(..., exposure=) take it."""
+        ref = self._exposure(ref_exposure, "exposure_for")
+        a, b = self.accepted_exposure[0], self.accepted_exposure[1]
+        return torch.stack([ref[0] + a, torch.exp(a) * ref[1] + b])

@@ -1183,6 +1183,39 @@ int gsaj_rgbd_align(int W, int H, float fx, float fy, float cx, float cy,
                     float *pix_out   /*[H,W,GSAJ_ALIGN_PIXEL_FLOATS] NULL ok*/, uint8_t *valid_out /*[H,W] NULL ok*/,
                     const uint32_t *skip /*NULL ok, as in gsaj_pose_gn_step*/, void *stream);
 
+/* The joint form -- the affine brightness change of the current frame solved with the pose (auto-exposure between two frames).
+ * The unknowns are x = [rho(3), theta(3), a, b], a and b additive as in gsaj_pose_gn8_step; the model is I_c = e^a I_r + b:
+ * (a, b) is the current frame's brightness RELATIVE TO THE REFERENCE FRAME, not an absolute camera exposure.
+ *
+ * gsaj_rgbd_align8 -- gsaj_rgbd_align with a gn8_state (a, b = gn8_state[33], [34], read on the device) and rows of
+ *   GSAJ_GN8_PARTIAL_FLOATS; the same two launches, no atomics, the same bits run to run.  Lines 0-3, 5 and 7 above are unchanged.
+ *   What differs, fp32, one rounding per operation:
+ *   4'. ea = expf(a), evaluated ONCE per workgroup (expf is not correctly rounded: gain_out, if not NULL, receives the float the
+ *       pass used; a = 0 gives exactly 1.0f);   g_I = ea I_r;   r_I = I_c - (g_I + b);   J_I as in line 4 and
+ *         J8 = [J_I[0..5], -g_I, -1.0f]          (the depth row has no exposure columns: [J_Z[0..5], 0, 0])
+ *   6'. s, h, l of both terms as in line 6, from the r_I of line 4'.  The pixel's terms, k <= l:
+ *         H8_kl = (h_I J8[k]) J8[l] + (h_Z J_Z[k]) J_Z[l]   for l < 6;      H8_kl = (h_I J8[k]) J8[l]   for l >= 6
+ *         g8_k  = s_I J8[k] + s_Z J_Z[k]                     for k < 6;      g8_k  = s_I J8[k]           for k >= 6
+ *       then l_I + l_Z, l_I, l_Z, 1, and 1 if the depth gate is open.
+ *   rows [gsaj_rgbd_align_partial_rows(W, H)][GSAJ_GN8_PARTIAL_FLOATS]: scratch as above.  gn8_row [GSAJ_GN8_PARTIAL_FLOATS], with
+ *   n = the number of valid pixels:  [0:36) H8 / n, the upper triangle by rows, [36:44) g8 / n, [44] loss / n, [45] L_photo / n,
+ *   [46] L_depth / n, [47] n, [48] the number of open depth gates, [49:64) zero -- the ONE row gsaj_pose_gn8_step is given,
+ *   n_partials = 1 (it reads [0:47)).  The overlap gate as above: H8 and g8 zero, the three losses +inf.
+ *   pix_out, valid_out: as above, r_I, s_I, h_I those of line 4'.  skip: a non-zero word changes nothing, gain_out included.
+ * GSAJ_ERR_INVALID_ARGUMENT: as gsaj_rgbd_align, with gn8_state and gn8_row in place of gn_state and gn_row. */
+int gsaj_rgbd_align8(int W, int H, float fx, float fy, float cx, float cy,
+                     const float *ref_color /*[3,H,W]*/, const float *ref_depth /*[H,W]*/,
+                     const float *ref_w2c   /*[16] device, row-major*/,
+                     const float *cur_color /*[3,H,W]*/, const float *cur_depth /*[H,W], NULL: photometric only*/,
+                     const float *gn8_state /*device; only W2C [0:16) and the exposure [33:35) are read*/,
+                     float w_depth, float delta_photo, float delta_depth, float depth_edge_ratio,
+                     float min_depth, float max_depth, float min_overlap,
+                     float *rows      /*[partial_rows][GSAJ_GN8_PARTIAL_FLOATS], no initialisation needed*/,
+                     float *gn8_row   /*[GSAJ_GN8_PARTIAL_FLOATS]: the ONE row gsaj_pose_gn8_step is given, n_partials = 1*/,
+                     float *gain_out  /*[1] NULL ok: the e^a the pass used*/,
+                     float *pix_out   /*[H,W,GSAJ_ALIGN_PIXEL_FLOATS] NULL ok*/, uint8_t *valid_out /*[H,W] NULL ok*/,
+                     const uint32_t *skip /*NULL ok, as in gsaj_pose_gn_step*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

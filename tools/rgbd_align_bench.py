@@ -11,7 +11,16 @@ Method of tools/gn_tracker_bench.py: device events, medians of `repeats` after a
                photometric only (the reference depth of these worlds is a splat render, not a surface).
 The reference frame is the render at the previous pose, the current frame the render at the true pose.
 
-usage: rgbd_align_bench.py [out.json] [window=50] [repeats=7]"""
+--exposure A B: the joint form (gsaj.JointRgbdAligner: the brightness change e^a I + b of the current frame solved with the pose) set
+against the pose-only form in the same session, the current frame's colour replaced by e^A I + B:
+  table        the analytic scene of tests/align_restated.py at 80x60, L = 2, default schedule, start at the reference pose: translation /
+               rotation error of both forms and the recovered (a, b), for m = 1, 2, with and without depth, at (0, 0), (A, B) and
+               (-0.15, 0.05)
+  align        ms per whole align() and us per iteration at every level, both forms, on 160x120 (L = 2) and cfg2's 640x480 (L = 3), with
+               the errors against the true pose and the recovered (a, b) at (A, B)
+(the map tracker is not run.)
+
+usage: rgbd_align_bench.py [out.json] [window=50] [repeats=7] [--exposure A B]"""
 import hashlib
 import json
 import math
@@ -114,25 +123,116 @@ def workload(name, cam_prev, cam, sc, levels, window, repeats, budget=30):
     return out
 
 
-def main():
-    argv = sys.argv[1:]
-    path = argv[0] if len(argv) > 0 else None
-    window = int(argv[1]) if len(argv) > 1 else 50
-    repeats = int(argv[2]) if len(argv) > 2 else 7
-    assert repeats >= 7, "median of at least 7"
-    res = []
+def time_aligner(al, cur, depth, levels, window, repeats, true):
+    """ms per whole align() and us per iteration at every level of one aligner on one frame, with where it ends."""
+    run = lambda: al.align(cur, depth)  # noqa: E731
+    for _ in range(3):
+        run()
+    w2c, overlap, loss, conv = al.result()
+    e = errors(w2c, true)
+    row = dict(ms_per_align_median_min_max=events_ms(run, repeats), overlap=round(overlap, 4), translation_error=e[0], rotation_error=e[1],
+               accepted_loss=loss, accepted=float(al.lm["accepted"]), rejected=float(al.lm["rejected"]))
+    if al.solve_exposure:
+        row["recovered_a_b"] = [round(float(v), 6) for v in al.relative_exposure.cpu()]
+    per = {}
+    for l in range(levels, -1, -1):
+        def its(l=l):
+            for _ in range(window):
+                A._residuals(al, l, depth is not None)
+                A._step(al, l)
+
+        al._reset(al.ref_w2c)
+        A._relevel(al, l)
+        its()
+        per[str(l)] = [round(1e3 * x, 2) for x in events_ms(its, repeats, per=window)]
+    row["us_per_iteration_per_level_median_min_max"] = per
+    return row
+
+
+def exposure_workload(name, cam_prev, cam, sc, levels, window, repeats, a, b):
+    W, H = cam["W"], cam["H"]
+    prev = np.ascontiguousarray(cam_prev["viewmatrix"].T).astype(np.float32)
+    true = np.ascontiguousarray(cam["viewmatrix"].T).astype(np.float64)
+    ref, cur = render(cam_prev, sc), render(cam, sc)
+    bright = math.exp(a) * cur[0] + b
+    before, before_rot = errors(prev, true)
+    out = dict(workload=name, W=W, H=H, levels=levels, brightness_a_b=[a, b], start_translation_error=before, start_rotation_error=before_rot)
+    for form, cls in (("pose_only", A.RgbdAligner), ("joint", A.JointRgbdAligner)):
+        al = cls(W, H, cam["fx"], cam["fy"], cam["cx"], cam["cy"], DEV, levels=levels)
+        al.set_reference(ref[0], ref[1], prev)
+        out[form] = {key: time_aligner(al, bright, depth, levels, window, repeats, true) for key, depth in (("rgbd", cur[1]), ("photometric", None))}
+    return out
+
+
+def exposure_table(a, b):
+    """The device's version of the restated loops' table (tests/test_cpu_align_joint.py), on the analytic scene."""
+    sys.path[:0] = [os.path.join(ROOT, "tests"), ROOT]   # (the restatements, and the oracle package they import)
+    import align_joint_restated as aj
+    import align_restated as ar
+    cam, rows = ar.camera(), []
+    dev = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(DEV)  # noqa: E731
+    for m in (1.0, 2.0):
+        for ea, eb in ((0.0, 0.0), (a, b), (-0.15, 0.05)):
+            for depth in (True, False):
+                case = aj.behaviour_case8(m, depth, ea, eb)
+                row = dict(m=m, a=ea, b=eb, term="depth" if depth else "photo", start=[round(v, 5) for v in ar.pose_error(case["w2c"], ar.motion(m))])
+                for form, cls in (("pose_only", A.RgbdAligner), ("joint", A.JointRgbdAligner)):
+                    al = cls(cam["W"], cam["H"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], DEV, levels=2)
+                    al.set_reference(dev(case["ref_color"]), dev(case["ref_depth"]), case["ref_w2c"])
+                    al.align(dev(case["cur_color"]), dev(case["cur_depth"]))
+                    row[form] = [round(v, 5) for v in ar.pose_error(al.result()[0], ar.motion(m))]
+                    if al.solve_exposure:
+                        row["recovered_a_b"] = [round(float(v), 4) for v in al.relative_exposure.cpu()]
+                rows.append(row)
+    return rows
+
+
+def exposure_main(path, window, repeats, a, b):
+    table = exposure_table(a, b)
     W, H, F = 160, 120, 140.0
     cams = syn.keyframe_cameras(4, radius=0.25, W=W, H=H, fx=F, fy=F, cx=W / 2 - 0.5, cy=H / 2 - 0.5)
     sc = syn.make_scene(3000, 21, cams[2], z_range=(1.0, 4.0), log_scale_range=(math.log(0.02), math.log(0.1)))
-    for k in range(1, 4):
-        res.append(workload("160x120, 3000 Gaussians, frame %d from frame %d" % (k, k - 1), cams[k - 1], cams[k], sc, 2, window, repeats))
+    res = [exposure_workload("160x120, 3000 Gaussians, frame 1 from frame 0", cams[0], cams[1], sc, 2, window, repeats, a, b)]
+    cam2, sc2, prev2 = cfg2_pair()
+    res.append(exposure_workload("cfg2 (640x480, 50 000 Gaussians), previous pose 1.2 cm / 0.3 degrees off", prev2, cam2, sc2, 3, window, repeats, a, b))
+    text = json.dumps(dict(device=torch.cuda.get_device_name(0), csrc_sha1=csrc_sha1(), window=window, repeats=repeats, table=table,
+                           cases=res), indent=1)
+    print(text)
+    if path:
+        with open(path, "w") as fh:
+            fh.write(text + "\n")
+
+
+def cfg2_pair():
     cam2, sc2 = syn.config_scene("cfg2")
     true2 = np.ascontiguousarray(cam2["viewmatrix"].T).astype(np.float64)
     a = math.radians(0.3)
     d = np.eye(4)
     d[:3, :3] = np.array([[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
     d[:3, 3] = [0.012, -0.008, 0.01]
-    prev2 = syn.make_camera((d @ true2), **{k: cam2[k] for k in ("W", "H", "fx", "fy", "cx", "cy")})
+    return cam2, sc2, syn.make_camera((d @ true2), **{k: cam2[k] for k in ("W", "H", "fx", "fy", "cx", "cy")})
+
+
+def main():
+    argv = sys.argv[1:]
+    exposure = None
+    if "--exposure" in argv:
+        i = argv.index("--exposure")
+        exposure = (float(argv[i + 1]), float(argv[i + 2]))
+        del argv[i:i + 3]
+    path = argv[0] if len(argv) > 0 else None
+    window = int(argv[1]) if len(argv) > 1 else 50
+    repeats = int(argv[2]) if len(argv) > 2 else 7
+    assert repeats >= 7, "median of at least 7"
+    if exposure is not None:
+        return exposure_main(path, window, repeats, *exposure)
+    res = []
+    W, H, F = 160, 120, 140.0
+    cams = syn.keyframe_cameras(4, radius=0.25, W=W, H=H, fx=F, fy=F, cx=W / 2 - 0.5, cy=H / 2 - 0.5)
+    sc = syn.make_scene(3000, 21, cams[2], z_range=(1.0, 4.0), log_scale_range=(math.log(0.02), math.log(0.1)))
+    for k in range(1, 4):
+        res.append(workload("160x120, 3000 Gaussians, frame %d from frame %d" % (k, k - 1), cams[k - 1], cams[k], sc, 2, window, repeats))
+    cam2, sc2, prev2 = cfg2_pair()
     res.append(workload("cfg2 (640x480, 50 000 Gaussians), previous pose 1.2 cm / 0.3 degrees off", prev2, cam2, sc2, 3, window, repeats))
     text = json.dumps(dict(device=torch.cuda.get_device_name(0), csrc_sha1=csrc_sha1(), window=window, repeats=repeats, cases=res), indent=1)
     print(text)
