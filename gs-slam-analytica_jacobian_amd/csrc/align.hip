@@ -1,17 +1,19 @@
 // align.hip -- frame-to-frame RGB-D alignment (include/gsaj.h "frame-to-frame alignment"): the start pose of a new frame from the
 // last tracked frame alone, no map, no binning, no lists.
-//   k_rgbd_align        one thread per REFERENCE pixel: back-project, transform, project into the current frame, bilinear sample,
-//                       photometric and depth residual with their pose Jacobians, IRLS seed / curvature / loss; the 32 partials of a
-//                       256-thread workgroup (64 x 4 pixels, lane = x) folded in registers (wave_reduce.h) and across its four waves
-//                       through LDS in a fixed order: ONE row of GSAJ_GN_PARTIAL_FLOATS per workgroup, no atomics
-//   k_rgbd_align_fold   one workgroup: the rows added in a fixed order in fp64, normalised by the number of valid pixels, the overlap
-//                       gate -> the one row gsaj_pose_gn_step takes with n_partials = 1
-//   k_rgbd_align8 / k_rgbd_align8_fold   the joint form (gsaj_rgbd_align8): the affine brightness change e^a I_r + b of the current
-//                       frame against the reference solved with the pose.  The same pass with two more Jacobian columns in the
-//                       photometric term: 49 partials per thread (H8 36, g8 8, three losses, two counts), five reduce10 per wave,
-//                       ONE row of GSAJ_GN8_PARTIAL_FLOATS per workgroup; the fold is gn_sum_rows<GN8_ROW> -> gsaj_pose_gn8_step's row.
-//                       The pixel pass is a second kernel (see there why); the two folds are one body.
-// Compiled without FMA contraction: tests/align_restated.py mirrors the per-pixel arithmetic one fp32 rounding at a time.
+//   rgbd_align_body<JOINT>   the pixel pass of both forms, one thread per REFERENCE pixel: back-project, transform, project into the
+//                       current frame, bilinear sample, photometric and depth residual with their Jacobians, IRLS seed / curvature /
+//                       loss; the partials of a 256-thread workgroup (64 x 4 pixels, lane = x) folded in registers (wave_reduce.h) and
+//                       across its four waves through LDS in a fixed order: ONE row per workgroup, no atomics
+//   k_rgbd_align        the pose-only form (gsaj_rgbd_align): 32 partials per thread (H 21, g 6, three losses, two counts), three
+//                       reduce10 and a reduce4 per wave, a row of GSAJ_GN_PARTIAL_FLOATS
+//   k_rgbd_align8       the joint form (gsaj_rgbd_align8): the affine brightness change e^a I_r + b of the current frame against the
+//                       reference solved with the pose.  Two more Jacobian columns in the photometric term: 49 partials per thread
+//                       (H8 36, g8 8, three losses, two counts), five reduce10 per wave, a row of GSAJ_GN8_PARTIAL_FLOATS
+//   rgbd_align_fold_body<ROW, VALID>   one workgroup: the rows added in a fixed order in fp64 (gn_sum_rows), normalised by the number of
+//                       valid pixels, the overlap gate -> the one row gsaj_pose_gn_step / gsaj_pose_gn8_step takes with n_partials = 1
+//                       (k_rgbd_align_fold, k_rgbd_align8_fold)
+// Compiled without FMA contraction: tests/align_restated.py and tests/align_joint_restated.py mirror the per-pixel arithmetic one fp32
+// rounding at a time, so both forms' floats depend on the expression trees below and on nothing the register allocator decides.
 #include "gsaj_common.h"
 #include "gn_state.h"
 #include "wave_reduce.h"
@@ -44,165 +46,30 @@ __device__ __forceinline__ void al_irls(float r, float kappa, float delta, float
   l = kappa * (ar >= delta ? ar - 0.5f * delta : (r * r) / (2.f * delta));
 }
 
-__global__ __launch_bounds__(256) void k_rgbd_align(AlignParams p) {
-  __shared__ float T[12];          // T_rel = W2C_cur inverse(W2C_ref), rows 0..2
-  __shared__ float part[4][40];    // per wave: three store10 slots of 12 floats, one store4 slot
+// ---- the pixel pass.  JOINT: the unknowns are [rho, theta, a, b]; r_I = I_c - (e^a I_r + b) with a, b the state's exposure (PS_EXP),
+// the photometric row J8 = [J_I, -(e^a I_r), -1], the depth row [J_Z, 0, 0].  gain_out (JOINT only; may be NULL): the e^a the pass used
+// -- expf is not correctly rounded, and tests/align_joint_restated.py evaluates its mirror with that very float.
+// The warp, the gates, the taps and the depth term are the same text for both forms; what the joint form adds stands under `if (JOINT)`.
+// A thread's partials: the upper triangle of H row by row (NH), g (NX), loss / L_photo / L_depth, the valid count, the open depth gates.
+template <bool JOINT>
+__device__ __forceinline__ void rgbd_align_body(const AlignParams &p, float *__restrict__ gain_out) {
+  constexpr int NX = JOINT ? 8 : 6, NH = NX * (NX + 1) / 2, ROW = JOINT ? AL8_ROW : AL_ROW;
+  constexpr int LIVE = NH + NX + 5;      // the row's live slots: 32 (all of the row) / 49 ([49:64) zero)
+  constexpr int G10 = JOINT ? 5 : 3;     // reduce10 groups per wave; the 6-form's two counts go through a reduce4 instead,
+  constexpr int NACC = JOINT ? 10 * G10 : LIVE;   // the joint form's ride in the fifth group, with one zero that fills it
+  constexpr int NT = JOINT ? 14 : 12, NPART = JOINT ? 12 * G10 : 12 * G10 + 4;
+  static_assert(10 * G10 == (JOINT ? LIVE + 1 : LIVE - 2) && LIVE <= ROW, "the partials and their reduce groups");
+  __shared__ float T[NT];             // T_rel = W2C_cur inverse(W2C_ref), rows 0..2; JOINT: e^a, b
+  __shared__ float part[4][NPART];    // per wave: G10 store10 slots of 12 floats; 6-form: one store4 slot
   if (p.skip && *p.skip != 0u) return;   // (workgroup-uniform)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t < 12) {
-    // the rigid inverse [R^T, -R^T t] of the reference pose and the product, every sum left to right
-    const float *c = p.state + PS_W2C, *r = p.ref_w2c;
-    const int i = t >> 2, j = t & 3;
-    if (j < 3) {
-      T[t] = (c[i * 4 + 0] * r[j * 4 + 0] + c[i * 4 + 1] * r[j * 4 + 1]) + c[i * 4 + 2] * r[j * 4 + 2];
-    } else {
-      float ti[3];
-      for (int k = 0; k < 3; k++) ti[k] = -((r[0 + k] * r[3] + r[4 + k] * r[7]) + r[8 + k] * r[11]);
-      T[t] = ((c[i * 4 + 0] * ti[0] + c[i * 4 + 1] * ti[1]) + c[i * 4 + 2] * ti[2]) + c[i * 4 + 3];
+  if (JOINT) {
+    if (t == 12) {   // one expf per workgroup; workgroup (0, 0) reports it
+      const float ea = expf(p.state[PS_EXP]);
+      T[NT - 2] = ea;
+      T[NT - 1] = p.state[PS_EXP + 1];
+      if (gain_out && blockIdx.x == 0 && blockIdx.y == 0) *gain_out = ea;
     }
-  }
-  __syncthreads();
-  const int W = p.W, H = p.H;
-  const int x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + wave;
-  const bool inside = x < W && y < H;
-  const size_t N = (size_t)W * H, at = inside ? (size_t)y * W + x : 0;
-
-  float acc[32];
-#pragma unroll
-  for (int k = 0; k < 32; k++) acc[k] = 0.f;
-  float rec[AL_PIX];
-#pragma unroll
-  for (int k = 0; k < AL_PIX; k++) rec[k] = 0.f;
-  uint32_t flags = 0u;
-
-  bool ok = inside;
-  float Ir = 0.f, Zr = 0.f;
-  if (ok) {
-    Ir = al_grey(p.ref_color, N, at);
-    Zr = p.ref_depth[at];
-    ok = al_finite(Ir) && al_finite(Zr) && Zr >= p.min_depth && Zr <= p.max_depth;
-  }
-  float Xc = 0.f, Yc = 0.f, Zc = 0.f;
-  if (ok) {
-    const float xn = (((float)x + 0.5f) - p.cx) / p.fx, yn = (((float)y + 0.5f) - p.cy) / p.fy;
-    const float Xr = xn * Zr, Yr = yn * Zr;
-    Xc = ((T[0] * Xr + T[1] * Yr) + T[2] * Zr) + T[3];
-    Yc = ((T[4] * Xr + T[5] * Yr) + T[6] * Zr) + T[7];
-    Zc = ((T[8] * Xr + T[9] * Yr) + T[10] * Zr) + T[11];
-    ok = al_finite(Xc) && al_finite(Yc) && al_finite(Zc) && Zc >= p.min_depth;
-  }
-  if (ok) {
-    const float iz = 1.f / Zc, fxz = p.fx * iz, fyz = p.fy * iz, px = fxz * Xc, py = fyz * Yc;
-    const float u = (px + p.cx) - 0.5f, v = (py + p.cy) - 0.5f;
-    const float x0f = floorf(u), y0f = floorf(v);
-    // 0 <= x0 and x0 + 1 <= W - 1, decided on the floats (a NaN or an inf fails): u = W - 1 exactly is outside
-    ok = x0f >= 0.f && x0f <= (float)(W - 2) && y0f >= 0.f && y0f <= (float)(H - 2);
-    if (ok) {
-      const size_t q = (size_t)(int)y0f * W + (size_t)(int)x0f;
-      const float a = u - x0f, b = v - y0f, oma = 1.f - a, omb = 1.f - b;
-      const float I00 = al_grey(p.cur_color, N, q), I01 = al_grey(p.cur_color, N, q + 1), I10 = al_grey(p.cur_color, N, q + W),
-                  I11 = al_grey(p.cur_color, N, q + W + 1);
-      ok = al_finite(I00) && al_finite(I01) && al_finite(I10) && al_finite(I11);
-      if (ok) {
-        const float Ic = (I00 * oma + I01 * a) * omb + (I10 * oma + I11 * a) * b;
-        const float gx = omb * (I01 - I00) + b * (I11 - I10), gy = oma * (I10 - I00) + a * (I11 - I01);
-        const float duz = -(px * iz), dvz = -(py * iz);
-        const float rI = Ic - Ir;
-        float J[6];
-        J[0] = gx * fxz;
-        J[1] = gy * fyz;
-        J[2] = gx * duz + gy * dvz;
-        J[3] = J[2] * Yc - J[1] * Zc;
-        J[4] = J[0] * Zc - J[2] * Xc;
-        J[5] = J[1] * Xc - J[0] * Yc;
-        float sI, hI, lI;
-        al_irls(rI, 1.f, p.delta_photo, sI, hI, lI);
-        flags = 1u;
-        rec[0] = u; rec[1] = v; rec[2] = Xc; rec[3] = Yc; rec[4] = Zc; rec[5] = Ic; rec[6] = gx; rec[7] = gy; rec[8] = rI; rec[9] = sI;
-        rec[10] = hI;
-        float sZ = 0.f, hZ = 0.f, lZ = 0.f, JZ[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (p.cur_depth) {
-          const float D00 = p.cur_depth[q], D01 = p.cur_depth[q + 1], D10 = p.cur_depth[q + W], D11 = p.cur_depth[q + W + 1];
-          const float dmin = fminf(fminf(D00, D01), fminf(D10, D11)), dmax = fmaxf(fmaxf(D00, D01), fmaxf(D10, D11));
-          const bool open = al_finite(D00) && al_finite(D01) && al_finite(D10) && al_finite(D11) && dmin >= p.min_depth && dmax <= p.max_depth &&
-                            dmax - dmin <= p.edge_ratio * dmin;
-          if (open) {
-            const float Dc = (D00 * oma + D01 * a) * omb + (D10 * oma + D11 * a) * b;
-            const float hx = omb * (D01 - D00) + b * (D11 - D10), hy = oma * (D10 - D00) + a * (D11 - D01);
-            const float rZ = Dc - Zc;
-            const float k0 = hx * fxz, k1 = hy * fyz, k2 = hx * duz + hy * dvz;
-            JZ[0] = k0;
-            JZ[1] = k1;
-            JZ[2] = k2 - 1.f;
-            JZ[3] = (k2 * Yc - k1 * Zc) - Yc;
-            JZ[4] = (k0 * Zc - k2 * Xc) + Xc;
-            JZ[5] = k1 * Xc - k0 * Yc;
-            al_irls(rZ, p.w_depth, p.delta_depth, sZ, hZ, lZ);
-            flags |= 2u;
-            rec[11] = Dc; rec[12] = rZ; rec[13] = sZ; rec[14] = hZ; rec[15] = 1.f;
-          }
-        }
-        int n = 0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-          const float a_k = hI * J[k], z_k = hZ * JZ[k];
-#pragma unroll
-          for (int l = k; l < 6; l++, n++) acc[n] = a_k * J[l] + z_k * JZ[l];
-        }
-#pragma unroll
-        for (int k = 0; k < 6; k++) acc[21 + k] = sI * J[k] + sZ * JZ[k];
-        acc[27] = lI + lZ;
-        acc[28] = lI;
-        acc[29] = lZ;
-        acc[30] = 1.f;
-        acc[31] = (flags & 2u) ? 1.f : 0.f;
-      }
-    }
-  }
-  if (inside) {
-    if (p.pix_out) {
-      float *o = p.pix_out + at * AL_PIX;   // (dword stores: pix_out needs no more than 4-byte alignment)
-#pragma unroll
-      for (int k = 0; k < AL_PIX; k++) o[k] = rec[k];
-    }
-    if (p.valid_out) p.valid_out[at] = (uint8_t)flags;
-  }
-
-  // the workgroup's row: three reduce10 and one reduce4 per wave (every lane takes part), then the four waves in order
-#pragma unroll
-  for (int g = 0; g < 3; g++) {
-    const float v10[10] = {acc[10 * g], acc[10 * g + 1], acc[10 * g + 2], acc[10 * g + 3], acc[10 * g + 4],
-                           acc[10 * g + 5], acc[10 * g + 6], acc[10 * g + 7], acc[10 * g + 8], acc[10 * g + 9]};
-    float x0, x1, x2;
-    reduce10(v10, x0, x1, x2);
-    store10(&part[wave][12 * g], lane, x0, x1, x2);
-  }
-  store4(&part[wave][36], lane, reduce4(acc[30], acc[31], 0.f, 0.f));
-  __syncthreads();
-  if (t < AL_ROW) {
-    const int slot = t < 30 ? 12 * (t / 10) + t % 10 : 36 + (t - 30);
-    const size_t row = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    p.rows[row * AL_ROW + t] = ((part[0][slot] + part[1][slot]) + part[2][slot]) + part[3][slot];
-  }
-}
-
-// ---- the joint form: the unknowns are [rho, theta, a, b]; r_I = I_c - (e^a I_r + b) with a, b the state's exposure (PS_EXP), the
-// photometric row J8 = [J_I, -(e^a I_r), -1], the depth row [J_Z, 0, 0].  gain_out (may be NULL): the e^a the pass used -- expf is not
-// correctly rounded, and tests/align_joint_restated.py evaluates its mirror with that very float.
-// A second kernel, not a template parameter of the first: with both forms under one body the compiler allocated k_rgbd_align's
-// registers differently (80 or 81 VGPRs for 82), and the 6-form's code object is to stay what it was.  The warp, the gates and the depth
-// term are k_rgbd_align's text line for line; what differs is marked "joint".
-__global__ __launch_bounds__(256) void k_rgbd_align8(AlignParams p, float *__restrict__ gain_out) {
-  constexpr int NX = 8, NH = NX * (NX + 1) / 2, NACC = 50;   // H8, g8, three losses, two counts (and one zero that fills the fifth reduce10)
-  __shared__ float T[14];          // T_rel = W2C_cur inverse(W2C_ref), rows 0..2; joint: e^a, b
-  __shared__ float part[4][60];    // per wave: five store10 slots of 12 floats
-  if (p.skip && *p.skip != 0u) return;   // (workgroup-uniform)
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 12) {   // joint: one expf per workgroup; workgroup (0, 0) reports it
-    const float ea = expf(p.state[PS_EXP]);
-    T[12] = ea;
-    T[13] = p.state[PS_EXP + 1];
-    if (gain_out && blockIdx.x == 0 && blockIdx.y == 0) *gain_out = ea;
   }
   if (t < 12) {
     // the rigid inverse [R^T, -R^T t] of the reference pose and the product, every sum left to right
@@ -262,11 +129,15 @@ __global__ __launch_bounds__(256) void k_rgbd_align8(AlignParams p, float *__res
         const float Ic = (I00 * oma + I01 * a) * omb + (I10 * oma + I11 * a) * b;
         const float gx = omb * (I01 - I00) + b * (I11 - I10), gy = oma * (I10 - I00) + a * (I11 - I01);
         const float duz = -(px * iz), dvz = -(py * iz);
-        const float gI = T[12] * Ir;   // joint: the reference grey as the current frame would show it, before the offset
-        const float rI = Ic - (gI + T[13]);
-        float J[NX];
-        J[6] = -gI;
-        J[7] = -1.f;
+        float rI, J[NX];
+        if (JOINT) {
+          const float gI = T[NT - 2] * Ir;   // the reference grey as the current frame would show it, before the offset
+          rI = Ic - (gI + T[NT - 1]);
+          J[NX - 2] = -gI;
+          J[NX - 1] = -1.f;
+        } else {
+          rI = Ic - Ir;
+        }
         J[0] = gx * fxz;
         J[1] = gy * fyz;
         J[2] = gx * duz + gy * dvz;
@@ -300,24 +171,17 @@ __global__ __launch_bounds__(256) void k_rgbd_align8(AlignParams p, float *__res
             rec[11] = Dc; rec[12] = rZ; rec[13] = sZ; rec[14] = hZ; rec[15] = 1.f;
           }
         }
-        // joint: the depth term has no part in the exposure columns -- those elements are the photometric product alone
+        // H row by row, then g.  The depth term has no part in the exposure columns (l >= 6): those elements are the photometric
+        // product alone
         int n = 0;
 #pragma unroll
-        for (int k = 0; k < 6; k++) {
-          const float a_k = hI * J[k], z_k = hZ * JZ[k];
+        for (int k = 0; k < NX; k++) {
+          const float a_k = hI * J[k], z_k = k < 6 ? hZ * JZ[k] : 0.f;
 #pragma unroll
-          for (int l = k; l < 6; l++, n++) acc[n] = a_k * J[l] + z_k * JZ[l];
-          acc[n++] = a_k * J[6];
-          acc[n++] = a_k * J[7];
+          for (int l = k; l < NX; l++, n++) acc[n] = l < 6 ? a_k * J[l] + z_k * JZ[l] : a_k * J[l];
         }
-        const float a_6 = hI * J[6], a_7 = hI * J[7];
-        acc[33] = a_6 * J[6];
-        acc[34] = a_6 * J[7];
-        acc[35] = a_7 * J[7];
 #pragma unroll
-        for (int k = 0; k < 6; k++) acc[NH + k] = sI * J[k] + sZ * JZ[k];
-        acc[NH + 6] = sI * J[6];
-        acc[NH + 7] = sI * J[7];
+        for (int k = 0; k < NX; k++) acc[NH + k] = k < 6 ? sI * J[k] + sZ * JZ[k] : sI * J[k];
         acc[NH + NX] = lI + lZ;
         acc[NH + NX + 1] = lI;
         acc[NH + NX + 2] = lZ;
@@ -335,23 +199,26 @@ __global__ __launch_bounds__(256) void k_rgbd_align8(AlignParams p, float *__res
     if (p.valid_out) p.valid_out[at] = (uint8_t)flags;
   }
 
-  // the workgroup's row: five reduce10 per wave (every lane takes part), then the four waves in order
+  // the workgroup's row: G10 reduce10 (and, 6-form, one reduce4) per wave (every lane takes part), then the four waves in order
 #pragma unroll
-  for (int g = 0; g < 5; g++) {
+  for (int g = 0; g < G10; g++) {
     const float v10[10] = {acc[10 * g], acc[10 * g + 1], acc[10 * g + 2], acc[10 * g + 3], acc[10 * g + 4],
                            acc[10 * g + 5], acc[10 * g + 6], acc[10 * g + 7], acc[10 * g + 8], acc[10 * g + 9]};
     float x0, x1, x2;
     reduce10(v10, x0, x1, x2);
     store10(&part[wave][12 * g], lane, x0, x1, x2);
   }
+  if (!JOINT) store4(&part[wave][12 * G10], lane, reduce4(acc[LIVE - 2], acc[LIVE - 1], 0.f, 0.f));
   __syncthreads();
-  if (t < AL8_ROW) {   // [49:64) zero
-    const int slot = t < 49 ? 12 * (t / 10) + t % 10 : 0;
+  if (t < ROW) {   // (joint form: [LIVE:ROW) zero)
+    const int slot = t >= LIVE ? 0 : t < 10 * G10 ? 12 * (t / 10) + t % 10 : 12 * G10 + (t - 10 * G10);
     const size_t row = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     const float sum = ((part[0][slot] + part[1][slot]) + part[2][slot]) + part[3][slot];
-    p.rows[row * AL8_ROW + t] = t < 49 ? sum : 0.f;
+    p.rows[row * ROW + t] = t < LIVE ? sum : 0.f;
   }
 }
+__global__ __launch_bounds__(256) void k_rgbd_align(AlignParams p) { rgbd_align_body<false>(p, nullptr); }
+__global__ __launch_bounds__(256) void k_rgbd_align8(AlignParams p, float *__restrict__ gain_out) { rgbd_align_body<true>(p, gain_out); }
 
 // ---- the fold: the step kernels' own gn_sum_rows (gn_state.h: the rows added in a fixed order in fp64), then the normalisation -------
 // ROW floats per row, the count of valid pixels in slot VALID: H and g before VALID - 3, the three losses, the two counts (and, in the
@@ -417,15 +284,13 @@ static int rgbd_align_launch(bool joint, int W, int H, float fx, float fy, float
   double need = __builtin_ceil((double)min_overlap * (double)W * (double)H);
   if (need < 1.0) need = 1.0;
   const dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4));
-  if (joint)
+  const auto fold = joint ? k_rgbd_align8_fold : k_rgbd_align_fold;
+  if (joint)   // (the two pixel kernels differ in their arguments: the joint form's takes gain_out)
     hipLaunchKernelGGL(k_rgbd_align8, grid, dim3(256), 0, (hipStream_t)stream, p, gain_out);
   else
     hipLaunchKernelGGL(k_rgbd_align, grid, dim3(256), 0, (hipStream_t)stream, p);
   GSAJ_HIP_CHECK(hipGetLastError());
-  if (joint)
-    hipLaunchKernelGGL(k_rgbd_align8_fold, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, rows, n, need, gn_row, skip);
-  else
-    hipLaunchKernelGGL(k_rgbd_align_fold, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, rows, n, need, gn_row, skip);
+  hipLaunchKernelGGL(fold, dim3(1), dim3(GN_SUM_THREADS), 0, (hipStream_t)stream, rows, n, need, gn_row, skip);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }

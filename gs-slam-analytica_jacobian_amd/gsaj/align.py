@@ -19,21 +19,18 @@ from .pyramid import MAX_LEVELS, ImagePyramid, level_camera
 
 
 def _residuals(al, l, depth):  # (the device work of one iteration, first half: host-logic tests replace it)
-    """gsaj_rgbd_align at level l: the reference level against the current level at the state's pose -> al.row."""
+    """gsaj_rgbd_align (joint form: gsaj_rgbd_align8) at level l: the reference level against the current level at the state's pose
+    -> al.row."""
     W, H, fx, fy, cx, cy = al.cams[l]
     rc, rd, cc, cd = al._level(al._ref, l) + al._level(al._cur, l)
+    name = "gsaj_rgbd_align8" if al.solve_exposure else "gsaj_rgbd_align"
+    # the joint form reads the state's exposure on the device; gain_out, its one more argument: the gain it used is not asked for
+    gain_out = (None,) if al.solve_exposure else ()
     with torch.cuda.device(al.dev):
-        if al.solve_exposure:   # (the joint form: the state's exposure is read on the device, the gain it used is not asked for)
-            _lib.check(al.lib.gsaj_rgbd_align8(W, H, fx, fy, cx, cy, rc.data_ptr(), rd.data_ptr(), al.ref_w2c.data_ptr(), cc.data_ptr(),
-                                               cd.data_ptr() if depth else None, al.state.data_ptr(), al.w_depth, al.delta_photo,
-                                               al.delta_depth, al.depth_edge_ratio, al.min_depth, al.max_depth, al.min_overlap,
-                                               al.rows.data_ptr(), al.row.data_ptr(), None, None, None, None, stream(al.dev)),
-                       "gsaj_rgbd_align8")
-            return
-        _lib.check(al.lib.gsaj_rgbd_align(W, H, fx, fy, cx, cy, rc.data_ptr(), rd.data_ptr(), al.ref_w2c.data_ptr(), cc.data_ptr(),
-                                          cd.data_ptr() if depth else None, al.state.data_ptr(), al.w_depth, al.delta_photo, al.delta_depth,
-                                          al.depth_edge_ratio, al.min_depth, al.max_depth, al.min_overlap, al.rows.data_ptr(),
-                                          al.row.data_ptr(), None, None, None, stream(al.dev)), "gsaj_rgbd_align")
+        _lib.check(getattr(al.lib, name)(W, H, fx, fy, cx, cy, rc.data_ptr(), rd.data_ptr(), al.ref_w2c.data_ptr(), cc.data_ptr(),
+                                         cd.data_ptr() if depth else None, al.state.data_ptr(), al.w_depth, al.delta_photo, al.delta_depth,
+                                         al.depth_edge_ratio, al.min_depth, al.max_depth, al.min_overlap, al.rows.data_ptr(),
+                                         al.row.data_ptr(), *gain_out, None, None, None, stream(al.dev)), name)
 
 
 def _step(al, l):  # (device work too)

@@ -1,5 +1,5 @@
 """NumPy restatements of the JOINT frame-to-frame RGB-D alignment -- csrc/align.hip: k_rgbd_align8, k_rgbd_align8_fold -- on top of
-tests/align_restated.py (imported, nothing in it changed) and tests/gn8_restated.py's step.  TEST INFRASTRUCTURE ONLY; shared by
+tests/align_restated.py and tests/gn8_restated.py's step.  TEST INFRASTRUCTURE ONLY; shared by
 tests/test_cpu_align_joint.py and tests/test_gpu_align_joint.py.
 
 The unknowns are x = [rho(3), theta(3), a, b]; the current frame is modelled as e^a I_r + b (include/gsaj.h, "the joint form" of the
@@ -10,7 +10,8 @@ is align_restated.pixels, called as it is; what is restated here is what the joi
                      One statement, evaluated in float64 (the restatement) or float32 (the MIRROR, one rounding per operation); `gain` is
                      an INPUT of both: expf is not correctly rounded, so the device reports the float it used (gain_out) and the mirror is
                      evaluated with it
-  fold8              k_rgbd_align8_fold: the terms summed in float64, normalised by the valid count, the overlap gate -> 64 slots
+  fold8, row_bound8, assert_row_close8   align_restated's fold, row_bound and assert_row_close at the joint row's layout (ROW8: 64
+                     slots, NX = 8): k_rgbd_align8_fold -- the terms summed in float64, normalised by the valid count, the overlap gate
   align8_loop        the aligner's joint loop on gn8_restated.lm8_step, the relevel's effect on the exposure included
   with_brightness    a case whose current frame's colour is e^a I + b
   exposure_tolerance the tolerance of the recovered (a, b): twice the distance between the loop in float64 and the same loop on the
@@ -23,6 +24,7 @@ Between a term and the row's slot lie: the wave's reduce10 tree -- one half-wave
 the four waves added IN ORDER, ((w0 + w1) + w2) + w3: 3 additions on the longest path (not 2: it is a chain, not a tree); the fold's
 float64 sums (2^-53: nothing) and its quotient rounded to float32 once: 1.  ROW_ROUNDINGS = 6 + 3 + 1 = 10, whatever the slot: the
 joint kernel's 49 partials go through five reduce10 of the same depth, none through a reduce4."""
+import functools
 import math
 
 import numpy as np
@@ -33,10 +35,11 @@ import gn_restated as gn
 
 F = np.float32
 EPS = ar.EPS
-ROW = 64
-NH, NX = 36, 8
-LOSS, VALID, GATES = 44, 47, 48     # [44] loss, [45] L_photo, [46] L_depth, [47] valid pixels, [48] open depth gates, [49:64) zero
 ROW_ROUNDINGS = 6 + 3 + 1
+ROW8 = ar.RowLayout(64, 8, ROW_ROUNDINGS)
+ROW, NH, NX = ROW8.ROW, ROW8.NH, ROW8.NX
+LOSS, VALID, GATES = ROW8.LOSS, ROW8.VALID, ROW8.GATES   # [44] loss, [45] L_photo, [46] L_depth, [47] valid pixels, [48] open depth gates, [49:64) zero
+assert (ROW, NH, LOSS, VALID, GATES) == (64, 36, 44, 47, 48)
 MUTANTS = ("a_column_sign", "a_column_without_gain", "b_column_plus_one", "gain_on_current", "exposure_in_depth_term", "h8_by_columns",
            "a_b_swapped")
 EXPOSURES = ((0.0, 0.0), (0.1, 0.03), (-0.15, 0.05))
@@ -130,27 +133,10 @@ def mirror8(case, gain=None, mutant=None):
 
 
 # ---- the fold ---------------------------------------------------------------------------------------------------------------------------
-def fold8(terms, case):
-    """-> the 64 slots of gn8_row in float64 from per-pixel terms [H,W,64]."""
-    s = np.asarray(terms, np.float64).reshape(-1, ROW).sum(0)
-    out = np.zeros(ROW)
-    out[VALID:] = s[VALID:]
-    if s[VALID] < ar.need_of(case):
-        out[LOSS:VALID] = np.inf
-    else:
-        out[:VALID] = s[:VALID] / s[VALID]
-    return out
-
-
-def row_bound8(terms, case, border=None):
-    """Per slot: ROW_ROUNDINGS 2^-24 sum|term| / n, plus each borderline pixel's own |term| / n (its other side is 'invalid', a zero, or
-    the other side of a gate: the larger of two terms of one size)."""
-    t = np.abs(np.asarray(terms, np.float64)).reshape(-1, ROW)
-    n = max(t[:, VALID].sum(), 1.0)
-    bound = ROW_ROUNDINGS * EPS * t.sum(0) / n
-    if border is not None and border.any():
-        bound = bound + t[border.reshape(-1)].sum(0) / n
-    return bound
+# k_rgbd_align8_fold: the terms summed in float64, normalised by the valid count, the overlap gate -> 64 slots; the bound per slot:
+# ROW_ROUNDINGS 2^-24 sum|term| / n, plus each borderline pixel's own |term| / n.  align_restated's functions at the joint row's layout.
+fold8 = functools.partial(ar.fold, lay=ROW8)
+row_bound8 = functools.partial(ar.row_bound, lay=ROW8)
 
 
 def rounding_bound8(case, px64, border, gain=None):
@@ -175,28 +161,8 @@ def rounding_bound8(case, px64, border, gain=None):
 
 
 # ---- the comparators of the GPU tests ---------------------------------------------------------------------------------------------------
-def assert_row_close8(got_row, terms, case, border, tag):
-    """gn8_row against the float64 sum of the per-pixel terms (the mirror's): every slot within row_bound8; the counts exact up to the
-    number of borderline pixels; [49:64) zero; below the overlap gate H8 and g8 exactly zero and the losses +inf.  -> worst err / bound."""
-    got = np.asarray(got_row, np.float64)
-    assert got.shape == (ROW,), (tag, got.shape)
-    want = fold8(terms, case)
-    nb = int(border.sum()) if border is not None else 0
-    assert not got[GATES + 1:].any(), "%s: the padding of the row is not zero: %s" % (tag, got[GATES + 1:])
-    assert abs(got[VALID] - want[VALID]) <= nb and abs(got[GATES] - want[GATES]) <= nb, (tag, got[VALID:GATES + 1], want[VALID:GATES + 1], nb)
-    need = ar.need_of(case)
-    if got[VALID] < need or want[VALID] < need:
-        assert nb or (got[VALID] < need) == (want[VALID] < need), (tag, got[VALID], want[VALID])
-        if got[VALID] < need:
-            assert not got[:LOSS].any() and np.isposinf(got[LOSS:VALID]).all(), (tag, got)
-        return 0.0
-    bound = row_bound8(terms, case, border)[:VALID]
-    err = np.abs(got[:VALID] - want[:VALID])
-    assert np.isfinite(got).all(), (tag, got)
-    bad = err > bound
-    assert not bad.any(), "%s: slot %s: got %.9e want %.9e, error %.3e = %.3g x bound" % (
-        tag, np.flatnonzero(bad)[0], got[:VALID][bad][0], want[:VALID][bad][0], err[bad][0], (err[bad] / np.maximum(bound[bad], 1e-300))[0])
-    return float((err / np.maximum(bound, 1e-300))[bound > 0].max(initial=0.0))
+# gn8_row against the float64 sum of the per-pixel terms (the mirror's): align_restated.assert_row_close at the joint row's layout
+assert_row_close8 = functools.partial(ar.assert_row_close, lay=ROW8)
 
 
 def assert_gain(gain, a, tag):

@@ -6,7 +6,8 @@ ONLY; shared by tests/test_cpu_align.py and tests/test_gpu_align.py.
   pixels             the per-pixel arithmetic of include/gsaj.h "frame-to-frame alignment", in the header's order of operations.  One
                      statement of it, evaluated in float64 (the restatement) or in float32 (the MIRROR: NumPy rounds every float32
                      operation once, as the kernel does without contraction; division, floor, min / max, negation included)
-  fold               k_rgbd_align_fold: the per-pixel terms summed in float64, normalised, gated by the overlap
+  RowLayout          the slots of a form's row from ROW and NX; ROW6 here, ROW8 in tests/align_joint_restated.py
+  fold               k_rgbd_align_fold / k_rgbd_align8_fold: the per-pixel terms summed in float64, normalised, gated by the overlap
   borderline         pixels whose gates a float32 evaluation may legally decide either way
   assert_pixels_equal / assert_row_close   the comparators
   align_loop         the restated Levenberg-Marquardt loop over the restated pyramid: gn_restated.lm_step, gsaj_pose_gn_relevel's effect
@@ -238,28 +239,45 @@ def need_of(case):
     return max(1.0, math.ceil(float(F(case["min_overlap"])) * case["W"] * case["H"]))
 
 
-def fold(terms, case):
-    """-> the 32 slots of gn_row in float64 from per-pixel terms [H,W,32] (any dtype), summed in float64."""
-    s = np.asarray(terms, np.float64).reshape(-1, 32).sum(0)
-    out = np.zeros(32)
-    out[30:] = s[30:]
-    if s[30] < need_of(case):
-        out[27:30] = np.inf
+class RowLayout:
+    """The slots of a form's row: H (NH, the upper triangle), g (NX), [LOSS] loss, L_photo, L_depth, [VALID] valid pixels, [GATES] open
+    depth gates, [GATES + 1 : ROW) zero; ROUNDINGS: the form's ROW_ROUNDINGS.  fold, row_bound and assert_row_close take one."""
+
+    def __init__(self, ROW, NX, ROUNDINGS):
+        self.ROW, self.NX, self.ROUNDINGS = ROW, NX, ROUNDINGS
+        self.NH = NX * (NX + 1) // 2
+        self.LOSS = self.NH + NX
+        self.VALID = self.LOSS + 3
+        self.GATES = self.VALID + 1
+        assert self.GATES < ROW
+
+
+ROW6 = RowLayout(32, 6, ROW_ROUNDINGS)   # gn_row: [27] loss ... [30] valid, [31] gates, no padding
+
+
+def fold(terms, case, lay=ROW6):
+    """-> the ROW slots of gn_row (gn8_row) in float64 from per-pixel terms [H,W,ROW] (any dtype), summed in float64."""
+    s = np.asarray(terms, np.float64).reshape(-1, lay.ROW).sum(0)
+    out = np.zeros(lay.ROW)
+    out[lay.VALID:] = s[lay.VALID:]
+    if s[lay.VALID] < need_of(case):
+        out[lay.LOSS:lay.VALID] = np.inf
     else:
-        out[:30] = s[:30] / s[30]
+        out[:lay.VALID] = s[:lay.VALID] / s[lay.VALID]
     return out
 
 
-def row_bound(terms, case, border=None, alt_terms=None):
+def row_bound(terms, case, border=None, alt_terms=None, lay=ROW6):
     """Per slot: ROW_ROUNDINGS 2^-24 sum|term| / n, plus for each borderline pixel the larger |term| of its two legal sides / n (alt_terms:
-    the pixel's terms on the other side; where none is given, the pixel's own |term| -- its other side is 'invalid', a zero)."""
-    t = np.abs(np.asarray(terms, np.float64)).reshape(-1, 32)
-    n = max(t[:, 30].sum(), 1.0)
-    bound = ROW_ROUNDINGS * EPS * t.sum(0) / n
+    the pixel's terms on the other side; where none is given, the pixel's own |term| -- its other side is 'invalid', a zero, or the
+    other side of a gate: the larger of two terms of one size)."""
+    t = np.abs(np.asarray(terms, np.float64)).reshape(-1, lay.ROW)
+    n = max(t[:, lay.VALID].sum(), 1.0)
+    bound = lay.ROUNDINGS * EPS * t.sum(0) / n
     if border is not None and border.any():
         extra = t[border.reshape(-1)]
         if alt_terms is not None:
-            extra = np.maximum(extra, np.abs(np.asarray(alt_terms, np.float64)).reshape(-1, 32)[border.reshape(-1)])
+            extra = np.maximum(extra, np.abs(np.asarray(alt_terms, np.float64)).reshape(-1, lay.ROW)[border.reshape(-1)])
         bound = bound + extra.sum(0) / n
     return bound
 
@@ -345,24 +363,29 @@ def assert_pixels_equal(got_pix, got_flags, mir, border, tag):
     return int(other.sum())
 
 
-def assert_row_close(got_row, terms, case, border, tag):
-    """gn_row against the float64 sum of the per-pixel terms (the mirror's): every slot within row_bound; the counts exact up to the
-    number of borderline pixels; below the overlap gate H and g exactly zero and the losses +inf.  -> worst err / bound."""
+def assert_row_close(got_row, terms, case, border, tag, lay=ROW6):
+    """gn_row (gn8_row) against the float64 sum of the per-pixel terms (the mirror's): every slot within row_bound; the counts exact up
+    to the number of borderline pixels; the padding behind them (joint form: [49:64)) zero; below the overlap gate H and g exactly zero
+    and the losses +inf.  -> worst err / bound."""
+    LOSS, VALID, GATES = lay.LOSS, lay.VALID, lay.GATES
     got = np.asarray(got_row, np.float64)
-    want = fold(terms, case)
+    assert got.shape == (lay.ROW,), (tag, got.shape)
+    want = fold(terms, case, lay)
     nb = int(border.sum()) if border is not None else 0
-    assert abs(got[30] - want[30]) <= nb and abs(got[31] - want[31]) <= nb, (tag, got[30:], want[30:], nb)
-    if got[30] < need_of(case) or want[30] < need_of(case):
-        assert nb or (got[30] < need_of(case)) == (want[30] < need_of(case)), (tag, got[30], want[30])
-        if got[30] < need_of(case):
-            assert not got[:27].any() and np.isposinf(got[27:30]).all(), (tag, got)
+    assert not got[GATES + 1:].any(), "%s: the padding of the row is not zero: %s" % (tag, got[GATES + 1:])
+    assert abs(got[VALID] - want[VALID]) <= nb and abs(got[GATES] - want[GATES]) <= nb, (tag, got[VALID:GATES + 1], want[VALID:GATES + 1], nb)
+    need = need_of(case)
+    if got[VALID] < need or want[VALID] < need:
+        assert nb or (got[VALID] < need) == (want[VALID] < need), (tag, got[VALID], want[VALID])
+        if got[VALID] < need:
+            assert not got[:LOSS].any() and np.isposinf(got[LOSS:VALID]).all(), (tag, got)
         return 0.0
-    bound = row_bound(terms, case, border)[:30]
-    err = np.abs(got[:30] - want[:30])
+    bound = row_bound(terms, case, border, lay=lay)[:VALID]
+    err = np.abs(got[:VALID] - want[:VALID])
     assert np.isfinite(got).all(), (tag, got)
     bad = err > bound
     assert not bad.any(), "%s: slot %s: got %.9e want %.9e, error %.3e = %.3g x bound" % (
-        tag, np.flatnonzero(bad)[0], got[:30][bad][0], want[:30][bad][0], err[bad][0], (err[bad] / np.maximum(bound[bad], 1e-300))[0])
+        tag, np.flatnonzero(bad)[0], got[:VALID][bad][0], want[:VALID][bad][0], err[bad][0], (err[bad] / np.maximum(bound[bad], 1e-300))[0])
     return float((err / np.maximum(bound, 1e-300))[bound > 0].max(initial=0.0))
 
 

@@ -9,13 +9,17 @@ float64 loop.  tests/test_cpu_align.py checks the premises all of this rests on.
 import numpy as np
 import pytest
 
+import align_calls
 import align_restated as ar
 import guards
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+DEV = align_calls.DEV
 F = np.float32
 _MEMO = {}
+_CALLS = align_calls.Calls(joint=False)   # the buffers of a gsaj_rgbd_align call, the call, gsaj_pose_gn_step on its row, RgbdAligner
+_tensors, _call, _run, _step, _aligner = _CALLS.tensors, _CALLS.call, _CALLS.run, _CALLS.step, _CALLS.aligner
+_bits, _dev = align_calls.bits, align_calls.dev
 
 
 def _expect(key, make):
@@ -25,47 +29,6 @@ def _expect(key, make):
         mir = ar.mirror(case)
         _MEMO[key] = (case, mir, ar.borderline(case))
     return _MEMO[key]
-
-
-def _tensors(case, torch):
-    """Every buffer of one call, taken from torch.empty / torch.zeros (the routes tests/guards.py fences), then filled."""
-    W, H = case["W"], case["H"]
-    from gsaj import _lib
-    lib = _lib.load()
-    t = dict(ref_color=torch.empty(3, H, W, dtype=torch.float32, device=DEV), ref_depth=torch.empty(H, W, dtype=torch.float32, device=DEV),
-             ref_w2c=torch.empty(16, dtype=torch.float32, device=DEV), cur_color=torch.empty(3, H, W, dtype=torch.float32, device=DEV),
-             cur_depth=torch.empty(H, W, dtype=torch.float32, device=DEV), state=torch.zeros(136, dtype=torch.float32, device=DEV),
-             rows=torch.empty(lib.gsaj_rgbd_align_partial_rows(W, H), 32, dtype=torch.float32, device=DEV),
-             row=torch.empty(32, dtype=torch.float32, device=DEV), pix=torch.empty(H, W, 16, dtype=torch.float32, device=DEV),
-             valid=torch.empty(H, W, dtype=torch.uint8, device=DEV))
-    for k in ("ref_color", "ref_depth", "cur_color"):
-        t[k].copy_(torch.from_numpy(np.ascontiguousarray(case[k], F)))
-    t["ref_w2c"].copy_(torch.from_numpy(np.asarray(case["ref_w2c"], F).reshape(16)))
-    t["cur_depth"].copy_(torch.from_numpy(np.zeros((H, W), F) if case.get("cur_depth") is None else np.ascontiguousarray(case["cur_depth"], F)))
-    t["state"][0:16] = torch.from_numpy(np.asarray(case["w2c"], F).reshape(16)).to(DEV)
-    return t
-
-
-def _call(case, t, skip=None, outputs=True):
-    import torch
-
-    from gsaj import _lib
-    lib = _lib.load()
-    _lib.check(lib.gsaj_rgbd_align(case["W"], case["H"], case["fx"], case["fy"], case["cx"], case["cy"], t["ref_color"].data_ptr(),
-                                   t["ref_depth"].data_ptr(), t["ref_w2c"].data_ptr(), t["cur_color"].data_ptr(),
-                                   None if case.get("cur_depth") is None else t["cur_depth"].data_ptr(), t["state"].data_ptr(), case["w_depth"],
-                                   case["delta_photo"], case["delta_depth"], case["ratio"], case["min_depth"], case["max_depth"],
-                                   case["min_overlap"], t["rows"].data_ptr(), t["row"].data_ptr(), t["pix"].data_ptr() if outputs else None,
-                                   t["valid"].data_ptr() if outputs else None, None if skip is None else skip.data_ptr(),
-                                   torch.cuda.current_stream().cuda_stream), "gsaj_rgbd_align")
-
-
-def _run(case):
-    import torch
-    t = _tensors(case, torch)
-    _call(case, t)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in t.items()}, t
 
 
 def _compare(case, mir, border, out, tag):
@@ -131,20 +94,6 @@ def test_planted_depths_on_either_side_of_min_depth_in_the_current_camera():
 
 
 # ---- the gates of the fold ----------------------------------------------------------------------------------------------------------------
-def _step(t, projection):
-    import torch
-
-    from gsaj import _lib
-    lib = _lib.load()
-    _lib.check(lib.gsaj_pose_gn_step(t["row"].data_ptr(), 1, ar.LM["lambda_init"], ar.LM["nu"], ar.LM["lambda_min"], ar.LM["lambda_max"],
-                                     ar.LM["converged_threshold"], projection.data_ptr(), t["state"].data_ptr(), None,
-                                     torch.cuda.current_stream().cuda_stream), "gsaj_pose_gn_step")
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint32)
-
-
 def test_a_frame_without_a_valid_pixel_gives_no_step_and_a_loss_that_every_proposal_loses_to():
     import torch
     good = ar.parity_case(80, 60, "depth")
@@ -248,17 +197,6 @@ def test_memory_contract_bands_poisoned_scratch_same_bits_on_any_stream(monkeypa
 
 
 # ---- behaviour ----------------------------------------------------------------------------------------------------------------------------
-def _aligner(**kw):
-    from gsaj import RgbdAligner
-    cam = ar.camera()
-    return RgbdAligner(cam["W"], cam["H"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], DEV, levels=2, **kw)
-
-
-def _dev(case, name):
-    import torch
-    return None if case.get(name) is None else torch.from_numpy(np.ascontiguousarray(case[name], F)).to(DEV)
-
-
 def _restated(m, depth):
     key = ("loop", m, depth)
     if key not in _MEMO:

@@ -11,56 +11,18 @@ checks the premises all of this rests on."""
 import numpy as np
 import pytest
 
+import align_calls
 import align_joint_restated as aj
 import align_restated as ar
 import guards
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+DEV = align_calls.DEV
 F = np.float32
 _MEMO = {}
-
-
-def _tensors(case, torch):
-    """Every buffer of one call, taken from torch.empty / torch.zeros (the routes tests/guards.py fences), then filled."""
-    W, H = case["W"], case["H"]
-    from gsaj import _lib
-    lib = _lib.load()
-    t = dict(ref_color=torch.empty(3, H, W, dtype=torch.float32, device=DEV), ref_depth=torch.empty(H, W, dtype=torch.float32, device=DEV),
-             ref_w2c=torch.empty(16, dtype=torch.float32, device=DEV), cur_color=torch.empty(3, H, W, dtype=torch.float32, device=DEV),
-             cur_depth=torch.empty(H, W, dtype=torch.float32, device=DEV), state=torch.zeros(152, dtype=torch.float32, device=DEV),
-             rows=torch.empty(lib.gsaj_rgbd_align_partial_rows(W, H), 64, dtype=torch.float32, device=DEV),
-             row=torch.empty(64, dtype=torch.float32, device=DEV), gain=torch.empty(1, dtype=torch.float32, device=DEV),
-             pix=torch.empty(H, W, 16, dtype=torch.float32, device=DEV), valid=torch.empty(H, W, dtype=torch.uint8, device=DEV))
-    for k in ("ref_color", "ref_depth", "cur_color"):
-        t[k].copy_(torch.from_numpy(np.ascontiguousarray(case[k], F)))
-    t["ref_w2c"].copy_(torch.from_numpy(np.asarray(case["ref_w2c"], F).reshape(16)))
-    t["cur_depth"].copy_(torch.from_numpy(np.zeros((H, W), F) if case.get("cur_depth") is None else np.ascontiguousarray(case["cur_depth"], F)))
-    t["state"][0:16] = torch.from_numpy(np.asarray(case["w2c"], F).reshape(16)).to(DEV)
-    t["state"][33:35] = torch.from_numpy(np.asarray(case.get("exposure", (0.0, 0.0)), F)).to(DEV)
-    return t
-
-
-def _call(case, t, skip=None, outputs=True):
-    import torch
-
-    from gsaj import _lib
-    lib = _lib.load()
-    _lib.check(lib.gsaj_rgbd_align8(case["W"], case["H"], case["fx"], case["fy"], case["cx"], case["cy"], t["ref_color"].data_ptr(),
-                                    t["ref_depth"].data_ptr(), t["ref_w2c"].data_ptr(), t["cur_color"].data_ptr(),
-                                    None if case.get("cur_depth") is None else t["cur_depth"].data_ptr(), t["state"].data_ptr(), case["w_depth"],
-                                    case["delta_photo"], case["delta_depth"], case["ratio"], case["min_depth"], case["max_depth"],
-                                    case["min_overlap"], t["rows"].data_ptr(), t["row"].data_ptr(), t["gain"].data_ptr() if outputs else None,
-                                    t["pix"].data_ptr() if outputs else None, t["valid"].data_ptr() if outputs else None,
-                                    None if skip is None else skip.data_ptr(), torch.cuda.current_stream().cuda_stream), "gsaj_rgbd_align8")
-
-
-def _run(case):
-    import torch
-    t = _tensors(case, torch)
-    _call(case, t)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in t.items()}, t
+_CALLS = align_calls.Calls(joint=True)   # the buffers of a gsaj_rgbd_align8 call, the call, gsaj_pose_gn8_step on its row, JointRgbdAligner
+_tensors, _call, _run, _step, _aligner = _CALLS.tensors, _CALLS.call, _CALLS.run, _CALLS.step, _CALLS.aligner
+_bits, _dev = align_calls.bits, align_calls.dev
 
 
 def _expect(key, make, gain):
@@ -133,20 +95,6 @@ def test_planted_pixels_on_every_gate_through_the_joint_form(sign):
 
 
 # ---- the gates of the fold ----------------------------------------------------------------------------------------------------------------
-def _step(t, projection):
-    import torch
-
-    from gsaj import _lib
-    lib = _lib.load()
-    _lib.check(lib.gsaj_pose_gn8_step(t["row"].data_ptr(), 1, ar.LM["lambda_init"], ar.LM["nu"], ar.LM["lambda_min"], ar.LM["lambda_max"],
-                                      ar.LM["converged_threshold"], projection.data_ptr(), t["state"].data_ptr(), None,
-                                      torch.cuda.current_stream().cuda_stream), "gsaj_pose_gn8_step")
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint32)
-
-
 def test_a_frame_without_a_valid_pixel_moves_neither_the_pose_nor_the_exposure():
     import torch
     good = aj.parity_case8(80, 60, "depth", 0.1, 0.03)
@@ -258,17 +206,6 @@ def test_memory_contract_bands_poisoned_scratch_same_bits_on_any_stream(monkeypa
 
 # ---- behaviour ----------------------------------------------------------------------------------------------------------------------------
 BRIGHT = (0.1, 0.03)
-
-
-def _aligner(**kw):
-    from gsaj import JointRgbdAligner
-    cam = ar.camera()
-    return JointRgbdAligner(cam["W"], cam["H"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], DEV, levels=2, **kw)
-
-
-def _dev(case, name):
-    import torch
-    return None if case.get(name) is None else torch.from_numpy(np.ascontiguousarray(case[name], F)).to(DEV)
 
 
 @pytest.mark.parametrize("m", [1.0, 2.0])
