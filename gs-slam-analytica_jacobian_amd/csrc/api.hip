@@ -95,7 +95,7 @@ int gsaj_profile_end(float *stage_ms, int *stage_launches) {
 }
 
 const char *gsaj_last_error(void) { return g_err; }
-int gsaj_version(void) { return 112; }
+int gsaj_version(void) { return 113; }
 
 // (+ 256: the base slack of a workspace carved from its next 256-byte boundary, workspace.h)
 size_t gsaj_geom_workspace_bytes(int P) { GeomWS g; return geom_carve(Carver(nullptr, ALIGN_BASE), (size_t)(P > 0 ? P : 0), &g) + 256; }
@@ -971,6 +971,35 @@ int gsaj_debug_launch_plan(int P, int views, int W, int H, int *plan) {
   plan[GSAJ_PLAN_GPT] = sc.gpt;
   plan[GSAJ_PLAN_SCAT_WORKGROUPS] = sc.workgroups;
   plan[GSAJ_PLAN_SCAT_LDS] = sc.counters_lds ? 1 : 0;
+  return GSAJ_OK;
+}
+
+int gsaj_debug_lds_budget(int P, int views, int W, int H, int M, int tile_list_capacity, int stereo_W, int stereo_D, int *budget) {
+  LdsRequest stereo;
+  if (P <= 0 || views <= 0 || W <= 0 || H <= 0 || M < 0 || tile_list_capacity < 0 || !budget ||
+      !lds_stereo_winner(stereo_W, stereo_D, &stereo)) {
+    gsaj_set_error("gsaj_debug_lds_budget: invalid argument (P=%d views=%d W=%d H=%d M=%d tile_list_capacity=%d stereo_W=%d stereo_D=%d)",
+                   P, views, W, H, M, tile_list_capacity, stereo_W, stereo_D);
+    return GSAJ_ERR_INVALID_ARGUMENT;
+  }
+  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;  // (as fwd_params and composite form them)
+  const PreprocessPlan pre = plan_preprocess(P, views, gx, gy);
+  const ScatterPlan sc = plan_scatter(P, views, gx, gy);
+  const SortPlan sp = plan_tile_sort(sort_cap_of(tile_list_capacity));  // (as the asynchronous forwards: 0 is SORT_CAP keys)
+  auto put = [&](int launch, const LdsRequest &r) {
+    int *row = budget + launch * GSAJ_LDS_FIELDS;
+    row[GSAJ_LDS_DYNAMIC] = (int)r.dynamic_bytes;
+    row[GSAJ_LDS_STATIC] = (int)r.static_bytes;
+    row[GSAJ_LDS_LIMIT] = (int)r.limit_bytes;
+    row[GSAJ_LDS_VARIANT] = r.variant;
+  };
+  put(GSAJ_LDS_PREPROCESS, lds_preprocess(pre, gx, gy, M == 16));
+  put(GSAJ_LDS_FRAME_SCAN, lds_frame_scan(pre, gx, gy));
+  put(GSAJ_LDS_SCATTER, lds_scatter(sc, gx, gy));
+  put(GSAJ_LDS_TILE_SORT, sp.lds[0]);
+  put(GSAJ_LDS_TILE_SORT_2, sp.lds[1]);
+  put(GSAJ_LDS_GAUSSIAN_BWD, lds_gaussian_bwd(M, M > 0));
+  put(GSAJ_LDS_STEREO_WINNER, stereo);
   return GSAJ_OK;
 }
 

@@ -214,11 +214,23 @@ __global__ __launch_bounds__(GB_BLOCK) void k_gaussian_bwd(BwdParams p, GeomWS g
 #endif
 }
 
+// k_gaussian_bwd's LDS: rows[] (one trip of 256 instance rows) and s_last as __shared__; with SH coefficients, GB_BLOCK padded rows of
+// 3 M + 1 floats of dynamic LDS (M <= 16: 12.25 KB at the most)
+constexpr size_t GAUSSIAN_BWD_STATIC_LDS = lds_static_round(sizeof(float4[256 * REC_F4]) + sizeof(bool));
+LdsRequest lds_gaussian_bwd(int M, bool has_shs) {
+  LdsRequest r;
+  r.dynamic_bytes = has_shs ? sizeof(float) * GB_BLOCK * (3 * (size_t)M + 1) : 0;
+  r.static_bytes = GAUSSIAN_BWD_STATIC_LDS;
+  r.limit_bytes = LDS_DEFAULT_LIMIT;
+  r.variant = has_shs && (M == 1 || M == 4 || M == 9 || M == 16) ? 3 * M : 0;
+  return r;
+}
+
 int launch_gaussian_backward(const BwdParams &p, const GeomWS &g, const BinWS &b, const ImageWS &im, hipStream_t s) {
   const int nblk = (p.P + GB_BLOCK - 1) / GB_BLOCK;
   {
     GsajProfScope ps(ST_GAUSSIAN_BWD, s);
-    const size_t lds = p.shs ? sizeof(float) * GB_BLOCK * (3 * (size_t)p.M + 1) : 0;
+    const size_t lds = lds_gaussian_bwd(p.M, p.shs != nullptr).dynamic_bytes;
     switch (p.shs ? p.M : -1) {
       case 1: hipLaunchKernelGGL(k_gaussian_bwd<3>, dim3(nblk), dim3(GB_BLOCK), lds, s, p, g, im.counters, b.inst_grad, b.reached); break;
       case 4: hipLaunchKernelGGL(k_gaussian_bwd<12>, dim3(nblk), dim3(GB_BLOCK), lds, s, p, g, im.counters, b.inst_grad, b.reached); break;

@@ -210,6 +210,30 @@ struct ScatterPlan {
 PreprocessPlan plan_preprocess(int P, int views, int grid_x, int grid_y);
 ScatterPlan plan_scatter(int P, int views, int grid_x, int grid_y);
 
+// The LDS of one launch: what the launcher passes as dynamic LDS, what the kernel declares as __shared__ (a sizeof expression beside
+// the kernel; tests/test_cpu_lds_budget.py holds it to the compiler's figure) and the limit the launcher has secured for the sum
+// (LDS_DEFAULT_LIMIT, or what it hands to hipFuncSetAttribute).  Every launcher with dynamic LDS takes `dynamic_bytes` from the
+// function below that gsaj_debug_lds_budget reports (host only, pure).  variant: which instantiation runs (per function).
+#define LDS_DEFAULT_LIMIT 65536  // bytes of LDS a workgroup may hold, static + dynamic, unless the function's limit was raised
+struct LdsRequest {
+  size_t dynamic_bytes, static_bytes, limit_bytes;
+  int variant;
+};
+constexpr size_t lds_static_round(size_t bytes) { return (bytes + 3) / 4 * 4; }  // (a kernel's LDS is allocated in 4-byte words)
+LdsRequest lds_preprocess(const PreprocessPlan &pl, int grid_x, int grid_y, bool sh16);  // variant: 2 SH16 + MULTI
+LdsRequest lds_frame_scan(const PreprocessPlan &pl, int grid_x, int grid_y);
+LdsRequest lds_scatter(const ScatterPlan &pl, int grid_x, int grid_y);
+// the one or two launches of k_tile_sort for a capacity of sort_cap keys; variant: threads per tile (128, 256, 512)
+struct SortPlan {
+  int launches;     // 1: pass 0; 2: pass 1 with `cap` keys, pass 2 with half of them
+  int keys[2];      // LDS capacity of each launch, keys
+  int pass[2];
+  LdsRequest lds[2];
+};
+SortPlan plan_tile_sort(int sort_cap);
+LdsRequest lds_gaussian_bwd(int M, bool has_shs);  // variant: SHW = 3 M of the instantiation (0: the runtime-M one)
+bool lds_stereo_winner(int W, int D, LdsRequest *out);  // variant: D; false: a size gsaj_stereo_match refuses
+
 int launch_preprocess(const FwdParams &p, int *radii, int *n_touched, const GeomWS &g, const ImageWS &im, ViewStrides vs,
                       hipStream_t s);
 // tile binning of `views` frames: instance scatter -> per-tile (depth, id) sort -> point_list, ranges, cleared `reached` flags.

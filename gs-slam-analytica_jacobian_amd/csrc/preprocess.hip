@@ -375,9 +375,24 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_frame_scan(int nblk, int tiles, i
 #ifndef SCAT_CLS
 #define SCAT_CLS 8
 #endif
-#define SCAT_LDS_TILES 4096  // class-local tiles the LDS counters hold (3 words each: 48 KB); more: direct global atomics
 #define SCAT_STAGE 4096      // instances a workgroup stages in LDS before writing them out (16 KB of ids + 8 KB of 16-bit tile indices: six
                              // workgroups per CU; with the 32-bit slot staged beside the id: 32 KB, four); more: stored directly
+// The kernel's LDS is ONE budget: what it declares (the staging area, the scan words, the carry) + the counters the launcher requests
+// (3 words per class-local tile) <= LDS_DEFAULT_LIMIT.  SCAT_LDS_FIT is the number of class-local tiles that leaves room for, derived
+// from the declared arrays (24 596 bytes -> 3411 tiles, 40 932 bytes of counters); a grid with more (4K frames: 240 x 135 tiles, 4080)
+// takes the direct-global-atomics body.  The function's limit is NOT raised instead: 72 KB a workgroup would leave a CU two of them.
+// Both the kernel (use_lds) and the host (plan_scatter, lds_scatter) decide by this constant.  SCAT_LDS_TILES states its value as a
+// number for whoever reads the source (tests/binning_restated.py does): the build fails here when the arrays move it.
+constexpr size_t SCAT_STATIC_LDS =
+    sizeof(uint32_t[SCAT_STAGE]) + sizeof(uint16_t[SCAT_STAGE]) + sizeof(uint32_t[PRE_BLOCK / 64]) + sizeof(uint32_t);
+constexpr size_t SCAT_LDS_TILE_BYTES = 3 * sizeof(uint32_t);  // count -> reserved base, fill cursor, staging base
+constexpr int SCAT_LDS_FIT = (int)((LDS_DEFAULT_LIMIT - SCAT_STATIC_LDS) / SCAT_LDS_TILE_BYTES);
+static_assert(SCAT_STATIC_LDS + SCAT_LDS_TILE_BYTES * SCAT_LDS_FIT <= LDS_DEFAULT_LIMIT && SCAT_LDS_FIT > 0 && SCAT_LDS_FIT <= 65536,
+              "k_scatter_instances: the LDS counters do not fit beside the staging area (stage_lt holds 16-bit tile indices)");
+#define SCAT_LDS_TILES 3411  // = SCAT_LDS_FIT: class-local tiles the LDS counters hold (40 932 bytes); more: direct global atomics
+static_assert(SCAT_LDS_TILES == SCAT_LDS_FIT,
+              "the declared LDS of k_scatter_instances moved the last grid with LDS counters: restate SCAT_LDS_TILES, and move the "
+              "scenes of tests/binning_restated.py that sit on this edge");
 GSAJ_TRACE_DEFINE(scat)
 
 __global__ __launch_bounds__(PRE_BLOCK) void k_scatter_instances(int P, int gx, int gy, int gpt, GeomWS g, ImageWS im,
@@ -404,7 +419,7 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_scatter_instances(int P, int gx, 
   const int cls = (int)(blockIdx.x % SCAT_CLS), gb = (int)(blockIdx.x / SCAT_CLS);
   const int rows_c = (gy - cls + SCAT_CLS - 1) / SCAT_CLS;  // tile rows y = cls + SCAT_CLS * j < gy
   const int ltiles = rows_c > 0 ? rows_c * gx : 0;
-  const bool use_lds = ((gy + SCAT_CLS - 1) / SCAT_CLS) * gx <= SCAT_LDS_TILES;
+  const bool use_lds = ((gy + SCAT_CLS - 1) / SCAT_CLS) * gx <= SCAT_LDS_FIT;
   uint32_t *cnt = lds, *fill = lds + ltiles, *lbase = lds + 2 * ltiles;
   if (use_lds) {
     for (int t = tid; t < 2 * ltiles; t += PRE_BLOCK) lds[t] = 0u;
@@ -437,7 +452,7 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_scatter_instances(int P, int gx, 
       }                                                                                              \
     }                                                                                                \
   }
-  if (!use_lds) {  // (more than SCAT_LDS_TILES class-local tiles, ceil(gy / 8) * gx > 4096: e.g. beyond 4096 x 2048 pixels)
+  if (!use_lds) {  // (more than SCAT_LDS_TILES class-local tiles, ceil(gy / 8) * gx > 3411: e.g. a 3840 x 2160 frame, 17 x 240 = 4080)
     SCAT_FOR_EACH_TILE({ inst_id[im.tile_offset[t] + atomicAdd(&im.tile_cursor[t], 1u)] = id; })
     return;
   }
@@ -964,8 +979,54 @@ ScatterPlan plan_scatter(int P, int views, int grid_x, int grid_y) {
   const int per = PRE_BLOCK * gpt;
   pl.gpt = gpt;
   pl.workgroups = ((P + per - 1) / per) * SCAT_CLS;
-  pl.counters_lds = ((grid_y + SCAT_CLS - 1) / SCAT_CLS) * grid_x <= SCAT_LDS_TILES;
+  pl.counters_lds = ((grid_y + SCAT_CLS - 1) / SCAT_CLS) * grid_x <= SCAT_LDS_FIT;
   return pl;
+}
+
+// ---- the LDS each launch below asks for (host only, pure: gsaj_common.h; gsaj_debug_lds_budget reports what they return) ------------
+// what the kernels declare as __shared__: k_preprocess its scan words; k_frame_scan its own scan words and maxima + those and the 64
+// length classes of tile_scan_and_schedule; k_scatter_instances SCAT_STATIC_LDS (above); k_tile_sort nothing
+constexpr size_t PREPROCESS_STATIC_LDS = sizeof(uint32_t[PRE_BLOCK / 64]);
+constexpr size_t FRAME_SCAN_STATIC_LDS = 2 * sizeof(uint32_t[PRE_BLOCK / 64]) + (2 * sizeof(uint32_t[PRE_BLOCK / 64]) + sizeof(uint32_t[64]));
+constexpr size_t TILE_SORT_STATIC_LDS = 0;
+static_assert(FRAME_SCAN_STATIC_LDS + sizeof(uint32_t) * LDS_TILES_MAX <= LDS_DEFAULT_LIMIT, "the LDS tile histogram does not fit");
+
+static size_t hist_lds_bytes(const PreprocessPlan &pl, int grid_x, int grid_y) {  // one word per tile, in both kernels
+  return pl.hist_lds ? sizeof(uint32_t) * (size_t)grid_x * (size_t)grid_y : 0;
+}
+LdsRequest lds_preprocess(const PreprocessPlan &pl, int grid_x, int grid_y, bool sh16) {
+  return LdsRequest{hist_lds_bytes(pl, grid_x, grid_y), PREPROCESS_STATIC_LDS, LDS_DEFAULT_LIMIT, (sh16 ? 2 : 0) + (pl.bpw > 1 ? 1 : 0)};
+}
+LdsRequest lds_frame_scan(const PreprocessPlan &pl, int grid_x, int grid_y) {
+  return LdsRequest{hist_lds_bytes(pl, grid_x, grid_y), FRAME_SCAN_STATIC_LDS, LDS_DEFAULT_LIMIT, 0};
+}
+LdsRequest lds_scatter(const ScatterPlan &pl, int grid_x, int grid_y) {
+  const size_t ltiles = (size_t)((grid_y + SCAT_CLS - 1) / SCAT_CLS) * (size_t)grid_x;
+  return LdsRequest{pl.counters_lds ? SCAT_LDS_TILE_BYTES * ltiles : 0, SCAT_STATIC_LDS, LDS_DEFAULT_LIMIT, 0};
+}
+SortPlan plan_tile_sort(int sort_cap) {
+  SortPlan sp;
+  int cap = 128;
+  while (cap < sort_cap && cap < SORT_CAP) cap <<= 1;
+  // lists of 8193 .. 16384 keys: more dynamic LDS than the 64 KB default limit, which launch_tile_binning then raises to the request
+  const size_t limit = sizeof(uint64_t) * (size_t)cap > LDS_DEFAULT_LIMIT ? sizeof(uint64_t) * (size_t)cap : LDS_DEFAULT_LIMIT;
+  // (+ the merge-path splits of a list longer than the capacity: behind the keys below 4096, inside the capacity from there on)
+  const size_t split_bytes = cap >= 4096 ? 0 : sizeof(uint32_t) * (PRE_BLOCK + 1);
+  // a launch with 32 KB of keys or more per workgroup runs 512 threads per tile (k_tile_sort)
+  auto request = [&](int keys, size_t extra) {
+    return LdsRequest{sizeof(uint64_t) * (size_t)keys + extra, TILE_SORT_STATIC_LDS, keys >= 4096 ? limit : (size_t)LDS_DEFAULT_LIMIT,
+                      keys >= 4096 ? 512 : keys > GSAJ_SORT_128_MAX ? 256 : 128};
+  };
+  if (cap >= 4096) {  // two launches by padded list length: the many lists below half the capacity run with half the LDS
+    sp.launches = 2;
+    sp.keys[0] = cap, sp.pass[0] = 1, sp.lds[0] = request(cap, 0);
+    sp.keys[1] = cap / 2, sp.pass[1] = 2, sp.lds[1] = request(cap / 2, 0);
+  } else {
+    sp.launches = 1;
+    sp.keys[0] = cap, sp.pass[0] = 0, sp.lds[0] = request(cap, split_bytes);
+    sp.keys[1] = 0, sp.pass[1] = 0, sp.lds[1] = LdsRequest{0, 0, 0, 0};
+  }
+  return sp;
 }
 
 int launch_preprocess(const FwdParams &p0, int *radii, int *n_touched, const GeomWS &g, const ImageWS &im, ViewStrides vs,
@@ -984,18 +1045,20 @@ int launch_preprocess(const FwdParams &p0, int *radii, int *n_touched, const Geo
   {
     GsajProfScope ps(ST_PREPROCESS, s);
     const int tiles = p.grid_x * p.grid_y;
-    const size_t lds = pl.hist_lds ? sizeof(uint32_t) * (size_t)tiles : 0;
 #ifndef GSAJ_PRE_NO_SHREGS
-    if (!p.colors_precomp && p.M == 16)
+    const bool sh16 = !p.colors_precomp && p.M == 16;
 #else
-    if (false)
+    const bool sh16 = false;
 #endif
+    const size_t lds = lds_preprocess(pl, p.grid_x, p.grid_y, sh16).dynamic_bytes;
+    if (sh16)
       if (p.bpw > 1) hipLaunchKernelGGL((k_preprocess<true, true>), dim3(nwg, views), dim3(PRE_BLOCK), lds, s, p, radii, n_touched, g, im, vs);
       else hipLaunchKernelGGL((k_preprocess<true, false>), dim3(nwg, views), dim3(PRE_BLOCK), lds, s, p, radii, n_touched, g, im, vs);
     else
       if (p.bpw > 1) hipLaunchKernelGGL((k_preprocess<false, true>), dim3(nwg, views), dim3(PRE_BLOCK), lds, s, p, radii, n_touched, g, im, vs);
       else hipLaunchKernelGGL((k_preprocess<false, false>), dim3(nwg, views), dim3(PRE_BLOCK), lds, s, p, radii, n_touched, g, im, vs);
-    hipLaunchKernelGGL(k_frame_scan, dim3(1, views), dim3(PRE_BLOCK), lds, s, nblk, tiles, p.capacity, g, im, vs);
+    hipLaunchKernelGGL(k_frame_scan, dim3(1, views), dim3(PRE_BLOCK), lds_frame_scan(pl, p.grid_x, p.grid_y).dynamic_bytes, s, nblk, tiles,
+                       p.capacity, g, im, vs);
   }
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
@@ -1005,9 +1068,8 @@ int launch_tile_binning(int P, int sort_cap, int rec16, int grid_x, int grid_y, 
                         int views, ViewStrides vs, hipStream_t s) {
   {
     GsajProfScope ps(ST_SCATTER, s);
-    const int ltiles = ((grid_y + SCAT_CLS - 1) / SCAT_CLS) * grid_x;
     const ScatterPlan pl = plan_scatter(P, views, grid_x, grid_y);  // (gpt: Gaussians per thread)
-    const size_t lds = pl.counters_lds ? 3 * sizeof(uint32_t) * (size_t)ltiles : 0;
+    const size_t lds = lds_scatter(pl, grid_x, grid_y).dynamic_bytes;
     hipLaunchKernelGGL(k_scatter_instances, dim3((unsigned)pl.workgroups, views), dim3(PRE_BLOCK), lds, s, P, grid_x, grid_y, pl.gpt,
                        g, im, b.point_list, vs);
     if (rec16)
@@ -1015,31 +1077,22 @@ int launch_tile_binning(int P, int sort_cap, int rec16, int grid_x, int grid_y, 
   }
   {
     GsajProfScope ps(ST_TILE_SORT, s);
-    int cap = 128;
-    while (cap < sort_cap && cap < SORT_CAP) cap <<= 1;
-    if (sizeof(uint64_t) * (size_t)cap > 65536)  // lists of 8193 .. 16384 keys: more dynamic LDS than the 64 KB default limit
+    const SortPlan sp = plan_tile_sort(sort_cap);  // (capacity class, one launch or two, threads and LDS of each)
+    if (sp.lds[0].limit_bytes > LDS_DEFAULT_LIMIT)  // lists of 8193 .. 16384 keys: more dynamic LDS than the 64 KB default limit
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile_sort<512>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(sizeof(uint64_t) * (size_t)cap));
-    // (+ the merge-path splits of a list longer than the capacity: behind the keys below 4096, inside the capacity from there on)
-    const size_t split_bytes = cap >= 4096 ? 0 : sizeof(uint32_t) * (PRE_BLOCK + 1);
-    // a launch with 32 KB of keys or more per workgroup runs 512 threads per tile (k_tile_sort)
-    auto launch = [&](int lds_keys, int pass, size_t extra) {
-      const size_t dyn = sizeof(uint64_t) * (size_t)lds_keys + extra;
-      if (lds_keys >= 4096)
+                                (int)sp.lds[0].limit_bytes);
+    for (int i = 0; i < sp.launches; i++) {
+      const int lds_keys = sp.keys[i], pass = sp.pass[i], threads = sp.lds[i].variant;
+      const size_t dyn = sp.lds[i].dynamic_bytes;
+      if (threads == 512)
         hipLaunchKernelGGL(k_tile_sort<512>, dim3(grid_x * grid_y, views), dim3(512), dyn, s, im, g.depths, b.keys_unsorted, b.keys,
                            b.point_list, b.reached, lds_keys, pass, rec16, vs);
-      else if (lds_keys > GSAJ_SORT_128_MAX)
+      else if (threads == 256)
         hipLaunchKernelGGL(k_tile_sort<256>, dim3(grid_x * grid_y, views), dim3(256), dyn, s, im, g.depths, b.keys_unsorted, b.keys,
                            b.point_list, b.reached, lds_keys, pass, rec16, vs);
       else
         hipLaunchKernelGGL(k_tile_sort<128>, dim3(grid_x * grid_y, views), dim3(128), dyn, s, im, g.depths, b.keys_unsorted, b.keys,
                            b.point_list, b.reached, lds_keys, pass, rec16, vs);
-    };
-    if (cap >= 4096) {  // two launches by padded list length: the many lists below half the capacity run with half the LDS
-      launch(cap, 1, 0);
-      launch(cap / 2, 2, 0);
-    } else {
-      launch(cap, 0, split_bytes);
     }
   }
   GSAJ_HIP_CHECK(hipGetLastError());

@@ -262,6 +262,20 @@ __global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_winner(StereoWinner p) 
   }
 }
 
+// k_stereo_winner's LDS: disp2 [W] 8-byte keys + d16 [W] ints of dynamic LDS, no __shared__ of its own.  W <= STEREO_MAX_W keeps the
+// request under LDS_DEFAULT_LIMIT (stereo_sizes_ok refuses a wider image before anything is launched).
+constexpr size_t STEREO_WINNER_STATIC_LDS = 0;
+static_assert(STEREO_WINNER_STATIC_LDS + (size_t)STEREO_MAX_W * (sizeof(unsigned long long) + sizeof(int)) <= LDS_DEFAULT_LIMIT,
+              "k_stereo_winner: STEREO_MAX_W columns no longer fit the LDS of a workgroup");
+bool lds_stereo_winner(int W, int D, LdsRequest *out) {
+  if ((D != 16 && D != 32 && D != 64 && D != 128) || W <= D || W > STEREO_MAX_W) return false;
+  out->dynamic_bytes = (size_t)W * (sizeof(unsigned long long) + sizeof(int));
+  out->static_bytes = STEREO_WINNER_STATIC_LDS;
+  out->limit_bytes = LDS_DEFAULT_LIMIT;
+  out->variant = D;
+  return true;
+}
+
 // ---- C ABI ----------------------------------------------------------------------------------------------------------------------------
 static bool stereo_sizes_ok(const char *who, int W, int H, int D, int paths) {
   if (D != 16 && D != 32 && D != 64 && D != 128) {
@@ -316,8 +330,11 @@ static hipError_t stereo_launch(int stages, int W, int H, const uint8_t *left, s
     constexpr int per_block = (STEREO_BLOCK / 64) * (D < 64 ? 64 / D : 1);
     hipLaunchKernelGGL(k_stereo_paths<D>, dim3((unsigned)((lines + per_block - 1) / per_block)), dim3(STEREO_BLOCK), 0, s, pp);
   }
-  if (stages & GSAJ_STEREO_STAGE_WINNER)
-    hipLaunchKernelGGL(k_stereo_winner<D>, dim3((unsigned)H), dim3(STEREO_BLOCK), (size_t)W * 12, s, wp);
+  if (stages & GSAJ_STEREO_STAGE_WINNER) {
+    LdsRequest lds;
+    if (!lds_stereo_winner(W, D, &lds)) return hipErrorInvalidValue;  // (cannot happen: stereo_sizes_ok has passed)
+    hipLaunchKernelGGL(k_stereo_winner<D>, dim3((unsigned)H), dim3(STEREO_BLOCK), lds.dynamic_bytes, s, wp);
+  }
   return hipGetLastError();
 }
 

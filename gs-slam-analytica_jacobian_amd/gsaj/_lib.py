@@ -67,6 +67,7 @@ SIGNATURES = {
     "gsaj_mark_visible": (c_int, [c_int, P, P, P, P, P]),
     "gsaj_debug_export": (c_int, [c_int] * 4 + [P] * 3 + [P] * 11 + [P]),
     "gsaj_debug_launch_plan": (c_int, [c_int] * 4 + [ctypes.POINTER(c_int)]),
+    "gsaj_debug_lds_budget": (c_int, [c_int] * 8 + [ctypes.POINTER(c_int)]),
     "gsaj_debug_export_taken": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
     "gsaj_debug_export_view_sums": (c_int, [c_int, P, P, P]),
     "gsaj_debug_export_view_sums_gather": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P]),

@@ -341,6 +341,22 @@ def launch_plan(P, views, W, H):
     return dict(zip(PLAN_FIELDS, (int(x) for x in plan)))
 
 
+LDS_LAUNCHES = ("preprocess", "frame_scan", "scatter", "tile_sort", "tile_sort_2", "gaussian_bwd", "stereo_winner")  # GSAJ_LDS_* rows
+LDS_FIELDS = ("dynamic", "static", "limit", "variant")  # GSAJ_LDS_* fields of include/gsaj.h, in order
+
+
+def lds_budget(P, views, W, H, M=1, tile_list_capacity=0, stereo_W=4096, stereo_D=64):
+    """The LDS of every launch that passes dynamic LDS, for ONE call with `views` views of P Gaussians (M SH coefficients per channel)
+    at W x H sorted with tile_list_capacity keys, and of the disparity winner of a stereo_W wide pair at stereo_D disparities, from
+    the functions the launchers take their byte counts from (gsaj_debug_lds_budget; host only, no device needed):
+    {launch: dict of LDS_FIELDS} over LDS_LAUNCHES."""
+    out = (ctypes.c_int * (len(LDS_LAUNCHES) * len(LDS_FIELDS)))()
+    _lib.check(_lib.load().gsaj_debug_lds_budget(int(P), int(views), int(W), int(H), int(M), int(tile_list_capacity), int(stereo_W),
+                                                 int(stereo_D), out), "gsaj_debug_lds_budget")
+    n = len(LDS_FIELDS)
+    return {name: dict(zip(LDS_FIELDS, (int(x) for x in out[i * n:(i + 1) * n]))) for i, name in enumerate(LDS_LAUNCHES)}
+
+
 def debug_export_taken(R, W, H, binningBuffer, imageBuffer):
     """(taken [R] int32 by list position, reached [R] uint8 by emission slot) of one view: which entries the forward compositor
     took per quadrant (byte q of a word), cleared beyond each quadrant's furthest last contributor as the reverse compositor

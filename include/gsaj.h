@@ -1109,7 +1109,7 @@ int gsaj_dense_tau(int N, int sh_coeffs, int sh_degree, const int *order, const 
  *   GSAJ_PLAN_HIST_LDS          1: its tile histogram is kept in LDS (at most 8192 tiles), 0: global atomics
  *   GSAJ_PLAN_GPT               blocks of 256 Gaussians per instance-scatter workgroup (4, 8, 9 or 10)
  *   GSAJ_PLAN_SCAT_WORKGROUPS   scatter workgroups per view: 8 row classes x ceil(P / (256 gpt))
- *   GSAJ_PLAN_SCAT_LDS          1: the scatter's tile counters are in LDS (ceil(tile rows / 8) x tile columns <= 4096)
+ *   GSAJ_PLAN_SCAT_LDS          1: the scatter's tile counters are in LDS (ceil(tile rows / 8) x tile columns <= 3411)
  * GSAJ_ERR_INVALID_ARGUMENT: P, views, W or H <= 0, or plan NULL. */
 #define GSAJ_PLAN_BPW 0
 #define GSAJ_PLAN_PRE_WORKGROUPS 1
@@ -1119,6 +1119,43 @@ int gsaj_dense_tau(int N, int sh_coeffs, int sh_degree, const int *order, const 
 #define GSAJ_PLAN_SCAT_LDS 5
 #define GSAJ_PLAN_COUNT 6
 int gsaj_debug_launch_plan(int P, int views, int W, int H, int *plan /*host [GSAJ_PLAN_COUNT]*/);
+
+/* The LDS of every launch that passes dynamic LDS (tests, debugging).  Host only, touches no device: for `views` views of P Gaussians
+ * with M SH coefficients per channel (0: precomputed colours) at W x H, sorted with tile_list_capacity keys of LDS (0: the default,
+ * 16384), and for the disparity winner of a stereo_W pixel wide pair at stereo_D disparities -- computed by the functions the launchers
+ * themselves take their byte counts from.  budget [GSAJ_LDS_LAUNCHES][GSAJ_LDS_FIELDS] (host memory), one row per launch:
+ *   GSAJ_LDS_PREPROCESS      the per-Gaussian forward: 4 bytes per tile, up to 8192 tiles          variant: 2 (M = 16) + 1 (bpw > 1)
+ *   GSAJ_LDS_FRAME_SCAN      the frame scan: the same
+ *   GSAJ_LDS_SCATTER         the instance scatter: 12 bytes per class-local tile while GSAJ_PLAN_SCAT_LDS
+ *   GSAJ_LDS_TILE_SORT       the tile sort's first (or only) launch: 8 bytes per key (+ 1028 below 4096 keys)    variant: threads per tile
+ *   GSAJ_LDS_TILE_SORT_2     its second launch, half the keys (from 4096 keys on; else a row of zeros)           variant: threads per tile
+ *   GSAJ_LDS_GAUSSIAN_BWD    the per-Gaussian backward: 64 rows of 3 M + 1 floats                                variant: 3 M, or 0
+ *   GSAJ_LDS_STEREO_WINNER   the disparity winner: 12 bytes per column                                           variant: stereo_D
+ * and per row:
+ *   GSAJ_LDS_DYNAMIC   bytes of dynamic LDS the launcher passes
+ *   GSAJ_LDS_STATIC    bytes of LDS the kernel itself declares
+ *   GSAJ_LDS_LIMIT     bytes a workgroup of that kernel may hold, static + dynamic, as the launcher has secured it: 65536, or what it
+ *                      raises the function's limit to (the tile sort above 8192 keys)
+ *   GSAJ_LDS_VARIANT   which instantiation of the kernel runs
+ * The instance scatter counts in LDS only while GSAJ_LDS_STATIC + GSAJ_LDS_DYNAMIC <= 65536: with 24 596 bytes declared, up to
+ * 3411 class-local tiles; a larger grid (3840 x 2160: 4080) requests none and counts with global atomics.
+ * GSAJ_ERR_INVALID_ARGUMENT: P, views, W or H <= 0, M or tile_list_capacity < 0, budget NULL, or a stereo size gsaj_stereo_match
+ * refuses (stereo_D not 16, 32, 64 or 128, stereo_W <= stereo_D or > 4096). */
+#define GSAJ_LDS_PREPROCESS 0
+#define GSAJ_LDS_FRAME_SCAN 1
+#define GSAJ_LDS_SCATTER 2
+#define GSAJ_LDS_TILE_SORT 3
+#define GSAJ_LDS_TILE_SORT_2 4
+#define GSAJ_LDS_GAUSSIAN_BWD 5
+#define GSAJ_LDS_STEREO_WINNER 6
+#define GSAJ_LDS_LAUNCHES 7
+#define GSAJ_LDS_DYNAMIC 0
+#define GSAJ_LDS_STATIC 1
+#define GSAJ_LDS_LIMIT 2
+#define GSAJ_LDS_VARIANT 3
+#define GSAJ_LDS_FIELDS 4
+int gsaj_debug_lds_budget(int P, int views, int W, int H, int M, int tile_list_capacity, int stereo_W, int stereo_D,
+                          int *budget /*host [GSAJ_LDS_LAUNCHES][GSAJ_LDS_FIELDS]*/);
 
 /* ---- frame-to-frame RGB-D alignment: the start pose of a new frame (csrc/align.hip) --------------------------------------------
  * The reference starts a new frame's tracking at the previous frame's pose (utils/slam_frontend.py:129-130) and has NO counterpart of

@@ -23,7 +23,7 @@ LAYOUT_GX = 7
 F = 64.0  # focal length of the one-tile scenes, pixels
 
 # what the layouts above (and the two scatter scenes of the tests) were designed for
-DESIGN_CONSTANTS = dict(PRE_BLOCK=256, SORT_CAP=16384, GSAJ_SORT_128_MAX=1024, SCAT_CLS=8, SCAT_LDS_TILES=4096, SCAT_STAGE=4096,
+DESIGN_CONSTANTS = dict(PRE_BLOCK=256, SORT_CAP=16384, GSAJ_SORT_128_MAX=1024, SCAT_CLS=8, SCAT_LDS_TILES=3411, SCAT_STAGE=4096,
                         LDS_TILES_MAX=8192)
 
 
@@ -139,10 +139,11 @@ def layout(name, depths, reverse=False):
 
 
 def scatter_scene(which):
-    """S1: 4097 x 1 tiles -- ceil(gy / 8) * gx = 4097 class-local tiles, one more than the scatter's LDS counters hold, while the
+    """S1: 4097 x 1 tiles -- ceil(gy / 8) * gx = 4097 class-local tiles, more than the scatter's LDS counters hold, while the
     4097 tiles still fit the LDS histogram of k_preprocess / k_frame_scan: k_scatter_instances takes its direct-global-atomics
     body.  S2: 8 x 8 tiles under 1100 screen-filling Gaussians: a scatter workgroup of 1024 Gaussians holds 8192 instances of
     every row class, twice the staging area, and the last workgroup (76 Gaussians) 608: both store paths in one launch.
+    S3 .. S5, H1, H2: BUDGET_SCENES below.
     -> (cam, scene)"""
     import helpers as hp
 
@@ -153,6 +154,32 @@ def scatter_scene(which):
         cam = hp.small_camera(128, 128, f=0.8 * 128, orthonormal=True)
         sc = syn.make_scene(1100, 21, cam, z_range=(1.0, 2.0), log_scale_range=(math.log(0.5), math.log(2.0)), sh_coeffs=1,
                             opacity_range=(0.002, 0.01), margin=0)
+    elif which in BUDGET_SCENES:
+        W, H, P, _ = BUDGET_SCENES[which]
+        f = 0.5 * max(W, H)
+        cam = hp.small_camera(W, H, f=f, orthonormal=True)
+        # sigma 0.5 .. 50 pixels at depth 1 (a quarter of that at depth 4): from inside one tile to some twenty tiles across
+        sc = syn.make_scene(P, 30 + sorted(BUDGET_SCENES).index(which), cam, z_range=(1.0, 4.0),
+                            log_scale_range=(math.log(2.0 / f), math.log(50.0 / f)), sh_coeffs=1, margin=0)
     else:
         raise KeyError(which)
     return cam, sc
+
+
+# The far ends of the size classes whose launches request dynamic LDS that grows with the tile grid: the scatter's counters (12 bytes
+# per class-local tile, ltiles = ceil(tile rows / 8) x tile columns, beside the 24 596 bytes k_scatter_instances declares: 3411 is
+# the last ltiles at which both fit in 64 KB) and the tile histogram of k_preprocess / k_frame_scan (4 bytes per tile up to
+# LDS_TILES_MAX = 8192).  id -> (W, H, Gaussians, backward run).  tests/test_cpu_lds_budget.py holds every premise to the library's plan.
+#   S3  379 x 65 tiles, ltiles 9 x 379 = 3411: the last launch with LDS counters, every row class populated
+#   S4  853 x 25 tiles, ltiles 4 x 853 = 3412: the first launch past the bound -- the global-atomics body on a grid with several
+#       row classes (S1 has one row)
+#   S5  240 x 135 tiles (3840 x 2160), ltiles 17 x 240 = 4080
+#   H1  128 x 64 = 8192 tiles: the last LDS histogram
+#   H2  241 x 34 = 8194 tiles: the first global histogram with the scatter still in LDS (ltiles 5 x 241 = 1205)
+BUDGET_SCENES = {
+    "S3": (6064, 1040, 3000, True),
+    "S4": (13648, 400, 3000, True),
+    "S5": (3840, 2160, 300, False),
+    "H1": (2048, 1024, 3000, True),
+    "H2": (3856, 544, 3000, True),
+}

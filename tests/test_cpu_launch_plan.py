@@ -86,13 +86,18 @@ def test_the_table_holds_every_shape_the_gpu_tests_run_with_the_variant_they_cla
 
 
 def test_the_tile_grid_moves_the_histogram_and_the_scatter_counters_out_of_lds():
-    """hist_lds: tiles <= 8192; scat_lds: ceil(tile rows / 8) x tile columns <= 4096 -- at their edges, and neither moves bpw or gpt."""
+    """hist_lds: tiles <= 8192; scat_lds: ceil(tile rows / 8) x tile columns <= 3411 (the counters, 12 bytes each, beside the 24 596
+    bytes k_scatter_instances declares, in 64 KB: tests/test_cpu_lds_budget.py) -- at their edges, and neither moves bpw or gpt."""
     for w, h, hist, scat, what in [
-        (16 * 4096, 16, 1, 1, "4096 x 1 tiles: the last strip the scatter counts in LDS"),
+        (16 * 3411, 16, 1, 1, "3411 x 1 tiles: the last strip the scatter counts in LDS"),
+        (16 * 3411 + 1, 16, 1, 0, "3412 x 1: the first strip past the budget"),
+        (16 * 4096, 16, 1, 0, "4096 x 1: the edge before the budget counted the declared LDS (73 748 bytes in all)"),
         (16 * 4096 + 1, 16, 1, 0, "4097 x 1 (scene S1 of tests/binning_restated.py)"),
         (16 * 8192, 16, 1, 0, "8192 tiles: the last histogram in LDS"),
         (16 * 8192 + 1, 16, 0, 0, "8193 tiles"),
-        (16 * 512, 16 * 64, 0, 1, "512 x 64 = 32768 tiles in 8 x 512 = 4096 class-local ones"),
+        (16 * 512, 16 * 48, 0, 1, "512 x 48 = 24576 tiles in 6 x 512 = 3072 class-local ones: the last multiple of 512 under 3411"),
+        (16 * 512, 16 * 48 + 1, 0, 0, "a 49th tile row: 7 x 512 = 3584"),
+        (16 * 512, 16 * 64, 0, 0, "512 x 64 in 8 x 512 = 4096: the other edge before the budget"),
         (16 * 512, 16 * 64 + 1, 0, 0, "a 65th tile row: 9 x 512"),
         (16384, 16, 1, 1, "1024 x 1: the widest image a backward takes"),
         (16, 16384, 1, 1, "1 x 1024: the tallest"),

@@ -170,7 +170,7 @@ def _scatter_parity(which, backward):
 
 
 def test_scatter_without_lds_counters():
-    """Scene S1 (4097 x 1 tiles: one class-local tile more than SCAT_LDS_TILES): the direct-global-atomics body of
+    """Scene S1 (4097 x 1 tiles: more class-local tiles than SCAT_LDS_TILES): the direct-global-atomics body of
     k_scatter_instances.  Premises: test_cpu_binning.test_scene_s1_has_more_class_local_tiles_than_the_scatter_counters."""
     _scatter_parity("S1", backward=False)
 
@@ -180,3 +180,13 @@ def test_scatter_past_the_staging_area():
     608 (staged).  Premises: test_cpu_binning.test_scene_s2_fills_and_overfills_the_staging_area.  Its 1100-entry lists of
     screen-filling Gaussians also go through the reverse compositor."""
     _scatter_parity("S2", backward=True)
+
+
+@pytest.mark.parametrize("which", sorted(br.BUDGET_SCENES))
+def test_the_far_end_of_every_lds_size_class(which):
+    """binning_restated.BUDGET_SCENES: the last launch whose scatter counters fit the LDS beside what the kernel declares (S3), the
+    first past it (S4) and a 3840 x 2160 frame (S5) -- both on the global-atomics body, over several row classes --, the last LDS
+    tile histogram (H1) and the first global one with the scatter still in LDS (H2).  Through the synchronous entry point: a launch
+    the runtime refuses is the library's error, not stale lists.  Premises (which body each launch takes, by the library's own plan
+    and LDS figures): tests/test_cpu_lds_budget.py."""
+    _scatter_parity(which, backward=br.BUDGET_SCENES[which][3])
