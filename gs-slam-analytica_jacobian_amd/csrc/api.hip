@@ -95,7 +95,7 @@ int gsaj_profile_end(float *stage_ms, int *stage_launches) {
 }
 
 const char *gsaj_last_error(void) { return g_err; }
-int gsaj_version(void) { return 113; }
+int gsaj_version(void) { return 114; }
 
 // (+ 256: the base slack of a workspace carved from its next 256-byte boundary, workspace.h)
 size_t gsaj_geom_workspace_bytes(int P) { GeomWS g; return geom_carve(Carver(nullptr, ALIGN_BASE), (size_t)(P > 0 ? P : 0), &g) + 256; }

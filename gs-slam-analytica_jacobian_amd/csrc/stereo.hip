@@ -98,12 +98,13 @@ __global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_cost(int W, int H, int 
 // ---- e. the paths ------------------------------------------------------------------------------------------------------------------------
 struct StereoPaths {
   int W, H, P1, P2, paths;
+  int xf;   // the first valid column: D for the rectified pair, 0 for a volume that is valid everywhere (sweep.hip)
   const uint16_t *C;
   uint32_t *S;
 };
 
-// The lines of direction (dx, dy) over the valid region x in [D, W): every pixel whose predecessor lies outside starts one.
-//   dy == 0: H lines; dx == 0: W - D lines; a diagonal: the W - D pixels of its first row, then the H - 1 others of its first column
+// The lines of direction (dx, dy) over the valid region x in [xf, W): every pixel whose predecessor lies outside starts one.
+//   dy == 0: H lines; dx == 0: W - xf lines; a diagonal: the W - xf pixels of its first row, then the H - 1 others of its first column
 __device__ __forceinline__ int stereo_line_count(int dx, int dy, int Wv, int H) { return dy == 0 ? H : dx == 0 ? Wv : Wv + H - 1; }
 
 template <int D>
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_paths(StereoPaths p) {
   constexpr int WIDTH = D < 64 ? D : 64, LPW = 64 / WIDTH, NV = D / WIDTH;   // lanes per line, lines per wave, disparities per lane
   const int DX[8] = {1, -1, 0, 0, 1, -1, 1, -1}, DY[8] = {0, 0, 1, -1, 1, 1, -1, -1};
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane & (WIDTH - 1);
-  const int Wv = p.W - D;
+  const int Wv = p.W - p.xf;
   int rem = ((int)blockIdx.x * (STEREO_BLOCK / 64) + wave) * LPW + lane / WIDTH;
   int dx = 0, dy = 0, x0 = 0, y0 = 0, len = 0;
   bool found = false;
@@ -128,16 +129,16 @@ __global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_paths(StereoPaths p) {
   if (found) {
     if (dy == 0) {
       y0 = rem;
-      x0 = dx > 0 ? D : p.W - 1;
+      x0 = dx > 0 ? p.xf : p.W - 1;
     } else if (dx == 0 || rem < Wv) {
-      x0 = D + rem;
+      x0 = p.xf + rem;
       y0 = dy > 0 ? 0 : p.H - 1;
     } else {
       const int j = rem - Wv + 1;   // 1 .. H - 1
-      x0 = dx > 0 ? D : p.W - 1;
+      x0 = dx > 0 ? p.xf : p.W - 1;
       y0 = dy > 0 ? j : p.H - 1 - j;
     }
-    const int lx = dx > 0 ? p.W - x0 : dx < 0 ? x0 - D + 1 : INT32_MAX;
+    const int lx = dx > 0 ? p.W - x0 : dx < 0 ? x0 - p.xf + 1 : INT32_MAX;
     const int ly = dy > 0 ? p.H - y0 : dy < 0 ? y0 + 1 : INT32_MAX;
     len = min(lx, ly);
   }
@@ -179,6 +180,31 @@ __global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_paths(StereoPaths p) {
     }
     c = cn;
   }
+}
+
+// One launch for every line of every direction over the columns [first_col, W) of C, after S has been zeroed on the stream (S is summed
+// into).  Shared with sweep.hip (gsaj_common.h); sizes are the caller's to have checked.
+template <int D>
+static void stereo_paths_launch(const StereoPaths &pp, hipStream_t s) {
+  const int Wv = pp.W - pp.xf;
+  const int lines = (pp.paths == 8 ? 4 : 0) * (Wv + pp.H - 1) + 2 * pp.H + 2 * Wv;
+  constexpr int per_block = (STEREO_BLOCK / 64) * (D < 64 ? 64 / D : 1);
+  hipLaunchKernelGGL(k_stereo_paths<D>, dim3((unsigned)((lines + per_block - 1) / per_block)), dim3(STEREO_BLOCK), 0, s, pp);
+}
+
+hipError_t launch_stereo_paths(int D, int W, int H, int first_col, int P1, int P2, int paths, const uint16_t *C, uint32_t *S, hipStream_t s) {
+  if ((D != 16 && D != 32 && D != 64 && D != 128) || first_col < 0 || first_col >= W || H < 1 || (paths != 4 && paths != 8)) return hipErrorInvalidValue;
+  const hipError_t e = hipMemsetAsync(S, 0, (size_t)W * H * D * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  StereoPaths pp;
+  pp.W = W; pp.H = H; pp.P1 = P1; pp.P2 = P2; pp.paths = paths; pp.xf = first_col; pp.C = C; pp.S = S;
+  switch (D) {
+    case 16: stereo_paths_launch<16>(pp, s); break;
+    case 32: stereo_paths_launch<32>(pp, s); break;
+    case 64: stereo_paths_launch<64>(pp, s); break;
+    default: stereo_paths_launch<128>(pp, s); break;
+  }
+  return hipGetLastError();
 }
 
 // ---- f-i. winner, uniqueness, sub-pixel, left-right check, depth -------------------------------------------------------------------------
@@ -324,11 +350,8 @@ static hipError_t stereo_launch(int stages, int W, int H, const uint8_t *left, s
                        0, s, W, H, r, ws.pl, ws.pr, ws.C);
   }
   if (stages & GSAJ_STEREO_STAGE_PATHS) {
-    const hipError_t e = hipMemsetAsync(ws.S, 0, (size_t)W * H * D * sizeof(uint32_t), s);   // S is summed into: zeroed here, on the stream
+    const hipError_t e = launch_stereo_paths(D, W, H, D, pp.P1, pp.P2, pp.paths, pp.C, pp.S, s);   // S is summed into: zeroed there, on the stream
     if (e != hipSuccess) return e;
-    const int lines = (pp.paths == 8 ? 4 : 0) * (Wv + H - 1) + 2 * H + 2 * Wv;
-    constexpr int per_block = (STEREO_BLOCK / 64) * (D < 64 ? 64 / D : 1);
-    hipLaunchKernelGGL(k_stereo_paths<D>, dim3((unsigned)((lines + per_block - 1) / per_block)), dim3(STEREO_BLOCK), 0, s, pp);
   }
   if (stages & GSAJ_STEREO_STAGE_WINNER) {
     LdsRequest lds;
@@ -387,7 +410,7 @@ extern "C" int gsaj_stereo_match(int W, int H, const uint8_t *left, size_t left_
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   StereoPaths pp;
-  pp.W = W; pp.H = H; pp.P1 = P1; pp.P2 = P2; pp.paths = paths; pp.C = ws.C; pp.S = ws.S;
+  pp.W = W; pp.H = H; pp.P1 = P1; pp.P2 = P2; pp.paths = paths; pp.xf = D; pp.C = ws.C; pp.S = ws.S;
   StereoWinner wp;
   wp.W = W; wp.H = H; wp.uniqueness = uniqueness; wp.lr_max_diff = lr_max_diff; wp.S = ws.S; wp.disp16 = disp16; wp.depth = out_depth;
   wp.bf = out_depth ? bf : 1.0;

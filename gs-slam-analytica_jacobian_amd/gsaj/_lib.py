@@ -153,6 +153,11 @@ SIGNATURES = {
     "gsaj_rgbd_align_partial_rows": (c_int, [c_int, c_int]),
     "gsaj_rgbd_align": (c_int, [c_int, c_int] + [c_float] * 4 + [P] * 6 + [c_float] * 7 + [P] * 6),
     "gsaj_rgbd_align8": (c_int, [c_int, c_int] + [c_float] * 4 + [P] * 6 + [c_float] * 7 + [P] * 7),
+    "gsaj_motion_stereo_bytes": (c_int, [c_int] * 4 + [ctypes.POINTER(c_size_t)]),
+    "gsaj_debug_motion_stereo_offsets": (c_int, [c_int] * 4 + [ctypes.POINTER(c_size_t)] * 3),
+    "gsaj_motion_stereo": (c_int, [c_int, c_int, P, c_size_t, P, c_size_t] + [c_float] * 4 + [P, P, c_float, c_float] + [c_int] * 8 +
+                           [P, c_size_t, P, P, P]),
+    "gsaj_grey_u8": (c_int, [c_int, c_int, P, P, c_size_t, P]),
 }
 
 _lib = None

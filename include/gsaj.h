@@ -1253,6 +1253,63 @@ int gsaj_rgbd_align8(int W, int H, float fx, float fy, float cx, float cy,
                      float *pix_out   /*[H,W,GSAJ_ALIGN_PIXEL_FLOATS] NULL ok*/, uint8_t *valid_out /*[H,W] NULL ok*/,
                      const uint32_t *skip /*NULL ok, as in gsaj_pose_gn_step*/, void *stream);
 
+/* ---- motion stereo: the depth of a monocular keyframe from a second frame (csrc/sweep.hip) --------------------------------------
+ * A monocular keyframe has no measured depth; the reference seeds its new Gaussians at the map's rendered depth or at a constant with
+ * noise (utils/slam_frontend.py:63-104) and has NO counterpart of what follows: a plane sweep of the keyframe (`ref`) against another
+ * frame (`src`) in general relative pose over D inverse-depth hypotheses, the semi-global aggregation of "stereo frames" above and a
+ * winner stage without a left-right check.  This library's own statement, equal bit for bit to tests/sweep_restated.py; nothing is
+ * pinned against OpenCV.
+ *
+ * gsaj_motion_stereo -- on `stream`, no host read, integer atomics only: the same bits run to run and on any stream.  ref, src: grey
+ *   uint8 [H,W] with row strides in bytes.  ref_w2c, src_w2c: device float[16], row-major (the first 16 floats of a pose state serve).
+ *   a. Gradient bytes of both images, coordinates clamped to the image:  Gx = clamp(gx, -15, 15) + 15, gx the horizontal Sobel of
+ *      line 1a of "stereo frames";  Gy the same with the transposed kernel, bottom rows minus top rows.
+ *   b. T = W2C_src inverse(W2C_ref): line 0 of "frame-to-frame alignment" with C = W2C_src, R = W2C_ref, fp32, every sum left to right.
+ *   c. step = (w_max - w_min) / (float)(D - 1);   w_d = w_min + (float)d step, fp32.  d = 0 is the farthest hypothesis; w = 0 is a point
+ *      at infinity.
+ *   d. The warp of reference pixel (x, y) under hypothesis d, fp32, one rounding per operation (no contraction):
+ *        xn = (((float)x + 0.5f) - cx) / fx,  yn likewise;        a_k = (T[k][0] xn + T[k][1] yn) + T[k][2]
+ *        p_k = a_k + w_d T[k][3]         (the source-camera point scaled by w: finite at w = 0)
+ *        iz = 1.0f / p_z;   u = ((fx iz) p_x + cx) - 0.5f,  v likewise;   x0 = floorf(u), y0 = floorf(v)
+ *      Inside iff, on the floats, p_z > 0, 0 <= x0 <= W - 2 and 0 <= y0 <= H - 2 (a NaN fails).
+ *        fa = (int)floorf((u - x0) 16.0f),  fb likewise: both in 0..15.
+ *   e. Integers.  For a gradient plane G of the source, taps G00 G01 / G10 G11 at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1):
+ *        s(G) = (16 - fa)(16 - fb) G00 + fa (16 - fb) G01 + (16 - fa) fb G10 + fa fb G11                       (in [0, 256 * 30])
+ *        inside:  pc = (|256 Gx_ref(x, y) - s(Gx_src)| + |256 Gy_ref(x, y) - s(Gy_src)|) >> 6   (<= 240);     outside:  pc = outside_cost
+ *   f. C(x, y, d) = the sum of pc over |dx|, |dy| <= r, window coordinates clamped to the image, each window pixel warped on its own
+ *      under the same d.  uint16: 225 * 240 = 54 000, hence r <= 7.
+ *   g. S = the sum over the 4 or 8 directions of L_rho, line 1e of "stereo frames", over ALL columns (the first column is 0).
+ *   h. Per pixel: d* = argmin S, the lowest d on ties; invalid if some d with |d - d*| > 1 has S(d) (100 - uniqueness) < 100 S(d*);
+ *      idx16 = 16 d* + ((S(d* - 1) - S(d* + 1)) 16 + den) / (2 den) for 0 < d* < D - 1, den = max(S(d* - 1) + S(d* + 1) - 2 S(d*), 1),
+ *      C division (lines 1f-1h of "stereo frames").  No disp2, no left-right check.  Invalid too if the pixel's OWN warp at d* (line d,
+ *      recomputed) is outside.  idx16 int16 [H,W]: the hypothesis index in sixteenths, -16 where invalid.
+ *   i. out_depth (may be NULL) float32 [H,W], fp64 rounded to float32 once:  w = (double)w_min + ((double)idx16 / 16.0) (double)step;
+ *      z = 1 / w if idx16 >= 0 and w > 0, else 0.
+ *   stages: GSAJ_SWEEP_STAGE_* to run on what the workspace holds; 0 = all three.
+ *   workspace: gsaj_motion_stereo_bytes(W, H, D, paths) bytes, 256-byte aligned, no initialisation needed (S is zeroed on the stream
+ *   inside the call): both images' gradient bytes (2 bytes per pixel each), pc uint8, C uint16 and S uint32 [H,W,D] --
+ *   gsaj_debug_motion_stereo_offsets gives the byte offsets of the last three (tests, tools).
+ * GSAJ_ERR_INVALID_ARGUMENT, before anything is launched: D not 16, 32, 64 or 128; W < 1, H < 1 or W H D > INT_MAX; paths not 4 or 8;
+ * r outside [0, 7]; not 0 <= P1 < P2 <= 1024; uniqueness outside [0, 99]; outside_cost outside [0, 240]; fx or fy not positive and
+ * finite, cx or cy not finite; w_min or w_max not finite, w_min < 0 or w_max <= w_min; unknown stage bits; a NULL ref, src, ref_w2c,
+ * src_w2c, workspace or idx16; a stride below W; a workspace not 256-byte, idx16 not 2-byte, out_depth or a pose not 4-byte aligned.
+ * GSAJ_ERR_WORKSPACE_TOO_SMALL: workspace_bytes below gsaj_motion_stereo_bytes.
+ *
+ * gsaj_grey_u8 -- a tracker's colour float32 [3,H,W] to grey bytes (rows out_stride bytes apart), one launch:
+ *   g = ((c0 + c1) + c2) (float)(1.0 / 3.0)   (the grey of "frame-to-frame alignment");   byte = min(max(floorf(g 255.0f + 0.5f), 0), 255);
+ *   a NaN gives 0.  GSAJ_ERR_INVALID_ARGUMENT: W or H < 1, W H > INT_MAX, a NULL color or out, out_stride < W. */
+#define GSAJ_SWEEP_STAGE_COST 1
+#define GSAJ_SWEEP_STAGE_PATHS 2
+#define GSAJ_SWEEP_STAGE_WINNER 4
+int gsaj_motion_stereo_bytes(int W, int H, int D, int paths, size_t *bytes);
+int gsaj_debug_motion_stereo_offsets(int W, int H, int D, int paths, size_t *pc_off, size_t *cost_off, size_t *sum_off);
+int gsaj_motion_stereo(int W, int H, const uint8_t *ref /*[H,W]*/, size_t ref_stride, const uint8_t *src /*[H,W]*/, size_t src_stride,
+                       float fx, float fy, float cx, float cy,
+                       const float *ref_w2c /*[16] device, row-major*/, const float *src_w2c /*[16] device, row-major*/,
+                       float w_min, float w_max, int D, int r, int P1, int P2, int paths, int uniqueness, int outside_cost, int stages,
+                       void *workspace, size_t workspace_bytes, int16_t *idx16 /*[H,W]*/, float *out_depth /*[H,W] NULL ok*/, void *stream);
+int gsaj_grey_u8(int W, int H, const float *color /*[3,H,W]*/, uint8_t *out /*[H,W]*/, size_t out_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NOCONTRACT = {"preprocess.hip", "seed.hip", "frame.hip", "densify_prune.hip", "map_step.hip", "eval.hip", "pyramid.hip", "ingest.hip", "stereo.hip", "align.hip"}  # csrc/Makefile
+NOCONTRACT = {"preprocess.hip", "seed.hip", "frame.hip", "densify_prune.hip", "map_step.hip", "eval.hip", "pyramid.hip", "ingest.hip", "stereo.hip", "align.hip", "sweep.hip"}  # csrc/Makefile
 KEYS = (("sgprs", r"^(?:Total)?SGPRs: (\d+)"), ("vgprs", r"^VGPRs: (\d+)"), ("agprs", r"^AGPRs: (\d+)"),
         ("scratch_bytes", r"^ScratchSize \[bytes/lane\]: (\d+)"), ("occupancy", r"^Occupancy \[waves/SIMD\]: (\d+)"),
         ("lds_bytes", r"^LDS Size \[bytes/block\]: (\d+)"))
