@@ -307,9 +307,7 @@ void launch_exclusive_scan_u32(int n, uint32_t *v, hipStream_t s);
 // order statistic `rank` (0-based, ascending) in *out_key (device).  The key of a float orders as an unsigned integer: a
 // non-negative float's bits with the sign bit set, a negative float's bits all flipped.  seed_ws: gsaj_seed_workspace_bytes(W, H).
 int launch_select_rank_f32(int W, int H, const float *values, uint32_t rank, uint32_t *out_key, void *seed_ws, hipStream_t s);
-// stereo.hip's path aggregation over the columns [first_col, W) of a cost volume C [H,W,D] (D 16, 32, 64 or 128; paths 4 or 8): S [H,W,D]
-// is zeroed on the stream, then ONE launch adds every line's L into it.  first_col: D for the rectified pair, 0 for motion stereo.
-hipError_t launch_stereo_paths(int D, int W, int H, int first_col, int P1, int P2, int paths, const uint16_t *C, uint32_t *S, hipStream_t s);
+// (launch_stereo_paths, which stereo.hip and sweep.hip share, is declared in sgm.h)
 
 // ---- small device helpers -------------------------------------------------------------------
 #ifdef __HIPCC__

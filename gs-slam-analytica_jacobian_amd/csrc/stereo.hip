@@ -1,21 +1,19 @@
 // stereo.hip -- a rectified stereo pair to a disparity and a depth map (include/gsaj.h "stereo frames"): semi-global matching in integer
-// arithmetic, the device's bits equal to tests/stereo_restated.py.
-//   k_stereo_prefilter  both images: the clipped horizontal Sobel, one byte per pixel
+// arithmetic, the device's bits equal to tests/stereo_restated.py.  What is named sgm_* / SGM_* is shared with sweep.hip: sgm.h.
+//   k_stereo_prefilter  both images: the clipped horizontal Sobel, one byte per pixel (sgm_sobel_bytes)
 //   k_stereo_cost       C [H,W,D] uint16, d innermost: |P_L - P_R| summed over the clamped window -- a thread owns one (x, d) and walks
-//                       down a band of rows with a running column sum: the entering row's sum is computed, the leaving row's comes
-//                       from a ring in LDS; pc is never stored
+//                       down a band of rows with a ring of row sums in LDS (SGM_BOX_WALK); pc is never stored
 //   k_stereo_paths      ONE launch for every line of every direction: a group of min(D, 64) lanes walks one line, a lane per disparity
 //                       (two per lane at D = 128, 64 / D lines per wave below 64); L(d +- 1) by lane shifts, m(q) by wave_min; the next
 //                       step's row of C is requested before this step's arithmetic; L is added into S [H,W,D] uint32 with atomics
 //                       (integer adds: exact in any order)
-//   k_stereo_winner     a workgroup per row: argmin by a packed (S, d) key, uniqueness, sub-pixel; disp2 by a packed-key atomic min in
-//                       LDS, so no result depends on which lane came first; then the left-right check, disp16 and the depth
+//   k_stereo_winner     a workgroup per row: argmin, uniqueness, sub-pixel (sgm_argmin, sgm_subsample16); disp2 by a packed-key atomic
+//                       min in LDS, so no result depends on which lane came first; then the left-right check, disp16 and the depth
 // Only the depth line is floating point (fp64, nothing there to contract); the file is compiled without FMA contraction all the same.
-#include "gsaj_common.h"
-#include "wave_reduce.h"
+#include "sgm.h"
 
-#define STEREO_BLOCK 256
-#define STEREO_BAND 64        // rows a thread of k_stereo_cost walks: the 2r + 1 row sums of its start are shared by this many outputs
+#define STEREO_RING 31        // 2 * 15 + 1 row sums
+#define STEREO_MAX_R 15       // 961 * 30 fits C's uint16
 #define STEREO_MAX_W 4096     // k_stereo_winner keeps 12 bytes of LDS per column
 #define STEREO_STAGES (GSAJ_STEREO_STAGE_COST | GSAJ_STEREO_STAGE_PATHS | GSAJ_STEREO_STAGE_WINNER)
 
@@ -38,18 +36,14 @@ static size_t stereo_carve(Carver c, int W, int H, int D, StereoWS *w, size_t *c
 }
 
 // ---- a. prefilter ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_prefilter(int W, int H, const uint8_t *__restrict__ left, size_t left_stride,
-                                                                   const uint8_t *__restrict__ right, size_t right_stride,
-                                                                   uint8_t *__restrict__ pl, uint8_t *__restrict__ pr) {
-  const size_t i = (size_t)blockIdx.x * STEREO_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(SGM_BLOCK) void k_stereo_prefilter(int W, int H, const uint8_t *__restrict__ left, size_t left_stride,
+                                                                const uint8_t *__restrict__ right, size_t right_stride,
+                                                                uint8_t *__restrict__ pl, uint8_t *__restrict__ pr) {
+  const size_t i = (size_t)blockIdx.x * SGM_BLOCK + threadIdx.x;
   if (i >= (size_t)W * H) return;
   const int x = (int)(i % (size_t)W), y = (int)(i / (size_t)W);
-  const uint8_t *img = blockIdx.y ? right : left;
-  const size_t stride = blockIdx.y ? right_stride : left_stride;
-  const int xm = max(x - 1, 0), xp = min(x + 1, W - 1);
-  const uint8_t *r0 = img + (size_t)max(y - 1, 0) * stride, *r1 = img + (size_t)y * stride, *r2 = img + (size_t)min(y + 1, H - 1) * stride;
-  const int gx = ((int)r0[xp] - (int)r0[xm]) + 2 * ((int)r1[xp] - (int)r1[xm]) + ((int)r2[xp] - (int)r2[xm]);
-  (blockIdx.y ? pr : pl)[i] = (uint8_t)(min(max(gx, -15), 15) + 15);
+  const int b = sgm_sobel_bytes(blockIdx.y ? right : left, blockIdx.y ? right_stride : left_stride, W, H, x, y);
+  (blockIdx.y ? pr : pl)[i] = (uint8_t)(b & 255);   // the horizontal byte alone
 }
 
 // ---- b, c. the block cost --------------------------------------------------------------------------------------------------------------
@@ -64,35 +58,16 @@ __device__ __forceinline__ int stereo_row_sum(const uint8_t *__restrict__ pl, co
   return s;
 }
 
-// grid: (columns of the valid region in groups of STEREO_BLOCK / D, bands of STEREO_BAND rows).  The 2r + 1 row sums of the window stay
-// in LDS, a ring of slots private to the thread (slot-major: a wave's reads and writes of one slot are contiguous, no barrier is
-// needed), so that a step computes ONE row sum, the entering row's, and takes the leaving row's from the ring.
-#define STEREO_RING 31   // 2 * 15 + 1
+// grid: (columns of the valid region in groups of SGM_BLOCK / D, bands of SGM_BAND rows); the walk and its ring of row sums: sgm.h
 template <int D>
-__global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_cost(int W, int H, int r, const uint8_t *__restrict__ pl, const uint8_t *__restrict__ pr,
-                                                              uint16_t *__restrict__ C) {
-  __shared__ uint16_t ring[STEREO_RING * STEREO_BLOCK];   // a row sum is <= 31 * 30
+__global__ __launch_bounds__(SGM_BLOCK) void k_stereo_cost(int W, int H, int r, const uint8_t *__restrict__ pl, const uint8_t *__restrict__ pr,
+                                                           uint16_t *__restrict__ C) {
+  __shared__ uint16_t ring[STEREO_RING * SGM_BLOCK];   // a row sum is <= 31 * 30
   const int d = threadIdx.x % D;
-  const int x = D + (int)blockIdx.x * (STEREO_BLOCK / D) + threadIdx.x / D;
+  const int x = D + (int)blockIdx.x * (SGM_BLOCK / D) + threadIdx.x / D;
   if (x >= W) return;
-  const int y0 = (int)blockIdx.y * STEREO_BAND, y1 = min(y0 + STEREO_BAND, H), n = 2 * r + 1;
-  uint16_t *mine = ring + threadIdx.x;
-  int v = 0;
-  for (int k = 0; k < n; k++) {   // slot k: row y0 - r + k
-    const int s = stereo_row_sum(pl, pr, W, min(max(y0 - r + k, 0), H - 1), x, d, r);
-    mine[k * STEREO_BLOCK] = (uint16_t)s;
-    v += s;
-  }
-  int slot = 0;   // the slot of row y - r, the one that leaves next
-  for (int y = y0; y < y1; y++) {
-    C[((size_t)y * W + x) * D + d] = (uint16_t)v;   // <= 961 * 30
-    if (y + 1 < y1) {
-      const int in = stereo_row_sum(pl, pr, W, min(y + 1 + r, H - 1), x, d, r);
-      v += in - (int)mine[slot * STEREO_BLOCK];
-      mine[slot * STEREO_BLOCK] = (uint16_t)in;
-      slot = slot + 1 == n ? 0 : slot + 1;
-    }
-  }
+#define STEREO_ROW_SUM(y) stereo_row_sum(pl, pr, W, y, x, d, r)
+  SGM_BOX_WALK(D, ring, x, d, W, H, r, C, STEREO_ROW_SUM)   // C <= 961 * 30
 }
 
 // ---- e. the paths ------------------------------------------------------------------------------------------------------------------------
@@ -108,12 +83,12 @@ struct StereoPaths {
 __device__ __forceinline__ int stereo_line_count(int dx, int dy, int Wv, int H) { return dy == 0 ? H : dx == 0 ? Wv : Wv + H - 1; }
 
 template <int D>
-__global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_paths(StereoPaths p) {
+__global__ __launch_bounds__(SGM_BLOCK) void k_stereo_paths(StereoPaths p) {
   constexpr int WIDTH = D < 64 ? D : 64, LPW = 64 / WIDTH, NV = D / WIDTH;   // lanes per line, lines per wave, disparities per lane
   const int DX[8] = {1, -1, 0, 0, 1, -1, 1, -1}, DY[8] = {0, 0, 1, -1, 1, 1, -1, -1};
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane & (WIDTH - 1);
   const int Wv = p.W - p.xf;
-  int rem = ((int)blockIdx.x * (STEREO_BLOCK / 64) + wave) * LPW + lane / WIDTH;
+  int rem = ((int)blockIdx.x * (SGM_BLOCK / 64) + wave) * LPW + lane / WIDTH;
   int dx = 0, dy = 0, x0 = 0, y0 = 0, len = 0;
   bool found = false;
   for (int k = 0; k < p.paths; k++) {
@@ -183,27 +158,22 @@ __global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_paths(StereoPaths p) {
 }
 
 // One launch for every line of every direction over the columns [first_col, W) of C, after S has been zeroed on the stream (S is summed
-// into).  Shared with sweep.hip (gsaj_common.h); sizes are the caller's to have checked.
+// into).  Shared with sweep.hip (sgm.h); sizes are the caller's to have checked.
 template <int D>
 static void stereo_paths_launch(const StereoPaths &pp, hipStream_t s) {
   const int Wv = pp.W - pp.xf;
   const int lines = (pp.paths == 8 ? 4 : 0) * (Wv + pp.H - 1) + 2 * pp.H + 2 * Wv;
-  constexpr int per_block = (STEREO_BLOCK / 64) * (D < 64 ? 64 / D : 1);
-  hipLaunchKernelGGL(k_stereo_paths<D>, dim3((unsigned)((lines + per_block - 1) / per_block)), dim3(STEREO_BLOCK), 0, s, pp);
+  constexpr int per_block = (SGM_BLOCK / 64) * (D < 64 ? 64 / D : 1);
+  hipLaunchKernelGGL(k_stereo_paths<D>, dim3((unsigned)((lines + per_block - 1) / per_block)), dim3(SGM_BLOCK), 0, s, pp);
 }
 
 hipError_t launch_stereo_paths(int D, int W, int H, int first_col, int P1, int P2, int paths, const uint16_t *C, uint32_t *S, hipStream_t s) {
-  if ((D != 16 && D != 32 && D != 64 && D != 128) || first_col < 0 || first_col >= W || H < 1 || (paths != 4 && paths != 8)) return hipErrorInvalidValue;
+  if (!sgm_d_ok(D) || first_col < 0 || first_col >= W || H < 1 || (paths != 4 && paths != 8)) return hipErrorInvalidValue;
   const hipError_t e = hipMemsetAsync(S, 0, (size_t)W * H * D * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
   StereoPaths pp;
   pp.W = W; pp.H = H; pp.P1 = P1; pp.P2 = P2; pp.paths = paths; pp.xf = first_col; pp.C = C; pp.S = S;
-  switch (D) {
-    case 16: stereo_paths_launch<16>(pp, s); break;
-    case 32: stereo_paths_launch<32>(pp, s); break;
-    case 64: stereo_paths_launch<64>(pp, s); break;
-    default: stereo_paths_launch<128>(pp, s); break;
-  }
+  sgm_for_d(D, [&](auto d) { stereo_paths_launch<decltype(d)::value>(pp, s); });
   return hipGetLastError();
 }
 
@@ -221,13 +191,13 @@ struct StereoWinner {
 // One workgroup per row.  LDS: disp2 [W] as packed keys S << 32 | (W - 1 - x) << 8 | d*, so that an integer min is the rule "smallest
 // S, then the largest x"; d16 [W] as int.
 template <int D>
-__global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_winner(StereoWinner p) {
-  constexpr int WIDTH = D < 64 ? D : 64, LPW = 64 / WIDTH, NV = D / WIDTH, GROUPS = (STEREO_BLOCK / 64) * LPW;
+__global__ __launch_bounds__(SGM_BLOCK) void k_stereo_winner(StereoWinner p) {
+  constexpr int WIDTH = SgmGroup<D>::WIDTH, LPW = SgmGroup<D>::LPW, GROUPS = SgmGroup<D>::GROUPS;
   extern __shared__ unsigned long long stereo_lds[];
   unsigned long long *disp2 = stereo_lds;
   int *d16s = reinterpret_cast<int *>(stereo_lds + p.W);
   const int y = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane & (WIDTH - 1), g = wave * LPW + lane / WIDTH;
-  for (int x = threadIdx.x; x < p.W; x += STEREO_BLOCK) {
+  for (int x = threadIdx.x; x < p.W; x += SGM_BLOCK) {
     disp2[x] = STEREO_NO_KEY;
     d16s[x] = -16;
   }
@@ -237,33 +207,14 @@ __global__ __launch_bounds__(STEREO_BLOCK) void k_stereo_winner(StereoWinner p) 
     const int x = xb + g;
     const bool active = x < p.W;
     const uint32_t *s = row + (size_t)(active ? x : D) * D;
-    uint32_t v[NV], key = 0xffffffffu;
-#pragma unroll
-    for (int j = 0; j < NV; j++) {
-      v[j] = s[sub * NV + j];
-      key = min(key, (v[j] << 7) | (uint32_t)(sub * NV + j));   // S < 2^25: the lowest d wins a tie
-    }
-    key = wave_min<WIDTH>(key);
-    const int dstar = (int)(key & 127u);
-    const uint32_t best = key >> 7;
-    uint32_t rival = 0u;
-#pragma unroll
-    for (int j = 0; j < NV; j++)
-      if (abs(sub * NV + j - dstar) > 1 && v[j] * (uint32_t)(100 - p.uniqueness) < best * 100u) rival = 1u;
-    rival = wave_max<WIDTH>(rival);
-    if (active && sub == 0 && !rival) {
-      int d16 = 16 * dstar;
-      if (dstar > 0 && dstar < D - 1) {
-        const int sm = (int)s[dstar - 1], sp = (int)s[dstar + 1];
-        const int den = max(sm + sp - 2 * (int)best, 1);
-        d16 += ((sm - sp) * 16 + den) / (2 * den);   // C division: towards zero
-      }
-      d16s[x] = d16;
-      atomicMin(&disp2[x - dstar], ((unsigned long long)best << 32) | ((unsigned long long)(uint32_t)(p.W - 1 - x) << 8) | (unsigned long long)dstar);
+    const SgmBest w = sgm_argmin<D>(s, sub, p.uniqueness);
+    if (active && sub == 0 && !w.rival) {
+      d16s[x] = sgm_subsample16<D>(s, w.d, w.S);
+      atomicMin(&disp2[x - w.d], ((unsigned long long)w.S << 32) | ((unsigned long long)(uint32_t)(p.W - 1 - x) << 8) | (unsigned long long)w.d);
     }
   }
   __syncthreads();
-  for (int x = threadIdx.x; x < p.W; x += STEREO_BLOCK) {
+  for (int x = threadIdx.x; x < p.W; x += SGM_BLOCK) {
     int v = d16s[x];
     if (v >= 0 && p.lr_max_diff >= 0) {
       int fails = 0;
@@ -294,7 +245,7 @@ constexpr size_t STEREO_WINNER_STATIC_LDS = 0;
 static_assert(STEREO_WINNER_STATIC_LDS + (size_t)STEREO_MAX_W * (sizeof(unsigned long long) + sizeof(int)) <= LDS_DEFAULT_LIMIT,
               "k_stereo_winner: STEREO_MAX_W columns no longer fit the LDS of a workgroup");
 bool lds_stereo_winner(int W, int D, LdsRequest *out) {
-  if ((D != 16 && D != 32 && D != 64 && D != 128) || W <= D || W > STEREO_MAX_W) return false;
+  if (!sgm_d_ok(D) || W <= D || W > STEREO_MAX_W) return false;
   out->dynamic_bytes = (size_t)W * (sizeof(unsigned long long) + sizeof(int));
   out->static_bytes = STEREO_WINNER_STATIC_LDS;
   out->limit_bytes = LDS_DEFAULT_LIMIT;
@@ -304,19 +255,11 @@ bool lds_stereo_winner(int W, int D, LdsRequest *out) {
 
 // ---- C ABI ----------------------------------------------------------------------------------------------------------------------------
 static bool stereo_sizes_ok(const char *who, int W, int H, int D, int paths) {
-  if (D != 16 && D != 32 && D != 64 && D != 128) {
-    gsaj_set_error("%s: D must be 16, 32, 64 or 128 (D=%d)", who, D);
-    return false;
-  }
-  if (H < 1 || W <= D || W > STEREO_MAX_W || (size_t)W * H * D > (size_t)INT32_MAX) {
+  return sgm_sizes_ok(who, D, paths, [&] {
+    if (H >= 1 && W > D && W <= STEREO_MAX_W && (size_t)W * H * D <= (size_t)INT32_MAX) return true;
     gsaj_set_error("%s: needs D < W <= %d, H >= 1 and W * H * D <= INT_MAX (W=%d H=%d D=%d)", who, STEREO_MAX_W, W, H, D);
     return false;
-  }
-  if (paths != 4 && paths != 8) {
-    gsaj_set_error("%s: paths must be 4 or 8 (paths=%d)", who, paths);
-    return false;
-  }
-  return true;
+  });
 }
 
 extern "C" int gsaj_stereo_workspace_bytes(int W, int H, int D, int paths, size_t *bytes) {
@@ -339,24 +282,24 @@ extern "C" int gsaj_debug_stereo_offsets(int W, int H, int D, int paths, size_t 
 
 template <int D>
 static hipError_t stereo_launch(int stages, int W, int H, const uint8_t *left, size_t left_stride, const uint8_t *right, size_t right_stride, int r,
-                          const StereoWS &ws, const StereoPaths &pp, const StereoWinner &wp, hipStream_t s) {
+                                int P1, int P2, int paths, const StereoWS &ws, const StereoWinner &wp, hipStream_t s) {
   const int Wv = W - D;
   if (stages & GSAJ_STEREO_STAGE_COST) {
     const size_t n = (size_t)W * H;
-    hipLaunchKernelGGL(k_stereo_prefilter, dim3((unsigned)((n + STEREO_BLOCK - 1) / STEREO_BLOCK), 2), dim3(STEREO_BLOCK), 0, s, W, H, left,
+    hipLaunchKernelGGL(k_stereo_prefilter, dim3((unsigned)((n + SGM_BLOCK - 1) / SGM_BLOCK), 2), dim3(SGM_BLOCK), 0, s, W, H, left,
                        left_stride, right, right_stride, ws.pl, ws.pr);
-    constexpr int XB = STEREO_BLOCK / D;
-    hipLaunchKernelGGL(k_stereo_cost<D>, dim3((unsigned)((Wv + XB - 1) / XB), (unsigned)((H + STEREO_BAND - 1) / STEREO_BAND)), dim3(STEREO_BLOCK),
+    constexpr int XB = SGM_BLOCK / D;
+    hipLaunchKernelGGL(k_stereo_cost<D>, dim3((unsigned)((Wv + XB - 1) / XB), (unsigned)((H + SGM_BAND - 1) / SGM_BAND)), dim3(SGM_BLOCK),
                        0, s, W, H, r, ws.pl, ws.pr, ws.C);
   }
   if (stages & GSAJ_STEREO_STAGE_PATHS) {
-    const hipError_t e = launch_stereo_paths(D, W, H, D, pp.P1, pp.P2, pp.paths, pp.C, pp.S, s);   // S is summed into: zeroed there, on the stream
+    const hipError_t e = launch_stereo_paths(D, W, H, D, P1, P2, paths, ws.C, ws.S, s);   // S is summed into: zeroed there, on the stream
     if (e != hipSuccess) return e;
   }
   if (stages & GSAJ_STEREO_STAGE_WINNER) {
     LdsRequest lds;
     if (!lds_stereo_winner(W, D, &lds)) return hipErrorInvalidValue;  // (cannot happen: stereo_sizes_ok has passed)
-    hipLaunchKernelGGL(k_stereo_winner<D>, dim3((unsigned)H), dim3(STEREO_BLOCK), lds.dynamic_bytes, s, wp);
+    hipLaunchKernelGGL(k_stereo_winner<D>, dim3((unsigned)H), dim3(SGM_BLOCK), lds.dynamic_bytes, s, wp);
   }
   return hipGetLastError();
 }
@@ -365,63 +308,31 @@ extern "C" int gsaj_stereo_match(int W, int H, const uint8_t *left, size_t left_
                                  int P1, int P2, int paths, int uniqueness, int lr_max_diff, int stages, void *workspace,
                                  size_t workspace_bytes, int16_t *disp16, float *out_depth, double bf, void *stream) {
   if (!stereo_sizes_ok("gsaj_stereo_match", W, H, D, paths)) return GSAJ_ERR_INVALID_ARGUMENT;
-  if (r < 0 || r > 15) {
-    gsaj_set_error("gsaj_stereo_match: the block radius must lie in [0, 15] (r=%d)", r);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (P1 < 0 || P1 >= P2 || P2 > 1024) {
-    gsaj_set_error("gsaj_stereo_match: needs 0 <= P1 < P2 <= 1024 (P1=%d P2=%d)", P1, P2);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (uniqueness < 0 || uniqueness > 99) {
-    gsaj_set_error("gsaj_stereo_match: uniqueness must lie in [0, 99] (uniqueness=%d)", uniqueness);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
+  if (!sgm_params_ok("gsaj_stereo_match", r, STEREO_MAX_R, P1, P2, uniqueness)) return GSAJ_ERR_INVALID_ARGUMENT;
   if (lr_max_diff < -1) {
     gsaj_set_error("gsaj_stereo_match: lr_max_diff must be >= -1 (lr_max_diff=%d)", lr_max_diff);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  if (stages & ~STEREO_STAGES) {
-    gsaj_set_error("gsaj_stereo_match: unknown stage bits (stages=0x%x)", (unsigned)stages);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (stages == 0) stages = STEREO_STAGES;
-  if (!left || !right || !workspace || !disp16) {
-    gsaj_set_error("gsaj_stereo_match: left, right, workspace and disp16 are required");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (left_stride < (size_t)W || right_stride < (size_t)W) {
-    gsaj_set_error("gsaj_stereo_match: a row stride is less than W (left_stride=%zu right_stride=%zu W=%d)", left_stride, right_stride, W);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
   StereoWS ws;
-  const size_t need = stereo_carve(Carver(workspace, BASE_AS_GIVEN), W, H, D, &ws);
-  if (workspace_bytes < need) {
-    gsaj_set_error("gsaj_stereo_match: the workspace has %zu bytes, gsaj_stereo_workspace_bytes says %zu", workspace_bytes, need);
-    return GSAJ_ERR_WORKSPACE_TOO_SMALL;
-  }
-  if (reinterpret_cast<size_t>(workspace) % 256 != 0 || reinterpret_cast<size_t>(disp16) % 2 != 0 ||
-      (out_depth && reinterpret_cast<size_t>(out_depth) % 4 != 0)) {
-    gsaj_set_error("gsaj_stereo_match: workspace must be 256-byte, disp16 2-byte and out_depth 4-byte aligned");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
+  const size_t need = stereo_carve(Carver(workspace, BASE_AS_GIVEN), W, H, D, &ws);   // (arithmetic only: a null base is refused below)
+  SgmBuffers b;
+  b.required = left && right && workspace && disp16; b.required_names = "left, right, workspace and disp16";
+  b.image[0] = "left"; b.image[1] = "right"; b.stride[0] = left_stride; b.stride[1] = right_stride;
+  b.workspace = workspace; b.workspace_bytes = workspace_bytes; b.need = need; b.size_fn = "gsaj_stereo_workspace_bytes";
+  b.out16 = disp16; b.out_depth = out_depth; b.others_aligned = true; b.aligned_names = "disp16 2-byte and out_depth 4-byte";
+  const int rc = sgm_buffers_ok("gsaj_stereo_match", W, &stages, STEREO_STAGES, b);
+  if (rc != GSAJ_OK) return rc;
   if (out_depth && (!(bf > 0.0) || !(bf < __builtin_inf()))) {
     gsaj_set_error("gsaj_stereo_match: with out_depth, bf must be positive and finite (bf=%g)", bf);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  StereoPaths pp;
-  pp.W = W; pp.H = H; pp.P1 = P1; pp.P2 = P2; pp.paths = paths; pp.xf = D; pp.C = ws.C; pp.S = ws.S;
   StereoWinner wp;
   wp.W = W; wp.H = H; wp.uniqueness = uniqueness; wp.lr_max_diff = lr_max_diff; wp.S = ws.S; wp.disp16 = disp16; wp.depth = out_depth;
   wp.bf = out_depth ? bf : 1.0;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e;
-  switch (D) {
-    case 16: e = stereo_launch<16>(stages, W, H, left, left_stride, right, right_stride, r, ws, pp, wp, s); break;
-    case 32: e = stereo_launch<32>(stages, W, H, left, left_stride, right, right_stride, r, ws, pp, wp, s); break;
-    case 64: e = stereo_launch<64>(stages, W, H, left, left_stride, right, right_stride, r, ws, pp, wp, s); break;
-    default: e = stereo_launch<128>(stages, W, H, left, left_stride, right, right_stride, r, ws, pp, wp, s); break;
-  }
+  const hipError_t e = sgm_for_d(D, [&](auto d) {
+    return stereo_launch<decltype(d)::value>(stages, W, H, left, left_stride, right, right_stride, r, P1, P2, paths, ws, wp, s);
+  });
   GSAJ_HIP_CHECK(e);
   return GSAJ_OK;
 }

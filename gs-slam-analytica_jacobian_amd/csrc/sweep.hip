@@ -1,22 +1,19 @@
 // sweep.hip -- motion stereo (include/gsaj.h "motion stereo"): the depth of a monocular keyframe from a second frame in general
 // relative pose, by a plane sweep over inverse-depth hypotheses and the semi-global aggregation of stereo.hip.  This project's own
 // statement (the reference has no counterpart); the device's bits equal tests/sweep_restated.py.
-//   k_sweep_grad            both images in one launch: the clipped Sobel bytes Gx | Gy << 8 per pixel
+//   k_sweep_grad            both images in one launch: the clipped Sobel bytes Gx | Gy << 8 per pixel (sgm_sobel_bytes)
 //   k_sweep_pixel_cost<D>   one lane per (x, d), d innermost: the reference pixel warped into the source frame under hypothesis d
 //                           (fp32, one rounding per operation), four taps of the source's gradient bytes blended in sixteenths, the
 //                           absolute differences to the reference's own bytes -> pc uint8 [H,W,D], a wave's 64 bytes contiguous
 //   k_sweep_box<D>          C uint16 [H,W,D]: pc summed over the clamped window -- k_stereo_cost's walk down a band of rows with its
-//                           ring of row sums in LDS, a row sum here 2r + 1 bytes of pc
+//                           ring of row sums in LDS (SGM_BOX_WALK), a row sum here 2r + 1 bytes of pc
 //   (paths)                 launch_stereo_paths of stereo.hip with the first column 0: S uint32 [H,W,D]
-//   k_sweep_winner<D>       a group of min(D, 64) lanes per pixel: argmin by a packed (S, d) key, uniqueness, the parabola step, the
-//                           centre warp of the winner once more (no mask is stored), idx16 and the depth; no LDS
+//   k_sweep_winner<D>       a group of min(D, 64) lanes per pixel: argmin, uniqueness, the parabola step (sgm_argmin, sgm_subsample16),
+//                           the centre warp of the winner once more (no mask is stored), idx16 and the depth; no LDS
 //   k_sweep_grey_u8         float32 [3,H,W] -> the grey byte (the trackers' frames as this matcher's input)
-// Compiled without FMA contraction: the warp is mirrored one fp32 rounding at a time.
-#include "gsaj_common.h"
-#include "wave_reduce.h"
+// What is named sgm_* / SGM_* is shared with stereo.hip: sgm.h.  Compiled without FMA contraction: the warp is mirrored one fp32 rounding at a time.
+#include "sgm.h"
 
-#define SWEEP_BLOCK 256
-#define SWEEP_BAND 64    // rows a thread of k_sweep_box walks (STEREO_BAND)
 #define SWEEP_RING 15    // 2 * 7 + 1 row sums
 #define SWEEP_MAX_R 7    // 225 * 240 = 54 000 fits C's uint16
 #define SWEEP_STAGES (GSAJ_SWEEP_STAGE_COST | GSAJ_SWEEP_STAGE_PATHS | GSAJ_SWEEP_STAGE_WINNER)
@@ -49,20 +46,13 @@ struct SweepCam {
 };
 
 // ---- a. gradient bytes ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_grad(int W, int H, const uint8_t *__restrict__ ref, size_t ref_stride,
-                                                            const uint8_t *__restrict__ src, size_t src_stride, uint16_t *__restrict__ gr,
-                                                            uint16_t *__restrict__ gs) {
-  const size_t i = (size_t)blockIdx.x * SWEEP_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(SGM_BLOCK) void k_sweep_grad(int W, int H, const uint8_t *__restrict__ ref, size_t ref_stride,
+                                                          const uint8_t *__restrict__ src, size_t src_stride, uint16_t *__restrict__ gr,
+                                                          uint16_t *__restrict__ gs) {
+  const size_t i = (size_t)blockIdx.x * SGM_BLOCK + threadIdx.x;
   if (i >= (size_t)W * H) return;
   const int x = (int)(i % (size_t)W), y = (int)(i / (size_t)W);
-  const uint8_t *img = blockIdx.y ? src : ref;
-  const size_t stride = blockIdx.y ? src_stride : ref_stride;
-  const int xm = max(x - 1, 0), xp = min(x + 1, W - 1);
-  const uint8_t *r0 = img + (size_t)max(y - 1, 0) * stride, *r1 = img + (size_t)y * stride, *r2 = img + (size_t)min(y + 1, H - 1) * stride;
-  const int gx = ((int)r0[xp] - (int)r0[xm]) + 2 * ((int)r1[xp] - (int)r1[xm]) + ((int)r2[xp] - (int)r2[xm]);
-  const int gy = ((int)r2[xm] - (int)r0[xm]) + 2 * ((int)r2[x] - (int)r0[x]) + ((int)r2[xp] - (int)r0[xp]);
-  const int bx = min(max(gx, -15), 15) + 15, by = min(max(gy, -15), 15) + 15;
-  (blockIdx.y ? gs : gr)[i] = (uint16_t)(bx | (by << 8));
+  (blockIdx.y ? gs : gr)[i] = (uint16_t)sgm_sobel_bytes(blockIdx.y ? src : ref, blockIdx.y ? src_stride : ref_stride, W, H, x, y);
 }
 
 // ---- b. element t (row-major, 3 x 4) of T = W2C_src inverse(W2C_ref): the rigid inverse [R^T, -R^T t] and the product, every sum left
@@ -93,12 +83,12 @@ __device__ __forceinline__ bool sweep_warp(const SweepCam &p, const float *T, in
 
 // ---- e. the pixel cost ---------------------------------------------------------------------------------------------------------------
 template <int D>
-__global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_pixel_cost(SweepCam p, int outside_cost, const uint16_t *__restrict__ gr,
-                                                                  const uint16_t *__restrict__ gs, uint8_t *__restrict__ pc) {
+__global__ __launch_bounds__(SGM_BLOCK) void k_sweep_pixel_cost(SweepCam p, int outside_cost, const uint16_t *__restrict__ gr,
+                                                                const uint16_t *__restrict__ gs, uint8_t *__restrict__ pc) {
   __shared__ float T[12];
   if (threadIdx.x < 12) T[threadIdx.x] = sweep_rel_pose(p.src_w2c, p.ref_w2c, threadIdx.x);
   __syncthreads();
-  const size_t i = (size_t)blockIdx.x * SWEEP_BLOCK + threadIdx.x, pix = i / D;
+  const size_t i = (size_t)blockIdx.x * SGM_BLOCK + threadIdx.x, pix = i / D;
   if (pix >= (size_t)p.W * p.H) return;
   const int d = (int)(i % D), x = (int)(pix % (size_t)p.W), y = (int)(pix / (size_t)p.W);
   const float w = p.w_min + (float)d * p.step;
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_pixel_cost(SweepCam p, in
   pc[i] = (uint8_t)cost;
 }
 
-// ---- f. the block cost: k_stereo_cost's walk, over every column, a row sum read from pc -------------------------------------------------
+// ---- f. the block cost: the walk of sgm.h over every column, a row sum read from pc -------------------------------------------------------
 __device__ __forceinline__ int sweep_row_sum(const uint8_t *__restrict__ pc, int W, int D, int y, int x, int d, int r) {
   const uint8_t *a = pc + (size_t)y * W * D + d;
   int s = 0;
@@ -121,31 +111,15 @@ __device__ __forceinline__ int sweep_row_sum(const uint8_t *__restrict__ pc, int
   return s;
 }
 
-// grid: (columns in groups of SWEEP_BLOCK / D, bands of SWEEP_BAND rows); the ring is slot-major and private to the thread: no barrier
+// grid: (columns in groups of SGM_BLOCK / D, bands of SGM_BAND rows)
 template <int D>
-__global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_box(int W, int H, int r, const uint8_t *__restrict__ pc, uint16_t *__restrict__ C) {
-  __shared__ uint16_t ring[SWEEP_RING * SWEEP_BLOCK];   // a row sum is <= 15 * 240
+__global__ __launch_bounds__(SGM_BLOCK) void k_sweep_box(int W, int H, int r, const uint8_t *__restrict__ pc, uint16_t *__restrict__ C) {
+  __shared__ uint16_t ring[SWEEP_RING * SGM_BLOCK];   // a row sum is <= 15 * 240
   const int d = threadIdx.x % D;
-  const int x = (int)blockIdx.x * (SWEEP_BLOCK / D) + threadIdx.x / D;
+  const int x = (int)blockIdx.x * (SGM_BLOCK / D) + threadIdx.x / D;
   if (x >= W) return;
-  const int y0 = (int)blockIdx.y * SWEEP_BAND, y1 = min(y0 + SWEEP_BAND, H), n = 2 * r + 1;
-  uint16_t *mine = ring + threadIdx.x;
-  int v = 0;
-  for (int k = 0; k < n; k++) {   // slot k: row y0 - r + k
-    const int s = sweep_row_sum(pc, W, D, min(max(y0 - r + k, 0), H - 1), x, d, r);
-    mine[k * SWEEP_BLOCK] = (uint16_t)s;
-    v += s;
-  }
-  int slot = 0;   // the slot of row y - r, the one that leaves next
-  for (int y = y0; y < y1; y++) {
-    C[((size_t)y * W + x) * D + d] = (uint16_t)v;   // <= 225 * 240
-    if (y + 1 < y1) {
-      const int in = sweep_row_sum(pc, W, D, min(y + 1 + r, H - 1), x, d, r);
-      v += in - (int)mine[slot * SWEEP_BLOCK];
-      mine[slot * SWEEP_BLOCK] = (uint16_t)in;
-      slot = slot + 1 == n ? 0 : slot + 1;
-    }
-  }
+#define SWEEP_ROW_SUM(y) sweep_row_sum(pc, W, D, y, x, d, r)
+  SGM_BOX_WALK(D, ring, x, d, W, H, r, C, SWEEP_ROW_SUM)   // C <= 225 * 240
 }
 
 // ---- h, i. winner, uniqueness, sub-sample step, the centre warp, depth ----------------------------------------------------------------
@@ -157,41 +131,22 @@ struct SweepWinner {
 };
 
 template <int D>
-__global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_winner(SweepCam p, SweepWinner q) {
-  constexpr int WIDTH = D < 64 ? D : 64, LPW = 64 / WIDTH, NV = D / WIDTH, GROUPS = (SWEEP_BLOCK / 64) * LPW;
+__global__ __launch_bounds__(SGM_BLOCK) void k_sweep_winner(SweepCam p, SweepWinner q) {
+  constexpr int WIDTH = SgmGroup<D>::WIDTH, LPW = SgmGroup<D>::LPW, GROUPS = SgmGroup<D>::GROUPS;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane & (WIDTH - 1), g = wave * LPW + lane / WIDTH;
   const size_t n = (size_t)p.W * p.H, pix = (size_t)blockIdx.x * GROUPS + g;
   const bool active = pix < n;   // (no early return: the reductions below are executed by every lane)
   const uint32_t *s = q.S + (active ? pix : 0) * D;
-  uint32_t v[NV], key = 0xffffffffu;
-#pragma unroll
-  for (int j = 0; j < NV; j++) {
-    v[j] = s[sub * NV + j];
-    key = min(key, (v[j] << 7) | (uint32_t)(sub * NV + j));   // S < 2^25: the lowest d wins a tie
-  }
-  key = wave_min<WIDTH>(key);
-  const int dstar = (int)(key & 127u);
-  const uint32_t best = key >> 7;
-  uint32_t rival = 0u;
-#pragma unroll
-  for (int j = 0; j < NV; j++)
-    if (abs(sub * NV + j - dstar) > 1 && v[j] * (uint32_t)(100 - q.uniqueness) < best * 100u) rival = 1u;
-  rival = wave_max<WIDTH>(rival);
+  const SgmBest w = sgm_argmin<D>(s, sub, q.uniqueness);
   if (!active || sub != 0) return;
   int i16 = -16;
-  if (!rival) {
+  if (!w.rival) {
     float T[12];
 #pragma unroll
     for (int t = 0; t < 12; t++) T[t] = sweep_rel_pose(p.src_w2c, p.ref_w2c, t);
     int tap, fa, fb;
-    if (sweep_warp(p, T, (int)(pix % (size_t)p.W), (int)(pix / (size_t)p.W), p.w_min + (float)dstar * p.step, tap, fa, fb)) {
-      i16 = 16 * dstar;
-      if (dstar > 0 && dstar < D - 1) {
-        const int sm = (int)s[dstar - 1], sp = (int)s[dstar + 1];
-        const int den = max(sm + sp - 2 * (int)best, 1);
-        i16 += ((sm - sp) * 16 + den) / (2 * den);   // C division: towards zero
-      }
-    }
+    if (sweep_warp(p, T, (int)(pix % (size_t)p.W), (int)(pix / (size_t)p.W), p.w_min + (float)w.d * p.step, tap, fa, fb))
+      i16 = sgm_subsample16<D>(s, w.d, w.S);
   }
   q.idx16[pix] = (int16_t)i16;
   if (q.depth) {
@@ -201,8 +156,8 @@ __global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_winner(SweepCam p, SweepW
 }
 
 // ---- grey bytes of a tracker's colour ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_grey_u8(int W, int H, const float *__restrict__ c, uint8_t *__restrict__ out, size_t stride) {
-  const size_t N = (size_t)W * H, i = (size_t)blockIdx.x * SWEEP_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(SGM_BLOCK) void k_sweep_grey_u8(int W, int H, const float *__restrict__ c, uint8_t *__restrict__ out, size_t stride) {
+  const size_t N = (size_t)W * H, i = (size_t)blockIdx.x * SGM_BLOCK + threadIdx.x;
   if (i >= N) return;
   const float g = ((c[i] + c[N + i]) + c[2 * N + i]) * (float)(1.0 / 3.0);   // al_grey of align.hip
   out[(i / (size_t)W) * stride + (i % (size_t)W)] = (uint8_t)fminf(fmaxf(floorf(g * 255.f + 0.5f), 0.f), 255.f);   // a NaN: fmaxf gives 0
@@ -210,19 +165,11 @@ __global__ __launch_bounds__(SWEEP_BLOCK) void k_sweep_grey_u8(int W, int H, con
 
 // ---- C ABI ----------------------------------------------------------------------------------------------------------------------------
 static bool sweep_sizes_ok(const char *who, int W, int H, int D, int paths) {
-  if (D != 16 && D != 32 && D != 64 && D != 128) {
-    gsaj_set_error("%s: D must be 16, 32, 64 or 128 (D=%d)", who, D);
-    return false;
-  }
-  if (W < 1 || H < 1 || (size_t)W * (size_t)H * (size_t)D > (size_t)INT32_MAX) {
+  return sgm_sizes_ok(who, D, paths, [&] {
+    if (W >= 1 && H >= 1 && (size_t)W * (size_t)H * (size_t)D <= (size_t)INT32_MAX) return true;
     gsaj_set_error("%s: needs W >= 1, H >= 1 and W * H * D <= INT_MAX (W=%d H=%d D=%d)", who, W, H, D);
     return false;
-  }
-  if (paths != 4 && paths != 8) {
-    gsaj_set_error("%s: paths must be 4 or 8 (paths=%d)", who, paths);
-    return false;
-  }
-  return true;
+  });
 }
 
 extern "C" int gsaj_motion_stereo_bytes(int W, int H, int D, int paths, size_t *bytes) {
@@ -249,12 +196,12 @@ static hipError_t sweep_launch(int stages, const SweepCam &cam, const uint8_t *r
   const int W = cam.W, H = cam.H;
   const size_t n = (size_t)W * H;
   if (stages & GSAJ_SWEEP_STAGE_COST) {
-    hipLaunchKernelGGL(k_sweep_grad, dim3((unsigned)((n + SWEEP_BLOCK - 1) / SWEEP_BLOCK), 2), dim3(SWEEP_BLOCK), 0, s, W, H, ref, ref_stride, src,
+    hipLaunchKernelGGL(k_sweep_grad, dim3((unsigned)((n + SGM_BLOCK - 1) / SGM_BLOCK), 2), dim3(SGM_BLOCK), 0, s, W, H, ref, ref_stride, src,
                        src_stride, ws.gr, ws.gs);
-    hipLaunchKernelGGL(k_sweep_pixel_cost<D>, dim3((unsigned)((n * D + SWEEP_BLOCK - 1) / SWEEP_BLOCK)), dim3(SWEEP_BLOCK), 0, s, cam, outside_cost,
+    hipLaunchKernelGGL(k_sweep_pixel_cost<D>, dim3((unsigned)((n * D + SGM_BLOCK - 1) / SGM_BLOCK)), dim3(SGM_BLOCK), 0, s, cam, outside_cost,
                        ws.gr, ws.gs, ws.pc);
-    constexpr int XB = SWEEP_BLOCK / D;
-    hipLaunchKernelGGL(k_sweep_box<D>, dim3((unsigned)((W + XB - 1) / XB), (unsigned)((H + SWEEP_BAND - 1) / SWEEP_BAND)), dim3(SWEEP_BLOCK), 0, s, W,
+    constexpr int XB = SGM_BLOCK / D;
+    hipLaunchKernelGGL(k_sweep_box<D>, dim3((unsigned)((W + XB - 1) / XB), (unsigned)((H + SGM_BAND - 1) / SGM_BAND)), dim3(SGM_BLOCK), 0, s, W,
                        H, r, ws.pc, ws.C);
   }
   if (stages & GSAJ_SWEEP_STAGE_PATHS) {
@@ -262,8 +209,7 @@ static hipError_t sweep_launch(int stages, const SweepCam &cam, const uint8_t *r
     if (e != hipSuccess) return e;
   }
   if (stages & GSAJ_SWEEP_STAGE_WINNER) {
-    constexpr int GROUPS = (SWEEP_BLOCK / 64) * (D < 64 ? 64 / D : 1);
-    hipLaunchKernelGGL(k_sweep_winner<D>, dim3((unsigned)((n + GROUPS - 1) / GROUPS)), dim3(SWEEP_BLOCK), 0, s, cam, wp);
+    hipLaunchKernelGGL(k_sweep_winner<D>, dim3((unsigned)((n + SgmGroup<D>::GROUPS - 1) / SgmGroup<D>::GROUPS)), dim3(SGM_BLOCK), 0, s, cam, wp);
   }
   return hipGetLastError();
 }
@@ -275,18 +221,7 @@ extern "C" int gsaj_motion_stereo(int W, int H, const uint8_t *ref, size_t ref_s
                                   int P2, int paths, int uniqueness, int outside_cost, int stages, void *workspace, size_t workspace_bytes,
                                   int16_t *idx16, float *out_depth, void *stream) {
   if (!sweep_sizes_ok("gsaj_motion_stereo", W, H, D, paths)) return GSAJ_ERR_INVALID_ARGUMENT;
-  if (r < 0 || r > SWEEP_MAX_R) {
-    gsaj_set_error("gsaj_motion_stereo: the block radius must lie in [0, %d] (r=%d)", SWEEP_MAX_R, r);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (P1 < 0 || P1 >= P2 || P2 > 1024) {
-    gsaj_set_error("gsaj_motion_stereo: needs 0 <= P1 < P2 <= 1024 (P1=%d P2=%d)", P1, P2);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (uniqueness < 0 || uniqueness > 99) {
-    gsaj_set_error("gsaj_motion_stereo: uniqueness must lie in [0, 99] (uniqueness=%d)", uniqueness);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
+  if (!sgm_params_ok("gsaj_motion_stereo", r, SWEEP_MAX_R, P1, P2, uniqueness)) return GSAJ_ERR_INVALID_ARGUMENT;
   if (outside_cost < 0 || outside_cost > 240) {
     gsaj_set_error("gsaj_motion_stereo: outside_cost must lie in [0, 240] (outside_cost=%d)", outside_cost);
     return GSAJ_ERR_INVALID_ARGUMENT;
@@ -299,31 +234,16 @@ extern "C" int gsaj_motion_stereo(int W, int H, const uint8_t *ref, size_t ref_s
     gsaj_set_error("gsaj_motion_stereo: needs finite 0 <= w_min < w_max (w_min=%g w_max=%g)", w_min, w_max);
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
-  if (stages & ~SWEEP_STAGES) {
-    gsaj_set_error("gsaj_motion_stereo: unknown stage bits (stages=0x%x)", (unsigned)stages);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (stages == 0) stages = SWEEP_STAGES;
-  if (!ref || !src || !ref_w2c || !src_w2c || !workspace || !idx16) {
-    gsaj_set_error("gsaj_motion_stereo: ref, src, ref_w2c, src_w2c, workspace and idx16 are required");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
-  if (ref_stride < (size_t)W || src_stride < (size_t)W) {
-    gsaj_set_error("gsaj_motion_stereo: a row stride is less than W (ref_stride=%zu src_stride=%zu W=%d)", ref_stride, src_stride, W);
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
   SweepWS ws;
-  const size_t need = sweep_carve(Carver(workspace, BASE_AS_GIVEN), W, H, D, &ws);
-  if (workspace_bytes < need) {
-    gsaj_set_error("gsaj_motion_stereo: the workspace has %zu bytes, gsaj_motion_stereo_bytes says %zu", workspace_bytes, need);
-    return GSAJ_ERR_WORKSPACE_TOO_SMALL;
-  }
-  if (reinterpret_cast<size_t>(workspace) % 256 != 0 || reinterpret_cast<size_t>(idx16) % 2 != 0 ||
-      (out_depth && reinterpret_cast<size_t>(out_depth) % 4 != 0) || reinterpret_cast<size_t>(ref_w2c) % 4 != 0 ||
-      reinterpret_cast<size_t>(src_w2c) % 4 != 0) {
-    gsaj_set_error("gsaj_motion_stereo: workspace must be 256-byte, idx16 2-byte, out_depth and the poses 4-byte aligned");
-    return GSAJ_ERR_INVALID_ARGUMENT;
-  }
+  const size_t need = sweep_carve(Carver(workspace, BASE_AS_GIVEN), W, H, D, &ws);   // (arithmetic only: a null base is refused below)
+  SgmBuffers b;
+  b.required = ref && src && ref_w2c && src_w2c && workspace && idx16; b.required_names = "ref, src, ref_w2c, src_w2c, workspace and idx16";
+  b.image[0] = "ref"; b.image[1] = "src"; b.stride[0] = ref_stride; b.stride[1] = src_stride;
+  b.workspace = workspace; b.workspace_bytes = workspace_bytes; b.need = need; b.size_fn = "gsaj_motion_stereo_bytes";
+  b.out16 = idx16; b.out_depth = out_depth; b.aligned_names = "idx16 2-byte, out_depth and the poses 4-byte";
+  b.others_aligned = reinterpret_cast<size_t>(ref_w2c) % 4 == 0 && reinterpret_cast<size_t>(src_w2c) % 4 == 0;
+  const int rc = sgm_buffers_ok("gsaj_motion_stereo", W, &stages, SWEEP_STAGES, b);
+  if (rc != GSAJ_OK) return rc;
   SweepCam cam;
   cam.W = W; cam.H = H; cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy; cam.w_min = w_min;
   cam.step = (w_max - w_min) / (float)(D - 1);
@@ -331,13 +251,9 @@ extern "C" int gsaj_motion_stereo(int W, int H, const uint8_t *ref, size_t ref_s
   SweepWinner wp;
   wp.uniqueness = uniqueness; wp.S = ws.S; wp.idx16 = idx16; wp.depth = out_depth;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e;
-  switch (D) {
-    case 16: e = sweep_launch<16>(stages, cam, ref, ref_stride, src, src_stride, r, P1, P2, paths, outside_cost, ws, wp, s); break;
-    case 32: e = sweep_launch<32>(stages, cam, ref, ref_stride, src, src_stride, r, P1, P2, paths, outside_cost, ws, wp, s); break;
-    case 64: e = sweep_launch<64>(stages, cam, ref, ref_stride, src, src_stride, r, P1, P2, paths, outside_cost, ws, wp, s); break;
-    default: e = sweep_launch<128>(stages, cam, ref, ref_stride, src, src_stride, r, P1, P2, paths, outside_cost, ws, wp, s); break;
-  }
+  const hipError_t e = sgm_for_d(D, [&](auto d) {
+    return sweep_launch<decltype(d)::value>(stages, cam, ref, ref_stride, src, src_stride, r, P1, P2, paths, outside_cost, ws, wp, s);
+  });
   GSAJ_HIP_CHECK(e);
   return GSAJ_OK;
 }
@@ -352,7 +268,7 @@ extern "C" int gsaj_grey_u8(int W, int H, const float *color, uint8_t *out, size
     return GSAJ_ERR_INVALID_ARGUMENT;
   }
   const size_t n = (size_t)W * H;
-  hipLaunchKernelGGL(k_sweep_grey_u8, dim3((unsigned)((n + SWEEP_BLOCK - 1) / SWEEP_BLOCK)), dim3(SWEEP_BLOCK), 0, (hipStream_t)stream, W, H, color, out,
+  hipLaunchKernelGGL(k_sweep_grey_u8, dim3((unsigned)((n + SGM_BLOCK - 1) / SGM_BLOCK)), dim3(SGM_BLOCK), 0, (hipStream_t)stream, W, H, color, out,
                      out_stride);
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;

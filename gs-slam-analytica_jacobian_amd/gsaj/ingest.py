@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _frames, _lib
 
 BGR, ROUND_U8, DEPTH_MUL = 1, 2, 4   # GSAJ_INGEST_*
 
@@ -21,13 +21,6 @@ def _dbl(values, n, what):
     if a.size != n:
         raise _lib.GsajError("%s must have %d values, got %d" % (what, n, a.size))
     return a
-
-
-def _device(device, who):
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.GsajError("%s needs a HIP device (there is no CPU path)" % who)
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())   # (compares equal to tensor.device)
 
 
 def _kmat(K, what):
@@ -43,7 +36,7 @@ class UndistortMap:
 
     def __init__(self, W, H, K, dist, device, R=None, new_K=None):
         self.lib = _lib.load()
-        self.W, self.H, self.dev = int(W), int(H), _device(device, "UndistortMap")
+        self.W, self.H, self.dev = int(W), int(H), _frames.device(device, "UndistortMap")
         if self.W < 1 or self.H < 1:
             raise _lib.GsajError("UndistortMap needs W >= 1 and H >= 1 (got W=%d H=%d)" % (self.W, self.H))
         self.K = _dbl(K, 4, "K")
@@ -56,19 +49,6 @@ class UndistortMap:
         with torch.cuda.device(self.dev):
             _lib.check(self.lib.gsaj_undistort_map(self.W, self.H, hp(self.K), hp(self.dist), hp(self.iR), self.map_x.data_ptr(),
                                                    self.map_y.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream), "gsaj_undistort_map")
-
-
-class _Staging:
-    """A pinned host buffer and its device twin for one kind of input (bytes), made on first use."""
-
-    def __init__(self, nbytes, dev):
-        self.host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-
-    def upload(self, array, np_dtype):
-        np.copyto(self.host.numpy().view(np_dtype).reshape(array.shape), array)   # (any strides: the staging buffer is tight)
-        self.dev.copy_(self.host, non_blocking=True)
-        return self.dev
 
 
 class FrameIngest:
@@ -88,7 +68,7 @@ class FrameIngest:
 
     def __init__(self, W, H, device, channels=3, src_size=None, undistort=None, depth_scale=None, depth_mul=False, bgr=False, round_u8=False):
         self.lib = _lib.load()
-        self.W, self.H, self.dev, self.C = int(W), int(H), _device(device, "FrameIngest"), int(channels)
+        self.W, self.H, self.dev, self.C = int(W), int(H), _frames.device(device, "FrameIngest"), int(channels)
         if self.W < 1 or self.H < 1 or self.C not in (1, 3, 4):
             raise _lib.GsajError("FrameIngest needs W >= 1, H >= 1 and channels 1, 3 or 4 (got W=%d H=%d channels=%d)" % (self.W, self.H, self.C))
         self.Ws, self.Hs = (self.W, self.H) if src_size is None else (int(src_size[0]), int(src_size[1]))
@@ -107,46 +87,17 @@ class FrameIngest:
         self.color = self.depth = None   # made by the first call that is not given out_color / out_depth
         self._stage_c = self._stage_d = self._event = None
 
-    def _source(self, t, name, dtype, np_dtype, shapes, stage_attr):
-        """-> (device tensor to read, its row stride in bytes)."""
-        item = np.dtype(np_dtype).itemsize
-        if isinstance(t, np.ndarray):
-            if t.dtype != np_dtype or tuple(t.shape) not in shapes:
-                raise _lib.GsajError("%s must be %s %s (got %s %s)" % (name, np.dtype(np_dtype).name, " or ".join(map(str, shapes)), t.dtype, tuple(t.shape)))
-            if getattr(self, stage_attr) is None:
-                setattr(self, stage_attr, _Staging(t.size * item, self.dev))
-            return getattr(self, stage_attr).upload(t, np_dtype), (t.size // t.shape[0]) * item
-        if not torch.is_tensor(t) or t.device != self.dev:
-            raise _lib.GsajError("%s must be a NumPy array or a tensor on %s" % (name, self.dev))
-        if t.dtype != dtype or tuple(t.shape) not in shapes:
-            raise _lib.GsajError("%s must be %s %s (got %s %s)" % (name, dtype, " or ".join(map(str, shapes)), t.dtype, tuple(t.shape)))
-        inner = (t.shape[2], 1) if t.dim() == 3 else (1,)
-        if tuple(t.stride()[1:]) != inner or t.stride(0) < t.shape[1] * inner[0]:
-            raise _lib.GsajError("%s: the pixels of a row must be contiguous (strides %r)" % (name, tuple(t.stride())))
-        return t, t.stride(0) * item
-
-    def _out(self, out, name, attr, numel):
-        if out is None:
-            if getattr(self, attr) is None:
-                setattr(self, attr, torch.empty((3, self.H, self.W) if attr == "color" else (self.H, self.W), dtype=torch.float32, device=self.dev))
-            return getattr(self, attr)
-        if not torch.is_tensor(out) or out.device != self.dev or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != numel:
-            raise _lib.GsajError("%s must be a contiguous float32 tensor of %d elements on %s" % (name, numel, self.dev))
-        return out
-
     def __call__(self, image, depth=None, out_color=None, out_depth=None):
         if (depth is not None) != (self.depth_scale is not None):
             raise _lib.GsajError("FrameIngest: depth must be given exactly when the object was made with a depth_scale")
         if depth is None and out_depth is not None:
             raise _lib.GsajError("FrameIngest: out_depth without depth")
-        n = self.W * self.H
-        oc = self._out(out_color, "out_color", "color", 3 * n)
-        od = None if depth is None else self._out(out_depth, "out_depth", "depth", n)
-        if self._event is not None and (isinstance(image, np.ndarray) or isinstance(depth, np.ndarray)):
-            self._event.synchronize()   # the previous call has read the staging buffers
+        oc = _frames.output(self, "color", out_color, "out_color", (3, self.H, self.W), dtype_name="float32")
+        od = None if depth is None else _frames.output(self, "depth", out_depth, "out_depth", (self.H, self.W), dtype_name="float32")
+        host = _frames.staging_free(self, image, depth)
         shapes = ((self.Hs, self.Ws, self.C),) + (((self.Hs, self.Ws),) if self.C == 1 else ())
-        src, src_stride = self._source(image, "image", torch.uint8, np.uint8, shapes, "_stage_c")
-        draw, d_stride = (None, 0) if depth is None else self._source(depth, "depth", torch.uint16, np.uint16, ((self.H, self.W),), "_stage_d")
+        src, src_stride = _frames.source(self, image, "image", shapes, "_stage_c")
+        draw, d_stride = (None, 0) if depth is None else _frames.source(self, depth, "depth", ((self.H, self.W),), "_stage_d", torch.uint16, np.uint16)
         m = self.undistort
         with torch.cuda.device(self.dev):
             stream = torch.cuda.current_stream(self.dev)
@@ -154,8 +105,5 @@ class FrameIngest:
                                                   None if m is None else m.map_x.data_ptr(), None if m is None else m.map_y.data_ptr(),
                                                   None if draw is None else draw.data_ptr(), d_stride, self.depth_scale or 1.0, self.flags,
                                                   oc.data_ptr(), None if od is None else od.data_ptr(), stream.cuda_stream), "gsaj_frame_ingest")
-            if isinstance(image, np.ndarray) or isinstance(depth, np.ndarray):
-                if self._event is None:
-                    self._event = torch.cuda.Event()
-                self._event.record(stream)
+            _frames.staging_read(self, host, stream)
         return oc.view(3, self.H, self.W), None if od is None else od.view(self.H, self.W)

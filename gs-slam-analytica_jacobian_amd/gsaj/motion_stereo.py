@@ -6,21 +6,12 @@ noise (utils/slam_frontend.py:63-104).  This is this library's own statement (in
 inverse-depth hypotheses, gsaj.stereo's semi-global aggregation, a winner stage without a left-right check -- equal bit for bit to
 tests/sweep_restated.py and pinned against nothing else (no OpenCV parity).  There is no CPU path.
 """
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _lib
-from .ingest import _device
-from .stereo import _bytes_source, _out
+from . import _frames, _lib
 
 STAGE_COST, STAGE_PATHS, STAGE_WINNER = 1, 2, 4   # GSAJ_SWEEP_STAGE_*
-
-
-def _check(rc, what):
-    if rc < 0:   # (every failure of this module is a GsajError, as in gsaj.stereo)
-        raise _lib.GsajError("%s failed (%d): %s" % (what, rc, _lib.load().gsaj_last_error().decode("utf-8", "replace")))
 
 
 def grey_u8(color, out=None):
@@ -36,12 +27,12 @@ def grey_u8(color, out=None):
             or out.stride(0) < W:
         raise _lib.GsajError("grey_u8: out must be a uint8 [%d,%d] tensor on %s whose rows are contiguous" % (H, W, color.device))
     with torch.cuda.device(color.device):
-        _check(_lib.load().gsaj_grey_u8(W, H, color.data_ptr(), out.data_ptr(), out.stride(0), torch.cuda.current_stream(color.device).cuda_stream),
-               "gsaj_grey_u8")
+        stream = torch.cuda.current_stream(color.device).cuda_stream
+        _frames.check(_lib.load().gsaj_grey_u8(W, H, color.data_ptr(), out.data_ptr(), out.stride(0), stream), "gsaj_grey_u8")
     return out
 
 
-class MotionStereo:
+class MotionStereo(_frames.Matcher):
     """Pre-allocated for one camera: idx16, depth = MotionStereo(W, H, device, fx, fy, cx, cy, ...)(ref, src, ref_w2c, src_w2c, w_min,
     w_max) -> int16 [H,W], the winning inverse-depth hypothesis in sixteenths (-16 where invalid), and float32 [H,W], the depth of the
     keyframe `ref` with 0 at invalid pixels -- the form seed_from_keyframe, median_depth and FrameEvaluator take.
@@ -53,10 +44,12 @@ class MotionStereo:
     uploaded per call.  [w_min, w_max]: the inverse-depth range the num_hypotheses are spread over, w_min >= 0 (0: infinity).
     The object owns its workspace (gsaj_motion_stereo_bytes) and, unless given out_idx16 / out_depth, its outputs, which the next call
     overwrites."""
+    SIZE_FN, OFFSETS_FN = "gsaj_motion_stereo_bytes", "gsaj_debug_motion_stereo_offsets"
+    VIEWS = (("pixel", torch.uint8), ("cost", torch.int16), ("sums", torch.int32))
 
     def __init__(self, W, H, device, fx, fy, cx, cy, num_hypotheses=64, block_radius=3, P1=100, P2=400, paths=8, uniqueness=10, outside_cost=80):
         self.lib = _lib.load()
-        self.W, self.H, self.dev = int(W), int(H), _device(device, "MotionStereo")
+        self.W, self.H, self.dev = int(W), int(H), _frames.device(device, "MotionStereo")
         self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
         self.D, self.r, self.P1, self.P2 = int(num_hypotheses), int(block_radius), int(P1), int(P2)
         self.paths, self.uniqueness, self.outside_cost = int(paths), int(uniqueness), int(outside_cost)
@@ -68,41 +61,20 @@ class MotionStereo:
                                  "(got %d, %d, %d, %d, %d)" % (self.r, self.P1, self.P2, self.uniqueness, self.outside_cost))
         if not (self.fx > 0.0 and self.fy > 0.0 and np.isfinite([self.fx, self.fy, self.cx, self.cy]).all()):
             raise _lib.GsajError("MotionStereo: fx and fy must be positive, all four intrinsics finite (got %r)" % ((fx, fy, cx, cy),))
-        nbytes = ctypes.c_size_t(0)
-        _check(self.lib.gsaj_motion_stereo_bytes(self.W, self.H, self.D, self.paths, ctypes.byref(nbytes)), "gsaj_motion_stereo_bytes")
-        self.workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=self.dev)
+        self._allocate()
         self.idx16 = self.depth = None
         self._stage_ref = self._stage_src = self._event = None
         self._pose_host = self._pose_dev = None
 
-    def _debug_view(self, which):
-        offs = [ctypes.c_size_t(0) for _ in range(3)]
-        _check(self.lib.gsaj_debug_motion_stereo_offsets(self.W, self.H, self.D, self.paths, *[ctypes.byref(o) for o in offs]),
-               "gsaj_debug_motion_stereo_offsets")
-        n = self.W * self.H * self.D
-        off, size, dtype = {"pixel": (offs[0].value, 1, torch.uint8), "cost": (offs[1].value, 2, torch.int16), "sums": (offs[2].value, 4, torch.int32)}[which]
-        return self.workspace[off:off + size * n].view(dtype).view(self.H, self.W, self.D)
-
     def gradient_bytes(self):
         """Tests and tools: the gradient bytes Gx | Gy << 8 of ref and src, int16 [2,H,W], as the last call left them (a copy: the two
         arrays open the workspace, each padded to 256 bytes)."""
-        off = ctypes.c_size_t(0)
-        _check(self.lib.gsaj_debug_motion_stereo_offsets(self.W, self.H, self.D, self.paths, ctypes.byref(off), None, None),
-               "gsaj_debug_motion_stereo_offsets")
-        n, half = self.W * self.H, off.value // 2
+        n, half = self.W * self.H, self._offsets()[0] // 2
         return torch.stack([self.workspace[o:o + 2 * n].view(torch.int16).view(self.H, self.W) for o in (0, half)])
 
     def pixel_costs(self):
         """Tests and tools: pc [H,W,D] uint8 as the last call left it (a view of the workspace)."""
         return self._debug_view("pixel")
-
-    def cost_volume(self):
-        """Tests and tools: C [H,W,D] as the last call left it (a view of the workspace; uint16 bits in an int16 tensor)."""
-        return self._debug_view("cost")
-
-    def sums(self):
-        """Tests and tools: S [H,W,D] int32 as the last call left it (a view of the workspace)."""
-        return self._debug_view("sums")
 
     def _pose(self, t, name, slot):
         """-> (device pointer of 16 floats, True if it went through the pinned pose staging)."""
@@ -120,36 +92,20 @@ class MotionStereo:
 
     def __call__(self, ref, src, ref_w2c, src_w2c, w_min, w_max, out_idx16=None, out_depth=None, stages=0):
         """stages: 0 = everything, else the STAGE_* to run on what the workspace holds (measurement and tests)."""
-        n = self.W * self.H
-        if out_idx16 is None:
-            if self.idx16 is None:
-                self.idx16 = torch.empty((self.H, self.W), dtype=torch.int16, device=self.dev)
-            oi = self.idx16
-        else:
-            oi = _out(out_idx16, "out_idx16", torch.int16, n, self.dev)
-        if out_depth is None:
-            if self.depth is None:
-                self.depth = torch.empty((self.H, self.W), dtype=torch.float32, device=self.dev)
-            oz = self.depth
-        else:
-            oz = _out(out_depth, "out_depth", torch.float32, n, self.dev)
-        host = any(isinstance(t, np.ndarray) for t in (ref, src, ref_w2c, src_w2c))
-        if self._event is not None and host:
-            self._event.synchronize()   # the previous call has read the staging buffers
-        a, astride = _bytes_source(self, ref, "ref", (self.H, self.W), "_stage_ref")
-        b, bstride = _bytes_source(self, src, "src", (self.H, self.W), "_stage_src")
+        oi = _frames.output(self, "idx16", out_idx16, "out_idx16", (self.H, self.W), torch.int16)
+        oz = _frames.output(self, "depth", out_depth, "out_depth", (self.H, self.W))
+        host = _frames.staging_free(self, ref, src, ref_w2c, src_w2c)
+        a, astride = _frames.source(self, ref, "ref", ((self.H, self.W),), "_stage_ref")
+        b, bstride = _frames.source(self, src, "src", ((self.H, self.W),), "_stage_src")
         pr, up_r = self._pose(ref_w2c, "ref_w2c", 0)
         ps, up_s = self._pose(src_w2c, "src_w2c", 1)
         with torch.cuda.device(self.dev):
             stream = torch.cuda.current_stream(self.dev)
             if up_r or up_s:
                 self._pose_dev.copy_(self._pose_host, non_blocking=True)
-            _check(self.lib.gsaj_motion_stereo(self.W, self.H, a.data_ptr(), astride, b.data_ptr(), bstride, self.fx, self.fy, self.cx, self.cy, pr, ps,
-                                               float(w_min), float(w_max), self.D, self.r, self.P1, self.P2, self.paths, self.uniqueness,
-                                               self.outside_cost, int(stages), self.workspace.data_ptr(), self.workspace.numel(), oi.data_ptr(),
-                                               oz.data_ptr(), stream.cuda_stream), "gsaj_motion_stereo")
-            if host:
-                if self._event is None:
-                    self._event = torch.cuda.Event()
-                self._event.record(stream)
+            _frames.check(self.lib.gsaj_motion_stereo(self.W, self.H, a.data_ptr(), astride, b.data_ptr(), bstride, self.fx, self.fy, self.cx, self.cy,
+                                                      pr, ps, float(w_min), float(w_max), self.D, self.r, self.P1, self.P2, self.paths, self.uniqueness,
+                                                      self.outside_cost, int(stages), self.workspace.data_ptr(), self.workspace.numel(), oi.data_ptr(),
+                                                      oz.data_ptr(), stream.cuda_stream), "gsaj_motion_stereo")
+            _frames.staging_read(self, host, stream)
         return oi.view(self.H, self.W), oz.view(self.H, self.W)

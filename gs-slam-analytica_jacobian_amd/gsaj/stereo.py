@@ -6,42 +6,16 @@ cv2.StereoSGBM, bf / disparity -- without OpenCV: the byte remap is gsaj_frame_i
 is this library's own integer statement of semi-global matching (include/gsaj.h "stereo frames"), equal bit for bit to
 tests/stereo_restated.py.  Its results DIFFER from cv2.StereoSGBM's and are not pinned against them.  There is no CPU path.
 """
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _lib
-from .ingest import UndistortMap, _device, _Staging
+from . import _frames, _lib
+from .ingest import UndistortMap
 
 STAGE_COST, STAGE_PATHS, STAGE_WINNER = 1, 2, 4   # GSAJ_STEREO_STAGE_*
 
 
-def _bytes_source(owner, t, name, shape, stage_attr):
-    """A uint8 [H,W] NumPy array (through the owner's pinned staging buffer) or device tensor (rows may be padded)
-    -> (device tensor, row stride in bytes)."""
-    if isinstance(t, np.ndarray):
-        if t.dtype != np.uint8 or tuple(t.shape) != shape:
-            raise _lib.GsajError("%s must be uint8 %s (got %s %s)" % (name, shape, t.dtype, tuple(t.shape)))
-        if getattr(owner, stage_attr) is None:
-            setattr(owner, stage_attr, _Staging(t.size, owner.dev))
-        return getattr(owner, stage_attr).upload(t, np.uint8), shape[1]
-    if not torch.is_tensor(t) or t.device != owner.dev:
-        raise _lib.GsajError("%s must be a NumPy array or a tensor on %s" % (name, owner.dev))
-    if t.dtype != torch.uint8 or tuple(t.shape) != shape:
-        raise _lib.GsajError("%s must be torch.uint8 %s (got %s %s)" % (name, shape, t.dtype, tuple(t.shape)))
-    if t.stride(1) != 1 or t.stride(0) < shape[1]:
-        raise _lib.GsajError("%s: the pixels of a row must be contiguous (strides %r)" % (name, tuple(t.stride())))
-    return t, t.stride(0)
-
-
-def _out(out, name, dtype, numel, dev):
-    if not torch.is_tensor(out) or out.device != dev or out.dtype != dtype or not out.is_contiguous() or out.numel() != numel:
-        raise _lib.GsajError("%s must be a contiguous %s tensor of %d elements on %s" % (name, dtype, numel, dev))
-    return out
-
-
-class StereoMatcher:
+class StereoMatcher(_frames.Matcher):
     """Pre-allocated for one rectified camera pair: disp16 = StereoMatcher(W, H, device, ...)(left, right) -> int16 [H,W], the
     disparity in sixteenths of a pixel, -16 where invalid (every column x < num_disparities is).  depth(bf), or
     m(left, right, bf=..., out_depth=...), gives bf / disparity as float32 [H,W] with 0 at invalid pixels.
@@ -50,10 +24,12 @@ class StereoMatcher:
     current stream; an event recorded behind the launches keeps the next call off the staging buffers until this one has read them.
     Device tensors are read in place (rows may be padded).  The object owns its workspace (gsaj_stereo_workspace_bytes) and, unless
     given out_disp16 / out_depth, its outputs, which the next call overwrites."""
+    SIZE_FN, OFFSETS_FN = "gsaj_stereo_workspace_bytes", "gsaj_debug_stereo_offsets"
+    VIEWS = (("cost", torch.int16), ("sums", torch.int32))   # (only columns x >= D of C carry a result, and S is zero before them)
 
     def __init__(self, W, H, device, num_disparities=64, block_radius=10, P1=2, P2=5, paths=8, uniqueness=40, lr_max_diff=1):
         self.lib = _lib.load()
-        self.W, self.H, self.dev = int(W), int(H), _device(device, "StereoMatcher")
+        self.W, self.H, self.dev = int(W), int(H), _frames.device(device, "StereoMatcher")
         self.D, self.r, self.P1, self.P2 = int(num_disparities), int(block_radius), int(P1), int(P2)
         self.paths, self.uniqueness, self.lr_max_diff = int(paths), int(uniqueness), int(lr_max_diff)
         if self.D not in (16, 32, 64, 128) or self.W <= self.D or self.H < 1 or self.paths not in (4, 8):
@@ -62,68 +38,26 @@ class StereoMatcher:
         if not (0 <= self.r <= 15 and 0 <= self.P1 < self.P2 <= 1024 and 0 <= self.uniqueness <= 99 and self.lr_max_diff >= -1):
             raise _lib.GsajError("StereoMatcher needs 0 <= block_radius <= 15, 0 <= P1 < P2 <= 1024, 0 <= uniqueness <= 99 and lr_max_diff >= -1 "
                                  "(got %d, %d, %d, %d, %d)" % (self.r, self.P1, self.P2, self.uniqueness, self.lr_max_diff))
-        nbytes = ctypes.c_size_t(0)
-        self._check(self.lib.gsaj_stereo_workspace_bytes(self.W, self.H, self.D, self.paths, ctypes.byref(nbytes)), "gsaj_stereo_workspace_bytes")
-        self.workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=self.dev)
+        self._allocate()
         self.disp16 = self._depth = self._last = None
         self._stage_l = self._stage_r = self._event = None
 
-    @staticmethod
-    def _check(rc, what):
-        if rc < 0:   # (every failure of this module is a GsajError, as in gsaj.ingest)
-            raise _lib.GsajError("%s failed (%d): %s" % (what, rc, _lib.load().gsaj_last_error().decode("utf-8", "replace")))
-
-    def _debug_view(self, which):
-        c_off, s_off = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        self._check(self.lib.gsaj_debug_stereo_offsets(self.W, self.H, self.D, self.paths, ctypes.byref(c_off), ctypes.byref(s_off)),
-                    "gsaj_debug_stereo_offsets")
-        n = self.W * self.H * self.D
-        if which == "cost":
-            return self.workspace[c_off.value:c_off.value + 2 * n].view(torch.int16).view(self.H, self.W, self.D)
-        return self.workspace[s_off.value:s_off.value + 4 * n].view(torch.int32).view(self.H, self.W, self.D)
-
-    def cost_volume(self):
-        """Tests and tools: C [H,W,D] as the last call left it (a view of the workspace; uint16 bits in an int16 tensor)."""
-        return self._debug_view("cost")
-
-    def sums(self):
-        """Tests and tools: S [H,W,D] int32 as the last call left it (a view of the workspace; columns x < D are zero)."""
-        return self._debug_view("sums")
-
     def __call__(self, left, right, bf=None, out_disp16=None, out_depth=None, stages=0):
         """stages: 0 = everything, else the STAGE_* to run on what the workspace holds (measurement and tests)."""
-        n = self.W * self.H
         if out_depth is not None and bf is None:
             raise _lib.GsajError("StereoMatcher: out_depth without bf")
-        if out_disp16 is None:
-            if self.disp16 is None:
-                self.disp16 = torch.empty((self.H, self.W), dtype=torch.int16, device=self.dev)
-            od = self.disp16
-        else:
-            od = _out(out_disp16, "out_disp16", torch.int16, n, self.dev)
-        oz = None
-        if bf is not None:
-            if out_depth is None:
-                if self._depth is None:
-                    self._depth = torch.empty((self.H, self.W), dtype=torch.float32, device=self.dev)
-                oz = self._depth
-            else:
-                oz = _out(out_depth, "out_depth", torch.float32, n, self.dev)
-        host = isinstance(left, np.ndarray) or isinstance(right, np.ndarray)
-        if self._event is not None and host:
-            self._event.synchronize()   # the previous call has read the staging buffers
-        l, ls = _bytes_source(self, left, "left", (self.H, self.W), "_stage_l")
-        r, rs = _bytes_source(self, right, "right", (self.H, self.W), "_stage_r")
+        od = _frames.output(self, "disp16", out_disp16, "out_disp16", (self.H, self.W), torch.int16)
+        oz = None if bf is None else _frames.output(self, "_depth", out_depth, "out_depth", (self.H, self.W))
+        host = _frames.staging_free(self, left, right)
+        l, ls = _frames.source(self, left, "left", ((self.H, self.W),), "_stage_l")
+        r, rs = _frames.source(self, right, "right", ((self.H, self.W),), "_stage_r")
         with torch.cuda.device(self.dev):
             stream = torch.cuda.current_stream(self.dev)
-            self._check(self.lib.gsaj_stereo_match(self.W, self.H, l.data_ptr(), ls, r.data_ptr(), rs, self.D, self.r, self.P1, self.P2, self.paths,
-                                                   self.uniqueness, self.lr_max_diff, int(stages), self.workspace.data_ptr(), self.workspace.numel(),
-                                                   od.data_ptr(), None if oz is None else oz.data_ptr(), 1.0 if bf is None else float(bf),
-                                                   stream.cuda_stream), "gsaj_stereo_match")
-            if host:
-                if self._event is None:
-                    self._event = torch.cuda.Event()
-                self._event.record(stream)
+            _frames.check(self.lib.gsaj_stereo_match(self.W, self.H, l.data_ptr(), ls, r.data_ptr(), rs, self.D, self.r, self.P1, self.P2, self.paths,
+                                                     self.uniqueness, self.lr_max_diff, int(stages), self.workspace.data_ptr(), self.workspace.numel(),
+                                                     od.data_ptr(), None if oz is None else oz.data_ptr(), 1.0 if bf is None else float(bf),
+                                                     stream.cuda_stream), "gsaj_stereo_match")
+            _frames.staging_read(self, host, stream)
         self._last = od
         return od.view(self.H, self.W) if bf is None else (od.view(self.H, self.W), oz.view(self.H, self.W))
 
@@ -168,34 +102,18 @@ class StereoIngest:
         self._stage_l = self._stage_r = self._event = None
 
     def __call__(self, image_left, image_right, out_color=None, out_depth=None):
-        n = self.W * self.H
-        if out_color is None:
-            if self.color is None:
-                self.color = torch.empty((3, self.H, self.W), dtype=torch.float32, device=self.dev)
-            oc = self.color
-        else:
-            oc = _out(out_color, "out_color", torch.float32, 3 * n, self.dev)
-        if out_depth is None:
-            if self.depth is None:
-                self.depth = torch.empty((self.H, self.W), dtype=torch.float32, device=self.dev)
-            oz = self.depth
-        else:
-            oz = _out(out_depth, "out_depth", torch.float32, n, self.dev)
-        host = isinstance(image_left, np.ndarray) or isinstance(image_right, np.ndarray)
-        if self._event is not None and host:
-            self._event.synchronize()   # the previous call has read the staging buffers
-        srcs = (_bytes_source(self, image_left, "image_left", (self.Hs, self.Ws), "_stage_l"),
-                _bytes_source(self, image_right, "image_right", (self.Hs, self.Ws), "_stage_r"))
+        oc = _frames.output(self, "color", out_color, "out_color", (3, self.H, self.W))
+        oz = _frames.output(self, "depth", out_depth, "out_depth", (self.H, self.W))
+        host = _frames.staging_free(self, image_left, image_right)
+        srcs = (_frames.source(self, image_left, "image_left", ((self.Hs, self.Ws),), "_stage_l"),
+                _frames.source(self, image_right, "image_right", ((self.Hs, self.Ws),), "_stage_r"))
         with torch.cuda.device(self.dev):
             stream = torch.cuda.current_stream(self.dev)
             for i, ((src, stride), m) in enumerate(zip(srcs, self.maps)):
-                StereoMatcher._check(self.lib.gsaj_rectify_u8(self.W, self.H, self.Ws, self.Hs, stride, src.data_ptr(),
-                                                              None if m is None else m.map_x.data_ptr(), None if m is None else m.map_y.data_ptr(),
-                                                              self.rect[i].data_ptr(), self.W, oc.data_ptr() if i == 0 else None, stream.cuda_stream),
-                                     "gsaj_rectify_u8")
-            if host:
-                if self._event is None:
-                    self._event = torch.cuda.Event()
-                self._event.record(stream)
+                _frames.check(self.lib.gsaj_rectify_u8(self.W, self.H, self.Ws, self.Hs, stride, src.data_ptr(),
+                                                       None if m is None else m.map_x.data_ptr(), None if m is None else m.map_y.data_ptr(),
+                                                       self.rect[i].data_ptr(), self.W, oc.data_ptr() if i == 0 else None, stream.cuda_stream),
+                              "gsaj_rectify_u8")
+            _frames.staging_read(self, host, stream)
             self.matcher(self.rect[0], self.rect[1], bf=self.bf, out_depth=oz)
         return oc.view(3, self.H, self.W), oz.view(self.H, self.W)

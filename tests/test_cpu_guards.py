@@ -1,6 +1,6 @@
 """The guarded allocator of tests/guards.py has teeth: every planted defect is reported, with the right allocation named, and a
 clean run reports nothing.  Runs the allocator on CPU tensors (device_filter), plus one GPU-marked case of the same kind; no
-project kernel is involved.  Also here: every gsaj_*_workspace_bytes function of the library has a row in the contract table of
+project kernel is involved.  Also here: every size function of the library has a row in the contract table of
 tests/test_gpu_memory_contracts.py."""
 import re
 
@@ -172,14 +172,14 @@ def test_gpu_planted_writes_are_reported(monkeypatch, fill):
 
 # ---- the contract table covers every workspace --------------------------------------------------------------------------------
 def test_every_workspace_function_has_a_contract_row():
-    """A new gsaj_*_workspace_bytes (or gsaj_pyramid_bytes) cannot arrive untested: it needs a row in CONTRACTS, and the row names a
-    test of the GPU file that runs the workspace under guard."""
+    """A new size function (every gsaj_*_bytes of the binding: the workspaces, the pyramid, motion stereo) cannot arrive untested: it
+    needs a row in CONTRACTS, and the row names a test of the GPU file that runs the workspace under guard."""
     from gsaj import _lib
 
     import test_gpu_memory_contracts as mc
 
-    sized = sorted(n for n in _lib.SIGNATURES if n.endswith("_workspace_bytes") or n == "gsaj_pyramid_bytes")
-    assert len(sized) >= 21, sized
+    sized = sorted(n for n in _lib.SIGNATURES if n.endswith("_bytes"))
+    assert len(sized) >= 22, sized
     with open(_lib.HEADER) as fh:
         header = fh.read().splitlines()
     missing = [n for n in sized if n not in mc.CONTRACTS]

@@ -163,7 +163,7 @@ def test_the_header_declares_the_entry_points_and_the_binding_matches():
     names = [p for _, p in decls["gsaj_motion_stereo"][1]]
     assert names == ["W", "H", "ref", "ref_stride", "src", "src_stride", "fx", "fy", "cx", "cy", "ref_w2c", "src_w2c", "w_min", "w_max", "D", "r", "P1",
                      "P2", "paths", "uniqueness", "outside_cost", "stages", "workspace", "workspace_bytes", "idx16", "out_depth", "stream"]
-    assert not any(n.endswith("_workspace_bytes") for n in NEW)   # (the guarded run is tests/test_gpu_motion_stereo_guarded.py)
+    assert not any(n.endswith("_workspace_bytes") for n in NEW)   # (the guarded run: test_motion_stereo of tests/test_gpu_memory_contracts.py)
     with open(L.HEADER) as fh:
         text = fh.read()
     for macro, value in (("GSAJ_SWEEP_STAGE_COST", 1), ("GSAJ_SWEEP_STAGE_PATHS", 2), ("GSAJ_SWEEP_STAGE_WINNER", 4)):

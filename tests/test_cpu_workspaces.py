@@ -2,7 +2,8 @@
 rounding edge.  No kernel is launched: the size functions are pure host code (csrc/workspace.h: a Carver over a null base).
 
 tests/golden/workspace_bytes.json was recorded with record() below from a library built from the commit BEFORE the layouts moved
-onto csrc/workspace.h (GSAJ_LIB_PATH pointing at that build):
+onto csrc/workspace.h (GSAJ_LIB_PATH pointing at that build), the motion-stereo entries from the commit before its entry points'
+checks moved to csrc/sgm.h:
 
     python -c "import sys; sys.path.insert(0, 'tests'); import test_cpu_workspaces as t; t.write_golden()"
 
@@ -57,6 +58,10 @@ CASES = {
     "gsaj_rgbd_align_partial_rows": _x(WH) + [(2, 2)],
 }
 STEREO = _x(WH + [(129, 3), (4096, 2)], [16, 64, 128], [4, 8]) + [(64, 48, 24, 4), (64, 48, 16, 5), (4097, 1, 16, 4)]
+MOTION_STEREO = _x(WH + [(129, 3), (4096, 2)], [16, 64, 128], [4, 8]) + [(64, 48, 24, 4), (64, 48, 16, 5), (0, 48, 16, 4)]   # (1, 1) is legal here
+# the two matchers: size function -> (offsets function, how many offsets it gives, the ladder)
+MATCHERS = {"gsaj_stereo_workspace_bytes": ("gsaj_debug_stereo_offsets", 2, STEREO),
+            "gsaj_motion_stereo_bytes": ("gsaj_debug_motion_stereo_offsets", 3, MOTION_STEREO)}
 PYRAMID_LEVELS = [a + (l,) for a in CASES["gsaj_pyramid_bytes"] for l in (1, 2, 4)]
 
 
@@ -66,15 +71,17 @@ def _key(args):
 
 def record(lib):
     """{function: {"a,b,..": value}} of the library at hand: the sizes, gsaj_stereo_workspace_bytes / gsaj_debug_stereo_offsets as
-    [rc, bytes, cost_off, sum_off] and gsaj_pyramid_level as [rc, W_l, H_l, color_off, depth_off, mask_off]."""
+    [rc, bytes, cost_off, sum_off], gsaj_motion_stereo_bytes / gsaj_debug_motion_stereo_offsets as [rc, bytes, pc_off, cost_off, sum_off]
+    and gsaj_pyramid_level as [rc, W_l, H_l, color_off, depth_off, mask_off]."""
     out = {name: {_key(a): int(getattr(lib, name)(*a)) for a in cases} for name, cases in CASES.items()}
-    st = out["gsaj_stereo_workspace_bytes"] = {}
-    for a in STEREO:
-        n, c, s = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
-        rc = lib.gsaj_stereo_workspace_bytes(*a, ctypes.byref(n))
-        rc2 = lib.gsaj_debug_stereo_offsets(*a, ctypes.byref(c), ctypes.byref(s))
-        assert rc == rc2, a
-        st[_key(a)] = [rc, n.value, c.value, s.value]
+    for size_fn, (offsets_fn, n_offs, ladder) in MATCHERS.items():
+        st = out[size_fn] = {}
+        for a in ladder:
+            n, offs = ctypes.c_size_t(0), [ctypes.c_size_t(0) for _ in range(n_offs)]
+            rc = getattr(lib, size_fn)(*a, ctypes.byref(n))
+            rc2 = getattr(lib, offsets_fn)(*a, *[ctypes.byref(o) for o in offs])
+            assert rc == rc2, a
+            st[_key(a)] = [rc, n.value] + [o.value for o in offs]
     lv = out["gsaj_pyramid_level"] = {}
     for a in PYRAMID_LEVELS:
         wl, hl = ctypes.c_int(0), ctypes.c_int(0)
@@ -121,7 +128,7 @@ def test_every_size_and_exported_offset_is_the_recorded_one(lib, golden):
 
 def test_every_contract_row_is_on_the_ladder():
     import test_gpu_memory_contracts as mc
-    missing = [n for n in mc.CONTRACTS if n not in CASES and n != "gsaj_stereo_workspace_bytes"]
+    missing = [n for n in mc.CONTRACTS if n not in CASES and n not in MATCHERS]
     assert not missing, missing
 
 
@@ -134,9 +141,10 @@ def test_the_ladder_is_not_trivial(golden):
         vals = list(golden[name].values())
         assert 0 in vals and max(vals) > 0, name
     assert golden["gsaj_dist2_workspace_bytes"]["0"] == 512 and golden["gsaj_dist2_workspace_bytes"]["-1"] == 512
-    st = list(golden["gsaj_stereo_workspace_bytes"].values())
-    assert any(v[0] == 0 and v[1] > 0 for v in st) and any(v[0] != 0 for v in st)
-    assert sum(len(v) for v in golden.values()) == sum(len(c) for c in CASES.values()) + len(STEREO) + len(PYRAMID_LEVELS)
+    for name in MATCHERS:
+        st = list(golden[name].values())
+        assert any(v[0] == 0 and v[1] > 0 for v in st) and any(v[0] != 0 for v in st), name
+    assert sum(len(v) for v in golden.values()) == sum(len(c) for c in CASES.values()) + len(STEREO) + len(MOTION_STEREO) + len(PYRAMID_LEVELS)
 
 
 def test_one_altered_number_is_noticed(lib, golden):

@@ -12,8 +12,7 @@ the workspace's contract allows one -- with
 Workspaces whose contract is "no initialisation needed" are poisoned again before every run; "zeroed once" workspaces are zeroed
 when allocated and then only reused, and (d) is their poisoning.
 
-CONTRACTS is the table: one row per gsaj_*_workspace_bytes function (and gsaj_pyramid_bytes) with the line of include/gsaj.h its
-contract comes from.  tests/test_cpu_guards.py fails if a size function of gsaj/_lib.py has no row, if a quoted line moved, or if a
+CONTRACTS is the table: one row per size function (gsaj_*_bytes) with the line of include/gsaj.h its contract comes from.  tests/test_cpu_guards.py fails if a size function of gsaj/_lib.py has no row, if a quoted line moved, or if a
 named test is missing.
 
 Operations that turned out not to be bit-reproducible between two runs (compared at their own GPU test's tolerance instead):
@@ -69,6 +68,7 @@ CONTRACTS = {
     "gsaj_eval_workspace_bytes": dict(line=1036, quote="ZEROED ONCE", init="zeroed once", tests=["test_eval_frame"]),
     "gsaj_dense_workspace_bytes": dict(line=1047, quote="no initialisation needed", init="none", tests=["test_dense_path"]),
     "gsaj_dense_project_workspace_bytes": dict(line=1072, quote="project_ws", init="none", tests=["test_dense_path"]),
+    "gsaj_motion_stereo_bytes": dict(line=1289, quote="no initialisation needed (S is zeroed on the stream", init="none", tests=["test_motion_stereo"]),
 }
 
 
@@ -443,6 +443,43 @@ def test_stereo_match(monkeypatch, paths):
     la, ra = _pair(96, 40, 16, seed=5)
     lb, rb = _pair(96, 40, 16, seed=6)
     _contract(monkeypatch, _op_stereo, (_t(la), _t(ra), paths), (_t(lb[::-1].copy()), _t(rb[::-1].copy()), paths), "stereo paths=%d" % paths)
+
+
+# ---- motion stereo -------------------------------------------------------------------------------------------------------------------
+def _op_sweep(inp, st):
+    import torch
+    from gsaj import MotionStereo
+
+    c, D, paths = inp
+    cam = c["cam"]
+    H, W = c["ref"].shape
+    key = ("m", W, H, D)
+    if key not in st:
+        st[key] = MotionStereo(W, H, DEV, cam["fx"], cam["fy"], cam["cx"], cam["cy"], num_hypotheses=D, block_radius=2, paths=paths)
+        st.setdefault("all", []).append(st[key].workspace)
+        st["scratch"] = lambda: st["all"]
+    m = st[key]
+    idx16 = E(H, W, dtype=torch.int16)
+    depth = E(H, W)
+    m(c["dev"][0], c["dev"][1], c["dev"][2], c["dev"][3], 0.2, 0.7, out_idx16=idx16, out_depth=depth)
+    return dict(idx16=idx16, depth=depth, grad=m.gradient_bytes(), pc=m.pixel_costs(), cost=m.cost_volume(), sums=m.sums())
+
+
+def _sweep_inputs(W, H, motion):
+    import sweep_restated as sw
+
+    c = dict(sw.case(W, H, motion))
+    c["dev"] = [_t(c[k]) for k in ("ref", "src", "ref_w2c", "src_w2c")]   # inputs: not a guarded route
+    return c
+
+
+@pytest.mark.parametrize("paths", [4, 8])
+def test_motion_stereo(monkeypatch, paths):
+    """A: 96 x 40, D = 32; B: 65 x 33, D = 16 -- a smaller image with fewer hypotheses on an object of its own: the sizes of a
+    MotionStereo are fixed when it is made.  pc, C and S end at the workspace's exact end; S is summed into and must start from the
+    call's own zeroes, not from the fill."""
+    A, B = _sweep_inputs(96, 40, "forward"), _sweep_inputs(65, 33, "mixed")
+    _contract(monkeypatch, _op_sweep, (A, 32, paths), (B, 16, paths), "motion stereo paths=%d" % paths)
 
 
 # ---- seeding and depth statistics ---------------------------------------------------------------------------------------------------

@@ -92,6 +92,26 @@ def test_the_cost_volume_and_the_sums_themselves(kind):
         assert S.max() > 65535
 
 
+@pytest.mark.parametrize("r", [0, 15])
+def test_a_second_band_of_rows_equals_the_restatement(r):
+    """20 x 70, D = 16: H = 70 gives k_stereo_cost two bands of rows, the second 6 rows under a window of up to 31 -- its ring is primed
+    from row 64 - r > 0 and the bottom clamp falls inside it; r = 15 uses every slot of the ring."""
+    import torch
+
+    W, H, D = 20, 70, 16
+    left, right = _pair(W, H, D)
+    m = _matcher(W, H, num_disparities=D, block_radius=r, paths=8, uniqueness=0, lr_max_diff=-1)
+    got = m(left, right)
+    C = sr.cost_volume(left, right, D, r)
+    S = sr.path_costs(C, D, 2, 5, 8)
+    got_C = m.cost_volume().cpu().numpy().view(np.uint16).astype(np.int64)
+    assert np.array_equal(got_C[:, D:], C[:, D:]), "r=%d: the cost volume differs at %d entries" % (r, int((got_C[:, D:] != C[:, D:]).sum()))
+    got_S = m.sums().cpu().numpy().astype(np.int64)
+    assert np.array_equal(got_S, S), "r=%d: the sums differ at %d entries" % (r, int((got_S != S).sum()))
+    assert torch.equal(got.cpu(), torch.from_numpy(sr.winner(S, D, 0, -1)))
+    assert len(np.unique(C[64:, D:])) > 1 and (got[:, D:] >= 0).all()
+
+
 @pytest.mark.parametrize("D", [16, 32, 64, 128])
 def test_planted_sums_through_the_winner_stage_alone_and_their_depth(D):
     """Ties, d* at both ends, negative sub-pixel numerators, two left pixels at equal cost for one right column, rivals exactly at the
