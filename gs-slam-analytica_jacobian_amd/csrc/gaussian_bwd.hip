@@ -16,14 +16,9 @@
 #include "gsaj_common.h"
 #include "last_block.h"
 #include "wave_reduce.h"
-__constant__ float bSH_C0 = 0.28209479177387814f;
-__constant__ float bSH_C1 = 0.4886025119029199f;
-__constant__ float bSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f,
-                                0.5462742152960396f};
-__constant__ float bSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                                -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
-#define GSAJ_SH_CONSTANTS_DEFINED
+#define GSAJ_SH_LINKAGE_EXTERN  // the SH constants have external linkage here and are loaded from constant memory (gaussian_chain.h)
 #include "gaussian_chain.h"
+#include <type_traits>
 
 // SHW = 3*M as a compile-time constant (0: runtime) -- the staging loops divide by it per element
 GSAJ_TRACE_DEFINE(gbwd)
@@ -226,18 +221,29 @@ LdsRequest lds_gaussian_bwd(int M, bool has_shs) {
   return r;
 }
 
+// The SH storage widths the per-Gaussian kernels are instantiated at: f(std::integral_constant<int, 3 M>) for M = 0 (no SH), 1, 4, 9 or
+// 16 coefficients; any other M: f is not called, false
+template <typename F>
+static bool sh_for_m(int M, F &&f) {
+  switch (M) {
+    case 0: f(std::integral_constant<int, 0>{}); return true;
+    case 1: f(std::integral_constant<int, 3>{}); return true;
+    case 4: f(std::integral_constant<int, 12>{}); return true;
+    case 9: f(std::integral_constant<int, 27>{}); return true;
+    case 16: f(std::integral_constant<int, 48>{}); return true;
+    default: return false;
+  }
+}
+
 int launch_gaussian_backward(const BwdParams &p, const GeomWS &g, const BinWS &b, const ImageWS &im, hipStream_t s) {
   const int nblk = (p.P + GB_BLOCK - 1) / GB_BLOCK;
   {
     GsajProfScope ps(ST_GAUSSIAN_BWD, s);
     const size_t lds = lds_gaussian_bwd(p.M, p.shs != nullptr).dynamic_bytes;
-    switch (p.shs ? p.M : -1) {
-      case 1: hipLaunchKernelGGL(k_gaussian_bwd<3>, dim3(nblk), dim3(GB_BLOCK), lds, s, p, g, im.counters, b.inst_grad, b.reached); break;
-      case 4: hipLaunchKernelGGL(k_gaussian_bwd<12>, dim3(nblk), dim3(GB_BLOCK), lds, s, p, g, im.counters, b.inst_grad, b.reached); break;
-      case 9: hipLaunchKernelGGL(k_gaussian_bwd<27>, dim3(nblk), dim3(GB_BLOCK), lds, s, p, g, im.counters, b.inst_grad, b.reached); break;
-      case 16: hipLaunchKernelGGL(k_gaussian_bwd<48>, dim3(nblk), dim3(GB_BLOCK), lds, s, p, g, im.counters, b.inst_grad, b.reached); break;
-      default: hipLaunchKernelGGL(k_gaussian_bwd<0>, dim3(nblk), dim3(GB_BLOCK), lds, s, p, g, im.counters, b.inst_grad, b.reached); break;
-    }
+    auto launch = [&](auto shw) {
+      hipLaunchKernelGGL(k_gaussian_bwd<decltype(shw)::value>, dim3(nblk), dim3(GB_BLOCK), lds, s, p, g, im.counters, b.inst_grad, b.reached);
+    };
+    if (!sh_for_m(p.shs ? p.M : 0, launch)) launch(std::integral_constant<int, 0>{});  // (any other M: the runtime-width instantiation)
   }
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
@@ -247,13 +253,11 @@ int launch_gaussian_backward(const BwdParams &p, const GeomWS &g, const BinWS &b
 // A mapping window renders every keyframe against the same Gaussians and back-propagates once, so the per-Gaussian
 // gradients accumulate over keyframes while every keyframe keeps its own dL/dtau (reference utils/slam_backend.py:168-232).
 // A whole window (gsaj_rasterize_backward_batch without GSAJ_BWD_ONLY_*): one launch per 8 views and one for dL/dtau,
-//  k_chain_window<SHW, true> + k_tau_sum: the chain kernel sums a Gaussian's per-instance partial-gradient rows ITSELF (the row
-//    walk of k_gather_sums, one wave per two views of 32 Gaussians, on k_gather_sums' own grid of 64-row groups: the same
-//    additions in the same order, the same bits) and runs the chain on the totals; gsum is neither written nor read.
+//  k_chain_window<SHW, true> + k_tau_sum: the chain kernel sums a Gaussian's per-instance partial-gradient rows ITSELF (RowWalk,
+//    one wave per two views of 32 Gaussians) and runs the chain on the totals; gsum is neither written nor read.
 // The two halves of a window called separately (GSAJ_BWD_ONLY_COMPOSITE, then GSAJ_BWD_ONLY_CHAIN: two streams, tile bands):
-//  k_gather_sums (grid x K, HBM-streaming, many waves in flight): a Gaussian's per-instance partial-gradient rows -- one
-//    contiguous run by emission slot, a wave's 64 Gaussians one contiguous block -- are streamed with coalesced loads and
-//    added in emission order; 48 bytes per Gaussian and view out (gsum).
+//  k_gather_sums (grid x K, HBM-streaming, many waves in flight): the same walk, one wave per 64 Gaussians of a view, the same
+//    bits; 48 bytes per Gaussian and view out (gsum).
 //  k_chain_window<SHW, false> + k_tau_sum: below; reads gsum.
 // one step of the keyed wave scan: lanes that receive a value through the DPP pattern CTRL (row mask ROWS) add it iff it comes from
 // the same owner; lanes the pattern does not reach see the key -1 and add nothing
@@ -285,77 +289,103 @@ __device__ __forceinline__ void scan_by_key_step(int own, float (&v)[10]) {
 }
 #undef GSAJ_SCAN_STEP
 
-// k_gather_sums: lane = ROW.  A wave owns 64 consecutive Gaussians, whose instance rows are ONE contiguous block ordered by
-// owner; it walks the block 64 rows at a time with fully coalesced loads (row + `reached` flag requested together: one memory
-// round trip; the next 64 rows are requested before the current ones are reduced), finds every row's owner by a 6-step binary
-// search over the owners' end slots (lane shuffles), runs a scan-by-key over the 64 rows (Hillis-Steele, add when the owner of
-// lane l equals the owner of lane l - d: exact for contiguous segments; DPP, no LDS), and each owner picks up its segment's total
-// from its segment's last row of the group.  No LDS staging, no per-lane loop over a heavy-tailed run length (that loop kept ~20 % of
-// the lanes busy and its scattered ds_read_b128 conflicted 4-way: 100 us; this form: see profiles/).  The additions follow a
-// fixed tree per 64-row group and the groups in order: bit-reproducible.
-GSAJ_TRACE_DEFINE(gath)
-__global__ __launch_bounds__(256) void k_gather_sums(int P, const int *__restrict__ radii0, GeomWS g0, ImageWS im0,
-                                                     const float4 *__restrict__ inst_grad0, const uint8_t *__restrict__ reached0,
-                                                     ViewStrides vs) {
-  GSAJ_TRACE_BEGIN(gath)
-  const size_t view = blockIdx.y;
-  const GeomWS g = geom_view(g0, view * vs.geom);
-  const float4 *inst_grad = gsaj_shift(inst_grad0, view * vs.bin);
-  const uint8_t *reached = gsaj_shift(reached0, view * vs.bin);
-  const uint32_t *counters = gsaj_shift(im0.counters, view * vs.image);
-  const int lane = threadIdx.x & 63;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  const size_t ii = (size_t)(idx < P ? idx : 0);
-  const bool live = idx < P && counters[4] == 0u;  // (an aborted async frame contributes nothing)
-  const uint32_t cnt = live ? g.tiles_touched[ii] : 0u;
-  const uint32_t endi_raw = live ? g.block_sums[ii / PRE_BLOCK] + g.point_offsets[ii] : 0u;  // (block-local scan + the block's offset)
-  // owners' end slots, made non-decreasing over the lanes (culled / out-of-range owners repeat their predecessor's end)
-  const uint32_t endi = wave_incl_scan_max(endi_raw);
-  const uint32_t first = live ? endi_raw - cnt : endi;
-  const uint32_t F = wave_min((cnt > 0) ? first : 0xffffffffu);
-  const uint32_t E = (uint32_t)__shfl((int)endi, 63);
-  float sum[10];
-#pragma unroll
-  for (int c = 0; c < 10; c++) sum[c] = 0.f;
-  if (F != 0xffffffffu && F < E) {
-    // rows the reverse compositor never wrote (`reached` = 0: no pixel of the tile got that far -- most of an opaque scene's
-    // instances) are not fetched: the one-byte flags run TWO groups ahead of the rows they admit, the rows one group ahead of
-    // their use; only the wave's first group is fetched without waiting for its flags
-    float4 a0, a1, a2;
-    uint8_t fl = 0, fl_a = 0, fl_b = 0;  // flags of the group in (a0, a1, a2), of the next group, of the one after
-    auto flags_of = [&](uint32_t base) -> uint8_t { return base + (uint32_t)lane < E ? reached[base + lane] : (uint8_t)0; };
-    auto rows_of = [&](uint32_t base) {
-      const float4 *src = inst_grad + (size_t)(base + lane) * REC_F4;
-      a0 = src[0]; a1 = src[1]; a2 = src[2];
-    };
-    fl = flags_of(F);
-    if (F + (uint32_t)lane < E) rows_of(F);
-    fl_a = flags_of(F + 64);
-    fl_b = flags_of(F + 128);
-    for (uint32_t base = F; base < E; base += 64) {
-      const uint32_t r = base + (uint32_t)lane;
-      const bool ok = fl != 0;
-      float v[10] = {ok ? a0.x : 0.f, ok ? a0.y : 0.f, ok ? a0.z : 0.f, ok ? a0.w : 0.f, ok ? a1.x : 0.f,
-                     ok ? a1.y : 0.f, ok ? a1.z : 0.f, ok ? a1.w : 0.f, ok ? a2.x : 0.f, ok ? a2.y : 0.f};
-      if (base + 64 < E) {
-        fl = fl_a;
-        if (fl) rows_of(base + 64);
-        fl_a = fl_b;
-        fl_b = flags_of(base + 192);
-      }
-      // a group none of whose rows was reached adds nothing (opaque scenes: most groups of the Gaussians that lie behind)
-      if (__builtin_amdgcn_ballot_w64(ok) == 0ull) continue;
+// The per-lane preamble of a RowWalk (below): lane = owner, N consecutive owners per wave (64) or half-wave (32)
+struct OwnerRows {
+  uint32_t cnt, first, endi;  // the lane's own run; its end slot, non-decreasing over the N lanes
+  uint32_t F, E;              // rows of the N owners (F = ~0u: none)
+  uint32_t block_off;         // rows before the owner's PRE_BLOCK block (the chain kernel derives its grid origin from it)
+};
+// live: the lane has a Gaussian whose frame was not aborted (an aborted async frame has no rows)
+template <int N>
+__device__ __forceinline__ OwnerRows owner_rows(bool live, const GeomWS &g, size_t ii) {
+  OwnerRows o;
+  o.cnt = live ? g.tiles_touched[ii] : 0u;
+  o.block_off = live ? g.block_sums[ii / PRE_BLOCK] : 0u;
+  const uint32_t endi_raw = live ? o.block_off + g.point_offsets[ii] : 0u;  // (block-local scan + the block's offset)
+  o.endi = wave_incl_scan_max<N>(endi_raw);  // (culled / out-of-range owners repeat their predecessor's end)
+  o.first = live ? endi_raw - o.cnt : o.endi;
+  o.F = wave_min<N>((o.cnt > 0) ? o.first : 0xffffffffu);
+  o.E = (uint32_t)__shfl((int)o.endi, N - 1, N);
+  return o;
+}
+
+// ---- RowWalk: the per-instance gradient rows of OWNERS consecutive Gaussians, summed per Gaussian ------------------------------
+// Gaussian i owns rows [first, first + cnt) of inst_grad by emission slot and consecutive Gaussians own consecutive runs, so the
+// rows of OWNERS consecutive Gaussians are ONE contiguous block [F, E) ordered by owner.  A wave walks it with lane = ROW, 64 rows
+// (a group) at a time with fully coalesced loads: every row finds its owner by a binary search over the owners' end slots (lane
+// shuffles), a scan-by-key runs over the 64 rows (Hillis-Steele, add when the owner of lane l equals the owner of lane l - d: exact
+// for contiguous segments; DPP, no LDS) and each owner picks up its run's total at its run's last row of the group.  No LDS staging
+// and no per-lane loop over a heavy-tailed run length (that loop kept ~20 % of the lanes busy and its scattered ds_read_b128
+// conflicted 4-way: 100 us; this form: see profiles/).
+//  The grid.  The additions follow a fixed tree per group and the groups in order, so a run's total depends on where the group
+//   boundaries fall inside it.  There is ONE grid per block of 64 Gaussians: groups start at G + 64 k, G = the block's first row.
+//   64 owners (k_gather_sums) are that block: the walk starts at F = G.  32 owners (k_chain_window, a half-block) start at the group
+//   of the same grid that holds their first row, G + ((F - G) & ~63): the same additions in the same order as the walk over all 64,
+//   the same bits.
+//  Foreign rows.  The first and the last group of 32 owners may hold rows of the other half-block: never fetched, value 0, owner key
+//   -2.  A segment's scan result depends on its own lanes only, and what the keyed fmac adds from another owner is x * 0 = +-0,
+//   which no non-zero value and no final sum -- sums start at +0 and +0 + -0 = +0 -- can tell apart.  (64 owners have none: rows
+//   past E are 0 and no owner's run reaches them.)
+//  Prefetch.  Rows the reverse compositor never wrote (`reached` = 0: no pixel of the tile got that far -- most of an opaque scene's
+//   instances) are not fetched: the one-byte flags run TWO groups ahead of the rows they admit, the rows ONE group ahead of their
+//   use; only the first group is fetched without waiting for its flags.  A group none of whose rows was reached adds nothing and
+//   is skipped.
+// The caller hands start() F, E and G as scalars (readfirstlane: the group loop and its bounds then run on the scalar unit; DESIGN.md has the figures);
+// endi (the owners' end slots, non-decreasing inside each group of OWNERS lanes), first and cnt (the lane's own run) are owner_rows'
+// above.
+template <int OWNERS>
+struct RowWalk {
+  static_assert(OWNERS == 32 || OWNERS == 64, "a wave or a half-wave of owners");
+  const float4 *__restrict__ inst_grad;
+  const uint8_t *__restrict__ reached;
+  uint32_t F, E, base;  // the owners' rows [F, E); first row of the current group
+  int src;              // first lane of the owners
+  float4 a0, a1, a2;
+  uint8_t fl, fl_a, fl_b;  // flags of the group in (a0, a1, a2), of the next group, of the one after
+
+  __device__ __forceinline__ bool active() const { return base < E; }  // a group is left to walk
+  __device__ __forceinline__ bool inside(uint32_t r) const { return (OWNERS == 64 || r >= F) && r < E; }
+  __device__ __forceinline__ uint8_t flags_of(uint32_t b, int lane) const { return inside(b + (uint32_t)lane) ? reached[b + lane] : (uint8_t)0; }
+  __device__ __forceinline__ void rows_of(uint32_t b, int lane) {
+    const float4 *rp = inst_grad + (size_t)(b + lane) * REC_F4;
+    a0 = rp[0]; a1 = rp[1]; a2 = rp[2];
+  }
+  // requests the first group's flags and rows (the rows without waiting for their flags) and the flags of the next two groups
+  __device__ __forceinline__ void start(bool on, int first_lane, int lane, uint32_t F_, uint32_t E_, uint32_t G, const float4 *ig,
+                                        const uint8_t *rc) {
+    inst_grad = ig; reached = rc;
+    src = first_lane; F = F_;
+    E = on && F != 0xffffffffu && F < E_ ? E_ : 0u;  // (no rows, no walk: nothing is inside)
+    base = OWNERS == 64 ? F : G + ((F - G) & ~63u);
+    fl = flags_of(base, lane);
+    if (inside(base + (uint32_t)lane)) rows_of(base, lane);
+    fl_a = flags_of(base + 64, lane);
+    fl_b = flags_of(base + 128, lane);
+  }
+  // one group of 64 rows: requests the next group's rows, reduces the current one, owners take their runs' totals
+  __device__ __forceinline__ void step(int lane, uint32_t endi, uint32_t first, uint32_t cnt, float (&sum)[10]) {
+    const uint32_t r = base + (uint32_t)lane;
+    const bool ok = fl != 0;
+    float v[10] = {ok ? a0.x : 0.f, ok ? a0.y : 0.f, ok ? a0.z : 0.f, ok ? a0.w : 0.f, ok ? a1.x : 0.f,
+                   ok ? a1.y : 0.f, ok ? a1.z : 0.f, ok ? a1.w : 0.f, ok ? a2.x : 0.f, ok ? a2.y : 0.f};
+    if (base + 64 < E) {
+      fl = fl_a;
+      if (fl) rows_of(base + 64, lane);
+      fl_a = fl_b;
+      fl_b = flags_of(base + 192, lane);
+    }
+    if (__builtin_amdgcn_ballot_w64(ok) != 0ull) {
       // owner of row r = number of owners whose end slot is <= r (end slots are non-decreasing): binary search by shuffles
       int own = 0;
 #pragma unroll
-      for (int step = 32; step > 0; step >>= 1) {
-        const uint32_t e = (uint32_t)__shfl((int)endi, own + step - 1);
-        if (e <= r) own += step;
+      for (int st = OWNERS / 2; st > 0; st >>= 1) {
+        const uint32_t e = (uint32_t)__shfl((int)endi, src + own + st - 1);
+        if (e <= r) own += st;
       }
-      // scan by key: after the last step lane l holds the sum of the rows of its owner in [max(segment start, base), r].
-      // All in the VALU (DPP): four row_shr steps inside each 16-lane row, then row_bcast:15 (rows 1, 3 take lane 15 / 47) and
-      // row_bcast:31 (rows 2, 3 take lane 31, which by then carries rows 0-1) -- the keyed form of the classic wave scan: a lane
-      // adds the incoming value iff it comes from the same owner, exact because an owner's rows are contiguous.
+      if (OWNERS < 64 && !inside(r)) own = -2;
+      // scan by key: after the last step lane l holds the sum of the rows of its owner in [max(run start, base), r].  All in the
+      // VALU (DPP): four row_shr steps inside each 16-lane row, then row_bcast:15 (rows 1, 3 take lane 15 / 47) and row_bcast:31
+      // (rows 2, 3 take lane 31, which by then carries rows 0-1) -- the keyed form of the classic wave scan
       scan_by_key_step<0x111, 0xF>(own, v);  // row_shr:1
       scan_by_key_step<0x112, 0xF>(own, v);  // row_shr:2
       scan_by_key_step<0x114, 0xF>(own, v);  // row_shr:4
@@ -364,7 +394,7 @@ __global__ __launch_bounds__(256) void k_gather_sums(int P, const int *__restric
       scan_by_key_step<0x143, 0xC>(own, v);  // row_bcast:31 -> rows 2, 3
       // every owner whose run meets this group takes the total at its run's last row inside the group
       const uint32_t run_lo = max(first, base), run_hi = min(first + cnt, min(base + 64u, E));
-      const bool mine = cnt > 0 && run_lo < run_hi;
+      const bool mine = (OWNERS == 64 || (lane & OWNERS) == src) && cnt > 0 && run_lo < run_hi;
       const int q = mine ? (int)(run_hi - 1u - base) : 0;
 #pragma unroll
       for (int c = 0; c < 10; c++) {
@@ -372,7 +402,30 @@ __global__ __launch_bounds__(256) void k_gather_sums(int P, const int *__restric
         sum[c] += mine ? t : 0.f;
       }
     }
+    base += 64;
   }
+};
+
+// k_gather_sums: one wave = one block of 64 Gaussians of one view, one RowWalk<64>; 48 bytes per Gaussian and view out (gsum)
+GSAJ_TRACE_DEFINE(gath)
+__global__ __launch_bounds__(256) void k_gather_sums(int P, const int *__restrict__ radii0, GeomWS g0, ImageWS im0,
+                                                     const float4 *__restrict__ inst_grad0, const uint8_t *__restrict__ reached0,
+                                                     ViewStrides vs) {
+  GSAJ_TRACE_BEGIN(gath)
+  const size_t view = blockIdx.y;
+  const GeomWS g = geom_view(g0, view * vs.geom);
+  const uint32_t *counters = gsaj_shift(im0.counters, view * vs.image);
+  const int lane = threadIdx.x & 63;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const size_t ii = (size_t)(idx < P ? idx : 0);
+  const OwnerRows o = owner_rows<64>(idx < P && counters[4] == 0u, g, ii);
+  float sum[10];
+#pragma unroll
+  for (int c = 0; c < 10; c++) sum[c] = 0.f;
+  RowWalk<64> w;
+  const uint32_t F = (uint32_t)__builtin_amdgcn_readfirstlane((int)o.F), E = (uint32_t)__builtin_amdgcn_readfirstlane((int)o.E);
+  w.start(true, 0, lane, F, E, F, gsaj_shift(inst_grad0, view * vs.bin), gsaj_shift(reached0, view * vs.bin));
+  while (w.active()) w.step(lane, o.endi, o.first, o.cnt, sum);
   if (idx < P) {
     g.gsum[3 * ii + 0] = make_float4(sum[0], sum[1], sum[2], sum[3]);
     g.gsum[3 * ii + 1] = make_float4(sum[4], sum[5], sum[6], sum[7]);
@@ -403,95 +456,10 @@ __global__ __launch_bounds__(256) void k_gather_sums(int P, const int *__restric
 #define CW_V 8    // views per pass
 GSAJ_TRACE_DEFINE(gbb)
 
-// k_chain_window<., GATHER = true>: the ten sums of a (view, Gaussian) lane formed in the kernel.  The 32 lanes of half-wave `half` are
-// the 32 Gaussians of one view; their instance rows are one contiguous block [F, E), which the WHOLE wave walks with lane = row exactly
-// as k_gather_sums walks the block of its 64 Gaussians.  A run's total depends on where the 64-row group boundaries fall, so the walk
-// keeps k_gather_sums' grid: groups start at G + 64 k, G = first row of the enclosing block of 64 Gaussians.  A half-block that does
-// not start that block begins with the group of the grid that holds its first row; rows of the other half-block inside its first
-// and last group are foreign: never fetched, value 0, owner key -2 (a segment's scan result depends on its own lanes only, and
-// what the keyed fmac adds from another owner is x * 0 = +-0, which no non-zero value and no final sum -- sums start at +0 and
-// +0 + -0 = +0 -- can tell apart).  Every sum is bit-identical to what k_gather_sums leaves in gsum.
-// A wave runs its two views' walks as two streams side by side (start, then step by turns), so that two groups of rows are on
-// their way at any time.  endi: owners' end slots, non-decreasing inside each half-wave; first, cnt: the lane's own run; F32, E32,
-// G32: per half-wave (uniform inside a half) the half-block's rows and the grid's origin.
-struct ChainRowStream {
-  const float4 *__restrict__ inst_grad;
-  const uint8_t *__restrict__ reached;
-  uint32_t F, E, base;  // the half-block's rows [F, E); first row of the current group (uniform)
-  int src;              // first lane of the half-wave that owns these rows
-  bool active;          // uniform
-  float4 a0, a1, a2;
-  uint8_t fl, fl_a, fl_b;  // flags of the group in (a0, a1, a2), of the next group, of the one after
-
-  __device__ __forceinline__ uint8_t flags_of(uint32_t b, int lane) const {
-    const uint32_t r = b + (uint32_t)lane;
-    return r >= F && r < E ? reached[r] : (uint8_t)0;
-  }
-  __device__ __forceinline__ void rows_of(uint32_t b, int lane) {
-    const float4 *rp = inst_grad + (size_t)(b + lane) * REC_F4;
-    a0 = rp[0]; a1 = rp[1]; a2 = rp[2];
-  }
-  // requests the first group's flags and rows (the rows without waiting for their flags) and the flags of the next two groups
-  __device__ __forceinline__ void start(bool on, int half, int lane, uint32_t F32, uint32_t E32, uint32_t G32, const float4 *ig,
-                                        const uint8_t *rc) {
-    inst_grad = ig; reached = rc;
-    src = half * CW_G;
-    F = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)F32, src));
-    E = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)E32, src));
-    const uint32_t G = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)G32, src));
-    active = on && F != 0xffffffffu && F < E;
-    fl = fl_a = fl_b = 0;
-    base = 0;
-    if (active) {
-      base = G + ((F - G) & ~63u);
-      fl = flags_of(base, lane);
-      if (base + (uint32_t)lane >= F && base + (uint32_t)lane < E) rows_of(base, lane);
-      fl_a = flags_of(base + 64, lane);
-      fl_b = flags_of(base + 128, lane);
-    }
-  }
-  // one group of 64 rows: requests the next group's rows, reduces the current one, owners take their runs' totals
-  __device__ __forceinline__ void step(int lane, uint32_t endi, uint32_t first, uint32_t cnt, float (&sum)[10]) {
-    const uint32_t r = base + (uint32_t)lane;
-    const bool ok = fl != 0;
-    float v[10] = {ok ? a0.x : 0.f, ok ? a0.y : 0.f, ok ? a0.z : 0.f, ok ? a0.w : 0.f, ok ? a1.x : 0.f,
-                   ok ? a1.y : 0.f, ok ? a1.z : 0.f, ok ? a1.w : 0.f, ok ? a2.x : 0.f, ok ? a2.y : 0.f};
-    if (base + 64 < E) {
-      fl = fl_a;
-      if (fl) rows_of(base + 64, lane);
-      fl_a = fl_b;
-      fl_b = flags_of(base + 192, lane);
-    }
-    if (__builtin_amdgcn_ballot_w64(ok) != 0ull) {  // (a group none of whose rows was reached adds nothing)
-      // owner of row r among the half-wave's 32: number of owners whose end slot is <= r; foreign rows get a key no owner has
-      int own = 0;
-#pragma unroll
-      for (int st = CW_G / 2; st > 0; st >>= 1) {
-        const uint32_t e = (uint32_t)__shfl((int)endi, src + own + st - 1);
-        if (e <= r) own += st;
-      }
-      if (r < F || r >= E) own = -2;
-      scan_by_key_step<0x111, 0xF>(own, v);  // row_shr:1
-      scan_by_key_step<0x112, 0xF>(own, v);  // row_shr:2
-      scan_by_key_step<0x114, 0xF>(own, v);  // row_shr:4
-      scan_by_key_step<0x118, 0xF>(own, v);  // row_shr:8
-      scan_by_key_step<0x142, 0xA>(own, v);  // row_bcast:15 -> rows 1, 3
-      scan_by_key_step<0x143, 0xC>(own, v);  // row_bcast:31 -> rows 2, 3
-      // every owner of this view whose run meets this group takes the total at its run's last row inside the group
-      const uint32_t run_lo = max(first, base), run_hi = min(first + cnt, min(base + 64u, E));
-      const bool mine = (lane & CW_G) == src && cnt > 0 && run_lo < run_hi;
-      const int q = mine ? (int)(run_hi - 1u - base) : 0;
-#pragma unroll
-      for (int c = 0; c < 10; c++) {
-        const float t = __shfl(v[c], q);
-        sum[c] += mine ? t : 0.f;
-      }
-    }
-    base += 64;
-    active = base < E;
-  }
-};
-
+// k_chain_window<., GATHER = true>: the ten sums of a (view, Gaussian) lane formed in the kernel.  The 32 lanes of a half-wave are the
+// 32 Gaussians of one view, a half-block of k_gather_sums' 64: the WHOLE wave walks their rows with a RowWalk<CW_G> on that block's
+// grid, so every sum is bit-identical to what k_gather_sums leaves in gsum.  A wave runs its two views' walks side by side (start,
+// then step by turns), so that two groups of rows are on their way at any time.
 template <int SHW, bool GATHER>
 __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, int v0, int K, GeomWS g0, ImageWS im0, ViewStrides vs,
                                                               const float4 *__restrict__ inst_grad0, const uint8_t *__restrict__ reached0,
@@ -547,32 +515,26 @@ __global__ __launch_bounds__(CW_G * CW_V, 4) void k_chain_window(BwdParams p, in
       aborted_w = gsaj_shift(im0.counters, vc * vs.image)[4];
       rad_w = p.radii[vc * p.P + ii];
       if (SHW > 0) { cl_w[0] = gw.clamped[3 * ii]; cl_w[1] = gw.clamped[3 * ii + 1]; cl_w[2] = gw.clamped[3 * ii + 2]; }
-      const bool live = v < K && idx < p.P && aborted_w == 0u;  // (an aborted frame has no rows)
-      const uint32_t cnt = live ? gw.tiles_touched[ii] : 0u;
-      const uint32_t bs = live ? gw.block_sums[ii / PRE_BLOCK] : 0u;
-      const uint32_t endi_raw = live ? bs + gw.point_offsets[ii] : 0u;
+      const bool live = v < K && idx < p.P && aborted_w == 0u;
+      const OwnerRows o = owner_rows<CW_G>(live, gw, ii);
       // the grid's origin: first row of the enclosing block of 64 Gaussians = end slot of the Gaussian before it (same PRE_BLOCK)
       const int i64 = ((int)blockIdx.x & ~1) * CW_G;
-      const uint32_t G32 = live ? bs + ((i64 % PRE_BLOCK) ? gw.point_offsets[i64 - 1] : 0u) : 0u;
-      // non-decreasing over the half-wave (out-of-range owners repeat their predecessor's end)
-      const uint32_t endi = wave_incl_scan_max<CW_G>(endi_raw);
-      const uint32_t first = live ? endi_raw - cnt : endi;
-      const uint32_t F32 = wave_min<CW_G>((cnt > 0) ? first : 0xffffffffu);
-      const uint32_t E32 = (uint32_t)__shfl((int)endi, CW_G - 1, CW_G);
-      const uint32_t G0 = (uint32_t)__shfl((int)G32, 0, CW_G);  // (lane 0 of a half is in range whenever the workgroup exists)
+      const uint32_t G32 = live ? o.block_off + ((i64 % PRE_BLOCK) ? gw.point_offsets[i64 - 1] : 0u) : 0u;
 #pragma unroll
       for (int c = 0; c < 10; c++) sum[c] = 0.f;
       // the wave's two views side by side: two independent row streams in flight (one after the other, a wave had one group of rows
-      // on its way at a time and the walk was bound by that round trip)
+      // on its way at a time and the walk was bound by that round trip).  Each stream's F, E, G: its half-wave's, made scalars.
+      // (G from lane 0 of the half, which is in range whenever the workgroup exists)
+      auto of_half = [&](uint32_t x, int half) { return (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)x, half * CW_G)); };
       const int vA = v0 + 2 * wv;
-      ChainRowStream sa, sb;
-      sa.start(vA < K, 0, lane, F32, E32, G0, gsaj_shift(inst_grad0, (size_t)min(vA, K - 1) * vs.bin),
+      RowWalk<CW_G> sa, sb;
+      sa.start(vA < K, 0, lane, of_half(o.F, 0), of_half(o.E, 0), of_half(G32, 0), gsaj_shift(inst_grad0, (size_t)min(vA, K - 1) * vs.bin),
                gsaj_shift(reached0, (size_t)min(vA, K - 1) * vs.bin));
-      sb.start(vA + 1 < K, 1, lane, F32, E32, G0, gsaj_shift(inst_grad0, (size_t)min(vA + 1, K - 1) * vs.bin),
+      sb.start(vA + 1 < K, CW_G, lane, of_half(o.F, 1), of_half(o.E, 1), of_half(G32, 1), gsaj_shift(inst_grad0, (size_t)min(vA + 1, K - 1) * vs.bin),
                gsaj_shift(reached0, (size_t)min(vA + 1, K - 1) * vs.bin));
-      while (sa.active || sb.active) {
-        if (sa.active) sa.step(lane, endi, first, cnt, sum);
-        if (sb.active) sb.step(lane, endi, first, cnt, sum);
+      while (sa.active() || sb.active()) {
+        if (sa.active()) sa.step(lane, o.endi, o.first, o.cnt, sum);
+        if (sb.active()) sb.step(lane, o.endi, o.first, o.cnt, sum);
       }
       // handed to the chain through LDS, in slots 0-9 of this view lane's part of rowv (320 floats: [32] float4 | [32] float4 | [32]
       // float2; the chain writes those slots last, after every read; a lane reads what it wrote itself: no barrier).  The chain below
@@ -793,21 +755,14 @@ int launch_gather_sums(int P, int K, const int *radii, const GeomWS &g, const Bi
 int launch_gaussian_backward_batch(const BwdParams &p, int K, const GeomWS &g, const BinWS &b, const ImageWS &im, ViewStrides vs,
                                    int accumulate, int gather, hipStream_t s) {
   GsajProfScope ps(ST_GAUSSIAN_BWD, s);
-#define CHAIN(SHW)                                                       \
-  if (gather) launch_chain<SHW, true>(p, K, g, b, im, vs, accumulate, s); \
-  else launch_chain<SHW, false>(p, K, g, b, im, vs, accumulate, s);       \
-  break
-  switch (p.shs ? p.M : 0) {
-    case 0: CHAIN(0);
-    case 1: CHAIN(3);
-    case 4: CHAIN(12);
-    case 9: CHAIN(27);
-    case 16: CHAIN(48);
-    default:
-      gsaj_set_error("batched backward: SH storage of %d coefficients is not supported (1, 4, 9 or 16)", p.M);
-      return GSAJ_ERR_INVALID_ARGUMENT;
+  const bool known = sh_for_m(p.shs ? p.M : 0, [&](auto shw) {
+    if (gather) launch_chain<decltype(shw)::value, true>(p, K, g, b, im, vs, accumulate, s);
+    else launch_chain<decltype(shw)::value, false>(p, K, g, b, im, vs, accumulate, s);
+  });
+  if (!known) {
+    gsaj_set_error("batched backward: SH storage of %d coefficients is not supported (1, 4, 9 or 16)", p.M);
+    return GSAJ_ERR_INVALID_ARGUMENT;
   }
-#undef CHAIN
   GSAJ_HIP_CHECK(hipGetLastError());
   return GSAJ_OK;
 }

@@ -4,15 +4,21 @@
 #pragma once
 #include "gsaj_common.h"
 
-// (gaussian_bwd.hip defines the four tables itself, with the external linkage its kernels were built with)
-#ifndef GSAJ_SH_CONSTANTS_DEFINED
-static __constant__ float bSH_C0 = 0.28209479177387814f;
-static __constant__ float bSH_C1 = 0.4886025119029199f;
-static __constant__ float bSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f,
-                                0.5462742152960396f};
-static __constant__ float bSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                                -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
+// The SH basis constants of the chain, one copy per translation unit that includes this.  The linkage is the includer's choice, because
+// it is part of the arithmetic: a `static` table is folded into the instructions as literals (signs and all: other multiplies,
+// other contractions), one with external linkage may be written by the host and is loaded from constant memory.  pose_jac.hip was
+// built with the first, gaussian_bwd.hip (which defines GSAJ_SH_LINKAGE_EXTERN) with the second; each keeps its instruction stream.
+#ifdef GSAJ_SH_LINKAGE_EXTERN
+#define GSAJ_SH_LINKAGE
+#else
+#define GSAJ_SH_LINKAGE static
 #endif
+GSAJ_SH_LINKAGE __constant__ float bSH_C0 = 0.28209479177387814f;
+GSAJ_SH_LINKAGE __constant__ float bSH_C1 = 0.4886025119029199f;
+GSAJ_SH_LINKAGE __constant__ float bSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f,
+                                0.5462742152960396f};
+GSAJ_SH_LINKAGE __constant__ float bSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
+                                -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
 
 __device__ __forceinline__ float3 dnormvdv(float3 v, float3 dv) {
   const float sum2 = v.x * v.x + v.y * v.y + v.z * v.z;

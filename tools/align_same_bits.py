@@ -10,21 +10,10 @@ process each, the same package; the calls and their arguments are the same, so t
     python tools/align_same_bits.py CHANGE.json
     python tools/align_same_bits.py --compare PARENT.json CHANGE.json OUT.json
 """
-import hashlib
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "gs-slam-analytica_jacobian_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+from same_bits import main, sha
 
 SIZES = ((2, 2), (65, 4), (97, 61), (70, 260))
 BRIGHT = (0.1, 0.03)
-
-
-def sha(t):
-    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
 
 
 def run(torch):
@@ -54,30 +43,7 @@ def run(torch):
     return out
 
 
-def main():
-    if sys.argv[1] == "--compare":
-        a, b = (json.load(open(p)) for p in sys.argv[2:4])
-        differing = sorted(k for k in set(a["hashes"]) | set(b["hashes"]) if a["hashes"].get(k) != b["hashes"].get(k))
-        doc = dict(what="tools/align_same_bits.py on the parent's library and on this change's, one process each, the same package: SHA-256 "
-                        "of every output of gsaj_rgbd_align and gsaj_rgbd_align8 on the parity cases and of the state and the row of both "
-                        "aligners after the default schedule", cases=len(a["hashes"]), buffers=sum(len(v) for v in a["hashes"].values()),
-                   libraries_differ=a["library_sha256"] != b["library_sha256"], differing=differing, equal=not differing, parent=a, change=b)
-        with open(sys.argv[4], "w") as fh:
-            json.dump(doc, fh, indent=1)
-            fh.write("\n")
-        print("align_same_bits: %d cases, %d buffers, %d cases differ %s" % (doc["cases"], doc["buffers"], len(differing), differing))
-        sys.exit(1 if differing else 0)
-    import torch
-
-    if not torch.cuda.is_available():
-        sys.exit("align_same_bits: no GPU")
-    from gsaj import _lib
-    doc = dict(device=torch.cuda.get_device_name(0), library_sha256=hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest(), hashes=run(torch))
-    with open(sys.argv[1], "w") as fh:
-        json.dump(doc, fh, indent=1)
-        fh.write("\n")
-    print("align_same_bits: %d cases written to %s" % (len(doc["hashes"]), sys.argv[1]))
-
-
 if __name__ == "__main__":
-    main()
+    main("align_same_bits", run, "tools/align_same_bits.py on the parent's library and on this change's, one process each, the same package: SHA-256 "
+         "of every output of gsaj_rgbd_align and gsaj_rgbd_align8 on the parity cases and of the state and the row of both "
+         "aligners after the default schedule")

@@ -7,26 +7,16 @@ same arguments in the same order, so there is no floating-point freedom.
     python tools/loops_same_bits.py OUT.json
     python tools/loops_same_bits.py --compare PARENT.json CHANGE.json OUT.json
 """
-import hashlib
-import json
 import math
-import os
-import sys
 import types
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "gs-slam-analytica_jacobian_amd")):
-    sys.path.insert(0, p)
+from same_bits import main, sha
 
 W, H, F, P = 160, 120, 140.0, 3000
 ARGS = types.SimpleNamespace(percent_dense=0.01, position_lr_init=1e-3, position_lr_final=1e-3, position_lr_delay_mult=1.0,
                              position_lr_max_steps=30000, feature_lr=5e-3, opacity_lr=2e-2, scaling_lr=2e-3, rotation_lr=1e-3)
-
-
-def sha(t):
-    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
 
 
 def world(torch):
@@ -122,29 +112,6 @@ def run(torch):
     return out
 
 
-def main():
-    if sys.argv[1] == "--compare":
-        a, b = (json.load(open(p)) for p in sys.argv[2:4])
-        differing = sorted(k for k in set(a["hashes"]) | set(b["hashes"]) if a["hashes"].get(k) != b["hashes"].get(k))
-        doc = dict(what="tools/loops_same_bits.py in a tree of the parent commit and in this tree, one process each, the same library: "
-                        "SHA-256 of every state buffer of the six device loops after each phase", phases=len(a["hashes"]),
-                   buffers=sum(len(v) for v in a["hashes"].values()), differing=differing, equal=not differing, parent=a, change=b)
-        with open(sys.argv[4], "w") as fh:
-            json.dump(doc, fh, indent=1)
-            fh.write("\n")
-        print("loops_same_bits: %d phases, %d differ %s" % (len(a["hashes"]), len(differing), differing))
-        sys.exit(1 if differing else 0)
-    import torch
-
-    if not torch.cuda.is_available():
-        sys.exit("loops_same_bits: no GPU")
-    from gsaj import _lib
-    doc = dict(device=torch.cuda.get_device_name(0), library_sha256=hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest(), hashes=run(torch))
-    with open(sys.argv[1], "w") as fh:
-        json.dump(doc, fh, indent=1)
-        fh.write("\n")
-    print("loops_same_bits: %d phases written to %s" % (len(doc["hashes"]), sys.argv[1]))
-
-
 if __name__ == "__main__":
-    main()
+    main("loops_same_bits", run, "tools/loops_same_bits.py in a tree of the parent commit and in this tree, one process each, the same library: "
+         "SHA-256 of every state buffer of the six device loops after each phase", unit="phases", one_library=True)

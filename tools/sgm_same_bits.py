@@ -9,20 +9,9 @@ same package; the calls and their arguments are the same, so the two outputs mus
     python tools/sgm_same_bits.py CHANGE.json
     python tools/sgm_same_bits.py --compare PARENT.json CHANGE.json OUT.json
 """
-import hashlib
-import json
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "gs-slam-analytica_jacobian_amd"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
-
-
-def sha(t):
-    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+from same_bits import main, sha
 
 
 def run(torch):
@@ -48,31 +37,7 @@ def run(torch):
     return out
 
 
-def main():
-    if sys.argv[1] == "--compare":
-        a, b = (json.load(open(p)) for p in sys.argv[2:4])
-        differing = sorted(k for k in set(a["hashes"]) | set(b["hashes"]) if a["hashes"].get(k) != b["hashes"].get(k))
-        doc = dict(what="tools/sgm_same_bits.py on the parent's library and on this change's, one process each, the same package: SHA-256 of "
-                        "disp16, depth, C and S of StereoMatcher and of idx16, depth, the gradient bytes, pc, C and S of MotionStereo at the "
-                        "sizes of tools/stereo_bench.py and tools/motion_stereo_bench.py", cases=len(a["hashes"]),
-                   buffers=sum(len(v) for v in a["hashes"].values()), libraries_differ=a["library_sha256"] != b["library_sha256"],
-                   differing=differing, equal=not differing, parent=a, change=b)
-        with open(sys.argv[4], "w") as fh:
-            json.dump(doc, fh, indent=1)
-            fh.write("\n")
-        print("sgm_same_bits: %d cases, %d buffers, %d cases differ %s" % (doc["cases"], doc["buffers"], len(differing), differing))
-        sys.exit(1 if differing else 0)
-    import torch
-
-    if not torch.cuda.is_available():
-        sys.exit("sgm_same_bits: no GPU")
-    from gsaj import _lib
-    doc = dict(device=torch.cuda.get_device_name(0), library_sha256=hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest(), hashes=run(torch))
-    with open(sys.argv[1], "w") as fh:
-        json.dump(doc, fh, indent=1)
-        fh.write("\n")
-    print("sgm_same_bits: %d cases written to %s" % (len(doc["hashes"]), sys.argv[1]))
-
-
 if __name__ == "__main__":
-    main()
+    main("sgm_same_bits", run, "tools/sgm_same_bits.py on the parent's library and on this change's, one process each, the same package: SHA-256 of "
+         "disp16, depth, C and S of StereoMatcher and of idx16, depth, the gradient bytes, pc, C and S of MotionStereo at the "
+         "sizes of tools/stereo_bench.py and tools/motion_stereo_bench.py")
